@@ -1,6 +1,6 @@
 """bench.py — images/sec of the RetinaNet R50-FPN detection path at 800x1333 on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 (N > 1: one rank per GPU.  Under torch.distributed.run (the driver's launch) each rank runs main(); run alone with --gpus N > 1 it
 starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a child process itself.  WORLD_SIZE != --gpus: exit 2.)
 
@@ -14,7 +14,17 @@ image with no data-path collective ("scaling": "weak": per-GPU batch fixed).  We
 architecture (no checkpoint exists in the reference); the classification bias is set so ~1 % of the 200,700 anchors
 per image pass the 0.05 score threshold, the load a trained detector puts on the NMS stage.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the JSON line: `metric`, `value` (images/sec), `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (one timed step), `steps`, `warmup` and the workload's `config`.  Nothing else runs.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its LAST timed step computed as DIR/<name>.npy (float32; float64 where
+the device holds float64): for inference the detect() outputs boxes (8, 300, 4), scores (8, 300) and labels (8, 300); for --mode
+train the loss sums of the step and a fixed, seeded sample of the updated parameters and of the gradient (see measure_train).  Pages
+and weights are seeded and depend only on the arguments (the classification bias is then calibrated on the device's own forward of
+page 0, deterministically), so two builds can be compared output for output.
+
+--full adds everything beside the headline (each measured after the timed region, none of it inside it):
+  config.ms_per_step_one_batch_at_a_time, config.gflop_per_image_*
   roofline     — bound "mfma": `achieved` = algorithmic conv FLOPs of a step / the TIMED region's time per step (the number the
                  driver's clock anchors; stream lanes overlap launches there), `frac` against the 2.5 PF dense bf16 peak;
                  `dominant` = the kernel with the largest share of GPU time (the head-tower layers), with its own FLOPs per
@@ -26,6 +36,8 @@ The JSON line also carries
                  host's cores on a bounded sample (whole path for 1 image of the same canvas).
   secondary    — BASELINE.json configs[2]/[3]: the batch-16-per-GPU TRAINING step (targets + forward + focal/smooth-L1 +
                  backward + bucketed gradient all-reduce under DP + clipnorm Adam), same timing protocol, 20 steps.
+(--no-cpu-baseline / --no-secondary leave those two out of a --full run.)  With --mode train, --full adds the training line's
+`roofline`.
 """
 import argparse
 import importlib
@@ -83,6 +95,21 @@ def conv_bytes(op_desc, batch):
 
 
 SECONDARY_TIMEOUT_S = 240          # multi-GPU only: see the `secondary` block of main()
+DUMP_MAX_BYTES = 64 << 20          # --dump-outputs: the whole dump stays below this
+DUMP_SAMPLE = 1 << 20              # --mode train: parameters / gradient elements in the seeded sample
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy, float64 arrays as they are and everything else in float32 (boxes,
+    scores, parameters and gradients are f32 on the device; labels are small integers, exact in f32)."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def pmc_traffic(n_conv_launches):
@@ -214,11 +241,13 @@ TRAIN_BATCH = 16                   # BASELINE.json configs[2]: batch 16 per GPU
 TRAIN_GFLOP_PER_IMAGE = 1248.4     # ~3x forward (dgrad + wgrad for every conv)
 
 
-def measure_train(steps, warmup, torch, dist, E, Wt, rank, local_rank, world, device):
+def measure_train(steps, warmup, torch, dist, E, Wt, rank, local_rank, world, device, full=True, dump_dir=None):
     """One step = forward + focal/smooth-L1 + backward + (bucketed RCCL all-reduce under DP) + clipnorm Adam on a batch of
     16 synthetic pages per GPU; anchor targets are produced on the device by rtn_anchor_targets inside the timed region.
     Same protocol as the inference line: `warmup` untimed steps, exactly `steps` timed steps between barrier + synchronize,
-    max over ranks.  Returns the result object on rank 0 (None elsewhere)."""
+    max over ranks.  `full`: the `roofline` object (its dominant-kernel timing launches extra work after the timed region).
+    `dump_dir`: rank 0 writes the last step's loss sums and a seeded sample of DUMP_SAMPLE parameters (after Adam) and gradient
+    elements there.  Returns the result object on rank 0 (None elsewhere)."""
     import ctypes as C
     import numpy as np
     T = importlib.import_module(PKG + ".trainer")
@@ -271,6 +300,22 @@ def measure_train(steps, warmup, torch, dist, E, Wt, rank, local_rank, world, de
         return None
     value = world * B * steps / elapsed
     s = tr.norm_sums.cpu().numpy()
+    if dump_dir is not None:
+        n = tr.master.numel()
+        idx = np.sort(np.random.RandomState(0).choice(n, min(DUMP_SAMPLE, n), replace=False))
+        idx_d = torch.as_tensor(idx).to(device)
+        dump_outputs(dump_dir, {"loss_sums": tr.loss_sums.cpu().numpy(),
+                                "params_sample": tr.master.index_select(0, idx_d).cpu().numpy(),
+                                "grad_sample": tr.grad.index_select(0, idx_d).cpu().numpy()})
+    out = {"metric": "images/sec RetinaNet R50-FPN 800x1333 training step", "value": value, "unit": "images/sec",
+           "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+           "config": {"workload": "ResNet50-FPN RetinaNet training step 800x1333 bf16 batch 16/GPU: targets + fwd + "
+                                  "focal/smooth-L1 + bwd + clipnorm Adam (BASELINE.json configs[2]/[3])",
+                      "batch_per_gpu": B, "positives_merged_batch": float(s[2]),
+                      "parallelism": "dp%d (bucketed gradient all-reduce overlapped with backward)" % world}}
+    if not full:
+        return out
     achieved = value * TRAIN_GFLOP_PER_IMAGE / 1e3 / world
     # dominant kernel of the training step: the head-tower weight gradients (8 launches of the nine-tap window kernel, the largest
     # single share of the backward pass).  Measured live after the timed region: events on the launch stream around each launch,
@@ -314,27 +359,23 @@ def measure_train(steps, warmup, torch, dist, E, Wt, rank, local_rank, world, de
         alg_bytes, alg_groups = train_algorithmic_bytes(eng, tr, bp, B, N, 1, cb)
     except Exception as e:              # beside the line, like `dominant`
         alg_groups = {"error": "%s: %s" % (type(e).__name__, e)}
-    return {"metric": "images/sec RetinaNet R50-FPN 800x1333 training step", "value": value, "unit": "images/sec",
-            "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "ResNet50-FPN RetinaNet training step 800x1333 bf16 batch 16/GPU: targets + fwd + "
-                                   "focal/smooth-L1 + bwd + clipnorm Adam (BASELINE.json configs[2]/[3])",
-                       "batch_per_gpu": B, "positives_merged_batch": float(s[2]),
-                       "parallelism": "dp%d (bucketed gradient all-reduce overlapped with backward)" % world},
-            "roofline": {"bound": "mfma", "kernel": "conv fwd+dgrad+wgrad (whole step)", "achieved": achieved,
-                         "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / BF16_DENSE_PEAK_TFLOPS,
-                         "flop_per_step": TRAIN_GFLOP_PER_IMAGE * 1e9 * B, "traffic": traffic, "traffic_per": "step",
-                         "traffic_source": traffic_note,
-                         "algorithmic_bytes_per_step": alg_bytes, "algorithmic_bytes_by_group": alg_groups,
-                         "hbm_floor_ms_at_6.3TBps": (alg_bytes / 6.3e12 * 1e3) if alg_bytes else None,
-                         "traffic_over_algorithmic": (traffic / alg_bytes) if (traffic and alg_bytes) else None,
-                         "dominant": dom}}
+    out["roofline"] = {"bound": "mfma", "kernel": "conv fwd+dgrad+wgrad (whole step)", "achieved": achieved,
+                       "peak": BF16_DENSE_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / BF16_DENSE_PEAK_TFLOPS,
+                       "flop_per_step": TRAIN_GFLOP_PER_IMAGE * 1e9 * B, "traffic": traffic, "traffic_per": "step",
+                       "traffic_source": traffic_note,
+                       "algorithmic_bytes_per_step": alg_bytes, "algorithmic_bytes_by_group": alg_groups,
+                       "hbm_floor_ms_at_6.3TBps": (alg_bytes / 6.3e12 * 1e3) if alg_bytes else None,
+                       "traffic_over_algorithmic": (traffic / alg_bytes) if (traffic and alg_bytes) else None,
+                       "dominant": dom}
+    return out
 
 
 def bench_train(args, torch, dist, E, Wt, rank, local_rank, world, device):
-    out = measure_train(args.steps, args.warmup, torch, dist, E, Wt, rank, local_rank, world, device)
+    out = measure_train(args.steps, args.warmup, torch, dist, E, Wt, rank, local_rank, world, device, full=args.full,
+                        dump_dir=args.dump_outputs)
     if rank == 0:
-        out["cpu_baseline"] = None
+        if args.full:
+            out["cpu_baseline"] = None
         print(json.dumps(out))
     if dist is not None:
         dist.barrier()
@@ -346,8 +387,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the training-step measurement (the `secondary` object)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline after the timed region: the one-batch-at-a-time ms per step, "
+                         "`roofline` (per-launch timings), `cpu_baseline` and `secondary` (the training step); off: the plain line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64), see the module docstring")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the training-step measurement (the `secondary` object)")
     ap.add_argument("--secondary-steps", type=int, default=20)
     ap.add_argument("--in-flight", type=int, default=2,
                     help="batches the engine keeps in flight (Engine.in_flight): consecutive steps run on that many buffer sets, one HIP "
@@ -358,6 +404,8 @@ def main():
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` by itself: start the N ranks as a CHILD torch.distributed.run (one rank per GPU) before this
         # process has imported torch or touched the GPU, pass its output through (rank 0 prints the one JSON line) and return its
@@ -448,20 +496,35 @@ def main():
     n_gpus = world
     images = n_gpus * BATCH * args.steps
     value = images / elapsed
-
-    one_ms = None
-    if args.in_flight > 1:                               # beside the line: the same steps one batch at a time (latency of a batch)
-        eng.in_flight = 1
-        for _ in range(3):
-            eng.detect(x)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(10):
-            eng.detect(x)
-        torch.cuda.synchronize()
-        one_ms = (time.perf_counter() - t1) / 10 * 1e3
+    ms_per_step = 1e3 * elapsed / args.steps
     out = None
     if rank == 0:
+        if args.dump_outputs:                            # the last timed step's detections: its buffer set is done (joined + synchronised)
+            dump_outputs(args.dump_outputs, {"boxes": boxes.cpu().numpy(), "scores": scores.cpu().numpy(), "labels": labels.cpu().numpy()})
+        last = eng._plan(BATCH, CANVAS[0], CANVAS[1], slot=(eng.last_slot + 1) if args.in_flight > 1 else 0)   # that step's buffer set
+        ncand = int((last["classification"] > 0.05).sum().item())
+        out = {"metric": "images/sec RetinaNet R50-FPN 800x1333 inference", "value": value, "unit": "images/sec",
+               "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+               "config": {"workload": "ResNet50-FPN RetinaNet inference 800x1333 bf16 batch 8/GPU incl. decode+NMS "
+                                      "(BASELINE.json configs[1])",
+                          "batch_per_gpu": BATCH, "canvas": list(CANVAS), "anchors_per_image": last["N"],
+                          "candidates_above_0.05_per_image": ncand / BATCH, "parallelism": "dp%d (images sharded, no collective)" % n_gpus,
+                          "batches_in_flight": args.in_flight}}
+    # ---- --full: everything beside the headline, measured after the timed region
+    if args.full:
+        one_ms = None
+        if args.in_flight > 1:                               # beside the line: the same steps one batch at a time (latency of a batch)
+            eng.in_flight = 1
+            for _ in range(3):
+                eng.detect(x)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(10):
+                eng.detect(x)
+            torch.cuda.synchronize()
+            one_ms = (time.perf_counter() - t1) / 10 * 1e3
+    if args.full and rank == 0:
         # ---- roofline.  `achieved` comes from the TIMED region (algorithmic conv FLOPs of a step / ms_per_step).  Beside it:
         # events around every launch of extra (untimed) steps, all launches on ONE stream one after another - the serial sum and
         # the solo duration of the dominant kernel (the head-tower layers: the largest share of GPU time).
@@ -483,7 +546,6 @@ def main():
         stem_2a = [op for op in plan["ops"] if op[0] == "conv" and op[2] == "res2a_branch2a"] if (stem_op and stem_op[0][7] is not None) else []
         if stem_2a:                                                    # res2a_branch2a runs inside the stem kernel: its FLOPs still count
             flops_step += conv_flops(stem_2a[0][1], BATCH)
-        ms_per_step = 1e3 * elapsed / args.steps
         achieved = flops_step / (ms_per_step * 1e-3) / 1e12
         reps = 3
         per_op_ms = eng.profile_ops(x, reps=reps)
@@ -503,7 +565,6 @@ def main():
                                          "on random operands, no staging / barriers / epilogue; register-only loop 1992 TF/s at 1.97 GHz",
                                          "source": "profiles/r3_micro_mfma_rate.txt (tools/micro/mfma_rate.hip, not measured in this run)"},
                    "how": "events on the launch stream around each launch, launches one after another, %d passes" % reps}
-        ncand = int((plan["classification"] > 0.05).sum().item())
         def op_bytes(op):
             if op[0] == "bneck":             # a_in + shortcut in, x_out (+ a_out) out, the three filters
                 m = op[3]
@@ -537,23 +598,16 @@ def main():
                     "serial_conv_ms_per_step": serial_conv_ms, "serial_non_conv_ms_per_step": serial_other_ms,
                     "serial_note": "per-launch event sums with every launch on one stream; larger than ms_per_step because the "
                                    "timed region runs the graph's forks on side streams"}
-        out = {"metric": "images/sec RetinaNet R50-FPN 800x1333 inference", "value": value, "unit": "images/sec",
-               "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-               "config": {"workload": "ResNet50-FPN RetinaNet inference 800x1333 bf16 batch 8/GPU incl. decode+NMS "
-                                      "(BASELINE.json configs[1])",
-                          "batch_per_gpu": BATCH, "canvas": list(CANVAS), "anchors_per_image": plan["N"],
-                          "candidates_above_0.05_per_image": ncand / BATCH, "parallelism": "dp%d (images sharded, no collective)" % n_gpus,
-                          "batches_in_flight": args.in_flight, "ms_per_step_one_batch_at_a_time": one_ms,
-                          "gflop_per_image_survey": GFLOP_PER_IMAGE, "gflop_per_image_counted": flops_step / BATCH / 1e9},
-               "roofline": roofline}
+        out["config"].update({"ms_per_step_one_batch_at_a_time": one_ms,
+                              "gflop_per_image_survey": GFLOP_PER_IMAGE, "gflop_per_image_counted": flops_step / BATCH / 1e9})
+        out["roofline"] = roofline
         if not args.no_cpu_baseline and n_gpus == 1:
             threads = min(os.cpu_count() or 1, 16)
             out["cpu_baseline"] = cpu_baseline(torch, state, threads)
         else:
             out["cpu_baseline"] = None
     # ---- secondary: the training step (BASELINE.json configs[2]; configs[3] when the driver launches N ranks), every rank takes part
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         del eng
         torch.cuda.empty_cache()
         # Under N ranks the training step holds collectives.  A rank that dies or diverges there would leave the others waiting in

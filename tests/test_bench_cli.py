@@ -66,3 +66,34 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1
     assert abs(j["value"] - 2 * 8 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+
+
+def test_steps_must_be_positive_before_any_gpu_work():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], env=_env(), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 2 and "--steps must be >= 1" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run prints the headline only (no `--full` measurements) and --dump-outputs writes the last timed step's detections;
+    two runs with the same arguments write the same arrays."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)],
+                           env=_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 2 and j["warmup"] == 1 and j["unit"] == "images/sec" and j["dtype"] == "bf16" and j["higher_is_better"]
+        assert abs(j["value"] - 8 * 2 / (j["ms_per_step"] * 2e-3)) < 1e-6 * j["value"]
+        assert not {"roofline", "cpu_baseline", "secondary"} & set(j)
+        got = {n: np.load(str(d / (n + ".npy"))) for n in ("boxes", "scores", "labels")}
+        assert got["boxes"].shape == (8, 300, 4) and got["scores"].shape == (8, 300) and got["labels"].shape == (8, 300)
+        assert all(a.dtype == np.float32 for a in got.values())
+        assert (got["scores"] > 0.05).any()                     # the calibrated bias leaves detections to compare
+        dumps.append(got)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

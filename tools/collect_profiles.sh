@@ -7,13 +7,13 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 TAG=$1; COMMIT=$2; O=gpurun_out/$TAG
 mkdir -p $O
-B="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --in-flight 1"     # (tools/pmc_traffic.py counts the batch-8 passes of the process itself)
-T="python3 bench.py --mode train --steps 3 --warmup 1"
-echo "== kernel trace / stats (inference, the bench default: two batches in flight)"; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/kt2.log 2>&1
-echo "== kernel trace / stats (inference, one batch at a time, lanes on)"; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --in-flight 1 > $O/kt.log 2>&1
-echo "== kernel trace / stats (inference, one stream)"; RTN_TWO_STREAMS=0 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --in-flight 1 > $O/kt1.log 2>&1
-echo "== kernel trace / stats (training)"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt -- python3 bench.py --mode train --steps 5 --warmup 2 > $O/ktt.log 2>&1
-echo "== kernel trace / stats (training, every launch alone on the device: no lanes)"; RTN_WGRAD_LANE=0 RTN_TWO_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt1 -- python3 bench.py --mode train --steps 5 --warmup 2 > $O/ktt1.log 2>&1
+B="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary --in-flight 1"     # (tools/pmc_traffic.py counts the batch-8 passes of the process itself)
+T="python3 bench.py --full --mode train --steps 3 --warmup 1"
+echo "== kernel trace / stats (inference, the bench default: two batches in flight)"; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary > $O/kt2.log 2>&1
+echo "== kernel trace / stats (inference, one batch at a time, lanes on)"; timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --in-flight 1 > $O/kt.log 2>&1
+echo "== kernel trace / stats (inference, one stream)"; RTN_TWO_STREAMS=0 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt1 -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-secondary --in-flight 1 > $O/kt1.log 2>&1
+echo "== kernel trace / stats (training)"; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt -- python3 bench.py --full --mode train --steps 5 --warmup 2 > $O/ktt.log 2>&1
+echo "== kernel trace / stats (training, every launch alone on the device: no lanes)"; RTN_WGRAD_LANE=0 RTN_TWO_STREAMS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ktt1 -- python3 bench.py --full --mode train --steps 5 --warmup 2 > $O/ktt1.log 2>&1
 for P in "f:FETCH_SIZE" "w:WRITE_SIZE" "m:SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE" "s:SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"; do
   k=${P%%:*}; c=${P#*:}
   echo "== pmc $c (inference)"; timeout -k 10 200 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$k -- $B > $O/pmc_$k.log 2>&1

@@ -1,7 +1,7 @@
 """MFMA-pipe busy share and wave-cycle shares per kernel from two rocprofv3 PMC passes over bench.py:
 
-  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d A -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
-  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d B -- python3 bench.py ...
+  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d rocprof_out/A -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
+  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d rocprof_out/B -- python3 bench.py --full ...
   python tools/pmc_mfma_util.py <A counter_collection.csv> <B counter_collection.csv> out.json
 
 mfma_util_pct = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 * 1024 SIMDs) * 100 (the CSV sums GRBM_GUI_ACTIVE over the 8 XCDs);

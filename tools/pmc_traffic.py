@@ -1,8 +1,8 @@
 """HBM traffic per step of the bench's conv launches from two rocprofv3 PMC passes (FETCH_SIZE and WRITE_SIZE need separate
 passes: MI355X_MICROARCH.md, rocprofv3 PMC slots):
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_f -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_w -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d rocprof_out/pmc_f -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d rocprof_out/pmc_w -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary
   python tools/pmc_traffic.py <fetch counter_collection.csv> <write counter_collection.csv> 7.125 profiles/rN_pmc_traffic.json [bench stdout]
 
 The third argument is the number of batch-8 forward passes the process ran (warmup + steps + 3 per-op profiling passes + 1/8 for the

@@ -1,8 +1,8 @@
-"""HBM traffic and MFMA-pipe busy share of the TRAINING step from rocprofv3 PMC passes over `bench.py --mode train`:
+"""HBM traffic and MFMA-pipe busy share of the TRAINING step from rocprofv3 PMC passes over `bench.py --full --mode train`:
 
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d A -- python3 bench.py --mode train --steps 3 --warmup 1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d B -- python3 bench.py --mode train --steps 3 --warmup 1
-  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d C -- python3 bench.py --mode train --steps 3 --warmup 1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d rocprof_out/A -- python3 bench.py --full --mode train --steps 3 --warmup 1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d rocprof_out/B -- python3 bench.py --full --mode train --steps 3 --warmup 1
+  rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d rocprof_out/C -- python3 bench.py --full --mode train --steps 3 --warmup 1
   python tools/pmc_train.py <A csv> <B csv> <C csv> <steps run = warmup + steps> <batch> <git commit> out_traffic.json out_mfma.json
 
 FETCH_SIZE / WRITE_SIZE are KiB; FETCH_SIZE is doubled (gfx950 tallies the 128-byte requests of 16 B/lane loads at 64 B:
