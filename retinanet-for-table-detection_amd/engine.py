@@ -66,6 +66,37 @@ def make_anchor_cfg(image_hw, params=None, levels=(3, 4, 5, 6, 7)):
     return cfg, off
 
 
+def schedule_lanes(lanes, io):
+    """Cross-lane events of an op list whose ops already have their HIP stream lanes.  io: per op, (pointers read, pointers
+    written); null pointers are skipped.  An op waits for the ops on OTHER lanes it has a read-after-write, write-after-write or
+    write-after-read hazard with - per lane only the latest, streams are in order.  The last op of every side lane is joined into
+    lane 0.  Returns {lanes, waits: per op the indices it waits for, events: the ops that record one, joins, nlanes}."""
+    writer, readers, waits = {}, {}, []
+    for i, (reads, writes) in enumerate(io):
+        reads = [p_ for p_ in reads if p_]
+        writes = [p_ for p_ in writes if p_]
+        deps = set()
+        for ptr in reads + writes:
+            j = writer.get(ptr)
+            if j is not None and lanes[j] != lanes[i]:
+                deps.add(j)
+        for ptr in writes:
+            deps.update(j for j in readers.get(ptr, ()) if lanes[j] != lanes[i])
+        latest = {}
+        for j in deps:
+            latest[lanes[j]] = max(latest.get(lanes[j], -1), j)
+        waits.append(sorted(latest.values()))
+        for ptr in reads:
+            readers.setdefault(ptr, []).append(i)
+        for ptr in writes:
+            writer[ptr] = i
+            readers[ptr] = []
+    last = {ln: i for i, ln in enumerate(lanes)}
+    joins = sorted(i for ln, i in last.items() if ln != 0)
+    events = set(j for w in waits for j in w) | set(joins)
+    return {"lanes": lanes, "waits": waits, "events": events, "joins": joins, "nlanes": max(lanes) + 1}
+
+
 class Engine:
     def __init__(self, backbone="resnet50", num_classes=1, num_anchors=9, dtype="bf16", device=0, anchor_params=None):
         if not torch.cuda.is_available():
@@ -581,51 +612,10 @@ class Engine:
             ops.append(self._conv(prefix, groups, B, pad=(1, 1), flags=last_flags, out_ld=self.A * per_anchor))
             tower_ranges.append((tower_start, len(ops)))
         ws_bytes = L.lib.rtn_detect_workspace_bytes(B, N, self.K)
-        sched = self._schedule(ops)
-        variants = {}
-        bneck_ok = self.dtype == "bf16" and not fp8_on
-        for fs in (0, 1, 2):                             # fuse_stem: 1 = conv1 + ReLU + pool1, 2 = ... + res2a_branch2a
-            for fd in (False, True):                     # fuse_shortcut
-                for fk in ((0, 1, 2) if bneck_ok else (0,)):      # fuse_bottleneck: 1 = inference, 2 = training (branch2b's output is kept)
-                  for fc in ((0, 1) if (bneck_ok and seams) else (0,)):      # fuse_chain
-                   for fp in ((0, 1) if (fk and fd) else (0,)):                    # fuse_proj_tail
-                    if not fs and not fd and not fk and not fc:
-                        continue
-                    v = list(ops)
-                    if fc:
-                        for sm in seams:
-                            v[sm["i_2c"]] = self._chain_op(sm)
-                            v[sm["i_2a"]] = None
-                    if fd:
-                        for fb in first_blocks:
-                            v[fb["i_2c"]] = self._dual_op(fb, B)
-                            v[fb["i_b1"]] = None
-                    if fk and fd:                            # res2a: branch2b + [branch2c | branch1] + ReLU as one launch
-                        for fb in first_blocks:
-                            if fb["f"] == 64 and fb["step"] == 1 and fb["i_2b"] is not None:
-                                nx0 = blocks64[0] if (blocks64 and fp) else None      # res2b's branch2a rides along
-                                v[fb["i_2b"]] = self._bneck_proj_op(fb, B, keep_h1=fk == 2, nxt=nx0)
-                                v[fb["i_2c"]] = None
-                                if nx0 is not None:
-                                    v[nx0["i_2a"]] = None
-                    if fk:
-                        for bi, blk in enumerate(blocks64):
-                            nxt = blocks64[bi + 1] if bi + 1 < len(blocks64) else None      # its branch2a rides along
-                            v[blk["i_2b"]] = self._bneck_op(blk, nxt, B, keep_h1=fk == 2)
-                            v[blk["i_2c"]] = None
-                            if nxt is not None:
-                                v[nxt["i_2a"]] = None
-                    if fs:
-                        sf = stem_fused
-                        fb0 = first_blocks[0]
-                        if fs == 2 and fb0["f"] == 64 and fb0["step"] == 1 and fb0["i_2a"] is not None and v[fb0["i_2a"]] is not None:
-                            w2a, b2a = self.w[fb0["n2a"]][:2]             # the pooled pixels go through res2a_branch2a before they leave the registers
-                            sf = stem_fused[:7] + ((fb0["a"], w2a, b2a), stem_fused[8])
-                            v[fb0["i_2a"]] = None
-                        v = [v[0], sf] + v[n_stem_ops:]                  # pack, then conv1 + ReLU + pool1 as one launch
-                    v = [op for op in v if op is not None]
-                    variants[(fs, fd, fk, fc, fp)] = (v, self._schedule(v))
-        plan = {"ops": ops, "towers": tower_ranges, "tower_acts": tower_acts, "a_acts": a_acts, "fp8": fp8_on, "sched": sched, "keep": keep, "variants": variants, "xin": xin, "cfg": cfg, "N": N, "regression": regression,
+        # what _variant() substitutes: the fused ops of a fusion key are built on its first use
+        fusion = {"stem": stem_fused, "n_stem_ops": n_stem_ops, "first_blocks": first_blocks, "blocks64": blocks64, "seams": seams}
+        plan = {"ops": ops, "towers": tower_ranges, "tower_acts": tower_acts, "a_acts": a_acts, "fp8": fp8_on, "sched": self._schedule(ops),
+                "keep": keep, "fusion": fusion, "variants": {}, "xin": xin, "cfg": cfg, "N": N, "regression": regression,
                 "classification": classification, "pyr": pyr, "feats": feats,
                 "det_ws": torch.empty(ws_bytes, dtype=torch.uint8, device=dev), "det_ws_bytes": ws_bytes,
                 "boxes": torch.empty(B, L.RTN_MAX_DET, 4, dtype=torch.float32, device=dev),
@@ -633,6 +623,60 @@ class Engine:
                 "labels": torch.empty(B, L.RTN_MAX_DET, dtype=torch.int32, device=dev)}
         self.plans[key] = plan
         return plan
+
+    def _variant(self, plan, key):
+        """{ops, sched, events} that forward() runs under the fusion key (fs, fd, fk, fc, fp) of _fused(): built on first use and
+        kept in the plan.  The all-zero key is the plan's own op list and schedule."""
+        rec = plan["variants"].get(key)
+        if rec is not None:
+            return rec
+        if not any(key):
+            ops, sched = plan["ops"], plan["sched"]
+        else:
+            fs, fd, fk, fc, fp = key
+            fu, B = plan["fusion"], plan["xin"]["B"]
+            first_blocks, blocks64 = fu["first_blocks"], fu["blocks64"]
+            v = list(plan["ops"])
+            if fc:
+                for sm in fu["seams"]:
+                    v[sm["i_2c"]] = self._chain_op(sm)
+                    v[sm["i_2a"]] = None
+            if fd:
+                # one set per plan, shared by its variants: dual ops run on lane 0, a plan's variants run in stream order, and every
+                # in-flight slot has a plan of its own
+                if "dual_ops" not in plan:
+                    plan["dual_ops"] = [self._dual_op(fb, B) for fb in first_blocks]
+                for fb, op in zip(first_blocks, plan["dual_ops"]):
+                    v[fb["i_2c"]] = op
+                    v[fb["i_b1"]] = None
+            if fk and fd:                            # res2a: branch2b + [branch2c | branch1] + ReLU as one launch
+                for fb in first_blocks:
+                    if fb["f"] == 64 and fb["step"] == 1 and fb["i_2b"] is not None:
+                        nx0 = blocks64[0] if (blocks64 and fp) else None      # res2b's branch2a rides along
+                        v[fb["i_2b"]] = self._bneck_proj_op(fb, B, keep_h1=fk == 2, nxt=nx0)
+                        v[fb["i_2c"]] = None
+                        if nx0 is not None:
+                            v[nx0["i_2a"]] = None
+            if fk:
+                for bi, blk in enumerate(blocks64):
+                    nxt = blocks64[bi + 1] if bi + 1 < len(blocks64) else None      # its branch2a rides along
+                    v[blk["i_2b"]] = self._bneck_op(blk, nxt, B, keep_h1=fk == 2)
+                    v[blk["i_2c"]] = None
+                    if nxt is not None:
+                        v[nxt["i_2a"]] = None
+            if fs:
+                sf = fu["stem"]
+                fb0 = first_blocks[0]
+                if fs == 2 and fb0["f"] == 64 and fb0["step"] == 1 and fb0["i_2a"] is not None and v[fb0["i_2a"]] is not None:
+                    w2a, b2a = self.w[fb0["n2a"]][:2]             # the pooled pixels go through res2a_branch2a before they leave the registers
+                    sf = sf[:7] + ((fb0["a"], w2a, b2a), sf[8])
+                    v[fb0["i_2a"]] = None
+                v = [v[0], sf] + v[fu["n_stem_ops"]:]              # pack, then conv1 + ReLU + pool1 as one launch
+            ops = [op for op in v if op is not None]
+            sched = self._schedule(ops)
+        rec = {"ops": ops, "sched": sched, "events": {i: torch.cuda.Event() for i in sched["events"]}}
+        plan["variants"][key] = rec
+        return rec
 
     # ------------------------------------------------------------------ lanes
     @staticmethod
@@ -678,37 +722,11 @@ class Engine:
             return 1
         return 0
 
-    def _schedule(self, ops):
-        """Per op: (lane, [indices of ops on OTHER lanes whose completion it must wait for], needs_event).  Dependencies are
-        read-after-write and write-after-write on the plan's buffers (every tensor of a plan is written by exactly one op
-        of a forward pass, so there are no write-after-read hazards inside a pass; passes are joined on lane 0)."""
-        lanes = [self._lane_of(op) for op in ops]
-        writer = {}
-        waits = []
-        for i, op in enumerate(ops):
-            reads, writes = self._op_io(op)
-            deps = set()
-            for ptr in reads + writes:
-                j = writer.get(ptr)
-                if j is not None and lanes[j] != lanes[i]:
-                    deps.add(j)
-            waits.append(sorted(deps))
-            for ptr in writes:
-                writer[ptr] = i
-        # per (consumer lane, producer lane) only the latest producer matters: streams are in order
-        slim = []
-        for i, deps in enumerate(waits):
-            latest = {}
-            for j in deps:
-                latest[lanes[j]] = max(latest.get(lanes[j], -1), j)
-            slim.append(sorted(latest.values()))
-        needs_event = set(j for deps in slim for j in deps)
-        last_on_lane = {}
-        for i, ln in enumerate(lanes):
-            last_on_lane[ln] = i
-        joins = sorted(i for ln, i in last_on_lane.items() if ln != 0)
-        needs_event.update(joins)
-        return {"lanes": lanes, "waits": slim, "events": needs_event, "joins": joins, "nlanes": max(lanes) + 1}
+    @staticmethod
+    def _schedule(ops):
+        """Lanes of a forward op list and their events (schedule_lanes).  Every tensor of a plan is written by exactly one op of a
+        forward pass, so only read-after-write hazards arise inside a pass; passes are joined on lane 0."""
+        return schedule_lanes([Engine._lane_of(op) for op in ops], [Engine._op_io(op) for op in ops])
 
     # ------------------------------------------------------------------ run
     def _bind_stream(self):
@@ -732,21 +750,21 @@ class Engine:
             self.plans = {k: v for k, v in self.plans.items() if not k[3]}      # new filters: new weight scales in the fp8 ops
         plan = self._plan(B, H, W)
         self._bind_stream()
-        fused = self._fused()
-        ops = plan["variants"][fused][0] if fused else plan["ops"]
-        if fused and fused[1]:
+        key = self._fused()
+        if key[1]:
             self._dual_weights()                         # refresh the concatenated filters if the weights changed
+        var = self._variant(plan, key)
+        ops = var["ops"]
         if not self.two_streams:
             for op in ops:
                 self._run_op(op, images)
             return plan["regression"], plan["classification"]
-        sched = plan["variants"][fused][1] if fused else plan["sched"]
+        sched, events = var["sched"], var["events"]
         main = torch.cuda.current_stream(self.device)
         if self._side is None:                               # three lanes that do not share a hardware queue with each other or with `main`
             self._side = self._concurrent_streams(3, beside=(main,))
         streams = [main] + self._side
         lanes, waits = sched["lanes"], sched["waits"]
-        events = plan.setdefault(("events", fused), {i: torch.cuda.Event() for i in sched["events"]})
         fork = plan.setdefault("fork", torch.cuda.Event())
         fork.record(main)                                    # side lanes start after everything queued before this pass
         for st in streams[1:sched["nlanes"]]:
@@ -768,7 +786,9 @@ class Engine:
         return plan["regression"], plan["classification"]
 
     def _fused(self):
-        """(stem fused: 0 / 1 / 2 = with res2a_branch2a, shortcut fused, 64-channel bottleneck blocks fused) or None.  Training keeps
+        """Fusion key (fs, fd, fk, fc, fp) of the engine's state, the variant of a plan that forward() runs (_variant): stem fused
+        (0 / 1 / 2 = with res2a_branch2a), shortcut folded, 64-channel bottleneck blocks fused (1 / 2 = keeping branch2b's output),
+        stage-3 seams chained, res2b_branch2a appended to res2a's block.  Training keeps
         every bottleneck tensor (the backward reads them) and, in fp32, conv1 / pool1 separate; the folded
         shortcut is used there too - no gradient needs the shortcut TENSOR, only its input and filters.  The fused stem and the fused
         bottleneck exist for bf16 only; the fp8 plan keeps its own branch2a / branch2b pairing."""
@@ -780,13 +800,11 @@ class Engine:
         # (training too: both tensors of a seam are written, which is all the backward pass reads)
         fc = 1 if (self.fuse_chain and self.dtype == "bf16" and not self._fp8_on()) else 0
         fp = 1 if (self.fuse_proj_tail and fk and self.fuse_shortcut) else 0
-        key = (fs, self.fuse_shortcut, fk, fc, fp)
-        return key if any(key) else None
+        return (fs, self.fuse_shortcut, fk, fc, fp)
 
     def active_ops(self, plan):
         """The op list forward() executes."""
-        fused = self._fused()
-        return plan["variants"][fused][0] if fused else plan["ops"]
+        return self._variant(plan, self._fused())["ops"]
 
     def _run_op(self, op, images):
         lib, h = L.lib, self.h
@@ -899,13 +917,13 @@ class Engine:
             self.join()
             self.plans = {k: v for k, v in self.plans.items() if not k[3]}
         plan = self._plan(B, H, W, slot=si + 1)             # slot 0 is forward()'s / the one-batch path's own buffer set
-        fused = self._fused()
-        ops = plan["variants"][fused][0] if fused else plan["ops"]
+        key = self._fused()
         caller = torch.cuda.current_stream(self.device)
-        if fused and fused[1] and self._dual_version != self.weights_version:
+        if key[1] and self._dual_version != self.weights_version:
             self.join()                                       # new weights: the concatenated filters are rewritten on the caller's
             self._dual_weights()                              # stream - nothing may be in flight on the old ones, and the batches
             caller.synchronize()                              # that follow on other streams must see the new ones
+        ops = self._variant(plan, key)["ops"]
         if slot.get("consumed") is not None:
             # the packer below rewrites this buffer set's packed image: its previous batch must have read it (the stem, that batch's
             # first kernel on the slot's stream).  NOT the whole previous batch: that would chain the slots through the caller's

@@ -27,6 +27,7 @@ import torch
 from . import _lib as L
 from . import weights as Wt
 from . import parallel as Par
+from .engine import schedule_lanes
 
 
 def _ceil128(v):
@@ -47,6 +48,7 @@ class Trainer:
         self._wg_stream = None
         self.record_impls = False      # tests: {(kind, layer): kernel code} of the last backward (rtn_debug_last_*_impl)
         self.impls = {}
+        self.fwd_key = None            # Engine._fused() of the last training forward (forward_backward)
         # a backward plan holds gradient buffers, descriptors into the forward plan's activations and every weight-gradient workspace
         # (row-info table + split slabs: GBs per canvas): it lives exactly as long as the engine's plan of the same canvas
         engine.on_plan_evict.append(weakref.WeakMethod(self._drop_bplan))
@@ -400,9 +402,8 @@ class Trainer:
     def _bschedule(self, bops, nwg, dyp_cls):
         """Lane of every backward op and the cross-lane events it must wait for.  Lane 0: the data-gradient chain; lanes
         1..nwg: weight / bias gradients (independent of each other: round-robin); lane nwg+1: the data gradients of the
-        classification tower, which only meet the rest of the graph where the pyramid gradients are summed.  Hazards are
-        tracked per buffer: read-after-write, write-after-write and write-after-read (gradient buffers are accumulated in
-        place by several ops)."""
+        classification tower, which only meet the rest of the graph where the pyramid gradients are summed.  Events come from
+        schedule_lanes; write-after-read hazards arise here (gradient buffers are accumulated in place by several ops)."""
         lanes, turn = [], 0
         extra = os.environ.get("RTN_BWD_EXTRA_LANE", "0") != "0"
         for b in bops:
@@ -415,39 +416,7 @@ class Trainer:
                 lanes.append(nwg + 2)
             else:
                 lanes.append(0)
-        writer, readers, waits = {}, {}, []
-        for i, b in enumerate(bops):
-            reads, writes = Trainer._bop_io(b)
-            reads = [p_ for p_ in reads if p_]
-            writes = [p_ for p_ in writes if p_]
-            deps = set()
-            for ptr in reads:
-                j = writer.get(ptr)
-                if j is not None and lanes[j] != lanes[i]:
-                    deps.add(j)
-            for ptr in writes:
-                j = writer.get(ptr)
-                if j is not None and lanes[j] != lanes[i]:
-                    deps.add(j)
-                for j in readers.get(ptr, ()):
-                    if lanes[j] != lanes[i]:
-                        deps.add(j)
-            latest = {}
-            for j in deps:
-                latest[lanes[j]] = max(latest.get(lanes[j], -1), j)
-            waits.append(sorted(latest.values()))
-            for ptr in reads:
-                readers.setdefault(ptr, []).append(i)
-            for ptr in writes:
-                writer[ptr] = i
-                readers[ptr] = []
-        events = set(j for w in waits for j in w)
-        last = {}
-        for i, ln in enumerate(lanes):
-            last[ln] = i
-        joins = sorted(i for ln, i in last.items() if ln != 0)
-        events.update(joins)
-        return {"lanes": lanes, "waits": waits, "events": events, "joins": joins, "nlanes": max(lanes) + 1}
+        return schedule_lanes(lanes, [Trainer._bop_io(b) for b in bops])
 
     def forward_backward(self, images, regression_batch, labels_batch):
         """Forward, loss and backward; leaves dL/dparams in self.grad (flat f32) and returns the device tensor
@@ -458,6 +427,7 @@ class Trainer:
         B, H, W, _ = images.shape
         eng.training = True
         try:
+            self.fwd_key = eng._fused()              # the fusion key this forward runs: the pool backward follows its stem
             reg, cls = eng.forward(images)
         finally:
             eng.training = False
@@ -547,7 +517,7 @@ class Trainer:
             elif kind == "poolbwd":
                 Bn, Hi, Wi, Cc = b[4]
                 # the fused stem (bf16 training forward) never writes conv1's output: the ReLU mask comes from the pooled tensor
-                fused = eng.fuse_stem and eng.fuse_stem_train and eng.dtype == "bf16"
+                fused = self.fwd_key[0] != 0
                 h.check(lib.rtn_maxpool3x3s2_tfsame_bwd_idx(h.raw, b[2].data_ptr(), b[5].data_ptr(), (b[6] if fused else b[1]).data_ptr(),
                                                             b[3].data_ptr(), eng.rdt, Bn, Hi, Wi, Cc, 2 if fused else 1))
             else:

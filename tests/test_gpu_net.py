@@ -266,6 +266,33 @@ def test_fused_shortcut_matches_separate_layers(pkg, state, dtype, hw):
 
 
 @pytest.mark.gpu
+def test_plan_builds_only_the_variants_that_run(pkg, state):
+    """A plan builds the fused op list of a fusion key on its first use (engine.Engine._variant), not every key up front: an
+    inference and a training forward leave exactly their two variants, and both run the same folded-shortcut ops - one descriptor
+    and one workspace per stage-first block for the whole plan."""
+    E, _ = mods(pkg)
+    B = 2
+    x = (torch.rand(B, CANVAS[0], CANVAS[1], 3, generator=torch.Generator().manual_seed(3)) * 2 - 1).cuda()
+    eng = E.Engine("resnet50", 1, 9, dtype="bf16")
+    eng.load_state(state)
+    eng.forward(x)
+    infer = eng._fused()
+    eng.training = True
+    try:
+        eng.forward(x)
+        train = eng._fused()
+    finally:
+        eng.training = False
+    torch.cuda.synchronize()
+    plan = eng._plan(B, CANVAS[0], CANVAS[1])
+    assert infer != train and set(plan["variants"]) == {infer, train}
+    infer_dual, train_dual = [{op[2]: op[1] for op in plan["variants"][k]["ops"] if op[0] == "dual"} for k in (infer, train)]
+    assert len(infer_dual) >= 3 and set(infer_dual) == set(train_dual)
+    for name, d in infer_dual.items():
+        assert d is train_dual[name] and d.workspace == train_dual[name].workspace
+
+
+@pytest.mark.gpu
 def test_full_size_passes_repeat_bit_for_bit(pkg, state):
     """BASELINE configuration (batch 8, 800x1333, bf16, every fusion and the stream lanes on): 40 back-to-back detect() calls must
     give the same bits as the first one (the kernels are deterministic - split-K sums in slice order, no float atomics in

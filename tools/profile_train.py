@@ -59,7 +59,7 @@ for b in bp["bops"]:
         elif kind == "zins": h.check(lib.rtn_zero_insert2(h.raw, b[1].data_ptr(), b[2].data_ptr(), eng.rdt, *b[3]))
         elif kind == "upbwd": h.check(lib.rtn_upsample_add_bwd(h.raw, b[1].data_ptr(), b[2].data_ptr(), eng.rdt, *b[3], b[4]))
         elif kind == "poolbwd":
-            fused = eng.fuse_stem and eng.fuse_stem_train and eng.dtype == "bf16"
+            fused = tr.fwd_key[0] != 0
             h.check(lib.rtn_maxpool3x3s2_tfsame_bwd_idx(h.raw, b[2].data_ptr(), b[5].data_ptr(), (b[6] if fused else b[1]).data_ptr(), b[3].data_ptr(), eng.rdt, *b[4], 2 if fused else 1))
     ms = timed(run)
     label = kind + ((":" + (b[3] if kind == "wgrad" else b[-1])) if kind in ("wgrad", "dgrad") else "")
