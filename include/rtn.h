@@ -34,7 +34,8 @@ extern "C" {
 
 typedef struct rtn_ctx* rtn_handle_t;
 
-typedef enum { RTN_BF16 = 0, RTN_F32 = 1, RTN_FP8 = 3 /* OCP e4m3fn bytes; rtn_conv2d_fp8_fwd / rtn_quantize_fp8 only */ } rtn_dtype_t;
+typedef enum { RTN_BF16 = 0, RTN_F32 = 1, RTN_FP8 = 3 /* OCP e4m3fn bytes; rtn_conv2d_fp8_fwd / rtn_quantize_fp8 only */,
+               RTN_I32 = 4 /* rtn_gather_detections only */ } rtn_dtype_t;
 
 #define RTN_MAX_GROUPS 5      /* pyramid levels P3..P7 in one grouped launch */
 #define RTN_MAX_GT     64     /* ground-truth boxes per image (anchor targets) */
@@ -469,6 +470,25 @@ int rtn_decode_filter_nms(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, in
                           float* boxes, float* scores, int32_t* labels,
                           void* workspace, size_t workspace_bytes);
 
+/* The other FilterDetections modes (model/layers.py:200-264), flags OR-ed:
+ *   RTN_DET_CLASS_AGNOSTIC  class_specific_filter=False: per anchor the max over the K scores is thresholded, one NMS (or
+ *                           top-k) per image; label = argmax (lowest class on ties), score = the max.
+ *   RTN_DET_NO_NMS          nms=False: threshold + top-k only (nms_threshold is ignored).
+ * Unknown bits: RTN_EINVAL from the launches, 0 from rtn_detect_workspace_bytes_ex.  Every mode fits the workspace
+ * rtn_detect_workspace_bytes(B, N, K) returns; rtn_detect_workspace_bytes_ex gives the exact (never larger) size.
+ * In class-agnostic mode the classes*max_detections <= 8192 limit does not apply.
+ * indices (device i32 [B][max_det], may be NULL): the anchor / box index n of every detection, -1 in the padding.
+ * flags = 0 with indices = NULL launches exactly what rtn_decode_filter_nms / rtn_filter_detections launch. */
+#define RTN_DET_CLASS_AGNOSTIC 1
+#define RTN_DET_NO_NMS         2
+size_t rtn_detect_workspace_bytes_ex(int B, int64_t N, int num_classes, int flags);
+int rtn_decode_filter_nms_ex(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes,
+                             const float* regression, const float* classification,
+                             int canvas_h, int canvas_w,
+                             float score_threshold, float nms_threshold, int max_detections,
+                             float* boxes, float* scores, int32_t* labels,
+                             void* workspace, size_t workspace_bytes, int flags, int32_t* indices);
+
 /* ---- page preprocessing -------------------------------------------------------------------------------
  * rtn_preprocess_dt3: DetectTablesUtils.preProcessSampleImages (DetectTablesUtils.py:251-261) for B equally sized pages:
  *   src uint8 [B][H][W][channels] (3 = BGR as cv2.imread gives, 1 = gray) -> dst uint8 [B][H][W][3] in OpenCV channel order
@@ -500,6 +520,13 @@ int rtn_warp_affine_u8(rtn_handle_t h, const uint8_t* src, int H, int W, int C, 
 int rtn_filter_detections(rtn_handle_t h, int B, int64_t N, int num_classes, const float* in_boxes, const float* classification,
                           float score_threshold, float nms_threshold, int max_detections, float* boxes, float* scores,
                           int32_t* labels, void* workspace, size_t workspace_bytes);
+int rtn_filter_detections_ex(rtn_handle_t h, int B, int64_t N, int num_classes, const float* in_boxes, const float* classification,
+                             float score_threshold, float nms_threshold, int max_detections, float* boxes, float* scores,
+                             int32_t* labels, void* workspace, size_t workspace_bytes, int flags, int32_t* indices);
+/* FilterDetections' `other` tensors (model/layers.py:245,254): dst[b][r][:] = src[b][indices[b][r]][:] for the indices an _ex call
+ * wrote, -1 where the index is -1.  src device [B][N][row_elems], dst device [B][max_det][row_elems]; dtype RTN_F32 or RTN_I32. */
+int rtn_gather_detections(rtn_handle_t h, int B, int64_t N, int max_detections, int64_t row_elems, int dtype, const void* src,
+                          const int32_t* indices, void* dst);
 int rtn_regress_boxes(rtn_handle_t h, const float* anchors, const float* deltas, int64_t n_boxes, const float* mean4 /* host */,
                       const float* std4 /* host */, float* out);
 int rtn_clip_boxes(rtn_handle_t h, const float* in, int64_t n_boxes, float width, float height, float* out);

@@ -15,7 +15,8 @@ import torch  # noqa: F401  (load order, see above)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RTN_LIB_PATH") or os.path.join(_HERE, "librtn.so")      # RTN_LIB_PATH: A/B two builds on one box
 
-RTN_BF16, RTN_F32, RTN_U8, RTN_FP8 = 0, 1, 2, 3
+RTN_BF16, RTN_F32, RTN_U8, RTN_FP8, RTN_I32 = 0, 1, 2, 3, 4
+RTN_DET_CLASS_AGNOSTIC, RTN_DET_NO_NMS = 1, 2
 RTN_MAX_GROUPS, RTN_MAX_GT, RTN_MAX_DET = 5, 64, 300
 
 CONV_RELU, CONV_SIGMOID, CONV_RES_SAME, CONV_RES_UPSAMPLE, CONV_OUT_F32, CONV_RELU_MASK, CONV_MASK_PRE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
@@ -171,6 +172,10 @@ SIGNATURES = {
     "rtn_retina_loss_bwd_dev": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _F, _F, _P, _I, _P, _P]),
     "rtn_detect_workspace_bytes": (_SZ, [_I, _I64, _I]),
     "rtn_decode_filter_nms": (_I, [_P, C.POINTER(AnchorCfg), _I, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _SZ]),
+    "rtn_detect_workspace_bytes_ex": (_SZ, [_I, _I64, _I, _I]),
+    "rtn_decode_filter_nms_ex": (_I, [_P, C.POINTER(AnchorCfg), _I, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _SZ, _I, _P]),
+    "rtn_filter_detections_ex": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _I, _P, _P, _P, _P, _SZ, _I, _P]),
+    "rtn_gather_detections": (_I, [_P, _I, _I64, _I, _I64, _I, _P, _P, _P]),
 }
 
 

@@ -19,6 +19,8 @@
 //   decode, drop those overlapping kept boxes, resolve 64 at a time (ballot / readlane), broadcast the
 //   newly kept boxes to the rest of the batch.  Exact TF semantics for ANY candidate count.
 // Stage 3 (one workgroup per image): top-k merge over classes, pad with -1.
+// The other modes (rtn_*_ex flags): class_specific_filter=False thresholds max_c per anchor into ONE list per image (label =
+//   first-index argmax, recomputed at the merge); nms=False skips 2b/2c, the head of 2a's sorted first batch is the top-k.
 #include "rtn_internal.h"
 #include "rtn_anchor_dev.h"
 
@@ -93,24 +95,15 @@ __device__ __forceinline__ bool iou_gt_flat(const NBox& a, const NBox& b, float 
 // block's slice of the (image, class) key list: a per-wave atomic made ~1500 same-address atomics per image at a
 // 1 % candidate rate and cost 50 us; the list order is irrelevant (keys are sorted later).
 constexpr int CAND_T = 1024, CAND_R = 4, CAND_PER_BLOCK = CAND_T * CAND_R;
-__global__ __launch_bounds__(CAND_T) void detect_candidates_kernel(int N, int K, const float* __restrict__ cls, float thr,
-                                                                   u64* __restrict__ keys, int* __restrict__ counts) {
+
+// The workgroup's passing anchors -> keys {score bits | ~n} appended to one list (count, keys).
+__device__ __forceinline__ void append_candidates(const float (&score)[CAND_R], const bool (&pass)[CAND_R], int* __restrict__ count,
+                                                  u64* __restrict__ keys) {
     __shared__ int s_cnt[CAND_R * (CAND_T / 64)];
-    const int bk = blockIdx.y;
-    const int b = bk / K, k = bk - b * K;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    float score[CAND_R];
     u64 mask[CAND_R];
-    bool pass[CAND_R];
 #pragma unroll
     for (int r = 0; r < CAND_R; ++r) {
-        const int n = blockIdx.x * CAND_PER_BLOCK + r * CAND_T + t;
-        score[r] = 0.f;
-        pass[r] = false;
-        if (n < N) {
-            score[r] = cls[((long long)b * N + n) * K + k];
-            pass[r] = score[r] > thr;
-        }
         mask[r] = __ballot(pass[r]);
         if (lane == 0) s_cnt[r * (CAND_T / 64) + wave] = __popcll(mask[r]);
     }
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(CAND_T) void detect_candidates_kernel(int N, int K,
         }
         const int total = __shfl(incl, 63, 64);
         int base = 0;
-        if (lane == 0 && total > 0) base = atomicAdd(&counts[bk], total);
+        if (lane == 0 && total > 0) base = atomicAdd(count, total);
         base = __shfl(base, 0, 64);
         s_cnt[lane] = base + incl - v;
     }
@@ -135,9 +128,61 @@ __global__ __launch_bounds__(CAND_T) void detect_candidates_kernel(int N, int K,
         if (pass[r]) {
             const int n = blockIdx.x * CAND_PER_BLOCK + r * CAND_T + t;
             const int pos = s_cnt[r * (CAND_T / 64) + wave] + __popcll(mask[r] & ((1ull << lane) - 1ull));
-            keys[(long long)bk * N + pos] = ((u64)__float_as_uint(score[r]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)n);
+            keys[pos] = ((u64)__float_as_uint(score[r]) << 32) | (u64)(0xFFFFFFFFu - (unsigned)n);
         }
     }
+}
+
+__global__ __launch_bounds__(CAND_T) void detect_candidates_kernel(int N, int K, const float* __restrict__ cls, float thr,
+                                                                   u64* __restrict__ keys, int* __restrict__ counts) {
+    const int bk = blockIdx.y;
+    const int b = bk / K, k = bk - b * K;
+    float score[CAND_R];
+    bool pass[CAND_R];
+#pragma unroll
+    for (int r = 0; r < CAND_R; ++r) {
+        const int n = blockIdx.x * CAND_PER_BLOCK + r * CAND_T + threadIdx.x;
+        score[r] = 0.f;
+        pass[r] = false;
+        if (n < N) {
+            score[r] = cls[((long long)b * N + n) * K + k];
+            pass[r] = score[r] > thr;
+        }
+    }
+    append_candidates(score, pass, counts + bk, keys + (long long)bk * N);
+}
+
+// max_c and first-index argmax_c of one anchor's K scores (keras.backend.max / argmax, model/layers.py:232-233: ties -> lowest c)
+__device__ __forceinline__ float best_class(const float* __restrict__ row, int K, int* arg) {
+    float m = row[0];
+    int a = 0;
+    for (int c = 1; c < K; ++c) {
+        const float v = row[c];
+        if (v > m) { m = v; a = c; }
+    }
+    *arg = a;
+    return m;
+}
+
+// class_specific_filter=False: grid = (ceil(N/CAND_PER_BLOCK), B), one list per image; a thread reads its anchor's K contiguous
+// scores and appends the anchor when their max passes.  The label (argmax) is recomputed where the detection is written out.
+__global__ __launch_bounds__(CAND_T) void detect_candidates_agnostic_kernel(int N, int K, const float* __restrict__ cls, float thr,
+                                                                            u64* __restrict__ keys, int* __restrict__ counts) {
+    const int b = blockIdx.y;
+    float score[CAND_R];
+    bool pass[CAND_R];
+#pragma unroll
+    for (int r = 0; r < CAND_R; ++r) {
+        const int n = blockIdx.x * CAND_PER_BLOCK + r * CAND_T + threadIdx.x;
+        score[r] = 0.f;
+        pass[r] = false;
+        if (n < N) {
+            int arg;
+            score[r] = best_class(cls + ((long long)b * N + n) * K, K, &arg);
+            pass[r] = score[r] > thr;
+        }
+    }
+    append_candidates(score, pass, counts + b, keys + (long long)b * N);
 }
 
 __device__ __forceinline__ void bitonic_sort_desc(u64* s, int P, int t, int nthreads) {
@@ -652,22 +697,106 @@ __global__ __launch_bounds__(NMS_T) void merge_topk_kernel(int K, int max_det, c
     }
 }
 
+// merge_topk_kernel for the other modes (rtn_decode_filter_nms_ex).  The L lists of image b are read from
+// src_keys / src_boxes[(b * L + l) * list_stride + j], their lengths from src_count[(b * L + l) * count_stride] (at most max_det
+// of each are taken):
+//   nms=True : the NMS output (sel_*, stride max_det, sel_count);   nms=False : the sorted first batch of nms_sort_kernel (stride
+//   CAP, meta[.][0]) - every list is in descending key order, so its first max_det entries are its share of the top-k.
+// agn_cls != NULL (class_specific_filter=False): one list per image, already in output order; the label is the first-index argmax
+// of the anchor's K scores.  indices (optional): the anchor index of every detection, -1 in the padding.
+__global__ __launch_bounds__(NMS_T) void merge_topk_ex_kernel(int L, int max_det, const u64* __restrict__ src_keys,
+                                                              const float4* __restrict__ src_boxes, long long list_stride,
+                                                              const int* __restrict__ src_count, int count_stride,
+                                                              const float* __restrict__ agn_cls, int N, int K,
+                                                              float* __restrict__ boxes, float* __restrict__ scores,
+                                                              int* __restrict__ labels, int* __restrict__ indices) {
+    __shared__ u64 s_keys[MCAP];
+    __shared__ unsigned short s_cls[MCAP];
+    __shared__ unsigned short s_j[MCAP];
+    __shared__ int s_total;
+    const int t = threadIdx.x;
+    const int b = blockIdx.x;
+    if (t == 0) {
+        int total = 0;
+        for (int l = 0; l < L; ++l) {
+            int cnt = src_count[(b * L + l) * count_stride];
+            cnt = cnt < max_det ? cnt : max_det;
+            for (int j = 0; j < cnt && total < MCAP; ++j, ++total) { s_cls[total] = (unsigned short)l; s_j[total] = (unsigned short)j; }
+        }
+        s_total = total;
+    }
+    __syncthreads();
+    const int total = s_total;
+    int P = 64;
+    while (P < total) P <<= 1;
+    for (int i = t; i < P; i += NMS_T) {
+        u64 key = 0;
+        if (i < total) {
+            const u64 sk = src_keys[((long long)b * L + s_cls[i]) * list_stride + s_j[i]];
+            key = (sk & 0xFFFFFFFF00000000ull) | (u64)(0xFFFFFFFFu - (unsigned)i);
+        }
+        s_keys[i] = key;
+    }
+    __syncthreads();
+    if (L > 1) bitonic_sort_desc(s_keys, P, t, NMS_T);
+    const int nout = total < max_det ? total : max_det;
+    for (int r = t; r < max_det; r += NMS_T) {
+        float4 bx = make_float4(-1.f, -1.f, -1.f, -1.f);
+        float sc = -1.f;
+        int lb = -1, n = -1;
+        if (r < nout) {
+            const u64 key = s_keys[r];
+            const int pos = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+            const int l = s_cls[pos], j = s_j[pos];
+            const long long src = ((long long)b * L + l) * list_stride + j;
+            bx = src_boxes[src];
+            sc = __uint_as_float((unsigned)(key >> 32));
+            n = (int)(0xFFFFFFFFu - (unsigned)(src_keys[src] & 0xFFFFFFFFull));
+            lb = l;
+            if (agn_cls) best_class(agn_cls + ((long long)b * N + n) * K, K, &lb);
+        }
+        reinterpret_cast<float4*>(boxes)[(long long)b * max_det + r] = bx;
+        scores[(long long)b * max_det + r] = sc;
+        labels[(long long)b * max_det + r] = lb;
+        if (indices) indices[(long long)b * max_det + r] = n;
+    }
+}
+
+// other_ = gather(o, indices) padded with -1 (model/layers.py:245,254): dst[b][r][e] = src[b][indices[b][r]][e] or `pad`.
+// 32-bit elements (float32 / int32, the pad's bit pattern carries the type).
+__global__ __launch_bounds__(256) void gather_detections_kernel(long long N, int max_det, long long row_elems, long long total,
+                                                                const unsigned* __restrict__ src, const int* __restrict__ indices,
+                                                                unsigned pad, unsigned* __restrict__ dst) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+        const long long r = i / row_elems, e = i - r * row_elems;     // r = b * max_det + detection
+        const long long b = r / max_det;
+        const int n = indices[r];
+        dst[i] = (n >= 0 && n < N) ? src[(b * N + n) * row_elems + e] : pad;
+    }
+}
+
 struct WsLayout { size_t keys, counts, sel_keys, sel_boxes, sel_count, sorted_keys, sorted_boxes, mask, meta, total; };
 
-WsLayout ws_layout(int B, long long N, int K) {
+constexpr int DET_AGN = RTN_DET_CLASS_AGNOSTIC, DET_NO_NMS = RTN_DET_NO_NMS;
+
+// flags = 0: the layout of rtn_detect_workspace_bytes.  Class-agnostic: one list per image instead of K; NMS-free: no NMS output
+// (sel_*) and no bit matrix.  Every region only shrinks, so each mode fits the flags = 0 size.
+WsLayout ws_layout(int B, long long N, int K, int flags = 0) {
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t BL = (size_t)B * ((flags & DET_AGN) ? 1 : K);
+    const bool nms = !(flags & DET_NO_NMS);
     WsLayout w;
     size_t o = 0;
-    w.keys = o;      o += al((size_t)B * K * N * 8);
-    w.counts = o;    o += al((size_t)B * K * 4 * 2);      // candidate counts then selected counts
-    w.sel_count = w.counts + (size_t)B * K * 4;
-    w.sel_keys = o;  o += al((size_t)B * K * RTN_MAX_DET * 8);
-    w.sel_boxes = o; o += al((size_t)B * K * RTN_MAX_DET * 16);
+    w.keys = o;      o += al(BL * N * 8);
+    w.counts = o;    o += al(BL * 4 * 2);      // candidate counts then selected counts
+    w.sel_count = w.counts + BL * 4;
+    w.sel_keys = o;  o += nms ? al(BL * RTN_MAX_DET * 8) : 0;
+    w.sel_boxes = o; o += nms ? al(BL * RTN_MAX_DET * 16) : 0;
     // first batch of every (image, class): sorted keys, decoded boxes, suppression bit matrix (CAP x CAP bits = 2 MiB)
-    w.sorted_keys = o;  o += al((size_t)B * K * CAP * 8);
-    w.sorted_boxes = o; o += al((size_t)B * K * CAP * 16);
-    w.mask = o;         o += al((size_t)B * K * CAP * (CAP / 64) * 8);
-    w.meta = o;         o += al((size_t)B * K * 16);
+    w.sorted_keys = o;  o += al(BL * CAP * 8);
+    w.sorted_boxes = o; o += al(BL * CAP * 16);
+    w.mask = o;         o += nms ? al(BL * CAP * (CAP / 64) * 8) : 0;
+    w.meta = o;         o += al(BL * 16);
     w.total = o;
     return w;
 }
@@ -679,11 +808,17 @@ extern "C" size_t rtn_detect_workspace_bytes(int B, int64_t N, int num_classes) 
     return ws_layout(B, N, num_classes).total;
 }
 
+extern "C" size_t rtn_detect_workspace_bytes_ex(int B, int64_t N, int num_classes, int flags) {
+    if (B < 1 || N < 1 || num_classes < 1 || (flags & ~(DET_AGN | DET_NO_NMS))) return 0;
+    return ws_layout(B, N, num_classes, flags).total;
+}
+
 static int detect_launch(rtn_handle_t h, const DevAnchorCfg& d, int N, int B, int num_classes, const float* regression,
                          const float4* boxes_explicit, const float* classification, int canvas_h, int canvas_w, float score_threshold,
                          float nms_threshold, int max_detections, float* boxes, float* scores, int32_t* labels, void* workspace,
-                         size_t workspace_bytes) {
-    const WsLayout w = ws_layout(B, N, num_classes);
+                         size_t workspace_bytes, int flags, int32_t* indices) {
+    const bool agn = flags & DET_AGN, nms = !(flags & DET_NO_NMS);
+    const WsLayout w = ws_layout(B, N, num_classes, flags);
     if (workspace_bytes < w.total) return rtn_fail(h, RTN_ENOMEM, "detect: workspace %zu < %zu", workspace_bytes, w.total);
     char* ws = (char*)workspace;
     u64* keys = (u64*)(ws + w.keys);
@@ -691,39 +826,59 @@ static int detect_launch(rtn_handle_t h, const DevAnchorCfg& d, int N, int B, in
     int* sel_count = (int*)(ws + w.sel_count);
     u64* sel_keys = (u64*)(ws + w.sel_keys);
     float4* sel_boxes = (float4*)(ws + w.sel_boxes);
-    const int BK = B * num_classes;
+    const int L = agn ? 1 : num_classes;             // candidate lists per image
+    const int BK = B * L;
     RTN_HIP(h, hipMemsetAsync(counts, 0, (size_t)BK * 4 * 2, h->stream));
-    hipLaunchKernelGGL(detect_candidates_kernel, dim3((N + CAND_PER_BLOCK - 1) / CAND_PER_BLOCK, BK), dim3(CAND_T), 0, h->stream, N, num_classes,
-                       classification, score_threshold, keys, counts);
-    RTN_CHECK_LAUNCH(h, "detect_candidates_kernel");
+    if (agn) {
+        hipLaunchKernelGGL(detect_candidates_agnostic_kernel, dim3((N + CAND_PER_BLOCK - 1) / CAND_PER_BLOCK, B), dim3(CAND_T), 0,
+                           h->stream, N, num_classes, classification, score_threshold, keys, counts);
+        RTN_CHECK_LAUNCH(h, "detect_candidates_agnostic_kernel");
+    } else {
+        hipLaunchKernelGGL(detect_candidates_kernel, dim3((N + CAND_PER_BLOCK - 1) / CAND_PER_BLOCK, BK), dim3(CAND_T), 0, h->stream,
+                           N, num_classes, classification, score_threshold, keys, counts);
+        RTN_CHECK_LAUNCH(h, "detect_candidates_kernel");
+    }
     u64* sorted_keys = (u64*)(ws + w.sorted_keys);
     float4* sorted_boxes = (float4*)(ws + w.sorted_boxes);
     u64* mask = (u64*)(ws + w.mask);
     int* meta = (int*)(ws + w.meta);
-    hipLaunchKernelGGL(nms_sort_kernel, dim3(BK), dim3(NMS_T), 0, h->stream, d, num_classes, regression, (const u64*)keys,
+    hipLaunchKernelGGL(nms_sort_kernel, dim3(BK), dim3(NMS_T), 0, h->stream, d, L, regression, (const u64*)keys,
                        (const int*)counts, (float)canvas_w, (float)canvas_h, boxes_explicit, N, sorted_keys, sorted_boxes, meta);
     RTN_CHECK_LAUNCH(h, "nms_sort_kernel");
-    int mask_blocks = 1024 / BK;                     // workgroups per (image, class): ~4 per CU in total
-    mask_blocks = mask_blocks < 1 ? 1 : (mask_blocks > 512 ? 512 : mask_blocks);
-    hipLaunchKernelGGL(nms_mask_kernel, dim3(mask_blocks, BK), dim3(MASK_T), 0, h->stream, (const float4*)sorted_boxes,
-                       (const int*)meta, nms_threshold, mask);
-    RTN_CHECK_LAUNCH(h, "nms_mask_kernel");
-    hipLaunchKernelGGL(nms_kernel, dim3(BK), dim3(NMS_T), 0, h->stream, d, num_classes, regression, (const u64*)keys,
-                       (const int*)counts, (float)canvas_w, (float)canvas_h, nms_threshold, max_detections, sel_keys, sel_boxes,
-                       sel_count, boxes_explicit, N, (const u64*)sorted_keys, (const float4*)sorted_boxes, (const u64*)mask,
-                       (const int*)meta);
-    RTN_CHECK_LAUNCH(h, "nms_kernel");
-    hipLaunchKernelGGL(merge_topk_kernel, dim3(B), dim3(NMS_T), 0, h->stream, num_classes, max_detections, (const u64*)sel_keys,
-                       (const float4*)sel_boxes, (const int*)sel_count, boxes, scores, labels);
-    RTN_CHECK_LAUNCH(h, "merge_topk_kernel");
+    if (nms) {
+        int mask_blocks = 1024 / BK;                 // workgroups per (image, class): ~4 per CU in total
+        mask_blocks = mask_blocks < 1 ? 1 : (mask_blocks > 512 ? 512 : mask_blocks);
+        hipLaunchKernelGGL(nms_mask_kernel, dim3(mask_blocks, BK), dim3(MASK_T), 0, h->stream, (const float4*)sorted_boxes,
+                           (const int*)meta, nms_threshold, mask);
+        RTN_CHECK_LAUNCH(h, "nms_mask_kernel");
+        hipLaunchKernelGGL(nms_kernel, dim3(BK), dim3(NMS_T), 0, h->stream, d, L, regression, (const u64*)keys,
+                           (const int*)counts, (float)canvas_w, (float)canvas_h, nms_threshold, max_detections, sel_keys, sel_boxes,
+                           sel_count, boxes_explicit, N, (const u64*)sorted_keys, (const float4*)sorted_boxes, (const u64*)mask,
+                           (const int*)meta);
+        RTN_CHECK_LAUNCH(h, "nms_kernel");
+    }
+    if (flags == 0 && !indices) {
+        hipLaunchKernelGGL(merge_topk_kernel, dim3(B), dim3(NMS_T), 0, h->stream, num_classes, max_detections, (const u64*)sel_keys,
+                           (const float4*)sel_boxes, (const int*)sel_count, boxes, scores, labels);
+        RTN_CHECK_LAUNCH(h, "merge_topk_kernel");
+    } else {
+        // nms=False: the top min(count, max_det) <= 300 < CAP keys of a list are the head of nms_sort_kernel's first batch
+        hipLaunchKernelGGL(merge_topk_ex_kernel, dim3(B), dim3(NMS_T), 0, h->stream, L, max_detections,
+                           (const u64*)(nms ? sel_keys : sorted_keys), (const float4*)(nms ? sel_boxes : sorted_boxes),
+                           (long long)(nms ? max_detections : CAP), (const int*)(nms ? sel_count : meta), nms ? 1 : 4,
+                           agn ? classification : nullptr, N, num_classes, boxes, scores, labels, indices);
+        RTN_CHECK_LAUNCH(h, "merge_topk_ex_kernel");
+    }
     return RTN_OK;
 }
 
 static int detect_check(rtn_handle_t h, int B, int num_classes, float score_threshold, int max_detections, const void* a, const void* b,
-                        const void* boxes, const void* scores, const void* labels, const void* workspace) {
-    if (B < 1 || num_classes < 1 || (long long)B * num_classes > 65535) return rtn_fail(h, RTN_EINVAL, "detect: B %d classes %d", B, num_classes);
+                        const void* boxes, const void* scores, const void* labels, const void* workspace, int flags = 0) {
+    if (flags & ~(DET_AGN | DET_NO_NMS)) return rtn_fail(h, RTN_EINVAL, "detect: unknown flags 0x%x", flags);
+    const int L = (flags & DET_AGN) ? 1 : num_classes;           // class-agnostic: one list per image, no cross-class merge
+    if (B < 1 || num_classes < 1 || (long long)B * L > 65535) return rtn_fail(h, RTN_EINVAL, "detect: B %d classes %d", B, num_classes);
     if (max_detections < 1 || max_detections > RTN_MAX_DET) return rtn_fail(h, RTN_EINVAL, "detect: max_detections %d not in [1,%d]", max_detections, RTN_MAX_DET);
-    if ((long long)num_classes * max_detections > MCAP) return rtn_fail(h, RTN_EINVAL, "detect: classes*max_detections > %d", MCAP);
+    if ((long long)L * max_detections > MCAP) return rtn_fail(h, RTN_EINVAL, "detect: classes*max_detections > %d", MCAP);
     if (!(score_threshold >= 0.f)) return rtn_fail(h, RTN_EINVAL, "detect: score_threshold must be >= 0");
     if (!a || !b || !boxes || !scores || !labels || !workspace) return rtn_fail(h, RTN_EINVAL, "detect: null pointer");
     if (((uintptr_t)a & 15) || ((uintptr_t)boxes & 15) || ((uintptr_t)workspace & 255))
@@ -731,32 +886,67 @@ static int detect_check(rtn_handle_t h, int B, int num_classes, float score_thre
     return RTN_OK;
 }
 
-extern "C" int rtn_decode_filter_nms(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes, const float* regression,
-                                     const float* classification, int canvas_h, int canvas_w, float score_threshold,
-                                     float nms_threshold, int max_detections, float* boxes, float* scores, int32_t* labels,
-                                     void* workspace, size_t workspace_bytes) {
+extern "C" int rtn_decode_filter_nms_ex(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes, const float* regression,
+                                        const float* classification, int canvas_h, int canvas_w, float score_threshold,
+                                        float nms_threshold, int max_detections, float* boxes, float* scores, int32_t* labels,
+                                        void* workspace, size_t workspace_bytes, int flags, int32_t* indices) {
     if (!h) return RTN_EINVAL;
-    int rc = detect_check(h, B, num_classes, score_threshold, max_detections, regression, classification, boxes, scores, labels, workspace);
+    int rc = detect_check(h, B, num_classes, score_threshold, max_detections, regression, classification, boxes, scores, labels, workspace,
+                          flags);
     if (rc) return rc;
     DevAnchorCfg d;
     rc = make_dev_cfg(h, cfg, &d);
     if (rc) return rc;
     return detect_launch(h, d, d.total, B, num_classes, regression, nullptr, classification, canvas_h, canvas_w, score_threshold,
-                         nms_threshold, max_detections, boxes, scores, labels, workspace, workspace_bytes);
+                         nms_threshold, max_detections, boxes, scores, labels, workspace, workspace_bytes, flags, indices);
+}
+
+extern "C" int rtn_decode_filter_nms(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes, const float* regression,
+                                     const float* classification, int canvas_h, int canvas_w, float score_threshold,
+                                     float nms_threshold, int max_detections, float* boxes, float* scores, int32_t* labels,
+                                     void* workspace, size_t workspace_bytes) {
+    return rtn_decode_filter_nms_ex(h, cfg, B, num_classes, regression, classification, canvas_h, canvas_w, score_threshold,
+                                    nms_threshold, max_detections, boxes, scores, labels, workspace, workspace_bytes, 0, nullptr);
 }
 
 /* FilterDetections on explicit boxes (model/layers.py:177-264, 267-332) */
-extern "C" int rtn_filter_detections(rtn_handle_t h, int B, int64_t N, int num_classes, const float* in_boxes, const float* classification,
-                                     float score_threshold, float nms_threshold, int max_detections, float* boxes, float* scores,
-                                     int32_t* labels, void* workspace, size_t workspace_bytes) {
+extern "C" int rtn_filter_detections_ex(rtn_handle_t h, int B, int64_t N, int num_classes, const float* in_boxes, const float* classification,
+                                        float score_threshold, float nms_threshold, int max_detections, float* boxes, float* scores,
+                                        int32_t* labels, void* workspace, size_t workspace_bytes, int flags, int32_t* indices) {
     if (!h) return RTN_EINVAL;
     if (N < 1 || N > (1 << 30)) return rtn_fail(h, RTN_EINVAL, "filter_detections: N");
-    const int rc = detect_check(h, B, num_classes, score_threshold, max_detections, in_boxes, classification, boxes, scores, labels, workspace);
+    const int rc = detect_check(h, B, num_classes, score_threshold, max_detections, in_boxes, classification, boxes, scores, labels,
+                                workspace, flags);
     if (rc) return rc;
     DevAnchorCfg d;
     memset(&d, 0, sizeof(d));
     return detect_launch(h, d, (int)N, B, num_classes, nullptr, (const float4*)in_boxes, classification, 0, 0, score_threshold,
-                         nms_threshold, max_detections, boxes, scores, labels, workspace, workspace_bytes);
+                         nms_threshold, max_detections, boxes, scores, labels, workspace, workspace_bytes, flags, indices);
+}
+
+extern "C" int rtn_filter_detections(rtn_handle_t h, int B, int64_t N, int num_classes, const float* in_boxes, const float* classification,
+                                     float score_threshold, float nms_threshold, int max_detections, float* boxes, float* scores,
+                                     int32_t* labels, void* workspace, size_t workspace_bytes) {
+    return rtn_filter_detections_ex(h, B, N, num_classes, in_boxes, classification, score_threshold, nms_threshold, max_detections,
+                                    boxes, scores, labels, workspace, workspace_bytes, 0, nullptr);
+}
+
+extern "C" int rtn_gather_detections(rtn_handle_t h, int B, int64_t N, int max_detections, int64_t row_elems, int dtype, const void* src,
+                                     const int32_t* indices, void* dst) {
+    if (!h) return RTN_EINVAL;
+    if (B < 1 || N < 1 || row_elems < 1 || max_detections < 1 || max_detections > RTN_MAX_DET)
+        return rtn_fail(h, RTN_EINVAL, "gather_detections: B %d N %lld max_detections %d row_elems %lld", B, (long long)N,
+                        max_detections, (long long)row_elems);
+    if (dtype != RTN_F32 && dtype != RTN_I32) return rtn_fail(h, RTN_EINVAL, "gather_detections: dtype %d (float32 or int32)", dtype);
+    if (!src || !indices || !dst) return rtn_fail(h, RTN_EINVAL, "gather_detections: null pointer");
+    const long long total = (long long)B * max_detections * row_elems;
+    const unsigned pad = dtype == RTN_F32 ? 0xBF800000u : 0xFFFFFFFFu;      // -1.0f / -1
+    long long g = (total + 255) / 256;
+    if (g > 4096) g = 4096;
+    hipLaunchKernelGGL(gather_detections_kernel, dim3((unsigned)g), dim3(256), 0, h->stream, (long long)N, max_detections,
+                       (long long)row_elems, total, (const unsigned*)src, (const int*)indices, pad, (unsigned*)dst);
+    RTN_CHECK_LAUNCH(h, "gather_detections_kernel");
+    return RTN_OK;
 }
 
 namespace {

@@ -44,6 +44,11 @@ class AnchorParams:
         return len(self.ratios) * len(self.scales)
 
 
+def detect_flags(nms=True, class_specific_filter=True):
+    """FilterDetections' switches (model/layers.py:200-264) -> the flags of rtn_decode_filter_nms_ex (0: the reference's pair)."""
+    return (0 if nms else L.RTN_DET_NO_NMS) | (0 if class_specific_filter else L.RTN_DET_CLASS_AGNOSTIC)
+
+
 def make_anchor_cfg(image_hw, params=None, levels=(3, 4, 5, 6, 7)):
     """rtn_anchor_cfg_t for a canvas: guess_shapes (model/anchors.py:155-165) + base anchors."""
     params = params or AnchorParams()
@@ -873,9 +878,10 @@ class Engine:
                 totals[i] += evs[i].elapsed_time(evs[i + 1])
         return [(op[0], totals[i]) for i, op in enumerate(ops)] + [("detect", totals[-1])]
 
-    def detect(self, images, score_threshold=0.05, nms_threshold=0.5, max_detections=300):
+    def detect(self, images, score_threshold=0.05, nms_threshold=0.5, max_detections=300, nms=True, class_specific_filter=True):
         """Inference model outputs [boxes (B,300,4), scores (B,300), labels (B,300)] (model/defineModel.py:310-315).
         Views of the plan's output buffers: overwritten by the next call with the same (B,H,W) - clone to keep them.
+        nms / class_specific_filter: FilterDetections' two switches (model/layers.py:200-264); the defaults are the reference's.
 
         in_flight > 1 (throughput mode; default 1): the call enqueues this batch on the next of `in_flight` buffer sets and returns at
         once; batches of consecutive calls then overlap on the device (separate HIP streams, one per buffer set: stage-4/5 layers
@@ -886,8 +892,9 @@ class Engine:
         md = int(max_detections)
         if not 1 <= md <= L.RTN_MAX_DET:
             raise ValueError("max_detections must be in [1, %d]" % L.RTN_MAX_DET)
+        flags = detect_flags(nms, class_specific_filter)
         if self.in_flight > 1 and not self.training:
-            return self._detect_in_flight(images, score_threshold, nms_threshold, md)
+            return self._detect_in_flight(images, score_threshold, nms_threshold, md, flags)
         reg, cls = self.forward(images)
         B, H, W, _ = images.shape
         plan = self._plan(B, H, W)
@@ -895,10 +902,10 @@ class Engine:
         boxes = plan["boxes"].view(-1)[:B * md * 4].view(B, md, 4)
         scores = plan["scores"].view(-1)[:B * md].view(B, md)
         labels = plan["labels"].view(-1)[:B * md].view(B, md)
-        self.postprocess(plan["cfg"], reg, cls, H, W, boxes, scores, labels, plan["det_ws"], score_threshold, nms_threshold, md)
+        self.postprocess(plan["cfg"], reg, cls, H, W, boxes, scores, labels, plan["det_ws"], score_threshold, nms_threshold, md, flags)
         return boxes, scores, labels
 
-    def _detect_in_flight(self, images, score_threshold, nms_threshold, md):
+    def _detect_in_flight(self, images, score_threshold, nms_threshold, md, flags=0):
         if images.device.type != "cuda" or images.dim() != 4 or images.shape[3] != 3:
             raise ValueError("images must be a (B,H,W,3) tensor on the GPU")
         if images.dtype not in _SRC_DT:
@@ -957,7 +964,7 @@ class Engine:
             scores = plan["scores"].view(-1)[:B * md].view(B, md)
             labels = plan["labels"].view(-1)[:B * md].view(B, md)
             self.postprocess(plan["cfg"], plan["regression"], plan["classification"], H, W, boxes, scores, labels, plan["det_ws"],
-                             score_threshold, nms_threshold, md)
+                             score_threshold, nms_threshold, md, flags)
             slot["done"] = torch.cuda.Event()
             slot["done"].record(st)
             if self.trace_in_flight is not None:
@@ -1013,10 +1020,17 @@ class Engine:
                 cur.wait_event(slot["done"])
 
     def postprocess(self, cfg, regression, classification, H, W, boxes, scores, labels, ws, score_threshold=0.05,
-                    nms_threshold=0.5, max_detections=300):
+                    nms_threshold=0.5, max_detections=300, flags=0):
+        """flags: detect_flags(nms, class_specific_filter); every mode fits the plan's workspace (rtn_detect_workspace_bytes)."""
         self._bind_stream()
         B = regression.shape[0]
-        self.h.check(L.lib.rtn_decode_filter_nms(self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(),
-                                                  classification.data_ptr(), H, W, score_threshold, nms_threshold,
-                                                  max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                                  ws.data_ptr(), ws.numel()))
+        if flags == 0:
+            self.h.check(L.lib.rtn_decode_filter_nms(self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(),
+                                                      classification.data_ptr(), H, W, score_threshold, nms_threshold,
+                                                      max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                                      ws.data_ptr(), ws.numel()))
+        else:
+            self.h.check(L.lib.rtn_decode_filter_nms_ex(self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(),
+                                                         classification.data_ptr(), H, W, score_threshold, nms_threshold,
+                                                         max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), flags, None))

@@ -40,9 +40,10 @@ class Model:
     (outputs [boxes, scores, labels])."""
 
     def __init__(self, backbone, num_classes, num_anchors, name='retinanet', bbox=False, base=None, anchor_params=None,
-                 dtype=None, seed=0):
+                 dtype=None, seed=0, nms=True, class_specific_filter=True):
         self.backbone, self.num_classes, self.num_anchors, self.name = backbone, num_classes, num_anchors, name
         self.bbox, self.base = bbox, base
+        self.nms, self.class_specific_filter = bool(nms), bool(class_specific_filter)   # FilterDetections' switches (bbox=True)
         self.anchor_params = anchor_params
         self.dtype = dtype or os.environ.get("RTN_DTYPE", "bf16")
         self.inputs = ["input_1"]
@@ -106,7 +107,7 @@ class Model:
         x = _rt.dev(x, torch.float32) if not (isinstance(x, np.ndarray) and x.dtype == np.uint8) else _rt.dev(x, torch.uint8)
         eng = self.engine()
         if self.bbox:
-            b, s, l = eng.detect(x)
+            b, s, l = eng.detect(x, nms=self.nms, class_specific_filter=self.class_specific_filter)
             return [_rt.host(b).copy(), _rt.host(s).copy(), _rt.host(l).copy()]
         r, c = eng.forward(x)
         return [_rt.host(r).copy(), _rt.host(c).copy()]
@@ -127,6 +128,7 @@ class Model:
         n = len(generator) if (steps is None and hasattr(generator, "__len__")) else steps
         it = (generator[i] for i in range(n)) if hasattr(generator, "__getitem__") and n is not None else iter(generator)
         outs, pending = ([], [], []), deque()
+        modes = {"nms": self.nms, "class_specific_filter": self.class_specific_filter}
 
         def fetch():
             slot, views = pending.popleft()
@@ -143,14 +145,14 @@ class Model:
                 x = item[0] if isinstance(item, (tuple, list)) else item
                 x = _rt.dev(x, torch.float32) if not (isinstance(x, np.ndarray) and x.dtype == np.uint8) else _rt.dev(x, torch.uint8)
                 if eng.in_flight == 1:
-                    views = eng.detect(x)
+                    views = eng.detect(x, **modes)
                     torch.cuda.current_stream().synchronize()
                     for o, v in zip(outs, views):
                         o.append(_rt.host(v).copy())
                     continue
                 if len(pending) == eng.in_flight:            # its buffer set is the one the next call rewrites
                     fetch()
-                views = eng.detect(x)
+                views = eng.detect(x, **modes)
                 pending.append((eng.last_slot, views))
             while pending:
                 fetch()
@@ -332,18 +334,22 @@ def retinanet(inputs, backbone_layers, num_classes, num_anchors=None, create_pyr
     return Model(backbone, num_classes, num_anchors, name=name)
 
 
-def retinanet_bbox(model=None, applyNms=True, class_specific_filter=True, name='retinanet-bbox', anchor_params=None, **kwargs):
+def retinanet_bbox(model=None, applyNms=None, class_specific_filter=True, name='retinanet-bbox', anchor_params=None, nms=None,
+                   **kwargs):
     """ model/defineModel.py:296-353: appends Anchors -> RegressBoxes -> ClipBoxes -> FilterDetections; outputs
-    [boxes, scores, labels]."""
+    [boxes, scores, labels].  applyNms (default True) and class_specific_filter are FilterDetections' two switches
+    (model/layers.py:200-264); `nms` is keras-retinanet's spelling of applyNms and may be given instead of it."""
+    if applyNms is not None and nms is not None and bool(applyNms) != bool(nms):
+        raise ValueError("retinanet_bbox: applyNms=%r and nms=%r disagree" % (applyNms, nms))
+    apply_nms = applyNms if applyNms is not None else (nms if nms is not None else True)
     if anchor_params is None:
         anchor_params = AnchorParameters_default
     if model is None:
         model = retinanet(num_anchors=anchor_params.num_anchors(), **kwargs)
     else:
         utils.assert_training_model(model)
-    if not applyNms or not class_specific_filter:
-        raise NotImplementedError("only applyNms=True, class_specific_filter=True (the reference's use) runs on the device")
-    return Model(model.backbone, model.num_classes, model.num_anchors, name=name, bbox=True, base=model, anchor_params=anchor_params)
+    return Model(model.backbone, model.num_classes, model.num_anchors, name=name, bbox=True, base=model, anchor_params=anchor_params,
+                 nms=apply_nms, class_specific_filter=class_specific_filter)
 
 
 def resnet_retinanet(num_classes, backbone='resnet50', inputs=None, modifier=None, **kwargs):

@@ -137,29 +137,50 @@ class ClipBoxes(_Layer):
         return input_shape[1]
 
 
-def _filter_batch(boxes, classification, score_threshold, max_detections, nms_threshold):
+_OTHER_DT = {torch.float32: L.RTN_F32, torch.int32: L.RTN_I32}
+
+
+def _filter_batch(boxes, classification, score_threshold, max_detections, nms_threshold, nms=True, class_specific_filter=True,
+                  other=()):
+    """[boxes, scores, labels] + the rows of every `other` (B, N, ...) array at the kept detections, padded with -1."""
     h = _rt.handle()
+    other = [o if isinstance(o, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(o)) for o in other]
+    for o in other:
+        if o.dtype not in _OTHER_DT:
+            raise TypeError("filter_detections: `other` tensors must be float32 or int32, not %s" % o.dtype)
+        if o.dim() < 2 or tuple(o.shape[:2]) != tuple(np.shape(classification)[:2]):
+            raise ValueError("filter_detections: `other` tensor of shape %s, expected (%d, %d, ...)"
+                             % (tuple(o.shape), *np.shape(classification)[:2]))
     b, c = _rt.dev(boxes, torch.float32), _rt.dev(classification, torch.float32)
     B, N, K = c.shape
-    wsb = L.lib.rtn_detect_workspace_bytes(B, N, K)
+    flags = _rt.engine.detect_flags(nms, class_specific_filter)
+    wsb = L.lib.rtn_detect_workspace_bytes_ex(B, N, K, flags)
     ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
     ob = torch.empty(B, max_detections, 4, dtype=torch.float32, device="cuda")
     os_ = torch.empty(B, max_detections, dtype=torch.float32, device="cuda")
     ol = torch.empty(B, max_detections, dtype=torch.int32, device="cuda")
-    h.check(L.lib.rtn_filter_detections(h.raw, B, N, K, b.data_ptr(), c.data_ptr(), score_threshold, nms_threshold, max_detections,
-                                        ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), ws.data_ptr(), wsb))
-    return _rt.host(ob), _rt.host(os_), _rt.host(ol)
+    idx = torch.empty(B, max_detections, dtype=torch.int32, device="cuda") if other else None
+    h.check(L.lib.rtn_filter_detections_ex(h.raw, B, N, K, b.data_ptr(), c.data_ptr(), score_threshold, nms_threshold, max_detections,
+                                           ob.data_ptr(), os_.data_ptr(), ol.data_ptr(), ws.data_ptr(), wsb, flags,
+                                           idx.data_ptr() if idx is not None else None))
+    outs = [ob, os_, ol]
+    for o in other:
+        src = o.to(device="cuda").contiguous()
+        dst = torch.empty((B, max_detections) + tuple(o.shape[2:]), dtype=o.dtype, device="cuda")
+        h.check(L.lib.rtn_gather_detections(h.raw, B, N, max_detections, int(np.prod(o.shape[2:], dtype=np.int64)), _OTHER_DT[o.dtype],
+                                            src.data_ptr(), idx.data_ptr(), dst.data_ptr()))
+        outs.append(dst)
+    return [_rt.host(t) for t in outs]
 
 
 def filter_detections(boxes, classification, other=None, class_specific_filter=True, nms=True, score_threshold=0.05,
                       max_detections=300, nms_threshold=0.5):
-    """ model/layers.py:177-264 for one image: (num_boxes,4), (num_boxes,num_classes) -> [boxes, scores, labels] padded with -1."""
-    if other:
-        raise NotImplementedError("`other` tensors are not carried through the device NMS")
-    if not class_specific_filter or not nms:
-        raise NotImplementedError("only the reference's configuration (class_specific_filter=True, nms=True) runs on the device")
-    b, s, l = _filter_batch(np.asarray(boxes)[None], np.asarray(classification)[None], score_threshold, max_detections, nms_threshold)
-    return [b[0], s[0], l[0]]
+    """ model/layers.py:177-264 for one image: (num_boxes,4), (num_boxes,num_classes), other [(num_boxes,...) float32 / int32]
+    -> [boxes, scores, labels, other[0], ...] padded with -1."""
+    other = [(o if isinstance(o, torch.Tensor) else np.asarray(o))[None] for o in (other or [])]
+    outs = _filter_batch(np.asarray(boxes)[None], np.asarray(classification)[None], score_threshold, max_detections, nms_threshold,
+                         nms=nms, class_specific_filter=class_specific_filter, other=other)
+    return [o[0] for o in outs]
 
 
 class FilterDetections(_Layer):
@@ -176,14 +197,15 @@ class FilterDetections(_Layer):
         super(FilterDetections, self).__init__(**kwargs)
 
     def call(self, inputs, **kwargs):
-        boxes, classification = inputs[0], inputs[1]
-        if len(inputs) > 2 or not self.nms or not self.class_specific_filter:
-            raise NotImplementedError("only [boxes, classification] with nms=True, class_specific_filter=True runs on the device")
-        return list(_filter_batch(boxes, classification, self.score_threshold, self.max_detections, self.nms_threshold))
+        """ inputs: [boxes, classification, other[0], other[1], ...] -> [boxes, scores, labels, other[0], ...]."""
+        boxes, classification, other = inputs[0], inputs[1], inputs[2:]
+        return _filter_batch(boxes, classification, self.score_threshold, self.max_detections, self.nms_threshold, nms=self.nms,
+                             class_specific_filter=self.class_specific_filter, other=other)
 
     def compute_output_shape(self, input_shape):
         return [(input_shape[0][0], self.max_detections, 4), (input_shape[1][0], self.max_detections),
-                (input_shape[1][0], self.max_detections)]
+                (input_shape[1][0], self.max_detections)] + \
+            [tuple([input_shape[i][0], self.max_detections] + list(input_shape[i][2:])) for i in range(2, len(input_shape))]
 
     def compute_mask(self, inputs, mask=None):
         return (len(inputs) + 1) * [None]

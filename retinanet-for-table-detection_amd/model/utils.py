@@ -90,9 +90,11 @@ def compute_overlap(boxes1, boxes2):
 
 
 def convert_model(model, nms=True, class_specific_filter=True, anchor_params=None):
-    """ model/utils.py:218-231: training model -> inference model."""
+    """ model/utils.py:218-231: training model -> inference model.  Unlike the reference, `nms` takes effect: the reference
+    passes it as retinanet_bbox(nms=...), which has no such parameter and drops it into **kwargs, so its
+    converted models always run NMS.  Here it is retinanet_bbox's applyNms."""
     from .defineModel import retinanet_bbox
-    return retinanet_bbox(model=model, nms=nms, class_specific_filter=class_specific_filter, anchor_params=anchor_params)
+    return retinanet_bbox(model=model, applyNms=nms, class_specific_filter=class_specific_filter, anchor_params=anchor_params)
 
 
 def assert_training_model(model):
