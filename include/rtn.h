@@ -489,6 +489,35 @@ int rtn_decode_filter_nms_ex(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B,
                              float* boxes, float* scores, int32_t* labels,
                              void* workspace, size_t workspace_bytes, int flags, int32_t* indices);
 
+/* ---- detection evaluation (model/eval.py: split_detections -> evaluate_detections -> compute_ap) ---------------------------------
+ * Two stages, both enqueued on the handle's stream, neither reading anything back; no float atomics (bit-reproducible).
+ * rtn_eval_match (once per batch, one workgroup per image) takes what rtn_decode_filter_nms writes:
+ *   boxes f32 [B][D][4] at network scale, scores f32 [B][D], labels i32 [B][D] (score-descending, padded with -1), D <= RTN_MAX_DET;
+ *   scales f64 [B] (each image's resize scale); annotations in ORIGINAL coordinates in the rtn_anchor_targets layout with
+ *   gt_stride (<= RTN_MAX_GT) annotations per image: gt_boxes f64 [B][gt_stride][4], gt_labels i32 [B][gt_stride], gt_count i32 [B].
+ *   A row is kept when (double)score > score_threshold (>= 0), the first max_detections kept rows in row order; its box becomes
+ *   (double)box / scale.  Per class the kept rows are sorted stably by descending score, matched against the image's annotations
+ *   of that class (IoU as rtn_compute_overlap, first-index argmax over all of them, taken or not) and walked greedily once per
+ *   threshold: a hit is iou >= (float)threshold on a not yet taken annotation.  iou_thresholds: host f64 [T], 1 <= T <= 16, each in
+ *   (0, 1].  Kept detection k of batch image b goes to slots[b][k] = {f32 score bits, T-bit hit mask | class << 16}; the other
+ *   slots of the image get {0, 0xFFFFFFFF}.  slots: device u32 [B][max_detections][2], i.e. the batch's first image's slot row
+ *   of the evaluation's [images][max_detections][2] array.  counts: device i32 [2][K], zeroed by the caller before the first batch:
+ *   counts[0][c] += annotations of class c, counts[1][c] += kept detections of class c (integer atomics).
+ * rtn_eval_finalize (once per evaluation) over slots [num_images][max_detections][2] and counts: per class c and threshold t,
+ *   result f64 [K][T][8] = {AP, n_ann, TP, FP, FN, P, R, F1}.  AP is compute_ap of the class's detections in the order
+ *   np.argsort(-score, kind="stable") of the slot order (a stable LSD radix sort); AP = 0 for a class without annotations.
+ *   TP/FP/FN/P/R/F1 count the detections with (float)score >= (float)f1_score_threshold: P = TP / (TP + FP), R = TP / n_ann,
+ *   F1 = 2PR / (P + R), each 0 when its denominator is 0.  workspace: rtn_eval_workspace_bytes(num_images * max_detections, K, T)
+ *   (0 = unsupported shape: K in [1, 65535], T in [1, 16], at most 2^28 slots). */
+size_t rtn_eval_workspace_bytes(int64_t num_slots, int num_classes, int num_thresholds);
+int rtn_eval_match(rtn_handle_t h, int B, int D, const float* boxes, const float* scores, const int32_t* labels, const double* scales,
+                   const double* gt_boxes, const int32_t* gt_labels, const int32_t* gt_count, int gt_stride, int num_classes,
+                   int num_thresholds, const double* iou_thresholds /* host */, double score_threshold, int max_detections,
+                   uint32_t* slots, int32_t* counts);
+int rtn_eval_finalize(rtn_handle_t h, int64_t num_images, int max_detections, const uint32_t* slots, const int32_t* counts,
+                      int num_classes, int num_thresholds, double f1_score_threshold, double* result, void* workspace,
+                      size_t workspace_bytes);
+
 /* ---- page preprocessing -------------------------------------------------------------------------------
  * rtn_preprocess_dt3: DetectTablesUtils.preProcessSampleImages (DetectTablesUtils.py:251-261) for B equally sized pages:
  *   src uint8 [B][H][W][channels] (3 = BGR as cv2.imread gives, 1 = gray) -> dst uint8 [B][H][W][3] in OpenCV channel order

@@ -176,6 +176,9 @@ SIGNATURES = {
     "rtn_decode_filter_nms_ex": (_I, [_P, C.POINTER(AnchorCfg), _I, _I, _P, _P, _I, _I, _F, _F, _I, _P, _P, _P, _P, _SZ, _I, _P]),
     "rtn_filter_detections_ex": (_I, [_P, _I, _I64, _I, _P, _P, _F, _F, _I, _P, _P, _P, _P, _SZ, _I, _P]),
     "rtn_gather_detections": (_I, [_P, _I, _I64, _I, _I64, _I, _P, _P, _P]),
+    "rtn_eval_workspace_bytes": (_SZ, [_I64, _I, _I]),
+    "rtn_eval_match": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_D), _D, _I, _P, _P]),
+    "rtn_eval_finalize": (_I, [_P, _I64, _I, _P, _P, _I, _I, _D, _P, _P, _SZ]),
 }
 
 

@@ -12,6 +12,7 @@
 // FP contraction is OFF in this file: the reference rounds every product and sum.
 #include "rtn_internal.h"
 #include "rtn_anchor_dev.h"
+#include "rtn_iou_dev.h"
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -215,14 +216,7 @@ __global__ __launch_bounds__(256) void compute_overlap_kernel(const double* __re
     const long long total = (long long)N * G;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int n = (int)(i / G), g = (int)(i - (long long)n * G);
-        const double* a = boxes + 4ll * n;
-        const double* b = gts + 4ll * g;
-        const double area1 = (a[2] - a[0]) * (a[3] - a[1]);
-        const double area2 = (b[2] - b[0]) * (b[3] - b[1]);
-        const double w = fmax(0.0, fmin(a[2], b[2]) - fmax(a[0], b[0]));
-        const double hh = fmax(0.0, fmin(a[3], b[3]) - fmax(a[1], b[1]));
-        const double inter = w * hh;
-        out[i] = (float)(inter / (area1 + area2 - inter));
+        out[i] = rtn_iou_f64(boxes + 4ll * n, gts + 4ll * g);
     }
 }
 

@@ -1012,6 +1012,11 @@ class Engine:
         if 0 <= si < len(self._slots) and self._slots[si]["done"] is not None:
             self._slots[si]["done"].synchronize()
 
+    def slot_stream(self, si):
+        """The HIP stream buffer set `si` runs its batches on (in_flight > 1): work enqueued there after detect() sees that batch's
+        outputs, and the set's next batch is ordered after it (model/eval.py DeviceEvaluator.add)."""
+        return self._slots[si]["stream"]
+
     def join(self):
         """The caller's current stream waits for every batch detect() has in flight (in_flight > 1)."""
         cur = torch.cuda.current_stream(self.device)

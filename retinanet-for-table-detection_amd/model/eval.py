@@ -9,12 +9,18 @@ derives from:
   recall = cumTP / #annotations, precision = cumTP / (cumTP + cumFP); AP = area under the monotone precision envelope
   evaluated at every recall change (all-point interpolation).
 IoU comes from the device (`rtn_compute_overlap`, the float32 IoU of model/utils.py:180-211): no GPU, no evaluator.
+
+DeviceEvaluator / evaluate_generator run the same evaluation on the device (csrc/rtn_eval.hip) at up to 16 IoU thresholds at once,
+with P/R/F1 at a score threshold, without a host sync per batch: callbacks.Evaluate uses them as a training metric.
 """
 import csv
+import ctypes as C
 
 import numpy as np
+import torch
 
-from .utils import compute_overlap
+from . import _rt
+from .utils import compute_overlap, compute_resize_scale
 
 
 def compute_ap(recall, precision):
@@ -122,3 +128,218 @@ def evaluate(model, images, annotations, scales=None, num_classes=1, iou_thresho
         ann = np.asarray(annotations[i], np.float64).reshape(-1, 5)
         all_anns.append([ann[ann[:, 4] == c, :4] for c in range(num_classes)])
     return evaluate_detections(all_dets, all_anns, num_classes, iou_threshold)
+
+
+COCO_IOU_THRESHOLDS = tuple(round(0.5 + 0.05 * i, 2) for i in range(10))     # 0.50:0.05:0.95
+
+
+def _micro_f1(tp, fp, fn):
+    p = tp / (tp + fp) if tp + fp > 0 else 0.0
+    r = tp / (tp + fn) if tp + fn > 0 else 0.0
+    return 2.0 * p * r / (p + r) if p + r > 0 else 0.0
+
+
+def summarize(iou_thresholds, average_precision, f1):
+    """The result dict of DeviceEvaluator.result() (tests/eval_multi_ref.py builds the same one from its NumPy restatement):
+      average_precision[t][c] = (AP, n_ann)                      evaluate_detections' {class: (AP, n_ann)} at IoU threshold t
+      f1[t][c] = (TP, FP, FN, P, R, F1)                          at the score threshold f1_score_threshold
+      mean_ap[t]                                                 mean_ap(average_precision[t]): classes with annotations
+      mAP                                                        mean of mean_ap over the requested thresholds
+      map_50_95                                                  the same over 0.50:0.05:0.95 when all ten were requested, else None
+      f1_micro[t]                                                F1 of TP, FP, FN summed over the classes
+      weighted_f1                                                sum_t t * f1_micro[t] / sum_t t (the IoU-weighted F1 of ICDAR cTDaR)"""
+    ts = [float(t) for t in iou_thresholds]
+    mean = {t: mean_ap(average_precision[t]) for t in ts}
+    micro = {}
+    for t in ts:
+        tp, fp, fn = (sum(v[i] for v in f1[t].values()) for i in range(3))
+        micro[t] = _micro_f1(tp, fp, fn)
+    coco = all(any(abs(t - c) < 1e-9 for t in ts) for c in COCO_IOU_THRESHOLDS)
+    return {"iou_thresholds": tuple(ts), "average_precision": average_precision, "f1": f1, "mean_ap": mean,
+            "mAP": float(sum(mean.values()) / len(ts)),
+            "map_50_95": float(np.mean([mean[t] for t in ts if any(abs(t - c) < 1e-9 for c in COCO_IOU_THRESHOLDS)])) if coco else None,
+            "f1_micro": micro, "weighted_f1": float(sum(t * micro[t] for t in ts) / sum(ts))}
+
+
+class DeviceEvaluator:
+    """evaluate_detections (+ split_detections) on the device, for up to 16 IoU thresholds at once (csrc/rtn_eval.hip).
+
+    add() takes one batch exactly as Engine.detect returns it - boxes (B,D,4) at network scale, scores (B,D), labels (B,D), device
+    tensors (NumPy arrays are uploaded) - with each image's resize scale and its annotations in ORIGINAL coordinates ((m,5) arrays
+    [x1,y1,x2,y2,label], or {'bboxes', 'labels'} dicts as Generator.load_annotations returns them).  It enqueues the match on
+    `stream` (default: the current stream) - the stream that produced the detections - and returns without a host sync.
+    result() runs the finalize kernels on the current stream and makes one small device-to-host copy: see summarize()."""
+
+    def __init__(self, num_classes, iou_thresholds=(0.5,), score_threshold=0.05, max_detections=300, f1_score_threshold=0.5,
+                 device=None):
+        self.K = int(num_classes)
+        self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
+        self.T = len(self.iou_thresholds)
+        if not 1 <= self.T <= 16:
+            raise ValueError("1 to 16 IoU thresholds, got %d" % self.T)
+        if not all(0.0 < t <= 1.0 for t in self.iou_thresholds):
+            raise ValueError("IoU thresholds must be in (0, 1], got %s" % (self.iou_thresholds,))
+        if not (score_threshold >= 0.0):
+            raise ValueError("score_threshold must be >= 0 (the device sort orders the score bits), got %r" % score_threshold)
+        if not 1 <= int(max_detections) <= _rt.L.RTN_MAX_DET:
+            raise ValueError("max_detections must be in [1, %d]" % _rt.L.RTN_MAX_DET)
+        if not 1 <= self.K <= 65535:
+            raise ValueError("num_classes must be in [1, 65535]")
+        self.score_threshold, self.S, self.f1_score_threshold = float(score_threshold), int(max_detections), float(f1_score_threshold)
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self._h = _rt.L.Handle(self.device.index)
+        self._thr = (C.c_double * self.T)(*self.iou_thresholds)
+        self.counts = torch.zeros(2 * self.K, dtype=torch.int32, device=self.device)
+        self.slots = torch.empty(0, 2, dtype=torch.int32, device=self.device)
+        self.num_images = 0
+        self._events = []               # matches enqueued on streams other than the caller's: result() waits for them
+        self._ws = None
+
+    def _join(self):
+        cur = torch.cuda.current_stream(self.device)
+        for ev in self._events:
+            cur.wait_event(ev)
+        self._events = []
+
+    def reserve(self, num_images):
+        """Room for `num_images` images in all.  The host decides (it knows the image count without asking the device); growing
+        copies the slots written so far on the current stream, after every match enqueued elsewhere."""
+        need = int(num_images) * self.S
+        if need <= self.slots.shape[0]:
+            return
+        self._join()
+        grown = torch.empty(max(need, 2 * self.slots.shape[0]), 2, dtype=torch.int32, device=self.device)
+        if self.num_images:
+            grown[:self.num_images * self.S].copy_(self.slots[:self.num_images * self.S])
+        self.slots = grown
+
+    def _annotations(self, annotations):
+        B = len(annotations)
+        gb = np.zeros((B, _rt.L.RTN_MAX_GT, 4), np.float64)
+        gl = np.zeros((B, _rt.L.RTN_MAX_GT), np.int32)
+        gc = np.zeros((B,), np.int32)
+        for i, a in enumerate(annotations):
+            if isinstance(a, dict):
+                boxes, labels = np.asarray(a["bboxes"], np.float64).reshape(-1, 4), np.asarray(a["labels"]).reshape(-1)
+            else:
+                a = np.asarray(a, np.float64).reshape(-1, 5)
+                boxes, labels = a[:, :4], a[:, 4]
+            n = boxes.shape[0]
+            if n > _rt.L.RTN_MAX_GT:
+                raise ValueError("at most %d annotations per image are supported, got %d" % (_rt.L.RTN_MAX_GT, n))
+            gb[i, :n], gl[i, :n], gc[i] = boxes, labels.astype(np.int32), n
+        return gb, gl, gc
+
+    def add(self, boxes, scores, labels, scales, annotations, stream=None):
+        B, D = int(scores.shape[0]), int(scores.shape[1])
+        if tuple(boxes.shape) != (B, D, 4) or tuple(labels.shape) != (B, D):
+            raise ValueError("boxes (B,D,4), scores (B,D), labels (B,D) expected, got %s %s %s"
+                             % (tuple(boxes.shape), tuple(scores.shape), tuple(labels.shape)))
+        if len(annotations) != B or len(scales) != B:
+            raise ValueError("one scale and one annotation set per image: %d images, %d scales, %d annotation sets"
+                             % (B, len(scales), len(annotations)))
+        if B == 0:
+            return
+        host = self._annotations(annotations) + (np.asarray(scales, np.float64).reshape(B),)
+        self.reserve(self.num_images + B)
+        caller = torch.cuda.current_stream(self.device)
+        st = stream if stream is not None else caller
+        with torch.cuda.stream(st):
+            gb, gl, gc, sc = [torch.from_numpy(a).pin_memory().to(self.device, non_blocking=True) for a in host]
+            b = _rt.dev(boxes, torch.float32)
+            s = _rt.dev(scores, torch.float32)
+            lab = _rt.dev(labels, torch.int32)
+            self._h.set_stream(st.cuda_stream)
+            first = self.slots[self.num_images * self.S:]
+            self._h.check(_rt.L.lib.rtn_eval_match(self._h.raw, B, D, b.data_ptr(), s.data_ptr(), lab.data_ptr(), sc.data_ptr(),
+                                                   gb.data_ptr(), gl.data_ptr(), gc.data_ptr(), _rt.L.RTN_MAX_GT, self.K, self.T,
+                                                   self._thr, self.score_threshold, self.S, first.data_ptr(), self.counts.data_ptr()))
+            if st != caller:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                self._events.append(ev)
+        self.num_images += B
+
+    def result(self):
+        K, T = self.K, self.T
+        ap = {t: {c: (0.0, 0) for c in range(K)} for t in self.iou_thresholds}
+        f1 = {t: {c: (0, 0, 0, 0.0, 0.0, 0.0) for c in range(K)} for t in self.iou_thresholds}
+        if self.num_images:
+            self._join()
+            nb = int(_rt.L.lib.rtn_eval_workspace_bytes(self.num_images * self.S, K, T))
+            if nb <= 0:
+                raise ValueError("rtn_eval_workspace_bytes: unsupported shape (%d images)" % self.num_images)
+            if self._ws is None or self._ws.numel() < nb:
+                self._ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            out = torch.empty(K * T * 8, dtype=torch.float64, device=self.device)
+            self._h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
+            self._h.check(_rt.L.lib.rtn_eval_finalize(self._h.raw, self.num_images, self.S, self.slots.data_ptr(), self.counts.data_ptr(),
+                                                      K, T, self.f1_score_threshold, out.data_ptr(), self._ws.data_ptr(),
+                                                      self._ws.numel()))
+            r = out.cpu().numpy().reshape(K, T, 8)
+            for ti, t in enumerate(self.iou_thresholds):
+                for c in range(K):
+                    v = r[c, ti]
+                    ap[t][c] = (float(v[0]), int(v[1]))
+                    f1[t][c] = (int(v[2]), int(v[3]), int(v[4]), float(v[5]), float(v[6]), float(v[7]))
+        return summarize(self.iou_thresholds, ap, f1)
+
+    def slot_view(self):
+        """(score f32, hit mask, class) of every slot [image][kept index] (class -1: empty): the match stage's output, for tests."""
+        torch.cuda.synchronize(self.device)
+        self._events = []
+        raw = self.slots[:self.num_images * self.S].cpu().numpy().view(np.uint32).reshape(self.num_images, self.S, 2)
+        empty = raw[..., 1] == 0xFFFFFFFF
+        cls = np.where(empty, -1, (raw[..., 1] >> 16).astype(np.int64))
+        mask = np.where(empty, 0, (raw[..., 1] & 0xFFFF).astype(np.int64))
+        return raw[..., 0].view(np.float32), mask, cls
+
+
+def _generator_batch(generator, group):
+    """The inputs half of Generator.compute_input_output (csv_generator.py:373-398) without augmentation: the pages of `group`
+    resized into one canvas by the generator's own compute_inputs on its stream, their resize scales, and their annotations in
+    original coordinates (load_annotations_group).  Returns (canvas on the current stream's order, scales, annotations)."""
+    images = generator.load_image_group(group)
+    annotations = generator.load_annotations_group(group)
+    with generator._lock, torch.cuda.stream(generator._stream):
+        generator._h.set_stream(generator._stream.cuda_stream)
+        pages = [generator._upload(im) for im in images]
+        scales = [compute_resize_scale(p.shape, generator.image_min_side, generator.image_max_side) for p in pages]
+        canvas, _ = generator.compute_inputs(pages, scales)
+        done = torch.cuda.Event()
+        done.record(generator._stream)
+    cur = torch.cuda.current_stream(generator.device)
+    cur.wait_event(done)
+    canvas.record_stream(cur)
+    return canvas, scales, annotations
+
+
+def evaluate_generator(model, generator, iou_thresholds=(0.5,), score_threshold=0.05, max_detections=300, f1_score_threshold=0.5,
+                       in_flight=2, steps=None):
+    """Evaluate an inference model (retinanet_bbox) on the groups of a CSVGenerator-style generator, all on the device: its pages go
+    through the generator's own load_image_group / compute_inputs (the canvases it builds for training, without augmentation) and
+    Engine.detect with `in_flight` batches at a time, as in Model.predict_generator; each batch's detections are matched on the
+    stream that produced them (DeviceEvaluator.add) and nothing is read back until the one small copy of the result.
+    Returns DeviceEvaluator.result()."""
+    if not getattr(model, "bbox", False):
+        raise ValueError("evaluate_generator: the inference model (retinanet_bbox / convert_model) is needed")
+    eng = model.engine()
+    modes = {"nms": model.nms, "class_specific_filter": model.class_specific_filter}
+    groups = generator.groups if steps is None else generator.groups[:int(steps)]
+    ev = DeviceEvaluator(model.num_classes, iou_thresholds, score_threshold, max_detections, f1_score_threshold,
+                         device=eng.device.index)
+    ev.reserve(sum(len(g) for g in groups))
+    prev = eng.in_flight
+    eng.join()
+    eng.in_flight = max(1, int(in_flight))
+    try:
+        for group in groups:
+            canvas, scales, annotations = _generator_batch(generator, group)
+            x = _rt.dev(canvas, torch.float32)
+            boxes, scores, labels = eng.detect(x, **modes)          # the model's own FilterDetections, as predict_on_batch
+            st = eng.slot_stream(eng.last_slot) if eng.in_flight > 1 and not eng.training else None
+            ev.add(boxes, scores, labels, scales, annotations, stream=st)
+    finally:
+        eng.join()
+        eng.in_flight = prev
+    return ev.result()
