@@ -333,6 +333,25 @@ int rtn_adam_clipnorm_step_segments(rtn_handle_t h, float* w, float* m, float* v
                                     void* w_fwd, int fwd_dtype, int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
                                     const int64_t* seg_begin_dev, int nseg, const double* sumsq_seg_dev, int64_t elem_offset,
                                     float clipnorm, float grad_mul);
+/* The same steps over a SUBSET of the flat vector: the trainable layers of frozen-layer training.  table_dev (int64, on the device)
+ * holds nr rows (begin, end, vbegin): range r is the flat slice [begin, end) (relative to w / m / v / g / gscale / fold / w_fwd) and
+ * occupies [vbegin, vbegin + end - begin) of the launch's index space, `span` long.  Rows are in increasing vbegin order and do not
+ * overlap there; vbegin = begin (mod 4) lets every quad inside a range use 16-byte accesses (rtn_ranges in _lib.py builds such a
+ * table).  Slots outside the ranges are never read or written; indices >= n are skipped.  Empty ranges are allowed; nr = 0 (span 0)
+ * is a no-op (rtn_sumsq_ranges then writes 0).
+ * rtn_sumsq_ranges: out (may be NULL) = sum over the ranges of (g*scale)^2, in a fixed order (the rtn_sumsq workspace); out_each
+ * (may be NULL, nr doubles) = the same sum per range.  rtn_adam_clipnorm_step_ranges clips by the global norm sqrt(sumsq[0]) as
+ * rtn_adam_clipnorm_step; rtn_adam_clipnorm_step_ranges_pertensor by each range's own norm sqrt(sumsq_each[r]) as
+ * rtn_adam_clipnorm_step_segments (one range per tensor).  Fold, gscale and the forward-weight re-emission as above. */
+int rtn_sumsq_ranges(rtn_handle_t h, const float* g, const float* scale, int64_t n, const int64_t* table_dev, int nr, int64_t span,
+                     double* out, double* out_each, void* workspace, size_t workspace_bytes);
+int rtn_adam_clipnorm_step_ranges(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale, const float* fold,
+                                  void* w_fwd, int fwd_dtype, int64_t n, const int64_t* table_dev, int nr, int64_t span, int64_t step,
+                                  float lr, float beta1, float beta2, float eps, const double* sumsq, float clipnorm, float grad_mul);
+int rtn_adam_clipnorm_step_ranges_pertensor(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale,
+                                            const float* fold, void* w_fwd, int fwd_dtype, int64_t n, const int64_t* table_dev, int nr,
+                                            int64_t span, int64_t step, float lr, float beta1, float beta2, float eps,
+                                            const double* sumsq_each, float clipnorm, float grad_mul);
 
 /* ---- stem input packing ------------------------------------------------------------
  * NHWC C=3 image batch -> zero-padded [B][Hp][Wp][4] so that the 7x7/2 stem conv

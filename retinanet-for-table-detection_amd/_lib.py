@@ -140,6 +140,9 @@ SIGNATURES = {
     "rtn_adam_clipnorm_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _F, _F, _F, _F, _P, _F, _F]),
     "rtn_sumsq_segments": (_I, [_P, _P, _P, _P, _I, _P]),
     "rtn_adam_clipnorm_step_segments": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _I64, _F, _F, _F, _F, _P, _I, _P, _I64, _F, _F]),
+    "rtn_sumsq_ranges": (_I, [_P, _P, _P, _I64, _P, _I, _I64, _P, _P, _P, _SZ]),
+    "rtn_adam_clipnorm_step_ranges": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P, _I, _I64, _I64, _F, _F, _F, _F, _P, _F, _F]),
+    "rtn_adam_clipnorm_step_ranges_pertensor": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I64, _P, _I, _I64, _I64, _F, _F, _F, _F, _P, _F, _F]),
     "rtn_stem_pack": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _I]),
     "rtn_stem_conv_pool": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I]),
     "rtn_stem_conv_pool_branch2a": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -260,3 +263,21 @@ def generate_anchors_f64(base_size, ratios, scales):
     if rc != 0:
         raise RtnError(rc, "rtn_generate_anchors")
     return out
+
+
+def ranges_table(ranges, device=None):
+    """[(begin, end)] flat element ranges (in increasing order, non-overlapping) -> (int64 table [nr][3] of (begin, end, vbegin),
+    nr, span) for rtn_sumsq_ranges / rtn_adam_clipnorm_step_ranges*: each range starts in the launch's index space at the next
+    position congruent to its `begin` modulo 4, so every quad inside a range is one 16-byte access.  device=None: a CPU tensor."""
+    rows, v = [], 0
+    for b, e in ranges:
+        b, e = int(b), int(e)
+        if e < b or b < 0:
+            raise ValueError("bad range [%d, %d)" % (b, e))
+        v += (b - v) % 4
+        rows.append((b, e, v))
+        v += e - b
+    t = torch.tensor(rows, dtype=torch.int64).reshape(-1, 3)
+    if device is not None:
+        t = t.to(device)
+    return t, len(rows), v

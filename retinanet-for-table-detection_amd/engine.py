@@ -130,6 +130,9 @@ class Engine:
         self.on_plan_evict = []        # weakref.WeakMethod callbacks key -> None (a Trainer drops its backward plan of the same canvas)
         self.state = None
         self.training = False          # set by trainer.Trainer: the pool then records its argmax taps
+        # set by trainer.Trainer around a training forward whose backward is pruned to the trainable layers: (keep branch2b of the
+        # fused 64-channel blocks, record the pool's taps) - what that backward reads; None = both (the full backward)
+        self.train_keep = None
         self.two_streams = os.environ.get("RTN_TWO_STREAMS", "1") != "0"    # graph forks on side HIP streams (_schedule)
         self.fuse_stem = os.environ.get("RTN_FUSE_STEM", "1") != "0"        # inference/bf16: conv1+ReLU+pool1 in one kernel
         self.fuse_stem_2a = os.environ.get("RTN_FUSE_STEM_2A", "1") != "0"  # ... which also applies res2a_branch2a to the pooled pixels
@@ -630,7 +633,7 @@ class Engine:
         return plan
 
     def _variant(self, plan, key):
-        """{ops, sched, events} that forward() runs under the fusion key (fs, fd, fk, fc, fp) of _fused(): built on first use and
+        """{ops, sched, events} that forward() runs under the fusion key (fs, fd, fk, fc, fp, ft) of _fused(): built on first use and
         kept in the plan.  The all-zero key is the plan's own op list and schedule."""
         rec = plan["variants"].get(key)
         if rec is not None:
@@ -638,7 +641,7 @@ class Engine:
         if not any(key):
             ops, sched = plan["ops"], plan["sched"]
         else:
-            fs, fd, fk, fc, fp = key
+            fs, fd, fk, fc, fp, ft = key
             fu, B = plan["fusion"], plan["xin"]["B"]
             first_blocks, blocks64 = fu["first_blocks"], fu["blocks64"]
             v = list(plan["ops"])
@@ -791,21 +794,28 @@ class Engine:
         return plan["regression"], plan["classification"]
 
     def _fused(self):
-        """Fusion key (fs, fd, fk, fc, fp) of the engine's state, the variant of a plan that forward() runs (_variant): stem fused
+        """Fusion key (fs, fd, fk, fc, fp, ft) of the engine's state, the variant of a plan that forward() runs (_variant): stem fused
         (0 / 1 / 2 = with res2a_branch2a), shortcut folded, 64-channel bottleneck blocks fused (1 / 2 = keeping branch2b's output),
-        stage-3 seams chained, res2b_branch2a appended to res2a's block.  Training keeps
+        stage-3 seams chained, res2b_branch2a appended to res2a's block, the pool's winning taps recorded.  A training forward whose
+        backward never reaches the stem or the 64-channel stage (frozen layers, train_keep) runs those launches in their inference
+        form: fk = 1, ft = 0 - the same bits, fewer stores.  Training keeps
         every bottleneck tensor (the backward reads them) and, in fp32, conv1 / pool1 separate; the folded
         shortcut is used there too - no gradient needs the shortcut TENSOR, only its input and filters.  The fused stem and the fused
         bottleneck exist for bf16 only; the fp8 plan keeps its own branch2a / branch2b pairing."""
         stem16 = self.dtype == "bf16" and (not self.training or self.fuse_stem_train)
+        keep_h1, ft = (self.train_keep or (True, True)) if self.training else (False, False)
         fk = 0
         if self.fuse_bottleneck and self.dtype == "bf16" and not self._fp8_on():
-            fk = 2 if self.training else 1               # training: the fused blocks also store branch2b's output for the backward pass
+            fk = 2 if keep_h1 else 1                     # training: the fused blocks also store branch2b's output for the backward pass
         fs = (2 if self.fuse_stem_2a else 1) if (self.fuse_stem and stem16) else 0
         # (training too: both tensors of a seam are written, which is all the backward pass reads)
         fc = 1 if (self.fuse_chain and self.dtype == "bf16" and not self._fp8_on()) else 0
         fp = 1 if (self.fuse_proj_tail and fk and self.fuse_shortcut) else 0
-        return (fs, self.fuse_shortcut, fk, fc, fp)
+        return (fs, self.fuse_shortcut, fk, fc, fp, int(ft))
+
+    def _taps(self):
+        """The pool (or the fused stem) records its winning taps: a training forward whose backward runs the pool's backward."""
+        return self.training and (self.train_keep is None or bool(self.train_keep[1]))
 
     def active_ops(self, plan):
         """The op list forward() executes."""
@@ -830,13 +840,14 @@ class Engine:
             h.check(lib.rtn_quantize_fp8(h.raw, op[1].data_ptr(), self.rdt, op[2].data_ptr(), op[1].numel(), op[3]))
         elif kind == "stem":
             Bn, Hn, Wn = op[2]
-            if op[7] is not None or self.training:       # + res2a_branch2a on the pooled pixels; training: + the pool's winning taps
+            taps = self._taps()
+            if op[7] is not None or taps:                # + res2a_branch2a on the pooled pixels; training: + the pool's winning taps
                 a_out, w2a, b2a = op[7] if op[7] is not None else (None, None, None)
                 h.check(lib.rtn_stem_conv_pool_branch2a(h.raw, op[5].data_ptr(), op[6][0], op[6][1], op[3].data_ptr(), op[3].shape[0],
                                                         op[4].data_ptr(), op[1].data_ptr(), Bn, Hn, Wn,
                                                         w2a.data_ptr() if w2a is not None else None, b2a.data_ptr() if b2a is not None else None,
                                                         a_out.data_ptr() if a_out is not None else None,
-                                                        op[8].data_ptr() if self.training else None))
+                                                        op[8].data_ptr() if taps else None))
             else:
                 h.check(lib.rtn_stem_conv_pool(h.raw, op[5].data_ptr(), op[6][0], op[6][1], op[3].data_ptr(), op[3].shape[0],
                                                op[4].data_ptr(), op[1].data_ptr(), Bn, Hn, Wn))
@@ -846,7 +857,7 @@ class Engine:
                                       xi["B"], xi["H"], xi["W"], xi["Hp"], xi["Wp"]))
         elif kind == "pool":
             Bn, Hi, Wi, Cc = op[3]
-            if self.training:
+            if self._taps():
                 h.check(lib.rtn_maxpool3x3s2_tfsame_fwd_idx(h.raw, op[1].data_ptr(), op[2].data_ptr(), op[4].data_ptr(), self.rdt, Bn, Hi, Wi, Cc))
             else:
                 h.check(lib.rtn_maxpool3x3s2_tfsame_fwd(h.raw, op[1].data_ptr(), op[2].data_ptr(), self.rdt, Bn, Hi, Wi, Cc))

@@ -20,6 +20,29 @@ class _LayerRef:
         self.output = "%s:output" % name
 
 
+def is_backbone_layer(name):
+    """The ResNet's own conv layers (keras_resnet's model): conv1 and res*.  The FPN (C*_reduced, P*) and the heads (pyramid_*) are
+    not."""
+    return name == "conv1" or name.startswith("res")
+
+
+class BackboneView:
+    """The ResNet backbone of a Model as the reference's `modifier` sees it (model/defineModel.py:384-386: freeze_model is applied to
+    the keras_resnet model only): `.layers` are the Model's own conv1 / res* layer objects, so a modifier that sets `trainable`
+    on them freezes exactly the backbone."""
+
+    def __init__(self, model):
+        self.model = model
+        self.name = model.backbone
+        self.layers = [l for l in model.layers if l.kind == "conv" and is_backbone_layer(l.name)]
+
+    def get_layer(self, name):
+        for l in self.layers:
+            if l.name == name:
+                return l
+        raise ValueError('No such layer: ' + name)
+
+
 class Adam:
     """ keras.optimizers.Adam(lr, clipnorm) stand-in accepted by Model.compile (RetinaNet.py:130).  `clipnorm` clips by the GLOBAL
     gradient norm (standalone Keras 2.x, the reference's `import keras`); global_clipnorm=False selects the per-tensor
@@ -84,6 +107,20 @@ class Model:
         if loss is not None and set(loss) != {'regression', 'classification'}:
             raise ValueError("loss must name the 'regression' and 'classification' outputs")
         self._compiled = optimizer if optimizer is not None else Adam(lr=1e-4, clipnorm=0.001)
+        root = self._root()
+        if root._trainer is not None:                             # Keras: `trainable` changes take effect at compile()
+            root._trainer.set_trainable(root._trainable_names())
+
+    def backbone_view(self):
+        """The ResNet part of this model (BackboneView): what resnet_retinanet(modifier=...) hands the modifier."""
+        return BackboneView(self._root())
+
+    def _trainable_names(self):
+        """None when every conv layer trains (the full backward), else the set of trainable conv layers."""
+        convs = [l for l in self._root().layers if l.kind == "conv"]
+        if all(l.trainable for l in convs):
+            return None
+        return frozenset(l.name for l in convs if l.trainable)
 
     def _get_trainer(self):
         root = self._root()
@@ -92,15 +129,10 @@ class Model:
             pg = None
             if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
                 pg = torch.distributed.group.WORLD
+            # utils.freeze / freeze_model: non-trainable layers get no gradient and no update (Trainer(trainable=...))
             root._trainer = _rt.trainer.Trainer(self.engine(), lr=opt.lr, clipnorm=(opt.clipnorm or 0.0), beta1=opt.beta_1,
                                                 beta2=opt.beta_2, eps=opt.epsilon, process_group=pg,
-                                                global_clip=getattr(opt, "global_clipnorm", True))
-            tr, eng = root._trainer, root._engine
-            for l in root.layers:                                 # utils.freeze / freeze_model: non-trainable layers get no update
-                if l.kind == "conv" and not l.trainable:
-                    lo = eng.layout[l.name]
-                    tr.gscale[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]] = 0
-                    tr.gscale[tr.NW + lo["boff"]:tr.NW + lo["boff"] + lo["rows"]] = 0
+                                                global_clip=getattr(opt, "global_clipnorm", True), trainable=root._trainable_names())
         return root._trainer
 
     def predict_on_batch(self, x):
@@ -357,8 +389,8 @@ def resnet_retinanet(num_classes, backbone='resnet50', inputs=None, modifier=Non
     if backbone not in ('resnet50', 'resnet101', 'resnet152'):
         raise ValueError('Backbone (\'{}\') is invalid.'.format(backbone))
     m = retinanet(inputs=inputs, num_classes=num_classes, backbone_layers=None, backbone=backbone, **kwargs)
-    if modifier:
-        m = modifier(m) or m
+    if modifier:                                  # on the ResNet only, as the reference (:384-386): the FPN and the heads still train
+        modifier(m.backbone_view())
     return m
 
 

@@ -30,7 +30,9 @@ class GradBucketer:
     right after the kernels producing that segment were enqueued, ON THE STREAM they were enqueued on (the trainer spreads the
     weight gradients over several HIP streams): it records an event there, one per (bucket, stream) - streams are in order, so the
     latest event of a stream covers every earlier layer on it.  When a bucket is complete its all-reduce is issued on the
-    communication stream behind ALL of the bucket's events.  finish() issues what is left and makes the compute stream wait."""
+    communication stream behind ALL of the bucket's events.  finish() issues what is left and makes the compute stream wait.
+    The segments need not tile `flat`: with frozen layers they are the trainable tensors only, and a bucket all-reduces each
+    contiguous run of its segments on its own, so no slot outside the segments is ever sent."""
 
     def __init__(self, flat, segments, group=None, bucket_bytes=32 << 20, stream_layer=None):
         """stream_layer: an object with torch.cuda's current_stream / Stream / Event / stream (tests pass a recording stub and drive the
@@ -60,10 +62,17 @@ class GradBucketer:
         self.last_marks = [set(m) for m in getattr(self, "marks", [])]     # streams each bucket of the step before waited for (tests)
         self.marks = [{} for _ in self.buckets]          # bucket -> {stream id: (stream, event recorded after its last layer there)}
 
+    def _runs(self, bi):
+        runs = []
+        for _, a, b in sorted(self.buckets[bi], key=lambda s: s[1]):
+            if runs and runs[-1][1] == a:
+                runs[-1][1] = b
+            else:
+                runs.append([a, b])
+        return runs
+
     def _launch(self, bi):
-        segs = self.buckets[bi]
-        lo, hi = min(s[1] for s in segs), max(s[2] for s in segs)
-        view = self.flat[lo:hi]
+        views = [self.flat[a:b] for a, b in self._runs(bi)]
         self.launched[bi] = True
         if self.cuda:
             marks = self.marks[bi]
@@ -72,9 +81,11 @@ class GradBucketer:
             with self.tc.stream(self.comm):
                 for _, ev in marks.values():
                     self.comm.wait_event(ev)
-                self.work.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+                for view in views:
+                    self.work.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
         else:
-            self.work.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
+            for view in views:
+                self.work.append(dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def _mark(self, bi):
         st = self.tc.current_stream(self.flat.device)

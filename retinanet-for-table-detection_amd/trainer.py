@@ -15,6 +15,12 @@ The backward graph is derived from the forward op list of engine.Engine._plan: e
 dgrad per input; ReLU, residual adds, UpsampleLike+Add, C6_relu, max-pool and the stride-2 convs are handled by epilogue
 flags of the dgrad launch or by the small kernels of rtn_backward.hip.  All arithmetic is in the HIP library; PyTorch
 provides memory, the stream and (optionally) torch.distributed for the gradient all-reduce.
+
+Frozen layers (Keras `trainable = False`, Trainer(trainable=...) / set_trainable): a tensor needs a gradient iff its producer is a
+trainable layer or one of its producer's inputs needs one.  The backward plan keeps a weight gradient for the trainable layers only
+and a data gradient (with its zero-insert / upsample / pool backward / head pad-cast) only into tensors that need one; the optimizer
+runs over the trainable layers' element ranges (rtn_*_ranges), the all-reduce over their segments, and the training forward runs the
+stem and the 64-channel blocks in their inference form when the backward never reads their extra outputs (Engine.train_keep).
 """
 import ctypes as C
 
@@ -34,11 +40,35 @@ def _ceil128(v):
     return -(-v // 128) * 128
 
 
+def grad_segments(layout, NW, NB, trainable=None):
+    """GradBucketer segments of the flat gradient [weights (NW) | bias slots (NB)] and the names the trainer reports for the bias
+    slots.  trainable None: every weight tensor, then all bias slots as one "__biases__" segment.  Otherwise the trainable layers
+    only (frozen gradients are never all-reduced): their weight tensors, then the bias slots of the trainable layers that own a
+    Keras bias, one "__biases__" segment per contiguous run ("__biases__:k" when frozen layers split them)."""
+    live = [(name, lo) for name, lo in layout.items() if trainable is None or name in trainable]
+    segs = [(name, lo["woff"], lo["woff"] + lo["rows"] * lo["K"]) for name, lo in live]
+    if trainable is None:
+        return segs + [("__biases__", NW, NW + NB)], ["__biases__"]
+    runs = []
+    for name, lo in live:
+        if lo["has_bias"]:
+            a, b = NW + lo["boff"], NW + lo["boff"] + lo["rows"]
+            if runs and runs[-1][1] == a:
+                runs[-1][1] = b
+            else:
+                runs.append([a, b])
+    names = ["__biases__"] if len(runs) == 1 else ["__biases__:%d" % i for i in range(len(runs))]
+    return segs + [(n, a, b) for n, (a, b) in zip(names, runs)], names
+
+
 class Trainer:
     WG_LANES = 3          # side streams a weight gradient may go to
     def __init__(self, engine, lr=1e-4, clipnorm=0.001, beta1=0.9, beta2=0.999, eps=1e-7, alpha=0.25, gamma=2.0, sigma=3.0,
-                 process_group=None, global_clip=True):
+                 process_group=None, global_clip=True, trainable=None):
+        """trainable: None (every layer trains: the full backward) or the names of the conv layers that train (the rest are frozen:
+        no weight gradient, no update, and no data gradient below the lowest trainable layer)."""
         self.eng = engine
+        self.trainable = self._check_names(trainable)
         self.global_clip = bool(global_clip)
         self.lr, self.clipnorm, self.b1, self.b2, self.eps = lr, clipnorm, beta1, beta2, eps
         self.alpha, self.gamma, self.sigma = alpha, gamma, sigma
@@ -54,6 +84,30 @@ class Trainer:
         engine.on_plan_evict.append(weakref.WeakMethod(self._drop_bplan))
         self._bind_engine_state()
 
+    def _check_names(self, names):
+        if names is None:
+            return None
+        names = frozenset(names)
+        unknown = names - set(self.eng.layout)
+        if unknown:
+            raise ValueError("not a conv layer of this engine: %s" % sorted(unknown))
+        return names
+
+    def set_trainable(self, names):
+        """Change the trainable set (None = every layer).  The backward plans and their lane schedules, the dgrad repack table, the
+        optimizer's range tables and the gradient bucketer all follow it; the weights and the optimizer state stay."""
+        names = self._check_names(names)
+        if names == self.trainable:
+            return
+        self.trainable = names
+        self.bplans = {}
+        self._pack_table = None
+        self._ranges = None
+        self._build_bucketer()
+
+    def _is_trainable(self, name):
+        return self.trainable is None or name in self.trainable
+
     def _drop_bplan(self, plan_key):
         if len(plan_key) == 4:                              # (B, H, W, fp8): the one-batch buffer set the backward plan points into
             self.bplans.pop(tuple(plan_key[:3]), None)
@@ -66,11 +120,14 @@ class Trainer:
         self._epoch = self.eng.load_epoch
         self.step_count = 0
         self.bplans = {}
+        self._ranges = None
         self._init_params()
+        self._build_bucketer()
+
+    def _build_bucketer(self):
         self.bucketer = None
-        if self.pg is not None:
-            segs = [(name, lo["woff"], lo["woff"] + lo["rows"] * lo["K"]) for name, lo in self.eng.layout.items()]
-            segs.append(("__biases__", self.NW, self.NW + self.NB))           # FPN/head biases: one last segment
+        segs, self.bias_names = grad_segments(self.eng.layout, self.NW, self.NB, self.trainable)
+        if self.pg is not None and segs:
             self.bucketer = Par.GradBucketer(self.grad, segs, group=self.pg)
 
     def _check_engine_state(self):
@@ -131,7 +188,9 @@ class Trainer:
             crun = self._dy_channels(name)
             self.wd[name] = torch.empty(_ceil128(lo["cin"]), lo["kh"] * lo["kw"] * crun, dtype=eng.tdt, device=dev)
         self._pack_table = None
-        self._repack_dgrad()
+        self._repack_dgrad(every=True)
+        if self.trainable is not None:               # the steps repack the trainable layers only
+            self._pack_table = None
 
     def _dy_channels(self, name):
         """Channels of the dY tensor a layer's backward reads: Cout, or the padded width for the skinny head outputs."""
@@ -143,19 +202,24 @@ class Trainer:
             return cp
         return cout
 
-    def _repack_dgrad(self):
-        """Every layer's dgrad weights from the (rewritten) forward weights, one launch: rtn_pack_dgrad_weights_multi."""
+    def _repack_dgrad(self, every=False):
+        """The dgrad weights of every layer whose forward weights an optimizer step rewrites (every=True: of all layers) from the
+        forward weights, one launch: rtn_pack_dgrad_weights_multi."""
         eng = self.eng
         eng._bind_stream()
         if self._pack_table is None or self._pack_table[3] != eng.wflat.data_ptr():      # (re)built when the weights were reallocated
             rows, total = [], 0
             for name, wd in self.wd.items():
+                if not (every or self._is_trainable(name)):
+                    continue
                 lo = eng.layout[name]
                 rows.append([eng.w[name][0].data_ptr(), wd.data_ptr(), lo["cout"], lo["kh"], lo["kw"], lo["cin"], self._dy_channels(name),
                              wd.shape[0], total, 0])
                 total += wd.numel()
             self._pack_table = (torch.tensor(rows, dtype=torch.int64, device=eng.device), len(rows), total, eng.wflat.data_ptr())
         table, n, total, _ = self._pack_table
+        if n == 0:
+            return
         eng.h.check(L.lib.rtn_pack_dgrad_weights_multi(eng.h.raw, table.data_ptr(), n, total, eng.rdt))
 
     def grad_views(self, name):
@@ -196,6 +260,17 @@ class Trainer:
                 relu_src[tid(op[2])] = op[1]                       # P6r -> P6
         for t_, src in relu_src.items():                            # a consumer of relu(S) counts as a consumer of S
             ncons[tid(src)] = ncons.get(tid(src), 0) + ncons.pop(t_, 0)
+        # needs-grad: a tensor needs a gradient iff its producer is a trainable layer or any input of its producer needs one.  Every
+        # consumer of a tensor is pruned alike, so the first-writer / accumulate order below is the full backward's, minus whole tensors.
+        need = set()
+        for op in ops:
+            if op[0] == "conv":
+                me = op[3]
+                if self._is_trainable(op[2]) or any(tid(x) in need for x in me["xs"]) or \
+                        any(r is not None and tid(r) in need for r in me["res"]):
+                    need.update(tid(y) for y in me["ys"])
+            elif op[0] in ("pool", "relu") and tid(op[1]) in need:
+                need.add(tid(op[2]))
 
         grads, gstate, done = {}, {}, {}
 
@@ -215,8 +290,10 @@ class Trainer:
         keep += [d_reg, d_cls, dyp_reg, dyp_cls]
         grads[tid(plan["regression"])] = dyp_reg
         grads[tid(plan["classification"])] = dyp_cls
-        bops.append(("padcast", d_reg, dyp_reg, B * cells_total, eng.A * 4, cp_reg))
-        bops.append(("padcast", d_cls, dyp_cls, B * cells_total, eng.A * eng.K, cp_cls))
+        if tid(plan["regression"]) in need:
+            bops.append(("padcast", d_reg, dyp_reg, B * cells_total, eng.A * 4, cp_reg))
+        if tid(plan["classification"]) in need:
+            bops.append(("padcast", d_cls, dyp_cls, B * cells_total, eng.A * eng.K, cp_cls))
 
         def group_fwd_geom(g, x):
             g.in_, g.in_elems = x.data_ptr(), x.numel()
@@ -226,6 +303,8 @@ class Trainer:
             kind = op[0]
             if kind == "conv":
                 d_f, name, me = op[1], op[2], op[3]
+                if tid(me["ys"][0]) not in need:             # frozen, and nothing below it trains
+                    continue
                 lo = eng.layout[name]
                 head_out = name in ("pyramid_regression", "pyramid_classification")
                 ng = d_f.ngroups
@@ -257,13 +336,14 @@ class Trainer:
                         cell_off += cells
                     else:
                         g.out_img_stride, g.out_off = cells * crun, 0
-                wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(dw))
-                max_ws = max(max_ws, wsb)
-                bops.append(("wgrad", dw, dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
+                if self._is_trainable(name):
+                    wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(dw))
+                    max_ws = max(max_ws, wsb)
+                    bops.append(("wgrad", dw, dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
                 # ---------- residual inputs of the forward epilogue
                 for gi in range(ng):
                     r = me["res"][gi]
-                    if r is None:
+                    if r is None or tid(r) not in need:
                         continue
                     done[tid(r)] = done.get(tid(r), 0) + 1
                     if me["flags"] & L.CONV_RES_SAME:
@@ -287,11 +367,16 @@ class Trainer:
                 stride, (pt, pl) = me["stride"], me["pad"]
                 flags_all = None
                 cell_off = 0
+                ngd = 0                                              # groups whose input needs a gradient
                 for gi in range(ng):
                     x = me["xs"][gi]
                     target, pre_mask = x, False
                     if tid(x) in relu_src:                           # x = relu(S): differentiate straight into S
                         target, pre_mask = relu_src[tid(x)], True
+                    if tid(target) not in need:
+                        if head_out:
+                            cell_off += d_f.g[gi].Hout * d_f.g[gi].Wout
+                        continue
                     done[tid(target)] = done.get(tid(target), 0) + 1
                     state = gstate.get(tid(target))
                     dy = dys[gi]
@@ -348,12 +433,18 @@ class Trainer:
                         flags_all = flags
                     elif flags_all != flags:
                         raise RuntimeError("grouped dgrad of %s needs uniform epilogue flags" % name)
-                    dd.g[gi] = g
+                    dd.g[ngd] = g
+                    ngd += 1
+                if ngd == 0:
+                    continue
+                dd.ngroups = ngd
                 dd.flags = flags_all
                 L.attach_conv_workspace(eng.h, dd)                   # caller-owned K-split slabs, one buffer per launch
                 bops.append(("dgrad", dd, name))
             elif kind == "pool":
                 x, y = op[1], op[2]
+                if tid(x) not in need:
+                    continue
                 dy = grads.get(tid(y))
                 done[tid(x)] = done.get(tid(x), 0) + 1
                 bops.append(("poolbwd", x, dy, gbuf(x), op[3], op[4], y))      # y: the pooled tensor (the fused stem's ReLU mask)
@@ -363,7 +454,13 @@ class Trainer:
         # every weight-gradient op owns its workspace (row-info table + the slabs of its ordered split reduction: 130 MB for a head
         # layer at batch 16 x 800 x 1333, 3.4 GB over the 107 layers), allocated at its first launch in forward_backward: ops on
         # different lanes never share scratch, and the table is built once per layer
+        # what the pruned backward reads of the training forward's extra outputs: branch2b of the fused 64-channel blocks, the pool taps
+        reads = set(p_ for b in bops for p_ in Trainer._bop_io(b)[0])
+        fu = plan["fusion"]
+        h1s = [blk["b2"] for blk in fu["blocks64"]] + [fb["b2"] for fb in fu["first_blocks"] if fb["f"] == 64]
+        keep_fwd = (any(t.data_ptr() in reads for t in h1s), any(b[0] == "poolbwd" for b in bops))
         bp = {"bops": bops, "keep": keep, "last_bias_bop": bias_bops[-1] if bias_bops else -1, "wgrad_ws_bytes": max_ws,
+              "keep_fwd": keep_fwd,
               "d_reg": d_reg, "d_cls": d_cls, "dyp_cls": dyp_cls, "loss_ws": loss_ws, "plan": plan, "rowinfo": {}}
         self.bplans[key] = bp
         return bp
@@ -427,11 +524,14 @@ class Trainer:
         B, H, W, _ = images.shape
         eng.training = True
         try:
+            bp = self._bplan(B, H, W)
+            # the full backward reads every extra output of the training forward; a pruned one maybe none (Engine._fused)
+            eng.train_keep = None if self.trainable is None else bp["keep_fwd"]
             self.fwd_key = eng._fused()              # the fusion key this forward runs: the pool backward follows its stem
             reg, cls = eng.forward(images)
         finally:
             eng.training = False
-        bp = self._bplan(B, H, W)
+            eng.train_keep = None
         N, K = bp["plan"]["N"], eng.K
         rows = B * N
         eng._bind_stream()
@@ -442,6 +542,8 @@ class Trainer:
         if self.pg is not None:                      # merged-batch normaliser (multi_gpu_model semantics)
             norm = Par.allreduce_loss_sums(self.loss_sums, self.pg)
         self.norm_sums = norm
+        if not bp["bops"]:                           # every layer frozen: the loss alone, no backward kernel
+            return self.loss_sums
         h.check(lib.rtn_retina_loss_bwd_dev(h.raw, rows, K, labels_batch.data_ptr(), regression_batch.data_ptr(), cls.data_ptr(),
                                             reg.data_ptr(), self.alpha, self.gamma, self.sigma, norm.data_ptr(), 1,
                                             bp["d_cls"].data_ptr(), bp["d_reg"].data_ptr()))
@@ -489,11 +591,13 @@ class Trainer:
                 if self.record_impls:
                     self.impls[("wgrad", b[3])] = lib.rtn_debug_last_wgrad_impl(h.raw)
                 if self.bucketer is not None:         # this layer's weight gradient is enqueued: its bucket may go out
-                    done_names = [b[3]] + (["__biases__"] if bi == bp["last_bias_bop"] else [])   # last fused bias gradient
-                    if len(done_names) > 1 and lane_on:   # the bias gradients came from every weight-gradient lane: mark them all
+                    last_bias = bi == bp["last_bias_bop"]
+                    done_names = [b[3]] + (self.bias_names if last_bias else [])   # last fused bias gradient
+                    if last_bias and lane_on:         # the bias gradients came from every weight-gradient lane: mark them all
                         for ln_ in range(1, nwg + 1):
                             with torch.cuda.stream(streams[ln_]):
-                                self.bucketer.mark("__biases__")
+                                for bn_ in self.bias_names:
+                                    self.bucketer.mark(bn_)
                     for dn in done_names:
                         if on_side:
                             with torch.cuda.stream(side):     # the bucket's event must follow the kernels on THEIR stream
@@ -543,6 +647,10 @@ class Trainer:
         if self.bucketer is not None:                # sum of per-rank gradients == gradient of the merged batch
             self.bucketer.finish()
         self.step_count += 1
+        lr = self.lr if lr is None else lr
+        if self.trainable is not None:
+            self._step_ranges(lr)
+            return
         n = self.NW + self.NB
         h.check(lib.rtn_sumsq(h.raw, self.grad.data_ptr(), self.gscale.data_ptr(), n, self.sumsq.data_ptr(), self.ss_ws.data_ptr(),
                               self.ss_ws.numel()))
@@ -564,6 +672,48 @@ class Trainer:
                                                self.sumsq.data_ptr(), self.clipnorm, 1.0))
         self._repack_dgrad()
         eng.weights_version += 1                        # fused inference copies of the filters are stale now
+
+    def _range_tables(self):
+        """Element ranges of the trainable tensors (one per weight tensor, one per bias vector): device tables for the whole flat
+        vector (the norms), the weights and the biases (relative to NW), built once per trainable set."""
+        if self._ranges is None:
+            dev = self.eng.device
+            wr = [(lo["woff"], lo["woff"] + lo["rows"] * lo["K"]) for name, lo in self.eng.layout.items() if self._is_trainable(name)]
+            br = [(lo["boff"], lo["boff"] + lo["rows"]) for name, lo in self.eng.layout.items()
+                  if lo["has_bias"] and self._is_trainable(name)]
+            allr = wr + [(self.NW + a, self.NW + b) for a, b in br]
+            self._ranges = {"all": L.ranges_table(allr, dev), "w": L.ranges_table(wr, dev), "b": L.ranges_table(br, dev),
+                            "each": torch.zeros(max(1, len(allr)), dtype=torch.float64, device=dev)}
+        return self._ranges
+
+    def _step_ranges(self, lr):
+        """optimizer_step over the trainable layers only (rtn_sumsq_ranges + rtn_adam_clipnorm_step_ranges[_pertensor]): frozen slots
+        of master / m / v / grad and of the forward weights are never read or written."""
+        eng, lib, h = self.eng, L.lib, self.eng.h
+        rt = self._range_tables()
+        tab, nr, span = rt["all"]
+        if nr == 0:                                     # nothing trains: no kernel, the weights and their copies stay
+            return
+        n = self.NW + self.NB
+        each = rt["each"]
+        h.check(lib.rtn_sumsq_ranges(h.raw, self.grad.data_ptr(), self.gscale.data_ptr(), n, tab.data_ptr(), nr, span,
+                                     self.sumsq.data_ptr() if self.global_clip else None, None if self.global_clip else each.data_ptr(),
+                                     self.ss_ws.data_ptr(), self.ss_ws.numel()))
+        nrw = rt["w"][1]
+        for part, lo_, cnt, wf, code, sums in (("w", 0, self.NW, eng.wflat, eng.rdt, 0), ("b", self.NW, self.NB, eng.bflat, L.RTN_F32, nrw)):
+            t, nrp, sp = rt[part]
+            if nrp == 0:
+                continue
+            off4 = lo_ * 4
+            args = (h.raw, self.master.data_ptr() + off4, self.m.data_ptr() + off4, self.v.data_ptr() + off4, self.grad.data_ptr() + off4,
+                    self.gscale.data_ptr() + off4, self.fold.data_ptr() + off4, wf.data_ptr(), code, cnt, t.data_ptr(), nrp, sp,
+                    self.step_count, lr, self.b1, self.b2, self.eps)
+            if self.global_clip:
+                h.check(lib.rtn_adam_clipnorm_step_ranges(*args, self.sumsq.data_ptr(), self.clipnorm, 1.0))
+            else:
+                h.check(lib.rtn_adam_clipnorm_step_ranges_pertensor(*args, each.data_ptr() + sums * 8, self.clipnorm, 1.0))
+        self._repack_dgrad()
+        eng.weights_version += 1
 
     def train_on_batch(self, images, regression_batch, labels_batch, lr=None):
         """Keras-style step. Returns (total, regression_loss, classification_loss) as Python floats (one host sync)."""
