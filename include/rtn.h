@@ -581,6 +581,35 @@ int rtn_clip_boxes(rtn_handle_t h, const float* in, int64_t n_boxes, float width
 int rtn_upsample_nearest(rtn_handle_t h, const void* src, void* dst, int dtype, int B, int Hs, int Ws, int Hd, int Wd, int C);
 int rtn_preprocess_image(rtn_handle_t h, const void* src, int src_dtype, float* dst, int64_t n, int mode, float scale, float sub);
 
+/* ---- baseline JPEG decode (read_image_bgr's Pillow / libjpeg-turbo decode, on the device) --------------------------------------
+ * Supported: baseline sequential (SOF0), 8-bit, Huffman, one scan holding every component, with or without restart intervals;
+ * 1 component, or 3 in YCbCr (JFIF; not Adobe transform 0; ids not R,G,B) sampled 4:4:4, 4:2:2 (2x1) or 4:2:0 (2x2).
+ * Output: uint8 (H, W, 3) B,G,R, bit-identical to libjpeg-turbo's default decode (ISLOW IDCT, fancy upsampling) as Pillow runs it;
+ * a grayscale page has Y in all three channels.
+ *
+ * rtn_jpeg_inspect (host only; h may be NULL, rtn_last_error(NULL) then gives this thread's failure text): parses the file_bytes of
+ * one file held in host memory.  RTN_OK fills *info; RTN_EINVAL names what is not supported or what is corrupt.  With blob == NULL
+ * it only fills *info, blob_bytes then being an upper bound; otherwise it writes the packed blob (header, Huffman lookup tables,
+ * quantisation tables, restart-segment offsets, entropy-coded bytes with stuffing and RST markers removed) into blob, which needs
+ * RTN_JPEG_BLOB_BOUND(file_bytes) bytes at most, and sets info->blob_bytes to the bytes written (a multiple of 16).
+ * rtn_jpeg_workspace_bytes: device scratch for decoding the n blobs at host_blobs + offsets[i].
+ * rtn_jpeg_decode: n pages in one batch.  host_blobs and dev_blobs are the same packed buffer on the host and on the device (one
+ *   copy), offsets[i] (host, multiples of 16) the start of page i's blob in both; pages (host array) the device outputs, each
+ *   H x W x 3 bytes; status (device, n int32) is written 0 for a decoded page and non-zero where the stream breaks JPEG's rules or
+ *   leaves the range the device decode reproduces exactly: the caller decodes those pages on the host.  workspace: 256-byte
+ *   aligned, >= rtn_jpeg_workspace_bytes. */
+typedef struct {
+    int32_t width, height, components, h_samp, v_samp;   /* h_samp / v_samp: luma sampling factors (2, 2 = 4:2:0) */
+    int32_t restart_interval;                             /* MCUs per restart segment, 0 = none */
+    int32_t huffman_tables, quant_tables;                 /* tables defined before the scan */
+    int64_t blob_bytes, workspace_bytes, scan_bytes;      /* scan_bytes: entropy-coded bytes after unstuffing */
+} rtn_jpeg_info_t;
+#define RTN_JPEG_BLOB_BOUND(file_bytes) (16384 + 4 * (size_t)(file_bytes))
+int rtn_jpeg_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_jpeg_info_t* info, void* blob, size_t blob_capacity);
+size_t rtn_jpeg_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
+int rtn_jpeg_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                    uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

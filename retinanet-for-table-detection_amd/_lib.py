@@ -94,6 +94,19 @@ class ChainDesc(C.Structure):
     ]
 
 
+class JpegInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("h_samp", C.c_int32), ("v_samp", C.c_int32),
+        ("restart_interval", C.c_int32), ("huffman_tables", C.c_int32), ("quant_tables", C.c_int32),
+        ("blob_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("scan_bytes", C.c_int64),
+    ]
+
+
+def jpeg_blob_bound(file_bytes):
+    """RTN_JPEG_BLOB_BOUND of include/rtn.h: the most bytes rtn_jpeg_inspect writes for a file of that size."""
+    return 16384 + 4 * int(file_bytes)
+
+
 class ConvFp8(C.Structure):
     _fields_ = [("acc_scale", C.c_float), ("out_scale", C.c_float), ("out_dtype", C.c_int32)]
 
@@ -182,6 +195,9 @@ SIGNATURES = {
     "rtn_eval_workspace_bytes": (_SZ, [_I64, _I, _I]),
     "rtn_eval_match": (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, C.POINTER(_D), _D, _I, _P, _P]),
     "rtn_eval_finalize": (_I, [_P, _I64, _I, _P, _P, _I, _I, _D, _P, _P, _SZ]),
+    "rtn_jpeg_inspect": (_I, [_P, _P, _SZ, C.POINTER(JpegInfo), _P, _SZ]),
+    "rtn_jpeg_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_jpeg_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
 }
 
 

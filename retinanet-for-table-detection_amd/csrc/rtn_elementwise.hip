@@ -46,7 +46,7 @@ extern "C" int rtn_set_stream(rtn_handle_t h, void* stream) {
     return RTN_OK;
 }
 
-extern "C" const char* rtn_last_error(rtn_handle_t h) { return h ? h->err : "null handle"; }
+extern "C" const char* rtn_last_error(rtn_handle_t h) { return h ? h->err : rtn_host_error_text(); }
 
 namespace {
 

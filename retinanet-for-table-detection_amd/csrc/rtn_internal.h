@@ -68,6 +68,9 @@ int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
                        int mi_force, unsigned* sync, void* ws, long long ws_cap, size_t* query, int sk_mode);
 int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool forced);
 
+// rtn_jpeg.hip: text of the calling thread's last failed host-only call made without a handle (rtn_last_error(NULL))
+const char* rtn_host_error_text();
+
 static inline int rtn_dtype_size(int dt) { return dt == RTN_F32 ? 4 : (dt == RTN_FP8 ? 1 : 2); }
 
 // bf16 helpers on raw bits (device + host)

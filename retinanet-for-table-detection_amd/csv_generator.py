@@ -3,8 +3,10 @@
 Same class names, constructor arguments and method names as the reference's Generator / CSVGenerator, so RetinaNet.py's train()
 (:234-247) constructs it unchanged; what differs is where the work runs:
 
-  host   CSV rows, grouping / shuffling, annotation filtering, the 3x3 augmentation matrices and box corners (a few flops)
-  device per page: uint8 upload -> [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
+  host   CSV rows, grouping / shuffling, annotation filtering, the 3x3 augmentation matrices and box corners (a few flops),
+         parsing the page files (rtn_jpeg_inspect)
+  device per batch: rtn_jpeg_decode of the baseline-JPEG pages (read_images_bgr; other files are decoded by Pillow and uploaded)
+         per page: [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
          x/127.5-1 normalisation (preprocess_image 'custom_tf'), the INTER_CUBIC resize and the write into the zero-padded batch
          canvas of compute_inputs;  per batch: rtn_anchor_targets (anchors, IoU, assignment, box deltas) -> regression, labels
 
@@ -55,6 +57,90 @@ def read_image_bgr(path):
     with Image.open(path) as im:
         rgb = np.asarray(im.convert("RGB"))
     return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def jpeg_inspect(data):
+    """Parse one file's bytes with rtn_jpeg_inspect (host only) -> (JpegInfo, blob bytes) for a baseline JPEG the device decodes,
+    or (None, reason) for anything else."""
+    info = L.JpegInfo()
+    blob = np.empty(L.jpeg_blob_bound(len(data)), np.uint8)
+    rc = L.lib.rtn_jpeg_inspect(None, data, len(data), C.byref(info), blob.ctypes.data, blob.size)
+    if rc != 0:
+        return None, L.lib.rtn_last_error(None).decode("utf-8", "replace")
+    return info, blob[:info.blob_bytes]
+
+
+def _decode_batch(paths, device, handle, stream):
+    """read_images_bgr on an explicit handle and stream: every page that rtn_jpeg_inspect accepts is decoded in one batched
+    rtn_jpeg_decode after one host->device copy of the blobs; the status words are read once, on `stream`; the other pages (and
+    the pages whose status is non-zero) go through read_image_bgr and are uploaded."""
+    from PIL import Image
+    out = [None] * len(paths)
+    on_host = []
+    datas = []
+    for i, path in enumerate(paths):
+        try:
+            with open(path, 'rb') as f:
+                datas.append((i, f.read()))
+        except OSError:
+            on_host.append(i)                       # read_image_bgr raises the same exception below, in page order
+    limit = Image.MAX_IMAGE_PIXELS
+    cap = sum(L.jpeg_blob_bound(len(d)) for _, d in datas)
+    with torch.cuda.stream(stream):
+        host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
+        hp = host.data_ptr()
+        offsets, pages, which, pos = [], [], [], 0
+        for i, data in datas:
+            info = L.JpegInfo()
+            rc = L.lib.rtn_jpeg_inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
+            if rc != 0 or (limit and info.width * info.height > limit):
+                on_host.append(i)
+                continue
+            offsets.append(pos)
+            pos += info.blob_bytes
+            pages.append(torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=device))
+            which.append(i)
+        if which:
+            n = len(which)
+            offs = np.asarray(offsets, np.int64)
+            dev_blobs = host[:pos].to(device, non_blocking=True)
+            ws_bytes = int(L.lib.rtn_jpeg_workspace_bytes(n, hp, offs.ctypes.data))
+            ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+            status = torch.empty(n, dtype=torch.int32, device=device)
+            ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+            handle.set_stream(stream.cuda_stream)
+            handle.check(L.lib.rtn_jpeg_decode(handle.raw, n, hp, dev_blobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
+                                               ws.data_ptr(), ws_bytes))
+            st = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            st.copy_(status, non_blocking=True)
+            stream.synchronize()
+            for k, i in enumerate(which):
+                if int(st[k]) == 0:
+                    out[i] = pages[k]
+                else:
+                    on_host.append(i)
+        for i in sorted(on_host):
+            out[i] = torch.from_numpy(read_image_bgr(paths[i])).to(device)
+    return out
+
+
+_readers = {}
+_readers_lock = threading.Lock()
+
+
+def read_images_bgr(paths, device=None):
+    """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits: baseline JPEGs (the files
+    cv2.imwrite writes for a .jpg name) are decoded on the device in one batched call (csrc/rtn_jpeg.hip) on the current stream;
+    every other file, and any JPEG whose stream the device decode flags, is decoded by read_image_bgr and uploaded.  A file
+    Pillow cannot open raises what read_image_bgr raises."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with _readers_lock:
+        h = _readers.get(dev.index)
+        if h is None:
+            h = _readers[dev.index] = L.Handle(dev.index)
+        return _decode_batch(list(paths), dev, h, torch.cuda.current_stream(dev))
 
 
 def _image_size(path):
@@ -289,12 +375,12 @@ class Generator:
         return [reg, lab]
 
     def compute_input_output(self, group):
-        """csv_generator.py:373-398.  Everything after the file reads runs on this generator's stream."""
-        image_group = self.load_image_group(group)
-        annotations_group = self.load_annotations_group(group)
-        image_group, annotations_group = self.filter_annotations(image_group, annotations_group, group)
+        """csv_generator.py:373-398.  Everything, the page decode included, runs on this generator's stream."""
         with self._lock, torch.cuda.stream(self._stream):
             self._h.set_stream(self._stream.cuda_stream)
+            image_group = self.load_image_group(group)
+            annotations_group = self.load_annotations_group(group)
+            image_group, annotations_group = self.filter_annotations(image_group, annotations_group, group)
             image_group, annotations_group = self.random_transform_group(image_group, annotations_group)
             pages = [self._upload(im) for im in image_group]
             scales = [compute_resize_scale(p.shape, self.image_min_side, self.image_max_side) for p in pages]
@@ -409,6 +495,11 @@ class CSVGenerator(Generator):
 
     def load_image(self, image_index):
         return read_image_bgr(self.image_data[image_index].image_path)
+
+    def load_image_group(self, group):
+        """The group's pages as device tensors (read_images_bgr on this generator's handle and stream): baseline JPEGs are decoded
+        on the device, other files by read_image_bgr."""
+        return _decode_batch([self.image_path(i) for i in group], self.device, self._h, self._stream)
 
     def load_annotations(self, image_index):
         """csv_generator.py:497-512 -> {'labels': (G,), 'bboxes': (G,4)} float64."""

@@ -1,0 +1,161 @@
+"""Measure the device JPEG decoder (csrc/rtn_jpeg.hip) on the sample-sized page: 2200x1712, built by tiling
+tests/golden/sample_page_crop.npz's processed_rgb and encoded q95 4:2:0 by Pillow (the file cv2.imwrite writes for a .jpg name),
+written as 16 files.
+
+  python tools/bench_decode.py [--batch 16] [--iters 20] [--host-pages 8]
+
+Reports
+  (a) GPU time of the three decode kernels per batch (events around rtn_jpeg_decode, blobs already on the device);
+  (b) wall time of read_images_bgr for the batch's files (read, parse, one copy, decode, status read-back);
+  (c) read_image_bgr (Pillow) pages/s on one thread;
+  (d) one CSVGenerator batch of those files end to end (decode, resize into the canvas, anchor targets), with the device decoder
+      and with every page decoded by read_image_bgr.
+For the per-kernel split: rocprofv3 --kernel-trace --stats -d rocprof_out -o jpeg -- python tools/bench_decode.py
+"""
+import argparse
+import ctypes as C
+import importlib
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+import warnings
+
+import numpy as np
+import torch
+from PIL import Image
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+CG = importlib.import_module("retinanet-for-table-detection_amd.csv_generator")
+L = importlib.import_module("retinanet-for-table-detection_amd._lib")
+
+
+def make_page():
+    crop = np.load(os.path.join(ROOT, "tests", "golden", "sample_page_crop.npz"))["processed_rgb"]
+    h, w = 2200, 1712
+    page = np.tile(crop, (h // crop.shape[0] + 1, w // crop.shape[1] + 1, 1))[:h, :w]
+    b = io.BytesIO()
+    Image.fromarray(np.ascontiguousarray(page)).save(b, "JPEG", quality=95, subsampling=2)
+    return b.getvalue()
+
+
+def median_ms(fn, iters):
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--host-pages", type=int, default=8)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    data = make_page()
+    tmp = tempfile.mkdtemp(prefix="bench_decode_")
+    paths = []
+    for i in range(a.batch):
+        p = os.path.join(tmp, "page_%02d.png" % i)        # the CSV reader keeps .png ids; the files hold JPEG data
+        with open(p, "wb") as f:
+            f.write(data)
+        paths.append(p)
+    info, blob = CG.jpeg_inspect(data)
+    assert info is not None
+    print("page: %dx%d, %d components, sampling %dx%d, file %d B, scan %d B, blob %d B, workspace %.1f MB" %
+          (info.width, info.height, info.components, info.h_samp, info.v_samp, len(data), info.scan_bytes, info.blob_bytes,
+           info.workspace_bytes / 1e6))
+
+    # (a) kernels alone
+    n = a.batch
+    host = np.concatenate([blob] * n)
+    offs = np.arange(n, dtype=np.int64) * blob.size
+    dblobs = torch.from_numpy(host).to(dev)
+    wsb = int(L.lib.rtn_jpeg_workspace_bytes(n, host.ctypes.data, offs.ctypes.data))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    pages = [torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    h = L.Handle(0)
+    h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def decode():
+        h.check(L.lib.rtn_jpeg_decode(h.raw, n, host.ctypes.data, dblobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
+                                      ws.data_ptr(), wsb))
+    for _ in range(3):
+        decode()
+    torch.cuda.synchronize()
+    assert int(status.abs().sum()) == 0
+    ref = CG.read_image_bgr(paths[0])
+    assert np.array_equal(pages[n - 1].cpu().numpy(), ref)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ts = []
+    for _ in range(a.iters):
+        ev[0].record()
+        decode()
+        ev[1].record()
+        torch.cuda.synchronize()
+        ts.append(ev[0].elapsed_time(ev[1]))
+    kern_ms = float(np.median(ts))
+    print("(a) decode kernels: %.3f ms per batch of %d (%.0f pages/s on the GPU)" % (kern_ms, n, n / kern_ms * 1e3))
+
+    # (b) read_images_bgr, files to device pages
+    for _ in range(2):
+        CG.read_images_bgr(paths)
+    torch.cuda.synchronize()
+    b_ms = median_ms(lambda: CG.read_images_bgr(paths), max(3, a.iters // 2))
+    print("(b) read_images_bgr: %.1f ms per %d files (%.0f pages/s)" % (b_ms, n, n / b_ms * 1e3))
+
+    # (c) Pillow, one thread
+    k = max(1, a.host_pages)
+    CG.read_image_bgr(paths[0])
+    t0 = time.perf_counter()
+    for i in range(k):
+        CG.read_image_bgr(paths[i % n])
+    c_ms = (time.perf_counter() - t0) * 1e3 / k
+    print("(c) read_image_bgr: %.1f ms per page (%.1f pages/s, one thread)" % (c_ms, 1e3 / c_ms))
+    print("    (b) / (c) = %.1fx" % ((n / b_ms) / (1.0 / c_ms)))
+
+    # (d) one CSVGenerator batch from the files
+    csvf = os.path.join(tmp, "train.csv")
+    with open(csvf, "w") as f:
+        f.write("image_id,xmin,ymin,xmax,ymax,label\n")
+        for p in paths:
+            f.write("%s,100,120,900,700,table\n" % os.path.basename(p))
+
+    def gen_ms(device_decode):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            gen = CG.CSVGenerator(csvf, tmp, {"table": 0}, batch_size=n, group_method="none", shuffle_groups=False)
+            if not device_decode:
+                gen.load_image_group = lambda group: CG.Generator.load_image_group(gen, group)
+            out = []
+
+            def one():
+                x, (reg, lab) = gen[0]
+                torch.cuda.current_stream(dev).synchronize()
+                out.append(x)
+            one()
+            ms = median_ms(one, max(3, a.iters // 4))
+            gen.close()
+        return ms, out[-1]
+    d_dev, x_dev = gen_ms(True)
+    d_host, x_host = gen_ms(False)
+    assert torch.equal(x_dev, x_host)
+    print("(d) CSVGenerator batch of %d files to canvas + targets: %.1f ms with the device decoder, %.1f ms with Pillow (%.1fx)" %
+          (n, d_dev, d_host, d_host / d_dev))
+    print(json.dumps({"batch": n, "kernels_ms": round(kern_ms, 3), "read_images_bgr_ms": round(b_ms, 2),
+                      "read_images_bgr_pages_s": round(n / b_ms * 1e3, 1), "pillow_ms_per_page": round(c_ms, 2),
+                      "pillow_pages_s": round(1e3 / c_ms, 2), "speedup_b_over_c": round((n / b_ms) / (1.0 / c_ms), 1),
+                      "generator_batch_ms_device": round(d_dev, 1), "generator_batch_ms_pillow": round(d_host, 1)}))
+    h.close()
+
+
+if __name__ == "__main__":
+    main()
