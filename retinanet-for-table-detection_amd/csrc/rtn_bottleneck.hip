@@ -19,12 +19,12 @@
 // of the taps is loaded, the left / right ones are lane shifts of it - "shifted taps" below), the shortcut likewise.
 // LDS: 17 weight images of [64 rows][128 B] (9 taps of W2b, 4 output chunks of W2c, 4 k-chunks of W2a') + biases = 137.5 KiB.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 #include <cstdlib>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
@@ -60,17 +60,6 @@ __device__ __forceinline__ int perm_row(int rho) {     // MFMA row (16 f + 4 q +
     return 32 * (f >> 1) + 8 * q + 4 * (f & 1) + r;
 }
 
-__device__ __forceinline__ void divmod24(int f, int d, float inv, int& q, int& r) {
-    q = (int)((float)f * inv);
-    r = f - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-}
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 __device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
@@ -524,23 +513,15 @@ extern "C" int rtn_bottleneck64_fwd(rtn_handle_t h, const rtn_bottleneck_desc_t*
     if (grid > wgs_needed) grid = wgs_needed;
     { const int gl = rtn_env_int("RTN_BNECK_GRID", 0); if (gl > 0 && gl < grid) grid = gl; }     // tests: several strips per wave on small inputs
     const bool rowpp = rtn_bneck_rowpp(nt);
-#define RTN_BK_LAUNCH_S(T, RP, PJ)                                                                       \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                 \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                  \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)bottleneck64_kernel<T, 512, RP, PJ>,         \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, BK_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                      \
-        }                                                                                                \
-        hipLaunchKernelGGL((bottleneck64_kernel<T, 512, RP, PJ>), dim3((unsigned)grid), dim3(512), BK_LDS, h->stream, p); \
-    } while (0)
-    if (proj) {
-        if (tail) RTN_BK_LAUNCH_S(true, true, true); else RTN_BK_LAUNCH_S(false, true, true);
-    } else {
-        if (rowpp) { if (tail) RTN_BK_LAUNCH_S(true, true, false); else RTN_BK_LAUNCH_S(false, true, false); }
-        else       { if (tail) RTN_BK_LAUNCH_S(true, false, false); else RTN_BK_LAUNCH_S(false, false, false); }
-    }
-#undef RTN_BK_LAUNCH_S
+    const dim3 gdim((unsigned)grid), bdim(512);
+    int lrc;
+    if (proj)       lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, true, true>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
+                               : rtn_launch_lds<bottleneck64_kernel<false, 512, true, true>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
+    else if (rowpp) lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, true, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
+                               : rtn_launch_lds<bottleneck64_kernel<false, 512, true, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
+    else            lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, false, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
+                               : rtn_launch_lds<bottleneck64_kernel<false, 512, false, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "bottleneck64_kernel");
     return RTN_OK;
 }

@@ -15,12 +15,12 @@
 // loaded into registers at the start of a chunk and written to the other buffer at its end); a wave owns a strip of 16 PX pixels,
 // keeps its h_in fragments and the a_out accumulators in registers for the whole pass and sees every filter chunk once.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 #include <cstdlib>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
@@ -43,10 +43,6 @@ struct ChParams {
 __device__ __forceinline__ int perm_row(int rho) {     // MFMA row (16 f + 4 q + r) -> channel 32 (f >> 1) + 8 q + 4 (f & 1) + r
     const int f = rho >> 4, q = (rho >> 2) & 3, r = rho & 3;
     return 32 * (f >> 1) + 8 * q + 4 * (f & 1) + r;
-}
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
 }
 __device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
@@ -242,12 +238,8 @@ int chain_launch(rtn_handle_t h, ChParams& p, int grid_limit) {
     int grid = h->num_cus > 0 ? h->num_cus : 256;
     if (grid > (p.nstrips + 7) / 8) grid = (p.nstrips + 7) / 8;
     if (grid_limit > 0 && grid > grid_limit) grid = grid_limit;
-    static std::atomic<unsigned long long> attr_set{0ull};      // one bit per device
-    if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {
-        RTN_HIP(h, hipFuncSetAttribute((const void*)chain1x1_kernel<CM, NCH, N3, PX, DEPTH>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);
-    }
-    hipLaunchKernelGGL((chain1x1_kernel<CM, NCH, N3, PX, DEPTH>), dim3((unsigned)grid), dim3(512), LDS, h->stream, p);
+    const int lrc = rtn_launch_lds<chain1x1_kernel<CM, NCH, N3, PX, DEPTH>>(h, dim3((unsigned)grid), dim3(512), LDS, LDS, p);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "chain1x1_kernel");
     return RTN_OK;
 }

@@ -17,6 +17,7 @@
 // Epilogue: accumulators -> LDS (f32) -> whole-row 16-byte stores, with bias, residual
 // (identity or legacy-TF nearest upsample gather), ReLU / sigmoid fused.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 #include <cstdlib>
 
 namespace {
@@ -25,7 +26,6 @@ constexpr int BM = 128;
 constexpr int NT = 256;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
@@ -36,18 +36,6 @@ __device__ __forceinline__ uint4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, unsi
     return make_uint4(v.x, v.y, v.z, v.w);
 }
 
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-
-// Buffer descriptor words in SGPRs (raw buffer, stride 0, range = `bytes`); every input is made wave-uniform.
-__device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
 
 // LDS-DMA: 64 lanes x 16 B land at LDS byte address `lds_addr` (wave-uniform) + lane*16; lanes whose `voff` is outside
 // the descriptor range write zeros.  Issued from asm so that hipcc's waitcnt insertion does not see it (it would
@@ -1320,14 +1308,59 @@ int rtn_env_int(const char* name, int dflt) {
 }
 
 
-// `query` != nullptr: no launch; *query = bytes of d->workspace this launch can use (the K-split paths below).
+// ---- the conv launcher: check the descriptor -> try generations 4 / 6 / 5 -> check the groups -> choose -> fill KParams -> launch.
+// A workspace query (rtn_conv2d_workspace_bytes) runs the same steps up to `choose` and returns the bytes that choice needs.
 static constexpr long long kMaxConvWorkspace = 256ll << 20;
-static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2 = nullptr, const rtn_conv_fp8_t* q8 = nullptr,
-                       float out8_scale = 0.f, size_t* query = nullptr) {
-    if (query) *query = 0;
-    if (!h) return RTN_EINVAL;
-    if (!d) return rtn_fail(h, RTN_EINVAL, "conv: null descriptor");
-    rtn_env_sync();
+
+namespace {
+struct ConvCall {                  // one launch as the entry points see it
+    const rtn_conv_desc_t* d;
+    const rtn_conv_src2_t* s2;     // K-concatenated second source (rtn_conv1x1_dual_fwd) or null
+    const rtn_conv_fp8_t* q8;      // fp8 operands (rtn_conv2d_fp8_fwd) or null
+    float out8_scale;              // != 0: bf16 layer with e4m3 output (rtn_conv2d_fwd_fp8out)
+};
+struct ConvShape {                 // what the descriptor checks derive on the way
+    int es, cshift;
+    long long K1, Ktot;            // elements of the first source's K range, of the whole K range
+    bool halo_ok, vec_ok;
+};
+// caller-owned scratch of the K-split paths (never allocated here).  Its first RTN_CONV_SYNC_BYTES are the sync block of the
+// in-launch reductions (flags; zero before and after every launch, see rtn_conv_workspace_init): every slab starts behind it.
+struct ConvScratch { unsigned* sync; float* ptr; long long cap; };
+struct ConvChoice {
+    int impl;                      // 1 = 128-row register-staged kernel, 2 = 256-row LDS-DMA kernel per tap, 3 = 256-row shared halo
+    int BM, BN, TM;                // tile rows and columns; output rows between two tiles (the halo kernel's tiles overlap)
+    long long grid;                // whole tiles
+    int tail_main, tail_tiles, tail_slices, tail_per;      // tail split (see KParams), tail_tiles == 0: none
+    int ksplit, kt_per_split, scratch_ld;                  // split-K of generation 1, ksplit == 1: none
+    int nstages, korder_chunks, korder_kw;                 // generations 2 / 3: LDS ring depth, K-step order
+    unsigned lds_bytes;
+    size_t workspace_bytes;        // scratch this choice needs behind the sync block
+};
+
+ConvScratch conv_scratch(const rtn_conv_desc_t* d) {
+    const bool ok = d->workspace && !((uintptr_t)d->workspace & 15) && d->workspace_bytes > RTN_CONV_SYNC_BYTES;
+    if (!ok) return ConvScratch{nullptr, nullptr, 0};
+    return ConvScratch{(unsigned*)d->workspace, (float*)((char*)d->workspace + RTN_CONV_SYNC_BYTES), (long long)d->workspace_bytes - RTN_CONV_SYNC_BYTES};
+}
+
+// halo-sharing kernel: stride-1 'same' KHxKW conv over dense NHWC inputs whose taps span whole 128-byte chunks
+bool conv_halo_shape(const rtn_conv_desc_t* d, int es) {
+    if (!(d->KW >= 2 && d->KW <= 4 && d->sy == 1 && d->sx == 1 && (d->Crun * es) % 128 == 0 && d->pix_stride == d->Crun &&
+          d->pad_l >= 0 && d->pad_l < d->KW && d->pad_t >= 0 && d->pad_t < d->KH)) return false;
+    for (int i = 0; i < d->ngroups; ++i) {
+        const rtn_conv_group_t& s = d->g[i];
+        if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
+            s.in_img_stride != (long long)s.Hin * s.in_row_stride) return false;
+    }
+    return true;
+}
+
+// Step 1: everything about the descriptor that does not depend on a group's tensors.
+int conv_check_desc(rtn_handle_t h, const ConvCall& c, ConvShape* sh) {
+    const rtn_conv_desc_t* d = c.d;
+    const rtn_conv_src2_t* s2 = c.s2;
+    const rtn_conv_fp8_t* q8 = c.q8;
     if (d->dtype != RTN_BF16 && d->dtype != RTN_F32 && !(d->dtype == RTN_FP8 && q8)) return rtn_fail(h, RTN_EINVAL, "conv: bad dtype %d", d->dtype);
     if (q8) {
         if (d->dtype != RTN_FP8) return rtn_fail(h, RTN_EINVAL, "conv fp8: the descriptor's dtype must be RTN_FP8");
@@ -1338,7 +1371,6 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
         if (d->N % 8 || d->out_ld % 8) return rtn_fail(h, RTN_EINVAL, "conv fp8: N and out_ld must be multiples of 8");
     }
     const int es = rtn_dtype_size(d->dtype);
-    const bool out_f32 = (d->dtype == RTN_F32) || (d->flags & RTN_CONV_OUT_F32);
     if (d->ngroups < 1 || d->ngroups > RTN_MAX_GROUPS) return rtn_fail(h, RTN_EINVAL, "conv: ngroups %d", d->ngroups);
     if (d->batch < 1 || d->N < 1 || d->KH < 1 || d->KW < 1 || d->sy < 1 || d->sx < 1)
         return rtn_fail(h, RTN_EINVAL, "conv: non-positive dimension");
@@ -1376,124 +1408,55 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
     }
     if ((d->flags & RTN_CONV_RES_SAME) && (d->flags & RTN_CONV_RES_UPSAMPLE))
         return rtn_fail(h, RTN_EINVAL, "conv: both residual modes set");
-    const bool has_res = d->flags & (RTN_CONV_RES_SAME | RTN_CONV_RES_UPSAMPLE);
-    // caller-owned scratch of the K-split paths (never allocated here).  Its first RTN_CONV_SYNC_BYTES are the sync block of the
-    // in-launch reductions (flags; zero before and after every launch, see rtn_conv_workspace_init): every slab starts behind it.
-    const bool ws_ok = !query && d->workspace && !((uintptr_t)d->workspace & 15) && d->workspace_bytes > RTN_CONV_SYNC_BYTES;
-    unsigned* const ws_sync = ws_ok ? (unsigned*)d->workspace : nullptr;
-    float* const ws_ptr = ws_ok ? (float*)((char*)d->workspace + RTN_CONV_SYNC_BYTES) : nullptr;
-    const long long ws_cap = query ? kMaxConvWorkspace : (ws_ptr ? (long long)d->workspace_bytes - RTN_CONV_SYNC_BYTES : 0);
-    if (!query) { h->last_conv_streamk = 0; h->last_conv_tile = 0; }
+    *sh = ConvShape{es, cshift, K1, Ktot, conv_halo_shape(d, es), false};
+    return RTN_OK;
+}
 
-    KParams p;
-    memset(&p, 0, sizeof(p));
+// Step 2: the persistent kernels, in this order, each where its precondition holds and its knob (or RTN_CONV_IMPL) lets it run.
+// They check their own bounds and answer 1 = "not mine" on anything odd, which the generic checks of step 3 then name.
+// RTN_OK: launched (or, for a workspace query, *query answered: their sizes come out of their own cost models); 1: none of them
+// takes the layer; < 0: error.
+//  4 (rtn_conv_halo8.hip): every stride-1 3x3 bf16 layer with 129..256 output channels and a bias/ReLU epilogue (the grouped head
+//    towers, P3-P5, res4 branch2b), and the fp8 layers.  Measured against generation 3 / 2 in one process (tools/ab_conv.py): head
+//    layer 0.225 -> 0.150 ms, P3 0.201 -> 0.150, res4 3x3 0.063 -> 0.049, P4 0.062 -> 0.047.  RTN_CONV_H8=0 turns it off (A/B);
+//    RTN_CONV_H8_GRID limits the workgroup count (tests: several tiles per workgroup on small layers), RTN_CONV_H8_STAGGER=0 runs
+//    the two wave groups in lockstep (A/B: 0.181 ms on the head layer).
+//  6 (rtn_conv_halon.hip): the head OUTPUT convolutions (3x3, <= 48 channels, f32 result in the concatenated tensor).  RTN_CONV_HN=0.
+//  5 (rtn_conv_gemm8.hip): the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or two sources.  RTN_CONV_G8=0;
+//    RTN_CONV_G8_MI pins the tile height (2 | 3 row fragments per wave); RTN_CONV_G8_SK: its stream-K form (-1 = cost model,
+//    0 = never, 1 = wherever the shape allows).
+int conv_try_persistent(rtn_handle_t h, const ConvCall& c, int forced, const ConvScratch& ws, size_t* query) {
+    const rtn_conv_desc_t* d = c.d;
+    const bool plain = c.out8_scale == 0.f;
+    const bool bf16 = d->dtype == RTN_BF16 && !c.q8;
+    const struct { int impl; bool applies, on; } gens[3] = {
+        {4, !c.s2 && plain && (c.q8 ? d->dtype == RTN_FP8 && !query : d->dtype == RTN_BF16), rtn_env_int("RTN_CONV_H8", 1) != 0},
+        {6, !query && !c.s2 && plain && bf16 && d->N <= 48 && (d->flags & RTN_CONV_OUT_F32), rtn_env_int("RTN_CONV_HN", 1) != 0},
+        {5, plain && bf16 && d->KH == 1 && d->KW == 1, rtn_env_int("RTN_CONV_G8", 1) != 0},
+    };
+    const int grid_limit = rtn_env_int("RTN_CONV_H8_GRID", 0);
+    const bool stagger = rtn_env_int("RTN_CONV_H8_STAGGER", 1) != 0;
+    for (const auto& g : gens) {
+        if (!g.applies || !(forced == g.impl || (forced == 0 && g.on))) continue;
+        const int rc = g.impl == 4 ? rtn_conv_halo8_try(h, d, grid_limit, stagger, forced == 4, rtn_env_int("RTN_CONV_H8_MI", 0), ws.ptr, ws.cap, query,
+                                                        rtn_env_int("RTN_CONV_H8_KSPLIT", 0), c.q8)
+                     : g.impl == 6 ? rtn_conv_halon_try(h, d, grid_limit, forced == 6)
+                                   : rtn_conv_gemm8_try(h, d, c.s2, grid_limit, stagger, forced == 5, rtn_env_int("RTN_CONV_G8_MI", 0), ws.sync, ws.ptr,
+                                                        ws.cap, query, rtn_env_int("RTN_CONV_G8_SK", -1));
+        if (rc == RTN_OK && !query) h->last_conv_impl = g.impl;
+        if (rc <= 0) return rc;                        // launched (or failed): done; 1 = not eligible, the next one
+    }
+    return 1;
+}
+
+// Step 3: every group's tensors against the descriptor, then the epilogue modes that need vector-aligned outputs.
+int conv_check_groups(rtn_handle_t h, const ConvCall& c, ConvShape* sh) {
+    const rtn_conv_desc_t* d = c.d;
+    const int es = sh->es;
+    const bool has_res = d->flags & (RTN_CONV_RES_SAME | RTN_CONV_RES_UPSAMPLE);
     bool vec_ok = (d->N % 8 == 0) && (d->out_ld % 8 == 0);
-    long long mtiles = 0;
-    // ---- kernel generation: 2 = 256-row LDS-DMA kernel (compute-bound layers), 1 = 128-row register-staged kernel.
-    long long Mtot = 0;
-    for (int i = 0; i < d->ngroups; ++i) Mtot += (long long)d->g[i].Hout * d->g[i].Wout * d->batch;
-    int impl = rtn_conv_impl_override();
-    int bn2 = d->N <= 64 ? 64 : (d->N <= 128 ? 128 : 256);   // widest 256-row tile that N fills
-    {
-        // Tile choice, fitted to the same-process sweep in profiles/r1_conv_tile_sweep.txt (tools/ab_conv.py):
-        //  * the 256-row LDS-DMA kernel runs one workgroup per CU, so its time is (grid rounded up to whole
-        //    rounds of CUs) x (time of one tile); one 256x{64,128,256} tile costs 1 : 2.02 : 3.44 on a long K loop.
-        //    Wide tiles therefore only pay when the grid stays many rounds deep (the head towers);
-        //  * on short K loops the epilogue and HBM dominate and the narrow tile (more workgroups in flight) wins;
-        //  * the 128-row register-staged kernel (3 workgroups/CU) keeps the <=64-channel 1x1 layers with K >= 256
-        //    (res2*_branch2a: pure streaming, 0.074 vs 0.080 ms); the grouped head outputs moved to the 256-row kernel
-        //    once it had dynamic LDS (0.113 -> 0.087 ms).
-        const long long mt2 = (Mtot + BM2 - 1) / BM2;
-        const int cus = h->num_cus > 0 ? h->num_cus : 256;
-        if (Ktot * es >= 2048 && d->N > 64) {
-            const int cand[3] = {64, 128, 256};
-            const double wgt[3] = {1.0, 2.02, 3.44};
-            const int widest = bn2;
-            double best = 0;
-            for (int c = 0; c < 3 && cand[c] <= widest; ++c) {
-                const long long grid = mt2 * ((d->N + cand[c] - 1) / cand[c]);
-                const double cost = (double)((grid + cus - 1) / cus) * wgt[c];
-                if (c == 0 || cost < best * 0.97) { best = cost; bn2 = cand[c]; }   // ties go to the narrower tile
-            }
-        } else if (d->N > 64) {
-            bn2 = 64;
-        }
-        if (impl == 0) {
-            const bool stream64 = d->N <= 64 && d->KH * d->KW == 1 && Ktot * es >= 512;
-            // tiny-M, long-K layers (P6, P7): only the 128-row kernel has the split-K path
-            const long long grid1 = ((Mtot + BM - 1) / BM) * ((d->N + 127) / 128);
-            const bool splitk = d->ngroups == 1 && grid1 < 128 && Ktot * es / 128 >= 16;
-            impl = (stream64 || splitk) ? 1 : 2;
-        }
-    }
-    // halo-sharing kernel: stride-1 'same' KHxKW conv over dense NHWC inputs whose taps span whole 128-byte chunks
-    bool halo_ok = d->KW >= 2 && d->KW <= 4 && d->sy == 1 && d->sx == 1 && (d->Crun * es) % 128 == 0 && d->pix_stride == d->Crun &&
-                   d->pad_l >= 0 && d->pad_l < d->KW && d->pad_t >= 0 && d->pad_t < d->KH;
-    for (int i = 0; i < d->ngroups && halo_ok; ++i) {
-        const rtn_conv_group_t& s = d->g[i];
-        if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
-            s.in_img_stride != (long long)s.Hin * s.in_row_stride) halo_ok = false;
-    }
-    if (s2) impl = 2;                                  // only the 256-row per-tap kernel walks a second source
-    if (q8) {                                          // fp8 layers: the shapes the halo kernel accepts (either kernel runs them)
-        if (!halo_ok) return rtn_fail(h, RTN_EINVAL, "conv fp8: only stride-1 'same' KHxKW (KW 2..4) layers over dense NHWC inputs with whole 128-byte channel chunks");
-        impl = bn2 == 256 ? 3 : 2;                     // as for bf16: halo kernel with 256-wide tiles, per-tap kernel below
-    }
-    if (impl == 3 && !halo_ok) impl = 2;
-    // measured (tools/ab_conv.py): with 256-wide tiles (the grouped head layers) the halo kernel and the per-tap kernel are level
-    // (0.2113 vs 0.2116 ms) and the halo kernel stays; with the 64-wide tiles the cost model gives the single-group layers
-    // (res4/res5 3x3, P3, P4) the per-tap kernel is 1-10 % faster since both request their first fragments ahead of the staging
-    // issue (res5 3x3 0.0749 vs 0.0821 ms, res4 0.0609 vs 0.0634), so those went back to it.  RTN_CONV_HALO=2 forces the halo
-    // kernel wherever it applies, 0 disables it.
-    const int halo_env = rtn_env_int("RTN_CONV_HALO", 1);
-    if (impl == 2 && halo_ok && rtn_conv_impl_override() == 0 && (halo_env == 2 || (halo_env == 1 && d->N >= 256 && bn2 == 256))) impl = 3;
-    // Fourth generation (rtn_conv_halo8.hip): every stride-1 3x3 bf16 layer with 129..256 output channels and a bias/ReLU epilogue
-    // (the grouped head towers, P3-P5, res4 branch2b), persistent and on the staggered 8-phase schedule.  Measured against
-    // generation 3 / 2 in one process (tools/ab_conv.py): head layer 0.225 -> 0.150 ms, P3 0.201 -> 0.150, res4 3x3 0.063 -> 0.049,
-    // P4 0.062 -> 0.047.  RTN_CONV_H8=0 turns it off (A/B), RTN_CONV_IMPL=4 forces it like any other generation;
-    // RTN_CONV_H8_GRID limits the workgroup count (tests: several tiles per workgroup on small layers), RTN_CONV_H8_STAGGER=0 runs
-    // the two wave groups in lockstep (A/B: 0.181 ms on the head layer).
-    if (!s2 && out8_scale == 0.f && (q8 ? d->dtype == RTN_FP8 && !query : d->dtype == RTN_BF16)) {
-        const int h8 = rtn_env_int("RTN_CONV_H8", 1);
-        const int forced = rtn_conv_impl_override();
-        if (forced == 4 || (forced == 0 && h8 != 0)) {
-            const int rc = rtn_conv_halo8_try(h, d, rtn_env_int("RTN_CONV_H8_GRID", 0), rtn_env_int("RTN_CONV_H8_STAGGER", 1) != 0, forced == 4,
-                                              rtn_env_int("RTN_CONV_H8_MI", 0), ws_ptr, ws_cap, query, rtn_env_int("RTN_CONV_H8_KSPLIT", 0), q8);
-            if (rc == RTN_OK && !query) h->last_conv_impl = 4;
-            if (rc <= 0) return rc;                    // launched (or failed): done; 1 = not eligible, fall through
-        }
-    }
-    // Sixth generation (rtn_conv_halon.hip): the head OUTPUT convolutions (3x3, <= 48 channels, f32 result in the concatenated
-    // tensor).  RTN_CONV_HN=0 turns it off, RTN_CONV_IMPL=6 forces it.
-    if (!query && !s2 && !q8 && out8_scale == 0.f && d->dtype == RTN_BF16 && d->N <= 48 && (d->flags & RTN_CONV_OUT_F32)) {
-        const int hn = rtn_env_int("RTN_CONV_HN", 1);
-        const int forced = rtn_conv_impl_override();
-        if (forced == 6 || (forced == 0 && hn != 0)) {
-            const int rc = rtn_conv_halon_try(h, d, rtn_env_int("RTN_CONV_H8_GRID", 0), forced == 6);
-            if (rc == RTN_OK) h->last_conv_impl = 6;
-            if (rc <= 0) return rc;
-        }
-    }
-    // Fifth generation (rtn_conv_gemm8.hip): the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or two sources.
-    // RTN_CONV_G8=0 turns it off, RTN_CONV_IMPL=5 forces it; RTN_CONV_G8_MI pins the tile height (2 | 3 row fragments per wave).
-    // RTN_CONV_G8_SK: its stream-K form (-1 = cost model, 0 = never, 1 = wherever the shape allows).
-    if (!q8 && out8_scale == 0.f && d->dtype == RTN_BF16 && d->KH == 1 && d->KW == 1) {
-        const int g8 = rtn_env_int("RTN_CONV_G8", 1);
-        const int forced = rtn_conv_impl_override();
-        if (forced == 5 || (forced == 0 && g8 != 0)) {
-            const int rc = rtn_conv_gemm8_try(h, d, s2, rtn_env_int("RTN_CONV_H8_GRID", 0), rtn_env_int("RTN_CONV_H8_STAGGER", 1) != 0,
-                                              forced == 5, rtn_env_int("RTN_CONV_G8_MI", 0), ws_sync, ws_ptr, ws_cap, query,
-                                              rtn_env_int("RTN_CONV_G8_SK", -1));
-            if (rc == RTN_OK && !query) h->last_conv_impl = 5;
-            if (rc <= 0) return rc;
-        }
-    }
-    if (impl == 4 || impl == 7) impl = halo_ok ? 3 : 2;
-    if (impl == 5 || impl == 6) impl = 2;
-    const int TM = impl == 3 ? BM2 - (d->KW - 1) : (impl == 2 ? BM2 : BM);
     for (int i = 0; i < d->ngroups; ++i) {
         const rtn_conv_group_t& s = d->g[i];
-        KGroup& g = p.g[i];
         if (!s.in || !s.out) return rtn_fail(h, RTN_EINVAL, "conv: group %d null in/out", i);
         if (((uintptr_t)s.in & 15) || ((uintptr_t)s.out & 15) || ((uintptr_t)s.res & 15))
             return rtn_fail(h, RTN_EINVAL, "conv: group %d pointer not 16-byte aligned", i);
@@ -1506,8 +1469,7 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
         if (in_max > s.in_elems) return rtn_fail(h, RTN_EBOUNDS, "conv: group %d taps reach element %lld of a %lld-element input", i, in_max, (long long)s.in_elems);
         if (s.in_elems * es >= (long long)OOB_OFFSET) return rtn_fail(h, RTN_EINVAL, "conv: group %d input of %lld bytes exceeds the 4 GiB buffer-descriptor range", i, (long long)s.in_elems * es);
         const long long cells = (long long)s.Hout * s.Wout;
-        const long long M = cells * d->batch;
-        if (M > (1ll << 30)) return rtn_fail(h, RTN_EINVAL, "conv: M too large");
+        if (cells * d->batch > (1ll << 30)) return rtn_fail(h, RTN_EINVAL, "conv: M too large");
         const int ostep = s.out_step > 1 ? s.out_step : 1;
         if (ostep > 1 && s.out_pix_w < (s.Wout - 1) * ostep + 1) return rtn_fail(h, RTN_EINVAL, "conv: group %d out_pix_w %d too small for out_step %d", i, s.out_pix_w, ostep);
         const long long last_pix = ostep > 1 ? (long long)(s.Hout - 1) * ostep * s.out_pix_w + (long long)(s.Wout - 1) * ostep : cells - 1;
@@ -1528,10 +1490,182 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
             if (mask_max > s.mask_elems) return rtn_fail(h, RTN_EBOUNDS, "conv: group %d mask reads reach %lld of %lld", i, mask_max, (long long)s.mask_elems);
             if (s.mask_ld % 8 || s.mask_img_stride % 8) vec_ok = false;
         }
+    }
+    if (c.out8_scale != 0.f) {                         // bf16 layer with e4m3 output
+        if (d->dtype != RTN_BF16 || (d->flags & (RTN_CONV_OUT_F32 | RTN_CONV_SIGMOID)) || !(c.out8_scale > 0.f))
+            return rtn_fail(h, RTN_EINVAL, "conv fp8-out: a bf16 layer without OUT_F32 / SIGMOID and a positive scale are required");
+        if (!vec_ok) return rtn_fail(h, RTN_EINVAL, "conv fp8-out: N, out_ld, output strides and offsets must be multiples of 8");
+    }
+    if (c.q8 && !vec_ok) return rtn_fail(h, RTN_EINVAL, "conv fp8: output strides and offsets must be multiples of 8 elements");
+    if ((d->flags & RTN_CONV_RELU_MASK) && !vec_ok) return rtn_fail(h, RTN_EINVAL, "conv: RELU_MASK needs N, out_ld, strides multiples of 8");
+    if ((long long)d->w_rows * sh->Ktot * es >= (long long)OOB_OFFSET) return rtn_fail(h, RTN_EINVAL, "conv: weights exceed the 4 GiB buffer-descriptor range");
+    const int kw_inv = (65536 + d->KW - 1) / d->KW;    // the kernels' reciprocal must reproduce kpos / KW for every tap index
+    for (int kp = 0; kp < d->KH * d->KW; ++kp)
+        if (((kp * kw_inv) >> 16) != kp / d->KW) return rtn_fail(h, RTN_EINVAL, "conv: KW %d unsupported", d->KW);
+    sh->vec_ok = vec_ok;
+    return RTN_OK;
+}
+
+// Step 4: which of generations 1 / 2 / 3 runs a checked layer, on which tile, in which decomposition, with how much scratch.
+// A function of the layer, the chip (`cus`), the scratch on offer (`ws_cap` bytes behind the sync block; rtn_conv2d_workspace_bytes
+// offers kMaxConvWorkspace) and the knobs: it launches nothing and leaves the handle alone, so the sizing call and the launch agree.
+// `forced`: RTN_CONV_IMPL (0 = heuristic).
+ConvChoice conv_choose(const ConvCall& c, const ConvShape& sh, int cus, long long ws_cap, int forced) {
+    const rtn_conv_desc_t* d = c.d;
+    const int es = sh.es;
+    const long long Ktot = sh.Ktot;
+    ConvChoice ch;
+    memset(&ch, 0, sizeof(ch));
+    ch.ksplit = 1;
+    long long Mtot = 0;
+    for (int i = 0; i < d->ngroups; ++i) Mtot += (long long)d->g[i].Hout * d->g[i].Wout * d->batch;
+    // Tile choice, fitted to the same-process sweep in profiles/r1_conv_tile_sweep.txt (tools/ab_conv.py):
+    //  * the 256-row LDS-DMA kernel runs one workgroup per CU, so its time is (grid rounded up to whole
+    //    rounds of CUs) x (time of one tile); one 256x{64,128,256} tile costs 1 : 2.02 : 3.44 on a long K loop.
+    //    Wide tiles therefore only pay when the grid stays many rounds deep (the head towers);
+    //  * on short K loops the epilogue and HBM dominate and the narrow tile (more workgroups in flight) wins;
+    //  * the 128-row register-staged kernel (3 workgroups/CU) keeps the <=64-channel 1x1 layers with K >= 256
+    //    (res2*_branch2a: pure streaming, 0.074 vs 0.080 ms); the grouped head outputs moved to the 256-row kernel
+    //    once it had dynamic LDS (0.113 -> 0.087 ms).
+    int bn2 = d->N <= 64 ? 64 : (d->N <= 128 ? 128 : 256);   // widest 256-row tile that N fills
+    if (Ktot * es >= 2048 && d->N > 64) {
+        const long long mt2 = (Mtot + BM2 - 1) / BM2;
+        const int cand[3] = {64, 128, 256};
+        const double wgt[3] = {1.0, 2.02, 3.44};
+        const int widest = bn2;
+        double best = 0;
+        for (int k = 0; k < 3 && cand[k] <= widest; ++k) {
+            const long long grid = mt2 * ((d->N + cand[k] - 1) / cand[k]);
+            const double cost = (double)((grid + cus - 1) / cus) * wgt[k];
+            if (k == 0 || cost < best * 0.97) { best = cost; bn2 = cand[k]; }   // ties go to the narrower tile
+        }
+    } else if (d->N > 64) {
+        bn2 = 64;
+    }
+    int impl = forced;
+    if (impl == 0) {
+        const bool stream64 = d->N <= 64 && d->KH * d->KW == 1 && Ktot * es >= 512;
+        // tiny-M, long-K layers (P6, P7): only the 128-row kernel has the split-K path
+        const long long grid1 = ((Mtot + BM - 1) / BM) * ((d->N + 127) / 128);
+        const bool splitk = d->ngroups == 1 && grid1 < 128 && Ktot * es / 128 >= 16;
+        impl = (stream64 || splitk) ? 1 : 2;
+    }
+    if (c.s2) impl = 2;                                // only the 256-row per-tap kernel walks a second source
+    if (c.q8) impl = bn2 == 256 ? 3 : 2;               // as for bf16: halo kernel with 256-wide tiles, per-tap kernel below
+    if (impl == 3 && !sh.halo_ok) impl = 2;
+    // measured (tools/ab_conv.py): with 256-wide tiles (the grouped head layers) the halo kernel and the per-tap kernel are level
+    // (0.2113 vs 0.2116 ms) and the halo kernel stays; with the 64-wide tiles the cost model gives the single-group layers
+    // (res4/res5 3x3, P3, P4) the per-tap kernel is 1-10 % faster since both request their first fragments ahead of the staging
+    // issue (res5 3x3 0.0749 vs 0.0821 ms, res4 0.0609 vs 0.0634), so those went back to it.  RTN_CONV_HALO=2 forces the halo
+    // kernel wherever it applies, 0 disables it.
+    const int halo_env = rtn_env_int("RTN_CONV_HALO", 1);
+    if (impl == 2 && sh.halo_ok && forced == 0 && (halo_env == 2 || (halo_env == 1 && d->N >= 256 && bn2 == 256))) impl = 3;
+    if (impl == 4) impl = sh.halo_ok ? 3 : 2;          // a forced persistent generation that did not take the layer
+    if (impl == 5 || impl == 6) impl = 2;
+    ch.impl = impl;
+    ch.BM = impl >= 2 ? BM2 : BM;
+    ch.TM = impl == 3 ? BM2 - (d->KW - 1) : ch.BM;
+    ch.BN = impl >= 2 ? bn2 : (d->N <= 64 ? 64 : 128);
+    if (impl >= 2) {
+        const int bn_env = rtn_env_int("RTN_CONV_BN2", 0);   // A/B override of the 256-row kernel's tile width
+        if ((bn_env == 64 || bn_env == 128 || bn_env == 256) && bn_env <= ((d->N + 63) / 64) * 64) ch.BN = bn_env;
+    }
+    const int BN = ch.BN, nkt = (int)(Ktot * es / 128);
+    long long mtiles = 0;
+    for (int i = 0; i < d->ngroups; ++i) mtiles += ((long long)d->g[i].Hout * d->g[i].Wout * d->batch + ch.TM - 1) / ch.TM;
+    const long long grid = ch.grid = mtiles * ((d->N + BN - 1) / BN);
+
+    if (impl == 1) {
+        // split-K: a long K loop on a grid that cannot fill the chip (P6: 36 workgroups x 288 K steps)
+        const int ksplit_env = rtn_env_int("RTN_CONV_SPLITK", -1);
+        if (d->ngroups == 1 && grid < 128 && nkt >= 16 && ksplit_env != 0) {
+            int ksplit = (int)((512 + grid - 1) / grid);
+            if (ksplit > nkt / 4) ksplit = nkt / 4;
+            if (ksplit_env > 1) ksplit = ksplit_env < nkt ? ksplit_env : nkt;
+            const int ld = ((d->N + 7) / 8) * 8;
+            const long long slab = (long long)d->g[0].Hout * d->g[0].Wout * d->batch * ld * 4;
+            while (ksplit > 1 && slab * ksplit > ws_cap) --ksplit;
+            if (ksplit >= 2) {                                   // every slice must own at least one K step (it writes its whole slab)
+                const int per = (nkt + ksplit - 1) / ksplit;
+                ksplit = (nkt + per - 1) / per;
+                ch.ksplit = ksplit;
+                ch.kt_per_split = (nkt + ksplit - 1) / ksplit;
+                ch.scratch_ld = ld;
+                ch.workspace_bytes = (size_t)(slab * ksplit);
+            }
+        }
+        return ch;
+    }
+    // ---- generations 2 / 3.  LDS ring: two stages, never more than the K loop has steps (measured: deeper rings lose, they cost the
+    // second resident workgroup on the 64-wide tile; a third B stage beside the halos changed nothing measurable).  K-step order:
+    // (chunk, kw) inside a kernel row when a tap spans whole 128-byte chunks.
+    const unsigned epib = 8u * 32u * (unsigned)(BN / 2 + 4) * 4u;         // the wave-private epilogue slices (EPI_BYTES)
+    if (impl == 3) {
+        ch.nstages = 2;
+        ch.lds_bytes = 2u * BM2 * 128u + (unsigned)ch.nstages * (unsigned)BN * 128u;
+        ch.korder_chunks = d->Crun * es / 128;
+        ch.korder_kw = d->KW;
+    } else {
+        const unsigned sb = (unsigned)(BM2 + BN) * 128u;
+        int nst = 2;
+        while (nst > 1 && (unsigned)nst * sb > 160u * 1024u) --nst;
+        if (nst > nkt) nst = nkt;
+        if (nst < 2 && nkt > 1) nst = 2;
+        ch.nstages = nst < 2 ? 2 : nst;                // a single-step K loop never touches its second buffer
+        ch.lds_bytes = (unsigned)nst * sb;
+        ch.korder_chunks = nkt; ch.korder_kw = 1;
+        if (d->KW > 1 && (d->Crun * es) % 128 == 0) {
+            ch.korder_chunks = d->Crun * es / 128;
+            ch.korder_kw = d->KW;
+        }
+    }
+    if (ch.lds_bytes < epib) ch.lds_bytes = epib;
+    // ---- tail split (see KParams): the grid is a few tiles over a whole number of rounds of the resident slots
+    if (d->ngroups == 1 && !c.s2 && !c.q8 && rtn_env_int("RTN_CONV_TAIL", 1) != 0) {
+        long long slots = (long long)cus * (BN == 64 ? 2 : 1);
+        { const int sl_env = rtn_env_int("RTN_CONV_TAIL_SLOTS", 0); if (sl_env > 0) slots = sl_env; }   // tests: pretend a small chip
+        const long long rest = grid % slots;
+        const int units = impl == 3 ? d->KH * (d->Crun * es / 128) : nkt;        // (kh, chunk) groups | K steps
+        const int min_units = impl == 3 ? 1 : 2;
+        // measured (tools/ab_conv.py RTN_CONV_TAIL=0|1): -13 % on res4 3x3 / P4, -5 % on the res4 1x1 (one full round + a few tiles);
+        // +3..5 % where two or more full rounds precede the tail (res2, res3, C3: the extra launch costs more than the short
+        // last round), so only grids between one and two rounds are split
+        if (grid > slots && grid < 2 * slots && rest > 0 && rest * 4 <= slots && units >= 4 * min_units) {
+            long long S = slots / rest;
+            if (S > units / min_units) S = units / min_units;
+            if (S > 16) S = 16;
+            const int per = (int)((units + S - 1) / S);
+            S = (units + per - 1) / per;
+            const long long slab_bytes = rest * S * (long long)BM2 * BN * 4;
+            if (S >= 2 && slab_bytes <= ws_cap) {
+                ch.tail_main = (int)(grid - rest);
+                ch.tail_tiles = (int)rest;
+                ch.tail_slices = (int)S;
+                ch.tail_per = per;
+                ch.workspace_bytes = (size_t)slab_bytes;
+            }
+        }
+    }
+    return ch;
+}
+
+// Step 5: the kernels' argument block from descriptor + choice.
+void conv_fill_params(KParams* kp, const ConvCall& c, const ConvShape& sh, const ConvChoice& ch, float* scratch) {
+    const rtn_conv_desc_t* d = c.d;
+    const int es = sh.es;
+    const bool has_res = d->flags & (RTN_CONV_RES_SAME | RTN_CONV_RES_UPSAMPLE);
+    KParams& p = *kp;
+    memset(&p, 0, sizeof(p));
+    long long mtiles = 0;
+    bool dense_out = !(d->flags & RTN_CONV_RES_UPSAMPLE), dense_in = (d->KH == 1 && d->KW == 1 && d->sy == 1 && d->sx == 1 && d->pad_t == 0 && d->pad_l == 0);
+    for (int i = 0; i < d->ngroups; ++i) {
+        const rtn_conv_group_t& s = d->g[i];
+        KGroup& g = p.g[i];
+        const long long cells = (long long)s.Hout * s.Wout;
         g.mask = (const char*)s.mask;
         g.mask_img_stride = s.mask_img_stride;
         g.mask_ld = s.mask_ld;
-        g.out_step = ostep;
+        g.out_step = s.out_step > 1 ? s.out_step : 1;
         g.out_pix_w = s.out_pix_w;
         g.in = (const char*)s.in;
         g.out = (char*)s.out;
@@ -1547,40 +1681,33 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
         // legacy TF nearest: float32 ratio in/out (SURVEY §8a notes)
         g.rs_h = s.Hout > 0 ? (float)s.Hres / (float)s.Hout : 0.f;
         g.rs_w = s.Wout > 0 ? (float)s.Wres / (float)s.Wout : 0.f;
-        g.M = (int)M;
+        g.M = (int)(cells * d->batch);
         g.tile_begin = (int)mtiles;
-        mtiles += (M + TM - 1) / TM;
+        mtiles += (g.M + ch.TM - 1) / ch.TM;
+        if (s.out_step > 1 || s.out_off != 0 || s.out_img_stride != cells * d->out_ld) dense_out = false;
+        if (has_res && (s.res_img_stride != cells * s.res_ld)) dense_out = false;
+        if ((d->flags & RTN_CONV_RELU_MASK) && (s.mask_img_stride != cells * s.mask_ld)) dense_out = false;
+        if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
+            s.in_img_stride != (long long)s.Hin * s.in_row_stride) dense_in = false;
     }
-    (void)out_f32;
-    if (out8_scale != 0.f) {                           // bf16 layer with e4m3 output
-        if (d->dtype != RTN_BF16 || (d->flags & (RTN_CONV_OUT_F32 | RTN_CONV_SIGMOID)) || !(out8_scale > 0.f))
-            return rtn_fail(h, RTN_EINVAL, "conv fp8-out: a bf16 layer without OUT_F32 / SIGMOID and a positive scale are required");
-        if (!vec_ok) return rtn_fail(h, RTN_EINVAL, "conv fp8-out: N, out_ld, output strides and offsets must be multiples of 8");
-        p.out_fp8 = 1;
-        p.out_scale = out8_scale;
-    }
-    if (q8 && !vec_ok) return rtn_fail(h, RTN_EINVAL, "conv fp8: output strides and offsets must be multiples of 8 elements");
-    if (q8) { p.acc_scale = q8->acc_scale; p.out_scale = q8->out_scale; p.out_fp8 = q8->out_dtype == RTN_FP8 ? 1 : 0; }
-    if ((d->flags & RTN_CONV_RELU_MASK) && !vec_ok) return rtn_fail(h, RTN_EINVAL, "conv: RELU_MASK needs N, out_ld, strides multiples of 8");
-    int BN = impl >= 2 ? bn2 : (d->N <= 64 ? 64 : 128);
-    if (impl >= 2) {
-        const int bn_env = rtn_env_int("RTN_CONV_BN2", 0);   // A/B override of the 256-row kernel's tile width
-        if ((bn_env == 64 || bn_env == 128 || bn_env == 256) && bn_env <= ((d->N + 63) / 64) * 64) BN = bn_env;
-    }
+    p.dense_out = dense_out ? 1 : 0;
+    p.dense_in = dense_in ? 1 : 0;
+    if (c.out8_scale != 0.f) { p.out_fp8 = 1; p.out_scale = c.out8_scale; }
+    if (c.q8) { p.acc_scale = c.q8->acc_scale; p.out_scale = c.q8->out_scale; p.out_fp8 = c.q8->out_dtype == RTN_FP8 ? 1 : 0; }
     p.w = (const char*)d->w;
     p.bias = d->bias;
-    if ((long long)d->w_rows * Ktot * es >= (long long)OOB_OFFSET) return rtn_fail(h, RTN_EINVAL, "conv: weights exceed the 4 GiB buffer-descriptor range");
-    p.w_bytes = (unsigned)((long long)d->w_rows * Ktot * es);
+    p.w_bytes = (unsigned)((long long)d->w_rows * sh.Ktot * es);
     p.ngroups = d->ngroups;
-    p.ntiles_n = (d->N + BN - 1) / BN;
+    p.ntiles_n = (d->N + ch.BN - 1) / ch.BN;
     p.N = d->N;
-    p.Kbytes = (int)(Ktot * es);
+    p.Kbytes = (int)(sh.Ktot * es);
     p.nkt = p.Kbytes / 128;
-    p.cshift = cshift;
-    if (s2) {
+    p.cshift = sh.cshift;
+    if (c.s2) {
+        const rtn_conv_src2_t* s2 = c.s2;
         p.in2 = (const char*)s2->in;
         p.in2_bytes = (unsigned)(s2->in_elems * es);
-        p.nkt1 = (int)(K1 * es / 128);
+        p.nkt1 = (int)(sh.K1 * es / 128);
         p.in2_img_stride_b = s2->in_img_stride * es;
         p.in2_row_stride_b = (int)((long long)s2->in_row_stride * es);
         p.in2_pix_stride_b = (int)((long long)s2->pix_stride * es);
@@ -1591,217 +1718,163 @@ static int conv_launch(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
     p.KW = d->KW;
     p.KH = d->KH;
     p.kw_inv = (65536 + d->KW - 1) / d->KW;
-    {   // the reciprocal must reproduce kpos / KW for every tap index
-        for (int kp = 0; kp < d->KH * d->KW; ++kp)
-            if (((kp * p.kw_inv) >> 16) != kp / d->KW) return rtn_fail(h, RTN_EINVAL, "conv: KW %d unsupported", d->KW);
-    }
-    p.pix_stride_b = (int)pix_b;
+    p.pix_stride_b = (int)((long long)d->pix_stride * es);
     p.sy = d->sy; p.sx = d->sx; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
     p.out_ld = d->out_ld;
     p.flags = d->flags;
-    p.vec_ok = vec_ok ? 1 : 0;
-    {
-        bool dense_out = !(d->flags & RTN_CONV_RES_UPSAMPLE), dense_in = (d->KH == 1 && d->KW == 1 && d->sy == 1 && d->sx == 1 && d->pad_t == 0 && d->pad_l == 0);
-        for (int i = 0; i < d->ngroups; ++i) {
-            const rtn_conv_group_t& s = d->g[i];
-            const long long cells = (long long)s.Hout * s.Wout;
-            if (s.out_step > 1 || s.out_off != 0 || s.out_img_stride != cells * d->out_ld) dense_out = false;
-            if (has_res && (s.res_img_stride != cells * s.res_ld)) dense_out = false;
-            if ((d->flags & RTN_CONV_RELU_MASK) && (s.mask_img_stride != cells * s.mask_ld)) dense_out = false;
-            if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
-                s.in_img_stride != (long long)s.Hin * s.in_row_stride) dense_in = false;
-        }
-        p.dense_out = dense_out ? 1 : 0;
-        p.dense_in = dense_in ? 1 : 0;
+    p.vec_ok = sh.vec_ok ? 1 : 0;
+    p.nstages = ch.nstages;
+    p.korder_chunks = ch.korder_chunks;
+    p.korder_kw = ch.korder_kw;
+    if (ch.tail_tiles) {
+        p.tail_mode = 1;
+        p.tail_main = ch.tail_main;
+        p.tail_tiles = ch.tail_tiles;
+        p.tail_slices = ch.tail_slices;
+        p.tail_per = ch.tail_per;
+        p.scratch = scratch;
     }
-    const long long grid = mtiles * p.ntiles_n;
-    if (grid < 1 || grid > 0x7fffffffll) return rtn_fail(h, RTN_EINVAL, "conv: grid %lld", grid);
+    if (ch.ksplit > 1) {
+        p.ksplit = ch.ksplit;
+        p.kt_per_split = ch.kt_per_split;
+        p.scratch_ld = ch.scratch_ld;
+        p.scratch = scratch;
+    }
+}
 
-    dim3 gdim((unsigned)grid);
-    // ---- tail split (see KParams): the grid is a few tiles over a whole number of rounds of the resident slots
-    int tail_tiles = 0;
-    if (impl >= 2 && d->ngroups == 1 && !s2 && !q8 && rtn_env_int("RTN_CONV_TAIL", 1) != 0) {
-        long long slots = (long long)(h->num_cus > 0 ? h->num_cus : 256) * (BN == 64 ? 2 : 1);
-        { const int sl_env = rtn_env_int("RTN_CONV_TAIL_SLOTS", 0); if (sl_env > 0) slots = sl_env; }   // tests: pretend a small chip
-        const long long rest = grid % slots;
-        const int units = impl == 3 ? d->KH * (d->Crun * es / 128) : p.nkt;      // (kh, chunk) groups | K steps
-        const int min_units = impl == 3 ? 1 : 2;
-        // measured (tools/ab_conv.py RTN_CONV_TAIL=0|1): -13 % on res4 3x3 / P4, -5 % on the res4 1x1 (one full round + a few tiles);
-        // +3..5 % where two or more full rounds precede the tail (res2, res3, C3: the extra launch costs more than the short
-        // last round), so only grids between one and two rounds are split
-        if (grid > slots && grid < 2 * slots && rest > 0 && rest * 4 <= slots && units >= 4 * min_units) {
-            long long S = slots / rest;
-            if (S > units / min_units) S = units / min_units;
-            if (S > 16) S = 16;
-            const int per = (int)((units + S - 1) / S);
-            S = (units + per - 1) / per;
-            const long long slab_bytes = rest * S * (long long)BM2 * BN * 4;
-            if (query && S >= 2 && slab_bytes <= ws_cap) { *query = (size_t)slab_bytes; return RTN_OK; }
-            float* scratch = S >= 2 ? ws_ptr : nullptr;
-            if (scratch && slab_bytes <= ws_cap) {
-                tail_tiles = (int)rest;
-                p.tail_mode = 1;
-                p.tail_main = (int)(grid - rest);
-                p.tail_tiles = tail_tiles;
-                p.tail_slices = (int)S;
-                p.tail_per = per;
-                p.scratch = scratch;
-                gdim = dim3((unsigned)(grid - rest + rest * S));
+// Step 6: the launches.  Run-time values -> kernel instance, one rung per instance.
+// generations 2 / 3: one launch, or - with a tail split - the main launch (tail tiles cut into K slices) and the finish launch
+int conv_launch_gen23(rtn_handle_t h, KParams& p, const ConvChoice& ch, int es, bool dual) {
+    constexpr int LIM = 160 * 1024;
+    const dim3 bdim(NT2);
+    const int BN = ch.BN;
+    const unsigned lds = ch.lds_bytes;
+    for (int pass = 0; pass < (ch.tail_tiles ? 2 : 1); ++pass) {
+        dim3 gdim((unsigned)(ch.grid + (long long)ch.tail_tiles * (ch.tail_slices - 1)));
+        if (pass == 1) {                               // the finish launch: one workgroup per tail tile
+            RTN_CHECK_LAUNCH(h, "conv (tail-split main launch)");
+            p.tail_mode = 2;
+            gdim = dim3((unsigned)ch.tail_tiles);
+        }
+        int rc;
+        if (ch.impl == 3) {
+            if (es == 1) {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm3_kernel<1, 64>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm3_kernel<1, 128>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm3_kernel<1, 256>>(h, gdim, bdim, lds, LIM, p);
+            } else if (es == 2) {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm3_kernel<2, 64>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm3_kernel<2, 128>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm3_kernel<2, 256>>(h, gdim, bdim, lds, LIM, p);
+            } else {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm3_kernel<4, 64>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm3_kernel<4, 128>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm3_kernel<4, 256>>(h, gdim, bdim, lds, LIM, p);
             }
-        }
-    }
-    if (query && impl >= 2) return RTN_OK;
-    for (int pass = 0; pass < (tail_tiles ? 2 : 1); ++pass) {
-    if (pass == 1) {                                   // the finish launch: one workgroup per tail tile
-        RTN_CHECK_LAUNCH(h, "conv (tail-split main launch)");
-        p.tail_mode = 2;
-        gdim = dim3((unsigned)tail_tiles);
-    }
-    if (impl == 3) {
-        dim3 bdim(NT2);
-        const unsigned epib = 8u * 32u * (unsigned)(BN / 2 + 4) * 4u;
-        const int nbst = 2;      // (a third B stage fits beside the halos for every tile width and changed nothing measurable: round 1)
-        p.nstages = nbst;
-        unsigned ldsb = 2u * BM2 * 128u + (unsigned)nbst * (unsigned)BN * 128u;
-        if (ldsb < epib) ldsb = epib;
-        p.korder_chunks = d->Crun * es / 128;
-        p.korder_kw = d->KW;
-#define RTN_L3(E, B)                                                                                     \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_igemm3_kernel<E, B>,                        \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_igemm3_kernel<E, B>), gdim, bdim, ldsb, h->stream, p);                  \
-    } while (0)
-        if (es == 1) { if (BN == 64) RTN_L3(1, 64); else if (BN == 128) RTN_L3(1, 128); else RTN_L3(1, 256); }
-        else if (es == 2) { if (BN == 64) RTN_L3(2, 64); else if (BN == 128) RTN_L3(2, 128); else RTN_L3(2, 256); }
-        else         { if (BN == 64) RTN_L3(4, 64); else if (BN == 128) RTN_L3(4, 128); else RTN_L3(4, 256); }
-#undef RTN_L3
-    } else if (impl == 2) {
-        dim3 bdim(NT2);
-        // LDS: one stage when the K loop is a single step (the streaming 1x1 layers: more workgroups per CU), else two
-        // LDS ring depth: as many stages as fit 160 KB (64-wide: 3 by default, 128-wide: 3, 256-wide: 2), never more
-        // than the K loop has steps.
-        const unsigned epib = 8u * 32u * (unsigned)(BN / 2 + 4) * 4u;     // the wave-private epilogue slices (EPI_BYTES)
-        const unsigned sb = (unsigned)(BM2 + BN) * 128u;
-        int nst = 2;   // measured: deeper rings lose (they cost the second resident workgroup on the 64-wide tile)
-        while (nst > 1 && (unsigned)nst * sb > 160u * 1024u) --nst;
-        if (nst > p.nkt) nst = p.nkt;
-        if (nst < 2 && p.nkt > 1) nst = 2;
-        // K-step order: (chunk, kw) inside a kernel row when a tap spans whole 128-byte chunks
-        p.korder_chunks = p.nkt; p.korder_kw = 1;
-        if (d->KW > 1 && (d->Crun * es) % 128 == 0) {
-            p.korder_chunks = d->Crun * es / 128;
-            p.korder_kw = d->KW;
-        }
-        p.nstages = nst < 2 ? 2 : nst;      // a single-step K loop never touches its second buffer
-        unsigned ldsb = (unsigned)nst * sb;
-        if (ldsb < epib) ldsb = epib;
-#define RTN_L2K(E, B, I)                                                                                 \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_igemm2_kernel<E, B, I>,                     \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));           \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_igemm2_kernel<E, B, I>), gdim, bdim, ldsb, h->stream, p);               \
-    } while (0)
-#define RTN_L2(E, B)                                                                                     \
-    do {                                                                                                 \
-        RTN_L2K(E, B, false);   /* (DMA issues interleaved with the MFMA groups: measured 12 % slower in round 1, instance removed) */ \
-    } while (0)
-#define RTN_L2D(E, B)                                                                                    \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_igemm2_kernel<E, B, false, true>,           \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_igemm2_kernel<E, B, false, true>), gdim, bdim, ldsb, h->stream, p);     \
-    } while (0)
-        if (s2) {
-            if (es == 2) { if (BN == 64) RTN_L2D(2, 64); else if (BN == 128) RTN_L2D(2, 128); else RTN_L2D(2, 256); }
-            else         { if (BN == 64) RTN_L2D(4, 64); else if (BN == 128) RTN_L2D(4, 128); else RTN_L2D(4, 256); }
-        } else
-        if (es == 1) { if (BN == 64) RTN_L2K(1, 64, false); else if (BN == 128) RTN_L2K(1, 128, false); else RTN_L2K(1, 256, false); }
-        else if (es == 2) { if (BN == 64) RTN_L2(2, 64); else if (BN == 128) RTN_L2(2, 128); else RTN_L2(2, 256); }
-        else         { if (BN == 64) RTN_L2(4, 64); else if (BN == 128) RTN_L2(4, 128); else RTN_L2(4, 256); }
-#undef RTN_L2D
-#undef RTN_L2
-#undef RTN_L2K
-    }
-    }   // pass
-    if (impl < 2) {
-        if (query && !(d->ngroups == 1 && grid < 128 && p.nkt >= 16)) return RTN_OK;
-        dim3 bdim(NT);
-        // split-K: a long K loop on a grid that cannot fill the chip (P6: 36 workgroups x 288 K steps)
-        int ksplit = 1;
-        const int ksplit_env = rtn_env_int("RTN_CONV_SPLITK", -1);
-        if (d->ngroups == 1 && grid < 128 && p.nkt >= 16 && ksplit_env != 0) {
-            ksplit = (int)((512 + grid - 1) / grid);
-            if (ksplit > p.nkt / 4) ksplit = p.nkt / 4;
-            if (ksplit_env > 1) ksplit = ksplit_env < p.nkt ? ksplit_env : p.nkt;
-            const long long slab = (long long)p.g[0].M * (((d->N + 7) / 8) * 8) * 4;
-            while (ksplit > 1 && slab * ksplit > ws_cap) --ksplit;
-            if (ksplit >= 2) {                                   // every slice must own at least one K step (it writes its whole slab)
-                const int per = (p.nkt + ksplit - 1) / ksplit;
-                ksplit = (p.nkt + per - 1) / per;
+        } else if (dual) {                             // (no fp8 instance walks a second source)
+            if (es == 2) {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm2_kernel<2, 64, false, true>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm2_kernel<2, 128, false, true>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm2_kernel<2, 256, false, true>>(h, gdim, bdim, lds, LIM, p);
+            } else {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm2_kernel<4, 64, false, true>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm2_kernel<4, 128, false, true>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm2_kernel<4, 256, false, true>>(h, gdim, bdim, lds, LIM, p);
             }
-            if (query) { if (ksplit >= 2) *query = (size_t)(slab * ksplit); return RTN_OK; }
-            float* scratch = ksplit >= 2 ? ws_ptr : nullptr;
-            if (ksplit < 2 || !scratch) ksplit = 1;
-            p.scratch = scratch;
-        }
-        if (query) return RTN_OK;                      // query mode never launches (RTN_CONV_SPLITK=0 skips the block above)
-        if (ksplit > 1) {
-            p.ksplit = ksplit;
-            p.kt_per_split = (p.nkt + ksplit - 1) / ksplit;
-            p.scratch_ld = ((d->N + 7) / 8) * 8;
-            gdim = dim3((unsigned)grid, (unsigned)ksplit);
-        }
-        if (es == 2) {
-            if (BN == 64) hipLaunchKernelGGL((conv_igemm_kernel<2, 64>), gdim, bdim, 0, h->stream, p);
-            else          hipLaunchKernelGGL((conv_igemm_kernel<2, 128>), gdim, bdim, 0, h->stream, p);
         } else {
-            if (BN == 64) hipLaunchKernelGGL((conv_igemm_kernel<4, 64>), gdim, bdim, 0, h->stream, p);
-            else          hipLaunchKernelGGL((conv_igemm_kernel<4, 128>), gdim, bdim, 0, h->stream, p);
+            if (es == 1) {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm2_kernel<1, 64, false>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm2_kernel<1, 128, false>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm2_kernel<1, 256, false>>(h, gdim, bdim, lds, LIM, p);
+            } else if (es == 2) {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm2_kernel<2, 64, false>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm2_kernel<2, 128, false>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm2_kernel<2, 256, false>>(h, gdim, bdim, lds, LIM, p);
+            } else {
+                if (BN == 64)       rc = rtn_launch_lds<conv_igemm2_kernel<4, 64, false>>(h, gdim, bdim, lds, LIM, p);
+                else if (BN == 128) rc = rtn_launch_lds<conv_igemm2_kernel<4, 128, false>>(h, gdim, bdim, lds, LIM, p);
+                else                rc = rtn_launch_lds<conv_igemm2_kernel<4, 256, false>>(h, gdim, bdim, lds, LIM, p);
+            }
         }
-        if (ksplit > 1) {
-            RTN_CHECK_LAUNCH(h, "conv_igemm_kernel (split-K)");
-            const long long work = (long long)p.g[0].M * (p.scratch_ld / 8);
-            long long fg = (work + 255) / 256;
-            if (fg > 2048) fg = 2048;
-            if (es == 2) hipLaunchKernelGGL((conv_splitk_finish_kernel<2>), dim3((unsigned)fg), dim3(256), 0, h->stream, p);
-            else         hipLaunchKernelGGL((conv_splitk_finish_kernel<4>), dim3((unsigned)fg), dim3(256), 0, h->stream, p);
-        }
+        if (rc != RTN_OK) return rc;
     }
-    RTN_CHECK_LAUNCH(h, "conv_igemm_kernel");
-    h->last_conv_impl = impl;
-    h->last_conv_tile = ((impl >= 2 ? BM2 : BM) << 16) | BN;
     return RTN_OK;
+}
+
+int conv_launch_gen1(rtn_handle_t h, const KParams& p, const ConvChoice& ch, int es) {
+    const dim3 gdim((unsigned)ch.grid, (unsigned)ch.ksplit), bdim(NT);
+    if (es == 2) {
+        if (ch.BN == 64) hipLaunchKernelGGL((conv_igemm_kernel<2, 64>), gdim, bdim, 0, h->stream, p);
+        else             hipLaunchKernelGGL((conv_igemm_kernel<2, 128>), gdim, bdim, 0, h->stream, p);
+    } else {
+        if (ch.BN == 64) hipLaunchKernelGGL((conv_igemm_kernel<4, 64>), gdim, bdim, 0, h->stream, p);
+        else             hipLaunchKernelGGL((conv_igemm_kernel<4, 128>), gdim, bdim, 0, h->stream, p);
+    }
+    if (ch.ksplit > 1) {                               // the slices' slabs -> output, in slice order
+        RTN_CHECK_LAUNCH(h, "conv_igemm_kernel (split-K)");
+        const long long work = (long long)p.g[0].M * (p.scratch_ld / 8);
+        long long fg = (work + 255) / 256;
+        if (fg > 2048) fg = 2048;
+        if (es == 2) hipLaunchKernelGGL((conv_splitk_finish_kernel<2>), dim3((unsigned)fg), dim3(256), 0, h->stream, p);
+        else         hipLaunchKernelGGL((conv_splitk_finish_kernel<4>), dim3((unsigned)fg), dim3(256), 0, h->stream, p);
+    }
+    return RTN_OK;
+}
+
+// Steps 1-4.  RTN_OK: a persistent kernel took the layer (launched it, or answered *query); 1: `*ch` says how generations 1-3 run
+// it; < 0: error.  With `query` nothing is launched and the handle's last_conv_* stay.
+int conv_plan(rtn_handle_t h, const ConvCall& c, size_t* query, ConvShape* sh, ConvScratch* ws, ConvChoice* ch) {
+    rtn_env_sync();
+    if (int rc = conv_check_desc(h, c, sh)) return rc;
+    *ws = query ? ConvScratch{nullptr, nullptr, kMaxConvWorkspace} : conv_scratch(c.d);
+    if (!query) { h->last_conv_streamk = 0; h->last_conv_tile = 0; }
+    if (c.q8 && !sh->halo_ok)                          // fp8 layers: the shapes the halo kernel accepts (either kernel runs them)
+        return rtn_fail(h, RTN_EINVAL, "conv fp8: only stride-1 'same' KHxKW (KW 2..4) layers over dense NHWC inputs with whole 128-byte channel chunks");
+    const int forced = rtn_conv_impl_override();
+    if (int rc = conv_try_persistent(h, c, forced, *ws, query); rc <= 0) return rc;
+    if (int rc = conv_check_groups(h, c, sh)) return rc;
+    *ch = conv_choose(c, *sh, h->num_cus > 0 ? h->num_cus : 256, ws->cap, forced);
+    if (ch->grid < 1 || ch->grid > 0x7fffffffll) return rtn_fail(h, RTN_EINVAL, "conv: grid %lld", ch->grid);
+    return 1;
+}
+}  // namespace
+
+static int conv_launch(rtn_handle_t h, const ConvCall& c) {
+    if (!h) return RTN_EINVAL;
+    if (!c.d) return rtn_fail(h, RTN_EINVAL, "conv: null descriptor");
+    ConvShape sh; ConvScratch ws; ConvChoice ch;
+    if (int rc = conv_plan(h, c, nullptr, &sh, &ws, &ch); rc <= 0) return rc;
+    KParams p;
+    conv_fill_params(&p, c, sh, ch, ws.ptr);
+    if (int rc = ch.impl == 1 ? conv_launch_gen1(h, p, ch, sh.es) : conv_launch_gen23(h, p, ch, sh.es, c.s2 != nullptr)) return rc;
+    RTN_CHECK_LAUNCH(h, "conv_igemm_kernel");
+    h->last_conv_impl = ch.impl;
+    h->last_conv_tile = (ch.BM << 16) | ch.BN;
+    return RTN_OK;
+}
+
+// bytes of d->workspace a launch of `c` can use (0: none), sync block included
+static size_t conv_workspace_bytes(rtn_handle_t h, const ConvCall& c) {
+    ConvShape sh; ConvScratch ws; ConvChoice ch;
+    size_t n = 0;
+    const int rc = conv_plan(h, c, &n, &sh, &ws, &ch);
+    if (rc < 0) return 0;
+    if (rc == 1) n = ch.workspace_bytes;
+    return n ? n + RTN_CONV_SYNC_BYTES : 0;
 }
 
 extern "C" int rtn_debug_last_conv_impl(rtn_handle_t h) { return h ? h->last_conv_impl : RTN_EINVAL; }
 
-extern "C" int rtn_conv2d_fwd(rtn_handle_t h, const rtn_conv_desc_t* d) { return conv_launch(h, d); }
+extern "C" int rtn_conv2d_fwd(rtn_handle_t h, const rtn_conv_desc_t* d) { return conv_launch(h, ConvCall{d, nullptr, nullptr, 0.f}); }
 
 extern "C" size_t rtn_conv2d_workspace_bytes(rtn_handle_t h, const rtn_conv_desc_t* d) {
-    size_t n = 0;
     if (!h || !d) return 0;
     // the K-split paths are taken by plain forward / dgrad launches and by the dual-source form (below), not by the fp8 variants
-    if (conv_launch(h, d, nullptr, nullptr, 0.f, &n) != RTN_OK) return 0;
-    return n ? n + RTN_CONV_SYNC_BYTES : 0;
+    return conv_workspace_bytes(h, ConvCall{d, nullptr, nullptr, 0.f});
 }
 extern "C" size_t rtn_conv1x1_dual_workspace_bytes(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2) {
-    size_t n = 0;
     if (!h || !d || !s2) return 0;
-    if (conv_launch(h, d, s2, nullptr, 0.f, &n) != RTN_OK) return 0;
-    return n ? n + RTN_CONV_SYNC_BYTES : 0;
+    return conv_workspace_bytes(h, ConvCall{d, s2, nullptr, 0.f});
 }
 extern "C" int rtn_conv_workspace_init(rtn_handle_t h, void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
@@ -1824,19 +1897,19 @@ extern "C" int rtn_debug_conv_sync_timeouts(rtn_handle_t h, const void* workspac
 extern "C" int rtn_conv1x1_dual_fwd(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2) {
     if (!h) return RTN_EINVAL;
     if (!s2) return rtn_fail(h, RTN_EINVAL, "conv dual: null second source");
-    return conv_launch(h, d, s2);
+    return conv_launch(h, ConvCall{d, s2, nullptr, 0.f});
 }
 
 extern "C" int rtn_conv2d_fwd_fp8out(rtn_handle_t h, const rtn_conv_desc_t* d, float out_scale) {
     if (!h) return RTN_EINVAL;
     if (!(out_scale > 0.f)) return rtn_fail(h, RTN_EINVAL, "conv fp8-out: scale must be positive");
-    return conv_launch(h, d, nullptr, nullptr, out_scale);
+    return conv_launch(h, ConvCall{d, nullptr, nullptr, out_scale});
 }
 
 extern "C" int rtn_conv2d_fp8_fwd(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_fp8_t* q) {
     if (!h) return RTN_EINVAL;
     if (!q) return rtn_fail(h, RTN_EINVAL, "conv fp8: null scale block");
-    return conv_launch(h, d, nullptr, q);
+    return conv_launch(h, ConvCall{d, nullptr, q, 0.f});
 }
 
 extern "C" int rtn_conv2d_dgrad(rtn_handle_t h, const rtn_conv_desc_t* d) {
@@ -1844,7 +1917,7 @@ extern "C" int rtn_conv2d_dgrad(rtn_handle_t h, const rtn_conv_desc_t* d) {
     if (!d) return rtn_fail(h, RTN_EINVAL, "dgrad: null descriptor");
     if (d->sy != 1 || d->sx != 1) return rtn_fail(h, RTN_EINVAL, "dgrad: runs as a stride-1 convolution over dY (use out_step / rtn_zero_insert2)");
     if (d->flags & (RTN_CONV_RELU | RTN_CONV_SIGMOID | RTN_CONV_RES_UPSAMPLE)) return rtn_fail(h, RTN_EINVAL, "dgrad: forward-only epilogue flag set");
-    return conv_launch(h, d);
+    return conv_launch(h, ConvCall{d, nullptr, nullptr, 0.f});
 }
 
 namespace {

@@ -37,6 +37,7 @@
 // counts up the error word of the sync block and goes on (wrong values, never a hang).  Flags are reset by the owner after the poll:
 // the sync block (first 4 KiB of the workspace) is zero before and after every launch.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 
 namespace {
 
@@ -53,9 +54,7 @@ __device__ unsigned long long g_g8_stamps[1024][8];
 #endif
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
@@ -104,42 +103,12 @@ struct G8Params {
 };
 constexpr int SK_ERR_WORD = 1023;
 
-__device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-__device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(lds_addr), "s"(srd), "s"(soff)
-                 : "memory");
-}
-
-__device__ __forceinline__ void divmod24(int f, int d, float inv, int& q, int& r) {
-    q = (int)((float)f * inv);
-    r = f - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-}
-
 // A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
 // them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
 // fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
 // inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
 // offset; tools/scan_store_hazard.py checks the built library.
 #define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // EPI: bit 0 = residual add (the `Add` closing a bottleneck block; accumulated gradient contributions in training), bit 1 = ReLU mask
 // of the tensor being differentiated (rtn_conv2d_dgrad): 16 bytes per lane and row, loaded one row fragment ahead of their use.
@@ -576,6 +545,33 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
     G8_STAMP(6)
 }
 
+template <int MI, bool ST, bool DU, int EP, int NW = 8, bool SK = false>
+int g8_go(rtn_handle_t h, int grid, const G8Params& p) {
+    return rtn_launch_lds<conv_gemm8_kernel<MI, ST, DU, EP, NW, SK>>(h, dim3((unsigned)grid), dim3(G8_THREADS), G8_LDS, G8_LDS, p);
+}
+// run-time values -> kernel instance, one rung per instance: the stream-K, the 128-column and the full-width instances
+template <int MI>
+int g8_pick_sk(rtn_handle_t h, int grid, const G8Params& p, bool dual, int epi) {
+    if (dual) return g8_go<MI, true, true, 0, 8, true>(h, grid, p);
+    if (epi == 0) return g8_go<MI, true, false, 0, 8, true>(h, grid, p);
+    return g8_go<MI, true, false, 1, 8, true>(h, grid, p);
+}
+template <int MI>
+int g8_pick_narrow(rtn_handle_t h, int grid, const G8Params& p, int epi) {
+    if (epi == 0) return g8_go<MI, true, false, 0, 4>(h, grid, p);
+    if (epi == 1) return g8_go<MI, true, false, 1, 4>(h, grid, p);
+    if (epi == 2) return g8_go<MI, true, false, 2, 4>(h, grid, p);
+    return g8_go<MI, true, false, 3, 4>(h, grid, p);
+}
+template <int MI>
+int g8_pick(rtn_handle_t h, int grid, const G8Params& p, bool dual, bool stagger, int epi) {
+    if (dual) return stagger ? g8_go<MI, true, true, 0>(h, grid, p) : g8_go<MI, false, true, 0>(h, grid, p);
+    if (!stagger && epi == 0) return g8_go<MI, false, false, 0>(h, grid, p);      // lockstep variant: A/B only
+    if (epi == 0) return g8_go<MI, true, false, 0>(h, grid, p);
+    if (epi == 1) return g8_go<MI, true, false, 1>(h, grid, p);
+    if (epi == 2) return g8_go<MI, true, false, 2>(h, grid, p);
+    return g8_go<MI, true, false, 3>(h, grid, p);
+}
 }  // namespace
 
 // Launcher: RTN_OK after a launch, 1 when the layer is not one this kernel takes, < 0 on error.
@@ -756,66 +752,13 @@ int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
         p.sk_slab_bytes = (unsigned)((size_t)sk_grid * (size_t)(mi * 4 * 2) * G8_THREADS * 16);
         p.sk_flags = sync;
     }
-#define RTN_G8_LAUNCH_SK(M_, DU, EP)                                                                     \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_gemm8_kernel<M_, true, DU, EP, 8, true>,    \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_gemm8_kernel<M_, true, DU, EP, 8, true>), dim3((unsigned)grid), dim3(G8_THREADS), G8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_G8_PICK_SK(M_)                                                                               \
-    do {                                                                                                 \
-        if (s2) RTN_G8_LAUNCH_SK(M_, true, 0);                                                           \
-        else if (epi == 0) RTN_G8_LAUNCH_SK(M_, false, 0);                                               \
-        else RTN_G8_LAUNCH_SK(M_, false, 1);                                                             \
-    } while (0)
-#define RTN_G8_LAUNCH(M_, ST, DU, EP)                                                                    \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_gemm8_kernel<M_, ST, DU, EP>,               \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_gemm8_kernel<M_, ST, DU, EP>), dim3((unsigned)grid), dim3(G8_THREADS), G8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_G8_PICK(M_)                                                                                  \
-    do {                                                                                                 \
-        if (s2) { if (stagger) RTN_G8_LAUNCH(M_, true, true, 0); else RTN_G8_LAUNCH(M_, false, true, 0); } \
-        else if (!stagger && epi == 0) RTN_G8_LAUNCH(M_, false, false, 0);  /* lockstep variant: A/B only */ \
-        else if (epi == 0) RTN_G8_LAUNCH(M_, true, false, 0);                                            \
-        else if (epi == 1) RTN_G8_LAUNCH(M_, true, false, 1);                                            \
-        else if (epi == 2) RTN_G8_LAUNCH(M_, true, false, 2);                                            \
-        else RTN_G8_LAUNCH(M_, true, false, 3);                                                          \
-    } while (0)
-#define RTN_G8_LAUNCH4(M_, EP)                                                                           \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_gemm8_kernel<M_, true, false, EP, 4>,       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_gemm8_kernel<M_, true, false, EP, 4>), dim3((unsigned)grid), dim3(G8_THREADS), G8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_G8_PICK4(M_)                                                                                 \
-    do {                                                                                                 \
-        if (epi == 0) RTN_G8_LAUNCH4(M_, 0); else if (epi == 1) RTN_G8_LAUNCH4(M_, 1);                   \
-        else if (epi == 2) RTN_G8_LAUNCH4(M_, 2); else RTN_G8_LAUNCH4(M_, 3);                            \
-    } while (0)
     const bool narrow = n128 && !s2 && stagger && rtn_env_int("RTN_CONV_G8_NARROW", 1) != 0;      // 0: N = 128 on the 256-column tile (A/B)
-    if (sk_grid) { if (mi == 3) RTN_G8_PICK_SK(3); else RTN_G8_PICK_SK(2); }
-    else if (narrow) { if (mi == 3) RTN_G8_PICK4(3); else RTN_G8_PICK4(2); }
-    else if (mi == 3) RTN_G8_PICK(3); else RTN_G8_PICK(2);
-#undef RTN_G8_PICK_SK
-#undef RTN_G8_LAUNCH_SK
-#undef RTN_G8_PICK4
-#undef RTN_G8_LAUNCH4
-#undef RTN_G8_PICK
-#undef RTN_G8_LAUNCH
+    const bool dual = s2 != nullptr;
+    int lrc;
+    if (sk_grid)     lrc = mi == 3 ? g8_pick_sk<3>(h, grid, p, dual, epi) : g8_pick_sk<2>(h, grid, p, dual, epi);
+    else if (narrow) lrc = mi == 3 ? g8_pick_narrow<3>(h, grid, p, epi) : g8_pick_narrow<2>(h, grid, p, epi);
+    else             lrc = mi == 3 ? g8_pick<3>(h, grid, p, dual, stagger, epi) : g8_pick<2>(h, grid, p, dual, stagger, epi);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_gemm8_kernel");
     h->last_conv_streamk = sk_grid;
     h->last_conv_tile = ((64 * mi) << 16) | (narrow ? 128 : 256);

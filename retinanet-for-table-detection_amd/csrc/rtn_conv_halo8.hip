@@ -24,6 +24,7 @@
 //
 // LDS (160 KiB, all of it): B ring 3 x 32 KiB at 0, halos 2 x 32 KiB at 96 KiB.  One workgroup (512 threads) per CU.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 
 #ifndef RTN_H8_ABLATE
 #define RTN_H8_ABLATE 0
@@ -47,9 +48,7 @@ __device__ unsigned long long g_h8_stamps[2][64];
 #endif
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned OOB = 0xFFFFFF00u;                 // beyond every descriptor: loads return zeros, stores are dropped
@@ -92,45 +91,12 @@ struct H8Params {
     int out_fp8;
 };
 
-__device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// 64 lanes x 16 B from (descriptor, per-lane byte offset `voff` + uniform `soff`) to LDS bytes [lds_addr, lds_addr + 1024).
-// asm so that hipcc neither counts nor drains it; the kernel's own counted waits cover it.
-__device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(lds_addr), "s"(srd), "s"(soff)
-                 : "memory");
-}
-
-// f / d for 0 <= f < 2^24 with inv = 1.0f / d: the float product is within one of the quotient
-__device__ __forceinline__ void divmod24(int f, int d, float inv, int& q, int& r) {
-    q = (int)((float)f * inv);
-    r = f - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
-}
-
 // A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
 // them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
 // fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
 // inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
 // offset; tools/scan_store_hazard.py checks the built library.
 #define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 // fp8 e4m3 x e4m3, K = 128 per instruction at twice the bf16 rate: a lane supplies 32 bytes of its row per operand - the two 16-byte
 // fragments the bf16 loop reads for k halves 0 and 1 (which 32 of the row's 128 K positions a lane holds is free as long as A and
@@ -740,6 +706,27 @@ __global__ __launch_bounds__(H8_THREADS, 2) void conv_halo8_kernel(const H8Param
     if (STAGGER && grp == 0) __builtin_amdgcn_s_barrier();
 }
 
+template <int MI, bool ST, int EP, bool SP, int NW = 8, int ES = 2>
+int h8_go(rtn_handle_t h, int grid, const H8Params& p) {
+    return rtn_launch_lds<conv_halo8_kernel<3, MI, ST, EP, SP, NW, ES>>(h, dim3((unsigned)grid), dim3(H8_THREADS), H8_LDS, H8_LDS, p);
+}
+// run-time values -> kernel instance, one rung per instance
+template <int MI>
+int h8_pick(rtn_handle_t h, int grid, const H8Params& p, bool fp8, bool half, bool split, bool stagger, int epi) {
+    if (fp8) return h8_go<3, true, 0, false, 8, 1>(h, grid, p);
+    if (half) {
+        if (epi == 0) return h8_go<MI, true, 0, false, 4>(h, grid, p);
+        if (epi == 1) return h8_go<MI, true, 1, false, 4>(h, grid, p);
+        if (epi == 2) return h8_go<MI, true, 2, false, 4>(h, grid, p);
+        return h8_go<MI, true, 3, false, 4>(h, grid, p);
+    }
+    if (split) return h8_go<MI, true, 0, true>(h, grid, p);
+    if (!stagger && epi == 0) return h8_go<MI, false, 0, false>(h, grid, p);      // lockstep variant: A/B only
+    if (epi == 0) return h8_go<MI, true, 0, false>(h, grid, p);
+    if (epi == 1) return h8_go<MI, true, 1, false>(h, grid, p);
+    if (epi == 2) return h8_go<MI, true, 2, false>(h, grid, p);
+    return h8_go<MI, true, 3, false>(h, grid, p);
+}
 }  // namespace
 
 // Launcher.  Returns RTN_OK after a launch, 1 when the layer is not one this kernel takes (the caller falls through to the other
@@ -876,58 +863,9 @@ int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
     int grid = cus;
     if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
     if (grid > p.nitems) grid = p.nitems;
-#define RTN_H8_LAUNCH(M_, ST, EP, SP)                                                                    \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_halo8_kernel<3, M_, ST, EP, SP>,            \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, H8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_halo8_kernel<3, M_, ST, EP, SP>), dim3((unsigned)grid), dim3(H8_THREADS), H8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_H8_LAUNCH4E(M_, EP)                                                                          \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_halo8_kernel<3, M_, true, EP, false, 4>,    \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, H8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_halo8_kernel<3, M_, true, EP, false, 4>), dim3((unsigned)grid), dim3(H8_THREADS), H8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_H8_LAUNCH4(M_)                                                                               \
-    do {                                                                                                 \
-        if (epi == 0) RTN_H8_LAUNCH4E(M_, 0); else if (epi == 1) RTN_H8_LAUNCH4E(M_, 1);                 \
-        else if (epi == 2) RTN_H8_LAUNCH4E(M_, 2); else RTN_H8_LAUNCH4E(M_, 3);                          \
-    } while (0)
-#define RTN_H8_LAUNCH8F(M_)                                                                              \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_halo8_kernel<3, M_, true, 0, false, 8, 1>,  \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, H8_LDS));         \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_halo8_kernel<3, M_, true, 0, false, 8, 1>), dim3((unsigned)grid), dim3(H8_THREADS), H8_LDS, h->stream, p); \
-    } while (0)
-#define RTN_H8_PICK(M_)                                                                                  \
-    do {                                                                                                 \
-        if (q8) RTN_H8_LAUNCH8F(3);                                                                      \
-        else if (half) RTN_H8_LAUNCH4(M_);                                                               \
-        else if (split) RTN_H8_LAUNCH(M_, true, 0, true);                                                \
-        else if (!stagger && epi == 0) RTN_H8_LAUNCH(M_, false, 0, false);      /* lockstep variant: A/B only */ \
-        else if (epi == 0) RTN_H8_LAUNCH(M_, true, 0, false);                                            \
-        else if (epi == 1) RTN_H8_LAUNCH(M_, true, 1, false);                                            \
-        else if (epi == 2) RTN_H8_LAUNCH(M_, true, 2, false);                                            \
-        else RTN_H8_LAUNCH(M_, true, 3, false);                                                          \
-    } while (0)
-    if (mi == 4) RTN_H8_PICK(4); else RTN_H8_PICK(3);
-#undef RTN_H8_PICK
-#undef RTN_H8_LAUNCH8F
-#undef RTN_H8_LAUNCH4
-#undef RTN_H8_LAUNCH4E
-#undef RTN_H8_LAUNCH
+    const int lrc = mi == 4 ? h8_pick<4>(h, grid, p, q8 != nullptr, half, split, stagger, epi)
+                            : h8_pick<3>(h, grid, p, q8 != nullptr, half, split, stagger, epi);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_halo8_kernel");
     h->last_conv_tile = ((64 * mi) << 16) | (half ? 128 : 256);
     if (S > 1) return rtn_conv_ksplit_finish(h, ws, S, Mtot, d->N, (int)slab_ld, d->bias, p.relu, d->g[0].out, d->out_ld);

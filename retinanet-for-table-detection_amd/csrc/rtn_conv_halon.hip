@@ -16,12 +16,12 @@
 //     count is not a multiple of 4), bias as the accumulators' initial value, sigmoid in registers.
 // LDS: 3 x (32 KiB + 6 NF KiB) + 1 KiB that swallows the surplus DMA pieces = 151 KiB for NF = 3.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned HN_OOB = 0xFFFFFF00u;              // beyond every descriptor: loads return zeros, stores are dropped
@@ -60,16 +60,6 @@ struct HNParams {
     int N, Kbytes, nchunk, pad_t, pad_l, relu, sigmoid, out_ld, pix_b, vec, xcd, kh_fast;
 };
 
-__device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
 // 64 lanes x 16 B from (descriptor, per-lane byte offset `voff` + uniform `soff`) to LDS bytes [lds_addr, lds_addr + 1024).
 // asm so that hipcc neither counts nor drains it; the kernel's own counted waits cover it.
 __device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
@@ -79,13 +69,6 @@ __device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned 
                  : "=&s"(keep)
                  : "v"(voff), "s"(la), "s"(srd), "s"(so)
                  : "memory");
-}
-
-__device__ __forceinline__ void divmod24(int f, int d, float inv, int& q, int& r) {
-    q = (int)((float)f * inv);
-    r = f - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) { ++q; r -= d; }
 }
 
 // A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
@@ -408,18 +391,11 @@ int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
     int grid = cus;
     if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
     if (grid > p.ntiles) grid = p.ntiles;
-#define RTN_HN_LAUNCH(NF_)                                                                               \
-    do {                                                                                                 \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                    \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                 \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_halon_kernel<NF_>,                          \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, HNCfg<NF_>::LDS)); \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                             \
-        }                                                                                                \
-        hipLaunchKernelGGL((conv_halon_kernel<NF_>), dim3((unsigned)grid), dim3(HN_THREADS), HNCfg<NF_>::LDS, h->stream, p); \
-    } while (0)
-    if (nf == 1) RTN_HN_LAUNCH(1); else if (nf == 2) RTN_HN_LAUNCH(2); else RTN_HN_LAUNCH(3);
-#undef RTN_HN_LAUNCH
+    const dim3 gdim((unsigned)grid), bdim(HN_THREADS);
+    const int lrc = nf == 1 ? rtn_launch_lds<conv_halon_kernel<1>>(h, gdim, bdim, HNCfg<1>::LDS, HNCfg<1>::LDS, p)
+                  : nf == 2 ? rtn_launch_lds<conv_halon_kernel<2>>(h, gdim, bdim, HNCfg<2>::LDS, HNCfg<2>::LDS, p)
+                            : rtn_launch_lds<conv_halon_kernel<3>>(h, gdim, bdim, HNCfg<3>::LDS, HNCfg<3>::LDS, p);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_halon_kernel");
     return RTN_OK;
 }

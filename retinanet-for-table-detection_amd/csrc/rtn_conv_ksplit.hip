@@ -3,15 +3,10 @@
 // with whole-K tiles, so their K loop is cut into S slices whose f32 partial sums land in caller-owned slabs [S][M][ld].  This
 // kernel adds the slices IN SLICE ORDER (bit-reproducible, unlike atomics), the bias, the ReLU, and stores bf16.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
 
 __global__ __launch_bounds__(256) void ksplit_finish_kernel(const float* __restrict__ slab, int S, long long M, int N, int ld,
                                                             const float* __restrict__ bias, int relu, unsigned short* __restrict__ out,

@@ -14,8 +14,7 @@ struct rtn_ctx {
     int num_cus;
     int last_conv_streamk;        // rtn_debug_last_conv_streamk: workgroups of the last conv launch if it ran in stream-K form, else 0
     int last_conv_tile;           // rtn_debug_last_conv_tile: (tile rows << 16) | tile columns of the last conv launch
-    int last_conv_impl;
-         // kernel generation of the last conv launch on this handle (rtn_debug_last_conv_impl)
+    int last_conv_impl;           // rtn_debug_last_conv_impl: kernel generation of the last conv launch on this handle
     int last_wgrad_impl;          // rtn_debug_last_wgrad_impl: 2 = 256x256 LDS-DMA, 3 = 128x128 LDS-DMA, 4 = rtn_wgrad_win.hip, 0 = register-staged
     char err[512];
 };
@@ -45,28 +44,46 @@ inline int rtn_fail(rtn_ctx* h, int code, const char* fmt, ...) {
                             hipGetErrorString(e_));                                        \
     } while (0)
 
-// rtn_conv_halo8.hip: persistent 8-phase kernel for the stride-1 3x3 layers with 129..256 output channels (head towers, P3-P5,
-// res4 branch2b).  RTN_OK = launched, 1 = not a layer this kernel takes, < 0 = error.
+// Launch `Kernel` with `lds` bytes of dynamic LDS on the handle's stream.  The first launch of a kernel instance on a device raises that
+// instance's dynamic-LDS limit to `lds_limit` (the 64 KiB default refuses the launch).  The template is keyed on the kernel itself, so
+// every instance owns a flag word, one bit per device.  The caller checks the launch (RTN_CHECK_LAUNCH).
+template <auto Kernel, class Params>
+inline int rtn_launch_lds(rtn_ctx* h, dim3 grid, dim3 block, unsigned lds, int lds_limit, const Params& p) {
+    static std::atomic<unsigned long long> attr_set{0ull};
+    const unsigned long long bit = 1ull << (h->device & 63);
+    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
+        RTN_HIP(h, hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit));
+        attr_set.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, h->stream, p);
+    return RTN_OK;
+}
+
 // integer environment knob (name must be a string literal): cached per thread, re-read when the environment changed, so one process
 // can still A/B kernel variants (tools/ab_conv.py).  rtn_env_sync() revalidates the cache: call it at the top of an entry point.
 int rtn_env_int(const char* name, int dflt);
 void rtn_env_sync();
+
+// rtn_conv_halo8.hip: persistent 8-phase kernel for the stride-1 3x3 layers with 129..256 output channels (head towers, P3-P5,
+// res4 branch2b).  RTN_OK = launched, 1 = not a layer this kernel takes, < 0 = error.
 int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool stagger, bool forced, int mi_force, float* ws,
                        long long ws_cap, size_t* query, int ksplit_force, const rtn_conv_fp8_t* q8 = nullptr);
+// rtn_conv_gemm8.hip: the same schedule as a plain GEMM for the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or
+// two (K-concatenated) sources, stride 1 or 2.
+int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2, int grid_limit, bool stagger, bool forced,
+                       int mi_force, unsigned* sync, void* ws, long long ws_cap, size_t* query, int sk_mode);
+// rtn_conv_halon.hip: the head output convolutions (3x3, <= 48 channels, f32 result in the concatenated tensor)
+int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool forced);
+// rtn_conv_ksplit.hip: sums the K-slice slabs of a conv launch in slice order and applies bias / ReLU
+int rtn_conv_ksplit_finish(rtn_handle_t h, const float* slab, int S, long long M, int N, int ld, const float* bias, int relu, void* out,
+                           int out_ld);
+
 struct rtn_wgrad_frag_t { int ncb, C, Ktot, wpt, co_tile; };   // slabs in the accumulator-fragment order of rtn_wgrad_win.hip (ncb > 0): waves per tile in the slab (8 / 4), filters per tile (128 / 64)
 int rtn_wgrad_finish(rtn_handle_t h, float* dW, const float* slab, int S, long long NK, float* db, const float* bslab, int N, int db_n,
                      int bS = 0 /* parts of bslab when not S */, const rtn_wgrad_frag_t* frag = nullptr);
 // rtn_wgrad_win.hip: all nine taps of a 128-filter x 64-channel block per workgroup over a sliding window of the input
 size_t rtn_wgrad_win_workspace_bytes(const rtn_conv_desc_t* d);
 int rtn_wgrad_win_try(rtn_handle_t h, const rtn_conv_desc_t* d, float* dW, float* db, int db_n, void* workspace, size_t workspace_bytes);
-int rtn_conv_ksplit_finish(rtn_handle_t h, const float* slab, int S, long long M, int N, int ld, const float* bias, int relu, void* out,
-                           int out_ld);
-
-// rtn_conv_gemm8.hip: the same schedule as a plain GEMM for the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or
-// two (K-concatenated) sources, stride 1 or 2.
-int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2, int grid_limit, bool stagger, bool forced,
-                       int mi_force, unsigned* sync, void* ws, long long ws_cap, size_t* query, int sk_mode);
-int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool forced);
 
 // rtn_jpeg.hip: text of the calling thread's last failed host-only call made without a handle (rtn_last_error(NULL))
 const char* rtn_host_error_text();

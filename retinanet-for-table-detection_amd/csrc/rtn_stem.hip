@@ -338,18 +338,13 @@ static int stem_launch(rtn_handle_t h, const void* packed, int Hp, int Wp, const
     long long grid = 2ll * (h->num_cus > 0 ? h->num_cus : 256);        // two workgroups per CU (LDS_BYTES each)
     { const int gl = rtn_env_int("RTN_STEM_GRID", 0); if (gl > 0 && gl < grid) grid = gl; }     // tests: many tiles per workgroup on small images
     if (grid > ntiles) grid = ntiles;
-#define RTN_STEM_LAUNCH(A2_, IDX_, LDSB)                                                                       \
-    do {                                                                                                      \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                         \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                      \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)stem_fused_kernel<A2_, IDX_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB)); \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                                  \
-        }                                                                                                     \
-        hipLaunchKernelGGL((stem_fused_kernel<A2_, IDX_>), dim3((unsigned)grid), dim3(256), LDSB, h->stream, p); \
-    } while (0)
-    if (a2) { if (idx) RTN_STEM_LAUNCH(true, true, LDS_BYTES_A2); else RTN_STEM_LAUNCH(true, false, LDS_BYTES_A2); }
-    else    { if (idx) RTN_STEM_LAUNCH(false, true, LDS_BYTES); else RTN_STEM_LAUNCH(false, false, LDS_BYTES); }
-#undef RTN_STEM_LAUNCH
+    const dim3 gdim((unsigned)grid), bdim(256);
+    int lrc;
+    if (a2) lrc = idx ? rtn_launch_lds<stem_fused_kernel<true, true>>(h, gdim, bdim, LDS_BYTES_A2, LDS_BYTES_A2, p)
+                      : rtn_launch_lds<stem_fused_kernel<true, false>>(h, gdim, bdim, LDS_BYTES_A2, LDS_BYTES_A2, p);
+    else    lrc = idx ? rtn_launch_lds<stem_fused_kernel<false, true>>(h, gdim, bdim, LDS_BYTES, LDS_BYTES, p)
+                      : rtn_launch_lds<stem_fused_kernel<false, false>>(h, gdim, bdim, LDS_BYTES, LDS_BYTES, p);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "stem_fused_kernel");
     return RTN_OK;
 }

@@ -36,13 +36,13 @@
 // halves of a step instead of two filter halves and add their accumulators through LDS at the end; dY rows are 128 B (24 KiB of
 // stages), which leaves room for a ring of 16 blocks: image rows of up to 382 pixels.
 #include "rtn_internal.h"
+#include "rtn_device.h"
 #include <type_traits>
 
 namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 
@@ -79,16 +79,6 @@ struct WWParams {
     int pix_b, dy_ld_b;
     unsigned xring;               // bytes of the X ring
 };
-
-__device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)ptr;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    return r;
-}
 
 __device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned lds_addr) {
     unsigned keep;
@@ -451,19 +441,11 @@ int rtn_wgrad_win_try(rtn_handle_t h, const rtn_conv_desc_t* d, float* dW, float
     if (ps && lds_bytes < 4 * 37 * 1024) lds_bytes = 4 * 37 * 1024;       // the exchange of the two wave groups' accumulators
     p.xring = (unsigned)ww_nblk(Dmax) * WW_XBLK;
     const unsigned grid = (unsigned)(p.ntiles * ((S + 7) / 8) * 8);
-#define RTN_WW_LAUNCH(E_, PS_)                                                                                                    \
-    do {                                                                                                                          \
-        static std::atomic<unsigned long long> attr_set{0ull};  /* one bit per device */                                                                                             \
-        if (!((attr_set.load(std::memory_order_relaxed) >> (h->device & 63)) & 1ull)) {                                                                                                          \
-            RTN_HIP(h, hipFuncSetAttribute((const void*)conv_wgrad_win_kernel<E_, PS_>, hipFuncAttributeMaxDynamicSharedMemorySize, WW_LDS_MAX)); \
-            attr_set.fetch_or(1ull << (h->device & 63), std::memory_order_relaxed);                                                                                                      \
-        }                                                                                                                         \
-        hipLaunchKernelGGL((conv_wgrad_win_kernel<E_, PS_>), dim3(grid), dim3(WW_THREADS), lds_bytes, h->stream, p);              \
-    } while (0)
     // (timing ablations EXP = 1 / 2 / 3 and the unstaggered staging were round-3 A/Bs: profiles/r3_wgrad_win_ab.txt; only the
     // production instances are built)
-    if (ps) RTN_WW_LAUNCH(0, true); else RTN_WW_LAUNCH(0, false);
-#undef RTN_WW_LAUNCH
+    const int lrc = ps ? rtn_launch_lds<conv_wgrad_win_kernel<0, true>>(h, dim3(grid), dim3(WW_THREADS), lds_bytes, WW_LDS_MAX, p)
+                       : rtn_launch_lds<conv_wgrad_win_kernel<0, false>>(h, dim3(grid), dim3(WW_THREADS), lds_bytes, WW_LDS_MAX, p);
+    if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_wgrad_win_kernel");
     const rtn_wgrad_frag_t fr = {p.ncb, p.C, Ktot, ps ? 4 : 8, ps ? 64 : 128};
     return rtn_wgrad_finish(h, dW, p.slab, S_used, (long long)d->N * Ktot, db, p.bslab, d->N, db ? db_n : 0, S_used * p.ncb, &fr);

@@ -598,9 +598,9 @@ def test_conv_rejects_bad_descriptors(pkg, handle):
 
 
 def test_workspace_query_never_launches(pkg, handle, monkeypatch):
-    """rtn_conv2d_workspace_bytes is conv_launch in query mode.  With RTN_CONV_SPLITK=0 the split-K sizing block (and its early
-    return) is skipped for a tiny-M long-K layer on generation 1; the query must still return before any kernel is launched: the
-    output buffer keeps its fill value and the handle's last-kernel record does not change."""
+    """rtn_conv2d_workspace_bytes runs the launcher's steps up to conv_choose.  With RTN_CONV_SPLITK=0 the split-K sizing is skipped
+    for a tiny-M long-K layer on generation 1; the query must still return before any kernel is launched: the output buffer keeps
+    its fill value and the handle's last-kernel record does not change."""
     L = pkg._lib
     dev = torch.device("cuda")
     B, H, W, cin, cout = 1, 6, 7, 2048, 64
