@@ -610,6 +610,31 @@ size_t rtn_jpeg_workspace_bytes(int n, const void* host_blobs, const int64_t* of
 int rtn_jpeg_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- baseline JPEG encode (Pillow's Image.save(f, "JPEG", quality=q, subsampling=s), on the device) ------------------------------
+ * Output: byte-identical to what Pillow 12 / libjpeg-turbo 3 writes with quality q (1..100) and subsampling s (0 = 4:4:4,
+ * 1 = 4:2:2, 2 = 4:2:0): SOI, APP0 (JFIF 1.01, density 1:1, no unit), DQT, SOF0, DHT, SOS, one interleaved baseline scan with the
+ * standard Huffman tables (no optimisation pass, no restart markers), EOI.  Input: uint8 (H, W, 3) B,G,R (3 components, YCbCr in
+ * the file) or (H, W) gray (1 component; s then only sets the sampling factors written in SOF0, as Pillow does).  Sides 1..65500.
+ *
+ * rtn_jpeg_encode_header (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): writes SOI .. SOS into out,
+ *   *written = bytes written (623 for 3 components, 328 for 1).  RTN_EINVAL for quality outside 1..100, a side outside 1..65500,
+ *   components not 1 or 3, subsampling not 0..2, or capacity too small.
+ * rtn_jpeg_encode_bound: the largest file one page can give (header, every block at its most Huffman bits, every byte stuffed,
+ *   EOI); 0 for an invalid page.  rtn_jpeg_encode_workspace_bytes: device scratch for encoding the n pages; 0 for an invalid page.
+ * rtn_jpeg_encode: n pages in one batch on the handle's stream, sizes, component counts, subsamplings and qualities mixed (host
+ *   arrays of n).  pages: host array of device pointers.  out: device memory; page i's slot is [out_offsets[i], out_offsets[i+1])
+ *   (host, n + 1 entries), rtn_jpeg_encode_bound bytes always suffice.  out_bytes (device, n int64): the file length, 0 where
+ *   status (device, n int32) is non-zero: a file that does not fit its slot, which the caller then encodes on the host.
+ *   workspace: 256-byte aligned, >= rtn_jpeg_encode_workspace_bytes. */
+int rtn_jpeg_encode_header(int width, int height, int components, int subsampling, int quality, uint8_t* out, size_t capacity,
+                           size_t* written);
+size_t rtn_jpeg_encode_bound(int width, int height, int components, int subsampling);
+size_t rtn_jpeg_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components,
+                                       const int32_t* subsampling);
+int rtn_jpeg_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* widths, const int32_t* heights,
+                    const int32_t* components, const int32_t* subsampling, const int32_t* quality, uint8_t* out,
+                    const int64_t* out_offsets, int64_t* out_bytes, int32_t* status, void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

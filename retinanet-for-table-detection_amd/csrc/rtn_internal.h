@@ -87,6 +87,8 @@ int rtn_wgrad_win_try(rtn_handle_t h, const rtn_conv_desc_t* d, float* dW, float
 
 // rtn_jpeg.hip: text of the calling thread's last failed host-only call made without a handle (rtn_last_error(NULL))
 const char* rtn_host_error_text();
+// ... and sets it (rtn_jpeg_enc.hip's host-only entry points)
+void rtn_set_host_error(const char* text);
 
 static inline int rtn_dtype_size(int dt) { return dt == RTN_F32 ? 4 : (dt == RTN_FP8 ? 1 : 2); }
 

@@ -798,6 +798,7 @@ extern "C" int rtn_jpeg_inspect(rtn_handle_t h, const void* file, size_t file_by
 }
 
 const char* rtn_host_error_text() { return g_host_err[0] ? g_host_err : "null handle"; }
+void rtn_set_host_error(const char* text) { snprintf(g_host_err, sizeof(g_host_err), "%s", text); }
 
 static bool jpeg_blob_ok(const uint8_t* b) {
     const JHdr* hd = reinterpret_cast<const JHdr*>(b);

@@ -33,6 +33,40 @@ def preprocess_pages(pages, return_binary=False):
     return (out, bo) if return_binary else out
 
 
+def preprocess_files(src_paths, dst_paths, quality=95):
+    """DetectTablesUtils.preProcessSampleImages / preProcessTrainValImages as a batch: read every page (csv_generator.read_images_bgr:
+    baseline JPEGs decoded on the device), run rtn_preprocess_dt3 on the device (one call per page size), and write the distance
+    maps (model.utils.write_images_bgr: .jpg / .jpeg / .jpe names encoded on the device at `quality`, 4:2:0, other names through
+    write_image).  On the JPEG -> JPEG path the pixels never come to the host.  A page wider than rtn_preprocess_dt3 takes raises
+    what preprocess_pages raises for it."""
+    import importlib
+    from .utils import write_images_bgr
+    src_paths, dst_paths = list(src_paths), list(dst_paths)
+    if len(src_paths) != len(dst_paths):
+        raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
+    if not src_paths:
+        return
+    read_images_bgr = importlib.import_module(_rt._pkg.__name__ + ".csv_generator").read_images_bgr
+    pages = read_images_bgr(src_paths)
+    h = _rt.handle()
+    groups = {}
+    for i, p in enumerate(pages):
+        groups.setdefault(tuple(p.shape[:2]), []).append(i)
+    out = [None] * len(pages)
+    for (H, W), idx in groups.items():
+        for k0 in range(0, len(idx), 21845):                    # rtn_preprocess_dt3 takes B * 3 <= 65535
+            part = idx[k0:k0 + 21845]
+            B = len(part)
+            src = torch.stack([pages[i] for i in part]) if B > 1 else pages[part[0]][None]
+            dst = torch.empty(B, H, W, 3, dtype=torch.uint8, device=src.device)
+            wsb = L.lib.rtn_preprocess_dt3_workspace_bytes(B, H, W)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=src.device)
+            h.check(L.lib.rtn_preprocess_dt3(h.raw, src.data_ptr(), 3, B, H, W, dst.data_ptr(), None, ws.data_ptr(), wsb))
+            for k, i in enumerate(part):
+                out[i] = dst[k]
+    write_images_bgr(dst_paths, out, quality=quality)
+
+
 def resize_cubic(img, scale):
     """cv2.resize(img, None, fx=scale, fy=scale, interpolation=cv2.INTER_CUBIC) of a float32 (H,W,C) image."""
     img = np.asarray(img, np.float32)

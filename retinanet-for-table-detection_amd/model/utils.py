@@ -219,6 +219,130 @@ def write_image(path, image):
     Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(path)
 
 
+JPEG_EXTENSIONS = ('.jpg', '.jpeg', '.jpe')
+JPEG_MAX_SIDE = 65500                                   # libjpeg's JPEG_MAX_DIMENSION
+
+
+def _check_page(i, p):
+    """(H, W, components) of one page for encode_jpeg_bgr, or ValueError."""
+    if not isinstance(p, (torch.Tensor, np.ndarray)):
+        p = np.asarray(p)
+    dtype, shape = p.dtype, tuple(p.shape)
+    if dtype != (torch.uint8 if isinstance(p, torch.Tensor) else np.uint8):
+        raise ValueError("page %d: uint8 pixels expected, got %s" % (i, dtype))
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+        raise ValueError("page %d: shape (H,W,3) B,G,R or (H,W) gray expected, got %s" % (i, shape))
+    if not (1 <= shape[0] <= JPEG_MAX_SIDE and 1 <= shape[1] <= JPEG_MAX_SIDE):
+        raise ValueError("page %d: %dx%d: sides must be 1..%d for JPEG" % (i, shape[0], shape[1], JPEG_MAX_SIDE))
+    return shape[0], shape[1], 1 if len(shape) == 2 else 3
+
+
+def _check_settings(quality, subsampling, n=None):
+    """(qualities, subsamplings) as lists of n, from ints or per-page sequences; ValueError for anything else."""
+    def per_page(v, name):
+        if isinstance(v, (list, tuple, np.ndarray)):
+            v = list(v)
+            if n is not None and len(v) != n:
+                raise ValueError("%d %s values for %d pages" % (len(v), name, n))
+            return v
+        return [v] * (n or 0)
+    qs, ss = per_page(quality, "quality"), per_page(subsampling, "subsampling")
+    for q in (qs if isinstance(quality, (list, tuple, np.ndarray)) else [quality]):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= 100:
+            raise ValueError("quality must be an integer 1..100, got %r" % (q,))
+    for s in (ss if isinstance(subsampling, (list, tuple, np.ndarray)) else [subsampling]):
+        if isinstance(s, bool) or s not in (0, 1, 2):
+            raise ValueError("subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r" % (s,))
+    return [int(q) for q in qs], [int(s) for s in ss]
+
+
+def _host_page(p):
+    return p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+
+
+def _pillow_jpeg(page, quality, subsampling):
+    """The host path: Pillow's JPEG of a B,G,R (or gray) page."""
+    import io
+    from PIL import Image
+    a = np.ascontiguousarray(_host_page(page))
+    b = io.BytesIO()
+    Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(b, "JPEG", quality=int(quality), subsampling=subsampling)
+    return b.getvalue()
+
+
+def encode_jpeg_bgr(pages, quality=95, subsampling=2):
+    """Baseline JPEG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), byte-identical to
+    Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling): one batched rtn_jpeg_encode on the current
+    stream (csrc/rtn_jpeg_enc.hip), one small copy of the n file lengths, then one copy of the used bytes to pinned host
+    memory.  A page the device flags is encoded by Pillow.  The defaults are cv2.imwrite's for a .jpg name; quality and
+    subsampling may also be sequences of one value per page.  Returns list[bytes]."""
+    import ctypes as C
+    pages = list(pages)
+    n = len(pages)
+    qs, ss = _check_settings(quality, subsampling, n)
+    dims = [_check_page(i, p) for i, p in enumerate(pages)]
+    if n == 0:
+        return []
+    h = _rt.handle()
+    dev = []
+    for p in pages:
+        t = p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
+        dev.append(t.to(device="cuda", non_blocking=True).contiguous())
+    arr = lambda v: np.ascontiguousarray(v, np.int32)                    # noqa: E731
+    H, W, Cc = arr([d[0] for d in dims]), arr([d[1] for d in dims]), arr([d[2] for d in dims])
+    S, Q = arr(ss), arr(qs)
+    offs = np.zeros(n + 1, np.int64)
+    offs[1:] = np.cumsum([L.lib.rtn_jpeg_encode_bound(int(w), int(hh), int(c), int(s)) for w, hh, c, s in zip(W, H, Cc, S)])
+    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda")
+    lengths = torch.empty(n, dtype=torch.int64, device="cuda")
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    wsb = int(L.lib.rtn_jpeg_encode_workspace_bytes(n, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, S.ctypes.data))
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in dev])
+    h.check(L.lib.rtn_jpeg_encode(h.raw, n, ptrs, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, S.ctypes.data, Q.ctypes.data,
+                                  out.data_ptr(), offs.ctypes.data, lengths.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb))
+    stream = torch.cuda.current_stream()
+    nb = torch.empty(n, dtype=torch.int64, pin_memory=True)
+    nb.copy_(lengths, non_blocking=True)
+    stream.synchronize()
+    nb = nb.numpy().copy()                                              # 0 = flagged (status != 0)
+    ok = [i for i in range(n) if nb[i] > 0]
+    files = [None] * n
+    if ok:
+        used = torch.cat([out[int(offs[i]):int(offs[i]) + int(nb[i])] for i in ok]) if len(ok) > 1 else \
+            out[int(offs[ok[0]]):int(offs[ok[0]]) + int(nb[ok[0]])]
+        host = torch.empty(used.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(used, non_blocking=True)
+        stream.synchronize()
+        buf = host.numpy()
+        pos = 0
+        for i in ok:
+            files[i] = buf[pos:pos + int(nb[i])].tobytes()
+            pos += int(nb[i])
+    for i in range(n):
+        if files[i] is None:
+            files[i] = _pillow_jpeg(pages[i], qs[i], ss[i])
+    return files
+
+
+def write_images_bgr(paths, pages, quality=95, subsampling=2):
+    """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
+    .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged."""
+    import os
+    paths, pages = list(paths), list(pages)
+    if len(paths) != len(pages):
+        raise ValueError("%d paths for %d pages" % (len(paths), len(pages)))
+    qs, ss = _check_settings(quality, subsampling, len(pages))
+    for i, p in enumerate(pages):
+        _check_page(i, p)
+    jpg = [i for i, path in enumerate(paths) if os.path.splitext(str(path))[1].lower() in JPEG_EXTENSIONS]
+    for i, data in zip(jpg, encode_jpeg_bgr([pages[i] for i in jpg], quality=[qs[i] for i in jpg], subsampling=[ss[i] for i in jpg])):
+        with open(paths[i], 'wb') as f:
+            f.write(data)
+    for i in sorted(set(range(len(paths))) - set(jpg)):
+        write_image(paths[i], _host_page(pages[i]))
+
+
 def render_detections(processed_page, draw, boxes, scores, labels, image_scale, result_dir, image_name, labels_to_names=None,
                       score_threshold=0.6):
     """The output step of test_image (RetinaNet.py:366-402) for one page.  boxes/scores/labels: the (1,300,·) detections of the
