@@ -236,6 +236,16 @@ typedef struct {
     const void* wproj;
     /* optional: branch2b's output h1 [batch][H][W][mid] is also written (the training forward keeps it for the backward pass) */
     void*       h1_out; int64_t h1_out_elems;
+    /* Quarter forms of the identity block, for a consumer that reads x_out only at pixels whose row and column are both even (the
+     * stride-2 1x1 convolutions of the next stage's first block).  A step of 0 or 1 is the dense tensor; a step of 2 means the tensor
+     * is the compact quarter [batch][(H+1)/2][(W+1)/2][4*mid] whose pixel (yc, xc) is dense pixel (2 yc, 2 xc), and its *_elems
+     * describe that compact tensor.  H, W, a_in (and a_out) stay dense.  Two combinations exist, every other one is RTN_EINVAL:
+     *   x_out_step = 2 with a_out (store-quarter): everything is computed and a_out written at every pixel; of x_out only the
+     *     even pixels are stored, at their compact address.
+     *   x_out_step = 2, x_in_step = 2, a_out = NULL (compute-quarter): only the even pixels are computed - the 3x3 reads the dense
+     *     a_in around (2 yc, 2 xc), the shortcut comes from the compact x_in.  Each stored pixel has the bits of the dense form.
+     * Neither combines with the projection form or with h1_out. */
+    int32_t x_out_step, x_in_step;
 } rtn_bottleneck_desc_t;
 int rtn_bottleneck64_fwd(rtn_handle_t h, const rtn_bottleneck_desc_t* d);
 

@@ -82,6 +82,7 @@ class BottleneckDesc(C.Structure):
         ("batch", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mid", C.c_int32), ("dtype", C.c_int32), ("w2c_ld", C.c_int32),
         ("p_in", C.c_void_p), ("p_in_elems", C.c_int64), ("wproj", C.c_void_p),
         ("h1_out", C.c_void_p), ("h1_out_elems", C.c_int64),
+        ("x_out_step", C.c_int32), ("x_in_step", C.c_int32),
     ]
 
 

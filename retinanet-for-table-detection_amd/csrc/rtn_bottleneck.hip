@@ -50,8 +50,11 @@ struct BkParams {
     const float* b2b;       // [64], [256], [64] f32 (folded BN shifts)
     const float* b2c;
     const float* b2a;
-    int M, H, W, nstrips;
-    float inv_cells, inv_w;
+    int M, H, W, nstrips;     // M: the pixels the strips walk (QUARTER == 2: the compact ones); H, W: the DENSE extent of a_in
+    float inv_cells, inv_w;   // 1 / (cells, width) of the walked pixel order
+    int Ma, Mo;               // pixels of a_in (dense) and of x_out (QUARTER: compact)
+    int Hc, Wc;               // QUARTER: the compact extent, (H + 1) / 2 x (W + 1) / 2
+    int xo_nt;                // QUARTER: the x_out stores carry the nt hint (the dense form always does)
     int dbg;                // always 0 (the round-2 timing ablations: 1 drop the 3x3's loads, 8 the a_out stores; profiles/r2_v2_bottleneck_fused.txt)
 };
 
@@ -90,7 +93,14 @@ __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 
 // for the strip's first fragment, one extra "edge" load that fetches just the two pixels beside the strip; where the neighbour lies
 // across an image edge (x = 0 / x = W - 1) the tap is zero padding and the lane is cleared.  12 + 6 loads per strip instead of 36:
 // the kernel is bound by the texture addresser (~60 cycles per fragment-shaped load, header), not by VALU issue.
-template <bool TAIL, int BK_THREADS, bool ROWPP, bool PROJ = false>
+// QUARTER (the consumer of x_out reads its even pixels only: rtn.h).  1, store-quarter: the dense walk, but an x_out line leaves only
+// for a pixel with even row and column, to its compact address; a store none of whose 8 pixels is even is skipped (whole strips on
+// odd rows).  2, compute-quarter: the strips walk the COMPACT pixels; the taps of compact pixel (yc, xc) are the dense a_in pixels
+// around (2 yc, 2 xc).  Neighbouring lanes are then two columns apart, so the centre tap no longer yields the side taps: all nine
+// taps are loaded (a quarter of the pixels: 36 fragment loads per strip where the dense form at full M issues 4 x 18).  The weight
+// images, the tap order (kh, kw, k half) and the MFMA chain per pixel are the dense form's, a padding tap is the same zero operand:
+// every stored pixel carries the dense form's bits.
+template <bool TAIL, int BK_THREADS, bool ROWPP, bool PROJ = false, int QUARTER = 0>
 __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_kernel(const BkParams p) {
     // PROJ && TAIL (res2a with res2b's branch2a appended): 21 images do not fit the LDS, so the three per-chunk filter sets are
     // STREAMED - chunk g of an output strip needs image g of branch2c, of the projection and of the next branch2a only: a ring of
@@ -127,9 +137,9 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
     }
     __syncthreads();
 
-    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.ain, 0, p.M * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t a_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.ain, 0, p.Ma * 128, 0x00020000);
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(PROJ ? p.pin : p.xin), 0, PROJ ? p.M * 128 : p.M * 512, 0x00020000);
-    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.xout, 0, p.M * 512, 0x00020000);
+    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.xout, 0, p.Mo * 512, 0x00020000);
     const __amdgpu_buffer_rsrc_t h_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(p.h1out ? p.h1out : p.xout), 0, p.h1out ? p.M * 128 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t n_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(TAIL ? p.aout : p.xout), 0, TAIL ? p.M * 128 : 0, 0x00020000);
 
@@ -166,7 +176,8 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
 #define BK_BIAS(BASE, F) (*reinterpret_cast<const f32x4*>(bias_l + (BASE) + 32 * ((F) >> 1) + 8 * q + 4 * ((F) & 1)))
 #define BK_MFMA(ACC, A, B) ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), ACC, 0, 0, 0)
 
-    const int cells = p.H * p.W;
+    const int cells = QUARTER == 2 ? p.Hc * p.Wc : p.H * p.W;      // of the walked pixel order
+    const int roww = QUARTER == 2 ? p.Wc : p.W;
     const int stride = (int)gridDim.x * (BK_THREADS / 64);
     // strips are dealt wave-major: the one or two extra strips of a launch go to the low wave indices of every workgroup
     // ---- geometry of a strip for this lane: its two pixels, the byte offsets of their taps, the shortcut / output offsets
@@ -176,6 +187,7 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
         unsigned xoff[2];           // byte offset in a 256-channel tensor (+ this lane's 8-channel group), out of range past M
         unsigned aoff[2];           // byte offset in the 64-channel output
         unsigned xs[2][2];          // byte offset in the 256-channel output of pixel 16 u + 8 j + (lane >> 3), + 16 (lane & 7)
+        unsigned xany;              // QUARTER == 1, wave-uniform: bit (2 u + j) = store (u, j) has an even pixel
     };
     auto geometry = [&](int strip, Geo& g) {
         const int p0 = strip * 32;
@@ -186,7 +198,9 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
             const int pc = live ? pix : 0;
             int b, rem, y, x;
             divmod24(pc, cells, p.inv_cells, b, rem);
-            divmod24(rem, p.W, p.inv_w, y, x);
+            divmod24(rem, roww, p.inv_w, y, x);
+            int dp = pc;            // the pixel's index in the dense a_in
+            if (QUARTER == 2) { y *= 2; x *= 2; dp = (b * p.H + y) * p.W + x; }
             unsigned m = 0;
 #pragma unroll
             for (int kh = 0; kh < 3; ++kh)
@@ -194,20 +208,46 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
                 for (int kw = 0; kw < 3; ++kw)
                     if (live && (unsigned)(y + kh - 1) < (unsigned)p.H && (unsigned)(x + kw - 1) < (unsigned)p.W) m |= 1u << (kh * 3 + kw);
             g.okmask[u] = (p.dbg & 1) ? 0u : m;
-            g.pbase[u] = (unsigned)pc * 128u + (unsigned)q * 16u;
+            g.pbase[u] = (unsigned)dp * 128u + (unsigned)q * 16u;
             g.xoff[u] = live ? (unsigned)pix * 512u + (unsigned)q * 16u : BK_OOB;
             g.aoff[u] = (live && !(p.dbg & 8)) ? (unsigned)pix * 128u + (unsigned)q * 16u : BK_OOB;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int px = p0 + 16 * u + 8 * j + (lane >> 3);
-                g.xs[u][j] = (strip < p.nstrips && px < p.M) ? (unsigned)px * 512u + (unsigned)(lane & 7) * 16u : BK_OOB;
+                const bool in = strip < p.nstrips && px < p.M;
+                if (QUARTER == 1) {     // only an even pixel has a line in the compact x_out
+                    int bq, rq, yq, xq;
+                    divmod24(in ? px : 0, cells, p.inv_cells, bq, rq);
+                    divmod24(rq, roww, p.inv_w, yq, xq);
+                    g.xs[u][j] = (in && !((yq | xq) & 1)) ? (unsigned)((bq * p.Hc + (yq >> 1)) * p.Wc + (xq >> 1)) * 512u + (unsigned)(lane & 7) * 16u : BK_OOB;
+                } else
+                    g.xs[u][j] = in ? (unsigned)px * 512u + (unsigned)(lane & 7) * 16u : BK_OOB;
             }
+        }
+        g.xany = 0;
+        if (QUARTER == 1) {
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    if (__builtin_amdgcn_ballot_w64(g.xs[u][j] != BK_OOB)) g.xany |= 1u << (2 * u + j);
         }
     };
     // a tap row in registers: the centre tap + the edge pixels
-    struct Row { uint4 v[1][2][2]; uint4 e[2]; };       // v[0][k half][u]; e[k half]: lane 0 = pixel left of the strip, lane 15 = right of it
+    // (QUARTER == 2: all three taps, v[kw][k half][u], and no edge pixels)
+    struct Row { uint4 v[QUARTER == 2 ? 3 : 1][2][2]; uint4 e[2]; };       // v[0][k half][u]; e[k half]: lane 0 = pixel left of the strip, lane 15 = right of it
 #define BK_LOAD_ROW(KH, G, DST)                                                                      \
-    {                                                                                                \
+    if (QUARTER == 2) {                                                                              \
+        const int delta_ = ((KH) - 1) * p.W * 128;                                                   \
+        _Pragma("unroll") for (int kw_ = 0; kw_ < 3; ++kw_)                                          \
+            _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                       \
+                const unsigned off_ = ((G.okmask[u_] >> ((KH) * 3 + kw_)) & 1u) ? G.pbase[u_] + (unsigned)(delta_ + (kw_ - 1) * 128) : BK_OOB; \
+                _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_) {                                \
+                    const u32x4 v_ = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, (int)off_, ks_ * 64, 0); \
+                    DST.v[QUARTER == 2 ? kw_ : 0][ks_][u_] = make_uint4(v_.x, v_.y, v_.z, v_.w);     \
+                }                                                                                    \
+            }                                                                                        \
+    } else {                                                                                         \
         const int delta_ = ((KH) - 1) * p.W * 128;                                                   \
         _Pragma("unroll") for (int u_ = 0; u_ < 2; ++u_) {                                           \
             const unsigned off_ = ((G.okmask[u_] >> ((KH) * 3 + 1)) & 1u) ? G.pbase[u_] + (unsigned)delta_ : BK_OOB; \
@@ -244,7 +284,11 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
                 BK_MFMA(acc1[f_][1], wf_, OPND[ks_][1]);                                             \
             }
 #define BK_MUL_ROW(KH, SRC, G)                                                                       \
-    {                                                                                                \
+    if (QUARTER == 2) {                                                                              \
+        BK_MUL_TAP(KH, 0, SRC.v[0])                                                                  \
+        BK_MUL_TAP(KH, 1, SRC.v[QUARTER == 2 ? 1 : 0])                                               \
+        BK_MUL_TAP(KH, 2, SRC.v[QUARTER == 2 ? 2 : 0])                                               \
+    } else {                                                                                         \
         uint4 nb_[2][2];                                                                             \
         _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_) {                                        \
             nb_[ks_][0] = keep_if(shift_right(SRC.e[ks_], SRC.v[0][ks_][0]), (G.okmask[0] >> ((KH) * 3 + 0)) & 1u);                        \
@@ -394,13 +438,16 @@ __global__ __launch_bounds__(BK_THREADS, BK_THREADS / 256) void bottleneck64_ker
                     // stores of 16 half lines: the texture addresser spends ~60 cycles on the latter (header)
 #pragma unroll
                     for (int j = 0; j < 2; ++j) {
+                        if (QUARTER == 1 && !((gc.xany >> (2 * u + j)) & 1u)) continue;      // uniform: none of the 8 pixels is even
                         const uint4 o = *reinterpret_cast<const uint4*>(xl + j * 1024 + xr_lane);
                         const u32x4 ov = {o.x, o.y, o.z, o.w};
                         // aux 2 = nt: a streaming store.  x_out (273 MB at batch 8) is many times the L2 and is read back by the next
                         // launch only; without the hint its lines push the tap rows and shortcut lines out of the L2 on their way to
                         // memory.  Launch alone 0.122 / 0.147 / 0.133 -> 0.102 / 0.140 / 0.123 ms, the step -0.4 % (tools/ab_engine.py);
                         // the same hint on the shortcut loads changed nothing.
-                        __builtin_amdgcn_raw_buffer_store_b128(ov, o_rsrc, (int)gc.xs[u][j], g * 128, 2);
+                        // (QUARTER: the compact x_out is a quarter of that and fits the last-level cache, the hint is the launcher's choice)
+                        if (QUARTER == 0 || p.xo_nt) __builtin_amdgcn_raw_buffer_store_b128(ov, o_rsrc, (int)gc.xs[u][j], g * 128, 2);
+                        else                         __builtin_amdgcn_raw_buffer_store_b128(ov, o_rsrc, (int)gc.xs[u][j], g * 128, 0);
                         BK_STORE_GUARD(ov)
                     }
                 }
@@ -474,13 +521,26 @@ extern "C" int rtn_bottleneck64_fwd(rtn_handle_t h, const rtn_bottleneck_desc_t*
     for (const void* q : need)
         if (!q || ((uintptr_t)q & 15)) return rtn_fail(h, RTN_EINVAL, "bottleneck64: null / misaligned pointer");
     const bool tail = d->a_out != nullptr;
+    // the quarter forms (rtn.h): 1 = store-quarter (x_out compact, with a_out), 2 = compute-quarter (x_in and x_out compact, no a_out)
+    if ((d->x_out_step != 0 && d->x_out_step != 1 && d->x_out_step != 2) || (d->x_in_step != 0 && d->x_in_step != 1 && d->x_in_step != 2))
+        return rtn_fail(h, RTN_EINVAL, "bottleneck64: x_out_step %d / x_in_step %d (0, 1 or 2)", d->x_out_step, d->x_in_step);
+    const bool xo2 = d->x_out_step == 2, xi2 = d->x_in_step == 2;
+    if ((xo2 || xi2) && (proj || d->h1_out))
+        return rtn_fail(h, RTN_EINVAL, "bottleneck64: a stepped tensor does not combine with the projection form or with h1_out");
+    if (xi2 && !xo2) return rtn_fail(h, RTN_EINVAL, "bottleneck64: x_in_step 2 needs x_out_step 2");
+    if (xo2 && xi2 == tail)
+        return rtn_fail(h, RTN_EINVAL, "bottleneck64: x_out_step 2 takes either a_out and a dense x_in, or a compact x_in and no a_out");
+    const int quarter = xo2 ? (xi2 ? 2 : 1) : 0;
+    const int Hc = (d->H + 1) / 2, Wc = (d->W + 1) / 2;
+    const long long Mc = (long long)d->batch * Hc * Wc;
+    const long long Mxi = xi2 ? Mc : M, Mxo = xo2 ? Mc : M;        // pixels of x_in / x_out
     const int w2c_ld = d->w2c_ld > 0 ? d->w2c_ld : 64;
     if (w2c_ld < 64 || w2c_ld % 8) return rtn_fail(h, RTN_EINVAL, "bottleneck64: w2c_ld %d", d->w2c_ld);
     if (proj && (((uintptr_t)d->wproj & 15) || d->p_in_elems < M * 64))
         return rtn_fail(h, RTN_EINVAL, "bottleneck64: the projection-shortcut form takes p_in [M][64] and an aligned wproj");
     if (tail && (!d->w2a || !d->b2a || ((uintptr_t)d->a_out & 15) || ((uintptr_t)d->w2a & 15) || ((uintptr_t)d->b2a & 15)))
         return rtn_fail(h, RTN_EINVAL, "bottleneck64: a_out needs aligned w2a / b2a");
-    if (d->a_in_elems < M * 64 || (!proj && d->x_in_elems < M * 256) || d->x_out_elems < M * 256 || (tail && d->a_out_elems < M * 64))
+    if (d->a_in_elems < M * 64 || (!proj && d->x_in_elems < Mxi * 256) || d->x_out_elems < Mxo * 256 || (tail && d->a_out_elems < M * 64))
         return rtn_fail(h, RTN_EBOUNDS, "bottleneck64: a tensor is smaller than batch x H x W x channels");
     if (d->h1_out && (((uintptr_t)d->h1_out & 15) || d->h1_out_elems < M * 64 || d->h1_out == d->a_in))
         return rtn_fail(h, RTN_EINVAL, "bottleneck64: h1_out must be an aligned [M][64] tensor other than a_in");
@@ -502,10 +562,14 @@ extern "C" int rtn_bottleneck64_fwd(rtn_handle_t h, const rtn_bottleneck_desc_t*
     p.w2b = (const char*)d->w2b; p.w2c = (const char*)d->w2c; p.w2a = (const char*)d->w2a;
     p.pin = (const char*)d->p_in; p.wproj = (const char*)d->wproj; p.w2c_ld = w2c_ld;
     p.b2b = d->b2b; p.b2c = d->b2c; p.b2a = d->b2a;
-    p.M = (int)M; p.H = d->H; p.W = d->W;
-    p.nstrips = (int)((M + 31) / 32);
-    p.inv_cells = 1.0f / (float)((long long)d->H * d->W);
-    p.inv_w = 1.0f / (float)d->W;
+    p.M = (int)Mxi; p.H = d->H; p.W = d->W;              // the strips walk the pixels of x_in
+    p.Ma = (int)M; p.Mo = (int)Mxo; p.Hc = Hc; p.Wc = Wc;
+    p.nstrips = (int)((Mxi + 31) / 32);
+    p.inv_cells = 1.0f / (float)(xi2 ? (long long)Hc * Wc : (long long)d->H * d->W);
+    p.inv_w = 1.0f / (float)(xi2 ? Wc : d->W);
+    // A compact x_out (68 MB at batch 8) fits the last-level cache and the next launch reads it: RTN_BNECK_COMPACT_NT chooses
+    // between the streaming hint of the dense form and plain stores (the A/B: DESIGN.md 6.4)
+    p.xo_nt = rtn_env_int("RTN_BNECK_COMPACT_NT", 1) != 0;
     p.dbg = 0;                                         // (timing ablations of round 2: profiles/r2_v2_bottleneck_fused.txt)
     const int nt = BK_NT;
     int grid = h->num_cus > 0 ? h->num_cus : 256;
@@ -515,7 +579,9 @@ extern "C" int rtn_bottleneck64_fwd(rtn_handle_t h, const rtn_bottleneck_desc_t*
     const bool rowpp = rtn_bneck_rowpp(nt);
     const dim3 gdim((unsigned)grid), bdim(512);
     int lrc;
-    if (proj)       lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, true, true>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
+    if (quarter == 1)      lrc = rtn_launch_lds<bottleneck64_kernel<true, 512, true, false, 1>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
+    else if (quarter == 2) lrc = rtn_launch_lds<bottleneck64_kernel<false, 512, true, false, 2>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
+    else if (proj)  lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, true, true>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
                                : rtn_launch_lds<bottleneck64_kernel<false, 512, true, true>>(h, gdim, bdim, BK_LDS, BK_LDS, p);
     else if (rowpp) lrc = tail ? rtn_launch_lds<bottleneck64_kernel<true, 512, true, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p)
                                : rtn_launch_lds<bottleneck64_kernel<false, 512, true, false>>(h, gdim, bdim, BK_LDS, BK_LDS, p);

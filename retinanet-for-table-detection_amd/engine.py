@@ -148,6 +148,9 @@ class Engine:
         # bf16: an identity block's branch2c + Add + ReLU and the next block's branch2a as one launch in the 128-channel stage
         # (rtn_chain1x1_fwd; the 256-channel instance measured no faster and left the library: profiles/r4_seam_kernel.txt)
         self.fuse_chain = os.environ.get("RTN_FUSE_CHAIN", "1") != "0"
+        # detect(): nobody outside the network sees the backbone features, and stage 3 reads C2 only at its even pixels (both readers
+        # are 1x1 / stride 2): res2b stores and res2c computes that quarter only (_fused(private=True); forward() keeps C2 whole)
+        self.skip_unread_c2 = os.environ.get("RTN_SKIP_UNREAD_C2", "1") != "0"
         self.weights_version = 0
         self.load_epoch = 0            # bumped by load_state(): a live Trainer re-derives its master copy / plans from it
         self._dual, self._dual_version = {}, -1
@@ -385,12 +388,13 @@ class Engine:
         return ("bneck", d, fb["n2b"] + "+2c+1" + ("+next2a" if nxt is not None else ""),
                 {"xs": [a, x], "ys": outs, "B": B, "H": fb["Ho"], "W": fb["Wo"], "tail": nxt is not None, "proj": True, "h1": keep_h1})
 
-    def _bneck_op(self, blk, nxt, B, keep_h1=False):
+    def _bneck_op(self, blk, nxt, B, keep_h1=False, xq=None, yq=None):
         """An identity block of the 64-channel stage as one launch (rtn_bottleneck64_fwd): branch2b + branch2c + Add + ReLU of
-        `blk`, and branch2a of the following identity block `nxt` when there is one."""
+        `blk`, and branch2a of the following identity block `nxt` when there is one.  xq / yq: compact quarter tensors (the even
+        pixels) that stand in for the shortcut / the block output (the library's x_in_step / x_out_step = 2)."""
         w2b, b2b = self.w[blk["n2b"]][:2]
         w2c, b2c = self.w[blk["n2c"]][:2]
-        a, x, y = blk["a"], blk["x"], blk["y"]
+        a, x, y = blk["a"], blk["x"] if xq is None else xq, blk["y"] if yq is None else yq
         d = L.BottleneckDesc()
         d.a_in, d.a_in_elems = a.data_ptr(), a.numel()
         d.x_in, d.x_in_elems = x.data_ptr(), x.numel()
@@ -403,11 +407,13 @@ class Engine:
             d.w2a, d.b2a = w2a.data_ptr(), b2a.data_ptr()
             outs.append(nxt["a"])
         d.batch, d.H, d.W, d.mid, d.dtype = B, blk["Ho"], blk["Wo"], 64, self.rdt
+        d.x_in_step, d.x_out_step = 1 if xq is None else 2, 1 if yq is None else 2
         if keep_h1:
             d.h1_out, d.h1_out_elems = blk["b2"].data_ptr(), blk["b2"].numel()
             outs.append(blk["b2"])
         name = blk["n2b"] + "+2c" + ("+next2a" if nxt is not None else "")
-        return ("bneck", d, name, {"xs": [a, x], "ys": outs, "B": B, "H": blk["Ho"], "W": blk["Wo"], "tail": nxt is not None, "h1": keep_h1})
+        return ("bneck", d, name, {"xs": [a, x], "ys": outs, "B": B, "H": blk["Ho"], "W": blk["Wo"], "tail": nxt is not None, "h1": keep_h1,
+                                   "x_in_step": int(d.x_in_step), "x_out_step": int(d.x_out_step)})
 
     def _chain_op(self, sm):
         """The seam between two identity blocks of the 128- / 256-channel stages as one launch (rtn_chain1x1_fwd): branch2c + Add +
@@ -633,15 +639,15 @@ class Engine:
         return plan
 
     def _variant(self, plan, key):
-        """{ops, sched, events} that forward() runs under the fusion key (fs, fd, fk, fc, fp, ft) of _fused(): built on first use and
-        kept in the plan.  The all-zero key is the plan's own op list and schedule."""
+        """{ops, sched, events} that forward() runs under the fusion key (fs, fd, fk, fc, fp, ft, fq) of _fused(): built on first use
+        and kept in the plan.  The all-zero key is the plan's own op list and schedule."""
         rec = plan["variants"].get(key)
         if rec is not None:
             return rec
         if not any(key):
             ops, sched = plan["ops"], plan["sched"]
         else:
-            fs, fd, fk, fc, fp, ft = key
+            fs, fd, fk, fc, fp, ft, fq = key
             fu, B = plan["fusion"], plan["xin"]["B"]
             first_blocks, blocks64 = fu["first_blocks"], fu["blocks64"]
             v = list(plan["ops"])
@@ -672,6 +678,21 @@ class Engine:
                     v[blk["i_2c"]] = None
                     if nxt is not None:
                         v[nxt["i_2a"]] = None
+            if fq:
+                # C2 is read at its even pixels only (res3a's branch2a and branch1: 1x1, stride 2).  The stage's last block computes
+                # and writes that quarter, the block before it stores the matching quarter of its output (whose only reader in
+                # memory is the last block's shortcut), and res3a reads the compact C2 with stride 1.
+                prev, last = blocks64[-2], blocks64[-1]
+                fb3 = [fb for fb in first_blocks if fb["x"] is last["y"]][0]
+                if "c2_quarter" not in plan:                  # two tensors a quarter of C2 each, shared by the variants like dual_ops
+                    hq, wq = (last["Ho"] + 1) // 2, (last["Wo"] + 1) // 2
+                    plan["c2_quarter"] = [torch.empty(B, hq, wq, 256, dtype=self.tdt, device=self.device) for _ in range(2)]
+                    plan["keep"] += plan["c2_quarter"]
+                    xq, c2q = plan["c2_quarter"]
+                    plan["c2_quarter_ops"] = (self._bneck_op(prev, last, B, yq=xq), self._bneck_op(last, None, B, xq=xq, yq=c2q),
+                                              self._conv(fb3["n2a"], [self._group(c2q, fb3["a"], fb3["Ho"], fb3["Wo"])], B, flags=L.CONV_RELU),
+                                              self._dual_op(dict(fb3, x=c2q, step=1), B))
+                v[prev["i_2b"]], v[last["i_2b"]], v[fb3["i_2a"]], v[fb3["i_2c"]] = plan["c2_quarter_ops"]
             if fs:
                 sf = fu["stem"]
                 fb0 = first_blocks[0]
@@ -740,14 +761,15 @@ class Engine:
     def _bind_stream(self):
         self.h.set_stream(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def forward(self, images):
+    def forward(self, images, private=False):
         """images: device tensor (B,H,W,3), float32 / bfloat16 (already normalised) or uint8 (raw 3-channel
         distance-transform page: the x/127.5-1 of model/utils.py:43-46 is fused into the stem packer).
         Returns device tensors regression (B,N,4) f32, classification (B,N,K) f32 — the training
         model's outputs in the reference's order (model/defineModel.py:244-249).
         The returned tensors are the plan's OWN output buffers for this (B,H,W): the next forward()/detect() call with the
         same shape overwrites them (no allocation per step).  Clone what must outlive the next call
-        (Model.predict_on_batch copies to the host)."""
+        (Model.predict_on_batch copies to the host).
+        private: the caller reads nothing but the two outputs (detect()), so launches may leave out what only plan["feats"] shows."""
         if images.device.type != "cuda" or images.dim() != 4 or images.shape[3] != 3:
             raise ValueError("images must be a (B,H,W,3) tensor on the GPU")
         if images.dtype not in _SRC_DT:
@@ -758,7 +780,7 @@ class Engine:
             self.plans = {k: v for k, v in self.plans.items() if not k[3]}      # new filters: new weight scales in the fp8 ops
         plan = self._plan(B, H, W)
         self._bind_stream()
-        key = self._fused()
+        key = self._fused(private)
         if key[1]:
             self._dual_weights()                         # refresh the concatenated filters if the weights changed
         var = self._variant(plan, key)
@@ -793,15 +815,17 @@ class Engine:
         self.h.set_stream(main.cuda_stream)
         return plan["regression"], plan["classification"]
 
-    def _fused(self):
-        """Fusion key (fs, fd, fk, fc, fp, ft) of the engine's state, the variant of a plan that forward() runs (_variant): stem fused
+    def _fused(self, private=False):
+        """Fusion key (fs, fd, fk, fc, fp, ft, fq) of the engine's state, the variant of a plan that forward() runs (_variant): stem fused
         (0 / 1 / 2 = with res2a_branch2a), shortcut folded, 64-channel bottleneck blocks fused (1 / 2 = keeping branch2b's output),
         stage-3 seams chained, res2b_branch2a appended to res2a's block, the pool's winning taps recorded.  A training forward whose
         backward never reaches the stem or the 64-channel stage (frozen layers, train_keep) runs those launches in their inference
         form: fk = 1, ft = 0 - the same bits, fewer stores.  Training keeps
         every bottleneck tensor (the backward reads them) and, in fp32, conv1 / pool1 separate; the folded
         shortcut is used there too - no gradient needs the shortcut TENSOR, only its input and filters.  The fused stem and the fused
-        bottleneck exist for bf16 only; the fp8 plan keeps its own branch2a / branch2b pairing."""
+        bottleneck exist for bf16 only; the fp8 plan keeps its own branch2a / branch2b pairing.
+        fq (only with `private`, i.e. from detect(): the backbone features stay inside the network): with the fused blocks in their
+        inference form and the shortcut folded, C2 and res2b's output exist only at the even pixels that stage 3 reads."""
         stem16 = self.dtype == "bf16" and (not self.training or self.fuse_stem_train)
         keep_h1, ft = (self.train_keep or (True, True)) if self.training else (False, False)
         fk = 0
@@ -811,15 +835,16 @@ class Engine:
         # (training too: both tensors of a seam are written, which is all the backward pass reads)
         fc = 1 if (self.fuse_chain and self.dtype == "bf16" and not self._fp8_on()) else 0
         fp = 1 if (self.fuse_proj_tail and fk and self.fuse_shortcut) else 0
-        return (fs, self.fuse_shortcut, fk, fc, fp, int(ft))
+        fq = 1 if (private and self.skip_unread_c2 and fk == 1 and self.fuse_shortcut and not self.training) else 0
+        return (fs, self.fuse_shortcut, fk, fc, fp, int(ft), fq)
 
     def _taps(self):
         """The pool (or the fused stem) records its winning taps: a training forward whose backward runs the pool's backward."""
         return self.training and (self.train_keep is None or bool(self.train_keep[1]))
 
-    def active_ops(self, plan):
-        """The op list forward() executes."""
-        return self._variant(plan, self._fused())["ops"]
+    def active_ops(self, plan, private=False):
+        """The op list forward() executes; private: the one detect() executes (the same launches, one for one)."""
+        return self._variant(plan, self._fused(private))["ops"]
 
     def _run_op(self, op, images):
         lib, h = L.lib, self.h
@@ -873,7 +898,7 @@ class Engine:
         B, H, W, _ = images.shape
         plan = self._plan(B, H, W)
         self._bind_stream()
-        ops = self.active_ops(plan)
+        ops = self.active_ops(plan, private=True)            # what detect() runs
         totals = [0.0] * (len(ops) + 1)
         for _ in range(reps):
             evs = [torch.cuda.Event(enable_timing=True) for _ in range(len(ops) + 2)]
@@ -906,7 +931,7 @@ class Engine:
         flags = detect_flags(nms, class_specific_filter)
         if self.in_flight > 1 and not self.training:
             return self._detect_in_flight(images, score_threshold, nms_threshold, md, flags)
-        reg, cls = self.forward(images)
+        reg, cls = self.forward(images, private=True)
         B, H, W, _ = images.shape
         plan = self._plan(B, H, W)
         # the library writes (B, max_detections, .) densely: hand it views of that shape over the plan's buffers
@@ -935,7 +960,7 @@ class Engine:
             self.join()
             self.plans = {k: v for k, v in self.plans.items() if not k[3]}
         plan = self._plan(B, H, W, slot=si + 1)             # slot 0 is forward()'s / the one-batch path's own buffer set
-        key = self._fused()
+        key = self._fused(private=True)
         caller = torch.cuda.current_stream(self.device)
         if key[1] and self._dual_version != self.weights_version:
             self.join()                                       # new weights: the concatenated filters are rewritten on the caller's

@@ -13,7 +13,7 @@ for _ in range(2): eng.detect(x)
 reps = 5
 per = eng.profile_ops(x, reps=reps)
 plan = eng._plan(bench.BATCH, *bench.CANVAS)
-ops = eng.active_ops(plan)
+ops = eng.active_ops(plan, private=True)      # what detect() and profile_ops() run
 GEN = {1: "1 (128-row, register-staged)", 2: "2 (256-row LDS-DMA per tap)", 3: "3 (256-row shared halo)", 4: "4 (persistent 8-phase 3x3)",
        5: "5 (persistent 8-phase 1x1)", 6: "6 (narrow-N head output)"}
 rows = []
@@ -33,7 +33,8 @@ for (kind, ms), op in zip(per, ops):
         rows.append((name, GEN.get(impl, str(impl)), tl, dec, shape, ms))
     elif kind == "bneck":
         m = op[3]
-        rows.append((name, "fused bottleneck (rtn_bottleneck64_fwd)", "32-pixel strips per wave", "persistent, all filters in LDS", "M %d" % (m["B"] * m["H"] * m["W"]), ms))
+        rows.append((name, "fused bottleneck (rtn_bottleneck64_fwd)", "32-pixel strips per wave", "persistent, all filters in LDS",
+                     "M %d%s" % (m["B"] * m["H"] * m["W"], {(1, 2): ", x_out at even pixels only", (2, 2): ", even pixels only"}.get((m.get("x_in_step", 1), m.get("x_out_step", 1)), "")), ms))
     elif kind == "chain":
         m = op[3]
         rows.append((name, "fused seam (rtn_chain1x1_fwd)", "%d-pixel strips per wave" % (32 if m["mid"] == 128 else 16), "persistent, filters streamed through LDS in 64-channel chunks",

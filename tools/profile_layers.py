@@ -28,13 +28,18 @@ per = eng.profile_ops(x, reps=reps)
 plan = eng._plan(B, *canvas)
 tot = 0.0
 print("%-28s %9s %9s %8s  shape" % ("op", "ms", "GFLOP", "TFLOP/s"))
-for (kind, ms), op in zip(per, eng.active_ops(plan) + [("detect",)]):
+for (kind, ms), op in zip(per, eng.active_ops(plan, private=True) + [("detect",)]):
     ms /= reps; tot += ms
     if kind == "bneck":
         m = op[3]; px = m["B"] * m["H"] * m["W"]
         fl = 2.0 * px * (576 * 64 + 64 * 256 + 256 * 64 * (int(bool(m["tail"])) + int(bool(m.get("proj")))))
         by = 2.0 * px * ((64 + 64 + 256 + (64 if m["tail"] else 0)) if m.get("proj") else (64 + 256 + 256 + (64 if m["tail"] else 0)))
-        print("%-28s %9.4f %9.2f %8.1f  fused bottleneck M=%d, %.0f MB -> %.2f TB/s" % (op[2], ms, fl / 1e9, fl / ms / 1e9, px, by / 1e6, by / ms / 1e9))
+        form = ""
+        if m.get("x_out_step", 1) == 2:                     # the quarter forms: x_out (and x_in) hold the even pixels only
+            pq = m["B"] * ((m["H"] + 1) // 2) * ((m["W"] + 1) // 2)
+            if m["x_in_step"] == 2: fl, by, form = fl * pq / px, 2.0 * (px * 64 + pq * 512), " compute-quarter"
+            else: by, form = 2.0 * (px * (64 + 256 + 64) + pq * 256), " store-quarter"
+        print("%-28s %9.4f %9.2f %8.1f  fused bottleneck%s M=%d, %.0f MB -> %.2f TB/s" % (op[2], ms, fl / 1e9, fl / ms / 1e9, form, px, by / 1e6, by / ms / 1e9))
     elif kind == "chain":
         m = op[3]; pc = m.get("proj_c", 0); fl = 2.0 * m["pixels"] * (2 * m["mid"] + pc) * 4 * m["mid"]; by = 2.0 * m["pixels"] * ((6 * m["mid"] + pc) if pc else 10 * m["mid"])
         print("%-28s %9.4f %9.2f %8.1f  fused seam M=%d, %.0f MB -> %.2f TB/s" % (op[2], ms, fl / 1e9, fl / ms / 1e9, m["pixels"], by / 1e6, by / ms / 1e9))
