@@ -326,33 +326,20 @@ int rtn_maxpool3x3s2_tfsame_bwd_idx(rtn_handle_t h, const void* dy, const uint8_
 /* ---- optimizer: Adam(lr, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=0.001)  (RetinaNet.py:130) ---------------
  * Parameters live in ONE flat f32 buffer (forward weight layout per layer).  gscale[i] multiplies the raw gradient
  * (frozen-BN fold factor of the layer's output channel; 0 for structurally-zero slots), fold[i] re-creates the forward
- * weight w_fwd[i] = cast(w[i] * fold[i]).  Clipping is by the GLOBAL norm of all gradients (standalone Keras 2.x,
- * SURVEY §8a a20): sumsq = sum((g*gscale)^2) from rtn_sumsq (all-reduced by the caller under data parallelism),
- * factor = min(1, clipnorm / (sqrt(sumsq) * |grad_mul|)); grad_mul rescales g (e.g. 1/world_size).  clipnorm <= 0: off. */
+ * weight w_fwd[i] = cast(w[i] * fold[i]).  grad_mul rescales g (e.g. 1/world_size).
+ * The step runs over element RANGES of that buffer: table_dev (int64, on the device) holds nr rows (begin, end, vbegin): range r is
+ * the flat slice [begin, end) (relative to w / m / v / g / gscale / fold / w_fwd) and occupies [vbegin, vbegin + end - begin) of the
+ * launch's index space, `span` long.  Rows are in increasing vbegin order and do not overlap there; vbegin = begin (mod 4) lets every
+ * quad inside a range use 16-byte accesses (ranges_table in _lib.py builds such a table).  Slots outside the ranges are never read
+ * or written; indices >= n are skipped.  Empty ranges are allowed; nr = 0 (span 0) is a no-op (rtn_sumsq_ranges then writes 0).
+ * The full step is one range per weight tensor and per bias vector; frozen-layer training leaves the frozen layers' rows out.
+ * Under global clipping ranges that touch may be passed as one row: the same elements at the same places, fewer rows to search.
+ * rtn_sumsq_ranges: out (may be NULL; needs the workspace) = sum over the ranges of (g*scale)^2, in a fixed order; out_each (may be
+ * NULL, nr doubles) = the same sum per range, one workgroup each.  Under data parallelism the caller all-reduces g first.
+ * Clipping (clipnorm <= 0: off): rtn_adam_clipnorm_step_ranges scales every gradient by min(1, clipnorm / (sqrt(sumsq[0]) * |grad_mul|)),
+ * the GLOBAL norm (standalone Keras 2.x); rtn_adam_clipnorm_step_ranges_pertensor scales range r by its own norm
+ * sqrt(sumsq_each[r]) in the same expression (tf.keras / Keras >= 2.4 semantics of Adam(clipnorm=c) when every range is one tensor). */
 size_t rtn_sumsq_workspace_bytes(void);
-int rtn_sumsq(rtn_handle_t h, const float* g, const float* scale, int64_t n, double* out, void* workspace, size_t workspace_bytes);
-int rtn_adam_clipnorm_step(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale, const float* fold,
-                           void* w_fwd, int fwd_dtype, int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
-                           const double* sumsq, float clipnorm, float grad_mul);
-/* The same step with PER-TENSOR clipping (tf.keras / Keras >= 2.4 semantics of Adam(clipnorm=c), RetinaNet.py:130 under those
- * versions): tensor t, the segment [seg_begin[t], seg_begin[t+1]) of the flat vector (int64 table on the device,
- * nseg + 1 entries, at most 2048 tensors), is scaled by clipnorm / max(norm_t, clipnorm).  rtn_sumsq_segments writes the nseg sums of
- * (g*scale)^2 in a fixed order (one workgroup per tensor); `elem_offset` is the flat index of w[0] when the step runs on a sub-range. */
-int rtn_sumsq_segments(rtn_handle_t h, const float* g, const float* scale, const int64_t* seg_begin_dev, int nseg, double* out_dev);
-int rtn_adam_clipnorm_step_segments(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale, const float* fold,
-                                    void* w_fwd, int fwd_dtype, int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
-                                    const int64_t* seg_begin_dev, int nseg, const double* sumsq_seg_dev, int64_t elem_offset,
-                                    float clipnorm, float grad_mul);
-/* The same steps over a SUBSET of the flat vector: the trainable layers of frozen-layer training.  table_dev (int64, on the device)
- * holds nr rows (begin, end, vbegin): range r is the flat slice [begin, end) (relative to w / m / v / g / gscale / fold / w_fwd) and
- * occupies [vbegin, vbegin + end - begin) of the launch's index space, `span` long.  Rows are in increasing vbegin order and do not
- * overlap there; vbegin = begin (mod 4) lets every quad inside a range use 16-byte accesses (rtn_ranges in _lib.py builds such a
- * table).  Slots outside the ranges are never read or written; indices >= n are skipped.  Empty ranges are allowed; nr = 0 (span 0)
- * is a no-op (rtn_sumsq_ranges then writes 0).
- * rtn_sumsq_ranges: out (may be NULL) = sum over the ranges of (g*scale)^2, in a fixed order (the rtn_sumsq workspace); out_each
- * (may be NULL, nr doubles) = the same sum per range.  rtn_adam_clipnorm_step_ranges clips by the global norm sqrt(sumsq[0]) as
- * rtn_adam_clipnorm_step; rtn_adam_clipnorm_step_ranges_pertensor by each range's own norm sqrt(sumsq_each[r]) as
- * rtn_adam_clipnorm_step_segments (one range per tensor).  Fold, gscale and the forward-weight re-emission as above. */
 int rtn_sumsq_ranges(rtn_handle_t h, const float* g, const float* scale, int64_t n, const int64_t* table_dev, int nr, int64_t span,
                      double* out, double* out_each, void* workspace, size_t workspace_bytes);
 int rtn_adam_clipnorm_step_ranges(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale, const float* fold,

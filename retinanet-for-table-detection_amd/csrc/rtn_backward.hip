@@ -6,7 +6,7 @@
 //   rtn_zero_insert2      dY -> zero-inserted dY for the data gradient of the stride-2 3x3 convs (P6, P7)
 //   rtn_upsample_add_bwd  adjoint of UpsampleLike (legacy-TF nearest) + Add  (model/layers.py:89-98)
 //   rtn_maxpool3x3s2_tfsame_bwd
-//   rtn_sumsq / rtn_adam_clipnorm_step   global-norm clip + Adam on the flat parameter buffer
+//   rtn_sumsq_ranges / rtn_adam_clipnorm_step_ranges[_pertensor]   clipnorm + Adam over element ranges of the flat parameter buffer
 //
 // wgrad on MFMA: the reduction runs over PIXELS, so both operands are needed pixel-major per lane while memory is
 // channel-major.  Tiles [64 pixels][16 x 16-byte chunks] are staged as they lie in memory (range-checked buffer loads:
@@ -989,129 +989,6 @@ __global__ __launch_bounds__(256) void pad_cast_rows8_kernel(const float* __rest
     }
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// sum over i of (g[i]*scale[i])^2 -> partial per block (fixed order), finished by sumsq_final
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, const float* __restrict__ scale, long long n,
-                                                    double* __restrict__ partial) {
-    double s = 0.0;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float v = g[i] * (scale ? scale[i] : 1.f);
-        s += (double)v * (double)v;
-    }
-    __shared__ double sh[4];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-__global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ out) {
-    __shared__ double sh[256];
-    double v = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) v += partial[i];
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = sh[0];
-}
-
-// Keras-2 Adam (RetinaNet.py:130: lr, beta 0.9/0.999, epsilon 1e-7, no decay) with global-norm clipping:
-//   g = grad * scale * min(1, clipnorm / norm);  lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)
-//   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  w -= lr_t * m / (sqrt(v) + eps)
-// and re-emission of the forward weights  w_fwd = cast(w * fold)  (fold = frozen-BN scale per output channel, 1 elsewhere).
-template <int ES>
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                                   const float* __restrict__ g, const float* __restrict__ gscale,
-                                                   const float* __restrict__ fold, char* __restrict__ w_fwd, long long n, float lr_t,
-                                                   float b1, float b2, float eps, const double* __restrict__ sumsq, float clipnorm,
-                                                   float grad_mul) {
-    float clip = 1.f;
-    if (clipnorm > 0.f && sumsq) {
-        const float norm = sqrtf((float)sumsq[0]) * fabsf(grad_mul);
-        if (norm > clipnorm) clip = clipnorm / norm;
-    }
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * (gscale ? gscale[i] : 1.f) * grad_mul * clip;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float wi = w[i] - lr_t * mi / (sqrtf(vi) + eps);
-        m[i] = mi; v[i] = vi; w[i] = wi;
-        if (w_fwd) {
-            const float wf = wi * (fold ? fold[i] : 1.f);
-            if constexpr (ES == 2) {
-                const __bf16 hb = (__bf16)wf;
-                reinterpret_cast<unsigned short*>(w_fwd)[i] = __builtin_bit_cast(unsigned short, hb);
-            } else {
-                reinterpret_cast<float*>(w_fwd)[i] = wf;
-            }
-        }
-    }
-}
-
-// Per-tensor clipping (tf.keras / Keras >= 2.4 semantics of Adam(clipnorm=c)): every gradient tensor t is scaled by
-// c / max(||g_t||, c).  The tensors are contiguous segments [seg_begin[s], seg_begin[s + 1]) of the flat parameter vector.
-__global__ __launch_bounds__(256) void sumsq_segments_kernel(const float* __restrict__ g, const float* __restrict__ scale,
-                                                             const long long* __restrict__ seg_begin, double* __restrict__ out) {
-    const long long lo = seg_begin[blockIdx.x], hi = seg_begin[blockIdx.x + 1];
-    double s = 0.0;
-    for (long long i = lo + threadIdx.x; i < hi; i += 256) {               // fixed order: the same bits on every run
-        const float v = g[i] * (scale ? scale[i] : 1.f);
-        s += (double)v * (double)v;
-    }
-    __shared__ double sh[4];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-}
-
-constexpr int ADAM_MAX_SEGS = 2048;
-template <int ES>
-__global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
-                                                            const float* __restrict__ g, const float* __restrict__ gscale,
-                                                            const float* __restrict__ fold, char* __restrict__ w_fwd, long long n, float lr_t,
-                                                            float b1, float b2, float eps, const long long* __restrict__ seg_begin, int nseg,
-                                                            const double* __restrict__ sumsq_seg, long long elem_offset, float clipnorm,
-                                                            float grad_mul) {
-    __shared__ long long sb[ADAM_MAX_SEGS + 1];
-    __shared__ float sclip[ADAM_MAX_SEGS];
-    for (int i = threadIdx.x; i <= nseg; i += 256) sb[i] = seg_begin[i];
-    for (int i = threadIdx.x; i < nseg; i += 256) {
-        const float norm = sqrtf((float)sumsq_seg[i]) * fabsf(grad_mul);
-        sclip[i] = (clipnorm > 0.f && norm > clipnorm) ? clipnorm / norm : 1.f;
-    }
-    __syncthreads();
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const long long gi_ = i + elem_offset;
-        int lo = 0, hi = nseg;                          // last segment whose begin <= gi_
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (sb[mid] <= gi_) lo = mid; else hi = mid;
-        }
-        const float gi = g[i] * (gscale ? gscale[i] : 1.f) * grad_mul * sclip[lo];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        const float wi = w[i] - lr_t * mi / (sqrtf(vi) + eps);
-        m[i] = mi; v[i] = vi; w[i] = wi;
-        if (w_fwd) {
-            const float wf = wi * (fold ? fold[i] : 1.f);
-            if constexpr (ES == 2) {
-                const __bf16 hb = (__bf16)wf;
-                reinterpret_cast<unsigned short*>(w_fwd)[i] = __builtin_bit_cast(unsigned short, hb);
-            } else {
-                reinterpret_cast<float*>(w_fwd)[i] = wf;
-            }
-        }
-    }
-}
-
 inline unsigned grid_for(long long work, int cap = 4096) {
     long long g = (work + 255) / 256;
     if (g < 1) g = 1;
@@ -1454,70 +1331,25 @@ extern "C" int rtn_maxpool3x3s2_tfsame_bwd(rtn_handle_t h, const void* x, const 
     return RTN_OK;
 }
 
-extern "C" size_t rtn_sumsq_workspace_bytes(void) { return 2048 * sizeof(double); }
+// ---- the optimizer: clipnorm Adam over element ranges of the flat parameter vector --------------------------------------------
+// Keras-2 Adam (RetinaNet.py:130: lr, beta 0.9/0.999, epsilon 1e-7, no decay), per element of the flat f32 vector
+// [weights | bias slots] that holds the unfolded master copy w, the moments m, v and the gradient:
+//   g = grad * gscale * grad_mul * clip;  lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t)
+//   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  w -= lr_t * m / (sqrt(v) + eps);  w_fwd = cast(w * fold)
+// gscale is the frozen-BN scale of the element's output channel (the gradient arrives w.r.t. the folded kernel) and 0 on slots
+// that never train (padding rows, structural zeros of the stem); fold is the same scale, 1 elsewhere, and re-emits the forward
+// weights from the master copy.
+// Which elements take part is a table of nr rows (begin, end, vbegin): range r is the flat slice [begin, end) and occupies
+// [vbegin, vbegin + end - begin) of the launch's index space, which is cut into quads of 4.  A thread finds the range of its quad
+// by a binary search over vbegin (the prefix sums), then walks on for the quad's other elements.  A quad that lies inside one
+// range at a 4-aligned flat index is one 16-byte access per array; everything else goes element by element.  Slots outside every
+// range are never read or written.  The full step is the table with one range per weight tensor and per bias vector; a
+// frozen-layer step is the same table without the frozen layers' rows.  Ranges that touch may be given as one row when no sum per
+// range is wanted: every element keeps its place in the index space, and the search has fewer rows.
+// Clipping: global norm (standalone Keras 2.x) takes one sum over all ranges, clip = min(1, clipnorm / norm); per tensor
+// (tf.keras / Keras >= 2.4) takes one sum per range and clips every range by its own norm.
+namespace {
 
-extern "C" int rtn_sumsq(rtn_handle_t h, const float* g, const float* scale, int64_t n, double* out, void* workspace, size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (!g || !out || !workspace || n < 1) return rtn_fail(h, RTN_EINVAL, "sumsq: bad argument");
-    if (workspace_bytes < rtn_sumsq_workspace_bytes()) return rtn_fail(h, RTN_ENOMEM, "sumsq: workspace too small");
-    const unsigned nb = grid_for(n, 2048);
-    hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, h->stream, g, scale, (long long)n, (double*)workspace);
-    RTN_CHECK_LAUNCH(h, "sumsq_kernel");
-    hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)workspace, (int)nb, out);
-    RTN_CHECK_LAUNCH(h, "sumsq_final_kernel");
-    return RTN_OK;
-}
-
-extern "C" int rtn_adam_clipnorm_step(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale,
-                                      const float* fold, void* w_fwd, int fwd_dtype, int64_t n, int64_t step, float lr, float beta1,
-                                      float beta2, float eps, const double* sumsq, float clipnorm, float grad_mul) {
-    if (!h) return RTN_EINVAL;
-    if (!w || !m || !v || !g || n < 1 || step < 1) return rtn_fail(h, RTN_EINVAL, "adam: bad argument");
-    if (w_fwd && fwd_dtype != RTN_BF16 && fwd_dtype != RTN_F32) return rtn_fail(h, RTN_EINVAL, "adam: bad forward dtype");
-    // Keras 2: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
-    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-    const unsigned nb = grid_for(n, 4096);
-    if (fwd_dtype == RTN_BF16)
-        hipLaunchKernelGGL((adam_kernel<2>), dim3(nb), dim3(256), 0, h->stream, w, m, v, g, gscale, fold, (char*)w_fwd, (long long)n, (float)lr_t, beta1, beta2, eps, sumsq, clipnorm, grad_mul);
-    else
-        hipLaunchKernelGGL((adam_kernel<4>), dim3(nb), dim3(256), 0, h->stream, w, m, v, g, gscale, fold, (char*)w_fwd, (long long)n, (float)lr_t, beta1, beta2, eps, sumsq, clipnorm, grad_mul);
-    RTN_CHECK_LAUNCH(h, "adam_kernel");
-    return RTN_OK;
-}
-
-extern "C" int rtn_sumsq_segments(rtn_handle_t h, const float* g, const float* scale, const int64_t* seg_begin_dev, int nseg, double* out_dev) {
-    if (!h) return RTN_EINVAL;
-    if (!g || !seg_begin_dev || !out_dev || nseg < 1 || nseg > ADAM_MAX_SEGS) return rtn_fail(h, RTN_EINVAL, "sumsq_segments: bad argument (1..%d segments)", ADAM_MAX_SEGS);
-    hipLaunchKernelGGL(sumsq_segments_kernel, dim3((unsigned)nseg), dim3(256), 0, h->stream, g, scale, (const long long*)seg_begin_dev, out_dev);
-    RTN_CHECK_LAUNCH(h, "sumsq_segments_kernel");
-    return RTN_OK;
-}
-
-extern "C" int rtn_adam_clipnorm_step_segments(rtn_handle_t h, float* w, float* m, float* v, const float* g, const float* gscale,
-                                               const float* fold, void* w_fwd, int fwd_dtype, int64_t n, int64_t step, float lr, float beta1,
-                                               float beta2, float eps, const int64_t* seg_begin_dev, int nseg, const double* sumsq_seg_dev,
-                                               int64_t elem_offset, float clipnorm, float grad_mul) {
-    if (!h) return RTN_EINVAL;
-    if (!w || !m || !v || !g || n < 1 || step < 1) return rtn_fail(h, RTN_EINVAL, "adam_segments: bad argument");
-    if (!seg_begin_dev || !sumsq_seg_dev || nseg < 1 || nseg > ADAM_MAX_SEGS || elem_offset < 0) return rtn_fail(h, RTN_EINVAL, "adam_segments: bad segment table");
-    if (w_fwd && fwd_dtype != RTN_BF16 && fwd_dtype != RTN_F32) return rtn_fail(h, RTN_EINVAL, "adam_segments: bad forward dtype");
-    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
-    const unsigned nb = grid_for(n, 4096);
-    if (fwd_dtype == RTN_BF16)
-        hipLaunchKernelGGL((adam_segments_kernel<2>), dim3(nb), dim3(256), 0, h->stream, w, m, v, g, gscale, fold, (char*)w_fwd, (long long)n, (float)lr_t, beta1, beta2, eps,
-                           (const long long*)seg_begin_dev, nseg, sumsq_seg_dev, (long long)elem_offset, clipnorm, grad_mul);
-    else
-        hipLaunchKernelGGL((adam_segments_kernel<4>), dim3(nb), dim3(256), 0, h->stream, w, m, v, g, gscale, fold, (char*)w_fwd, (long long)n, (float)lr_t, beta1, beta2, eps,
-                           (const long long*)seg_begin_dev, nseg, sumsq_seg_dev, (long long)elem_offset, clipnorm, grad_mul);
-    RTN_CHECK_LAUNCH(h, "adam_segments_kernel");
-    return RTN_OK;
-}
-
-// ---- the optimizer over trainable element ranges (frozen layers: include/rtn.h) -----------------------------------------------
-// The table holds nr rows (begin, end, vbegin): range r is the flat slice [begin, end) and occupies [vbegin, vbegin + end - begin)
-// of the launch's index space, which is cut into quads of 4.  A thread finds the range of its quad by a binary search over vbegin
-// (the prefix sums), then walks on for the quad's other elements.  A quad that lies inside one range at a 4-aligned flat index is
-// one 16-byte access per array; everything else goes element by element.  Slots outside every range are never touched.
 struct RangeRow { long long begin, end, vbegin; };
 
 __device__ __forceinline__ int range_of(const RangeRow* __restrict__ t, int nr, long long q) {
@@ -1536,6 +1368,21 @@ __device__ __forceinline__ long long range_flat(const RangeRow* __restrict__ t, 
     if (off < 0 || off >= t[r].end - t[r].begin) return -1;
     const long long f = t[r].begin + off;
     return (f >= 0 && f < n) ? f : -1;
+}
+
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// sum of the 256 threads' values in a fixed order (wave sums, then the four waves in turn); thread 0 stores it
+__device__ __forceinline__ void block_sum_store_d(double s, double* __restrict__ dst) {
+    __shared__ double sh[4];
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) *dst = sh[0] + sh[1] + sh[2] + sh[3];
 }
 
 // sum of (g*scale)^2 over the ranges: per-block partials in a fixed order, finished by sumsq_final_kernel
@@ -1566,11 +1413,19 @@ __global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restri
             s += (double)a * (double)a;
         }
     }
-    __shared__ double sh[4];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    block_sum_store_d(s, partial + blockIdx.x);
+}
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const double* __restrict__ partial, int nb, double* __restrict__ out) {
+    __shared__ double sh[256];
+    double v = 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) v += partial[i];
+    sh[threadIdx.x] = v;
     __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0];
 }
 
 // one workgroup per range (the per-tensor norms of tf.keras clipping when every range is one tensor), fixed order
@@ -1579,15 +1434,20 @@ __global__ __launch_bounds__(256) void sumsq_each_range_kernel(const float* __re
     const long long lo = t[blockIdx.x].begin;
     const long long hi = t[blockIdx.x].end < n ? t[blockIdx.x].end : n;
     double s = 0.0;
-    for (long long i = (lo > 0 ? lo : 0) + threadIdx.x; i < hi; i += 256) {
+    long long i = (lo > 0 ? lo : 0) + threadIdx.x;
+    // one workgroup walks a whole tensor, so the loop is bound by load latency: eight loads in flight, added in the order of the plain loop
+    for (; i + 7 * 256 < hi; i += 8 * 256) {
+        float a[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = g[i + k * 256] * (scale ? scale[i + k * 256] : 1.f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += (double)a[k] * (double)a[k];
+    }
+    for (; i < hi; i += 256) {
         const float v = g[i] * (scale ? scale[i] : 1.f);
         s += (double)v * (double)v;
     }
-    __shared__ double sh[4];
-    s = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    block_sum_store_d(s, out + blockIdx.x);
 }
 
 __device__ __forceinline__ float range_clip(const double* __restrict__ sumsq, int idx, float clipnorm, float grad_mul) {
@@ -1596,7 +1456,27 @@ __device__ __forceinline__ float range_clip(const double* __restrict__ sumsq, in
     return norm > clipnorm ? clipnorm / norm : 1.f;
 }
 
-// adam_kernel / adam_segments_kernel over the ranges.  PER: sumsq holds one sum per range (per-tensor clipping), else one global sum.
+// the Adam update of one element; gi is the scaled and clipped gradient
+struct AdamElem { float m, v, w; };
+__device__ __forceinline__ AdamElem adam_elem(float gi, float m, float v, float w, float lr_t, float b1, float b2, float eps) {
+    AdamElem e;
+    e.m = b1 * m + (1.f - b1) * gi;
+    e.v = b2 * v + (1.f - b2) * gi * gi;
+    e.w = w - lr_t * e.m / (sqrtf(e.v) + eps);
+    return e;
+}
+
+template <int ES>
+__device__ __forceinline__ void store_fwd(char* __restrict__ w_fwd, long long i, float wf) {
+    if constexpr (ES == 2) {
+        const __bf16 hb = (__bf16)wf;
+        reinterpret_cast<unsigned short*>(w_fwd)[i] = __builtin_bit_cast(unsigned short, hb);
+    } else {
+        reinterpret_cast<float*>(w_fwd)[i] = wf;
+    }
+}
+
+// PER: sumsq holds one sum per range (per-tensor clipping), else one global sum.
 template <int ES, bool VEC, bool PER>
 __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
                                                           const float* __restrict__ g, const float* __restrict__ gscale,
@@ -1623,11 +1503,9 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ w,
             float wf[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float gi = gg[j] * ss[j] * grad_mul * clip;
-                mm[j] = b1 * mm[j] + (1.f - b1) * gi;
-                vq[j] = b2 * vq[j] + (1.f - b2) * gi * gi;
-                ww[j] = ww[j] - lr_t * mm[j] / (sqrtf(vq[j]) + eps);
-                wf[j] = ww[j] * ff[j];
+                const AdamElem e = adam_elem(gg[j] * ss[j] * grad_mul * clip, mm[j], vq[j], ww[j], lr_t, b1, b2, eps);
+                mm[j] = e.m; vq[j] = e.v; ww[j] = e.w;
+                wf[j] = e.w * ff[j];
             }
             *reinterpret_cast<float4*>(m + f0) = make_float4(mm[0], mm[1], mm[2], mm[3]);
             *reinterpret_cast<float4*>(v + f0) = make_float4(vq[0], vq[1], vq[2], vq[3]);
@@ -1649,23 +1527,14 @@ __global__ __launch_bounds__(256) void adam_ranges_kernel(float* __restrict__ w,
             const long long i = range_flat(t, nr, q + j, r, n);
             if (i < 0) continue;
             const float clip = PER ? range_clip(sumsq, r, clipnorm, grad_mul) : clip_all;
-            const float gi = g[i] * (gscale ? gscale[i] : 1.f) * grad_mul * clip;
-            const float mi = b1 * m[i] + (1.f - b1) * gi;
-            const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-            const float wi = w[i] - lr_t * mi / (sqrtf(vi) + eps);
-            m[i] = mi; v[i] = vi; w[i] = wi;
-            if (w_fwd) {
-                const float wf = wi * (fold ? fold[i] : 1.f);
-                if constexpr (ES == 2) {
-                    const __bf16 hb = (__bf16)wf;
-                    reinterpret_cast<unsigned short*>(w_fwd)[i] = __builtin_bit_cast(unsigned short, hb);
-                } else {
-                    reinterpret_cast<float*>(w_fwd)[i] = wf;
-                }
-            }
+            const AdamElem e = adam_elem(g[i] * (gscale ? gscale[i] : 1.f) * grad_mul * clip, m[i], v[i], w[i], lr_t, b1, b2, eps);
+            m[i] = e.m; v[i] = e.v; w[i] = e.w;
+            if (w_fwd) store_fwd<ES>(w_fwd, i, e.w * (fold ? fold[i] : 1.f));
         }
     }
 }
+
+}  // namespace
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -1674,6 +1543,13 @@ static int check_ranges(rtn_handle_t h, const char* what, const float* g, int64_
         return rtn_fail(h, RTN_EINVAL, "%s: bad argument (n %lld, %d ranges, span %lld)", what, (long long)n, nr, (long long)span);
     return RTN_OK;
 }
+
+// Keras 2: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t)
+static float adam_lr_t(float lr, float beta1, float beta2, int64_t step) {
+    return (float)((double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step)));
+}
+
+extern "C" size_t rtn_sumsq_workspace_bytes(void) { return 2048 * sizeof(double); }
 
 extern "C" int rtn_sumsq_ranges(rtn_handle_t h, const float* g, const float* scale, int64_t n, const int64_t* table_dev, int nr,
                                 int64_t span, double* out, double* out_each, void* workspace, size_t workspace_bytes) {
@@ -1711,13 +1587,13 @@ static int adam_ranges_launch(rtn_handle_t h, float* w, float* m, float* v, cons
     if (PER && !sumsq && clipnorm > 0.f) return rtn_fail(h, RTN_EINVAL, "adam_ranges: per-range sums missing");
     if (w_fwd && fwd_dtype != RTN_BF16 && fwd_dtype != RTN_F32) return rtn_fail(h, RTN_EINVAL, "adam_ranges: bad forward dtype");
     if (span == 0) return RTN_OK;
-    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, (double)step)) / (1.0 - pow((double)beta1, (double)step));
+    const float lr_t = adam_lr_t(lr, beta1, beta2, step);
     const unsigned nb = grid_for((span + 3) / 4, 4096);
     const bool vec = aligned16(w) && aligned16(m) && aligned16(v) && aligned16(g) && (!gscale || aligned16(gscale)) &&
                      (!fold || aligned16(fold)) && (!w_fwd || ((uintptr_t)w_fwd & (fwd_dtype == RTN_BF16 ? 7 : 15)) == 0);
     const RangeRow* t = (const RangeRow*)table_dev;
 #define RTN_ADAM_RANGES(ES, VEC) hipLaunchKernelGGL((adam_ranges_kernel<ES, VEC, PER>), dim3(nb), dim3(256), 0, h->stream, w, m, v, g, gscale, \
-        fold, (char*)w_fwd, (long long)n, t, nr, (long long)span, (float)lr_t, beta1, beta2, eps, sumsq, clipnorm, grad_mul)
+        fold, (char*)w_fwd, (long long)n, t, nr, (long long)span, lr_t, beta1, beta2, eps, sumsq, clipnorm, grad_mul)
     if (fwd_dtype == RTN_BF16) { if (vec) RTN_ADAM_RANGES(2, true); else RTN_ADAM_RANGES(2, false); }
     else                       { if (vec) RTN_ADAM_RANGES(4, true); else RTN_ADAM_RANGES(4, false); }
 #undef RTN_ADAM_RANGES

@@ -9,7 +9,9 @@ Mirrors what the reference gets from Keras (RetinaNet.py:125-131, 280-291):
     forward weights, so the gradient w.r.t. the Keras kernel is fold[n] * dL/dW_folded and Adam runs on the unfolded
     master copy;
   * clipnorm: global-norm clipping by default (standalone Keras 2.x semantics, what the reference's `import keras` resolves to);
-    `global_clip=False` clips every gradient tensor by its own norm (tf.keras / Keras >= 2.4 semantics).
+    `global_clip=False` clips every gradient tensor by its own norm (tf.keras / Keras >= 2.4 semantics; SURVEY §8a a20);
+  * the optimizer runs over element ranges of the flat parameter vector, one per trainable weight tensor and bias vector
+    (rtn_sumsq_ranges + rtn_adam_clipnorm_step_ranges[_pertensor]): the same kernels whether every layer trains or a few.
 
 The backward graph is derived from the forward op list of engine.Engine._plan: every conv gets a wgrad (+ bias grad) and a
 dgrad per input; ReLU, residual adds, UpsampleLike+Add, C6_relu, max-pool and the stride-2 convs are handled by epilogue
@@ -18,8 +20,8 @@ provides memory, the stream and (optionally) torch.distributed for the gradient 
 
 Frozen layers (Keras `trainable = False`, Trainer(trainable=...) / set_trainable): a tensor needs a gradient iff its producer is a
 trainable layer or one of its producer's inputs needs one.  The backward plan keeps a weight gradient for the trainable layers only
-and a data gradient (with its zero-insert / upsample / pool backward / head pad-cast) only into tensors that need one; the optimizer
-runs over the trainable layers' element ranges (rtn_*_ranges), the all-reduce over their segments, and the training forward runs the
+and a data gradient (with its zero-insert / upsample / pool backward / head pad-cast) only into tensors that need one; the optimizer's
+range tables hold the trainable layers only, the all-reduce runs over their segments, and the training forward runs the
 stem and the 64-channel blocks in their inference form when the backward never reads their extra outputs (Engine.train_keep).
 """
 import ctypes as C
@@ -38,6 +40,19 @@ from .engine import schedule_lanes
 
 def _ceil128(v):
     return -(-v // 128) * 128
+
+
+def merge_adjacent(ranges):
+    """[(begin, end)] with every range that starts where the previous one ends joined to it.  _lib.ranges_table puts such a range
+    right behind its neighbour (no alignment gap), so the joined table places every element where the separate rows did: the same
+    quads per thread, the same sums, fewer rows to search."""
+    out = []
+    for a, b in ranges:
+        if out and out[-1][1] == a:
+            out[-1] = (out[-1][0], b)
+        else:
+            out.append((a, b))
+    return out
 
 
 def grad_segments(layout, NW, NB, trainable=None):
@@ -172,12 +187,6 @@ class Trainer:
         self.v = torch.zeros(NW + NB, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(NW + NB, dtype=torch.float32, device=dev)
         self.sumsq = torch.zeros(1, dtype=torch.float64, device=dev)
-        # per-tensor clipping: one segment per conv kernel and per bias vector (a Keras weight tensor each), in flat order
-        begins = [lo["woff"] for lo in eng.layout.values()] + [NW + lo["boff"] for lo in eng.layout.values()] + [NW + NB]
-        assert begins == sorted(begins)
-        self.seg_begin = torch.tensor(begins, dtype=torch.int64, device=dev)
-        self.nseg = len(begins) - 1
-        self.sumsq_seg = torch.zeros(self.nseg, dtype=torch.float64, device=dev)
         self.ss_ws = torch.empty(L.lib.rtn_sumsq_workspace_bytes(), dtype=torch.uint8, device=dev)
         self.loss_sums = torch.zeros(4, dtype=torch.float64, device=dev)
         # dgrad weights (re-packed from the forward weights after every optimizer step)
@@ -637,7 +646,10 @@ class Trainer:
         return self.loss_sums
 
     def optimizer_step(self, lr=None):
-        """Global-norm clip + Adam on the flat parameter vector, re-emission of the forward and dgrad weights."""
+        """Clipnorm + Adam over the trainable tensors' element ranges of the flat parameter vector (every layer's when trainable is
+        None), re-emission of their forward and dgrad weights.  Slots outside the ranges (frozen layers, bias slots of layers without a
+        Keras bias) are never read or written.  global_clip: the global sum lands in self.sumsq and one norm clips everything;
+        otherwise one sum per range (a Keras weight tensor each) clips that range and the global sum is not computed."""
         if self._epoch != self.eng.load_epoch:
             raise RuntimeError("Engine.load_state() ran between forward_backward() and optimizer_step(): the gradient belongs to "
                                "the previous weights")
@@ -648,48 +660,6 @@ class Trainer:
             self.bucketer.finish()
         self.step_count += 1
         lr = self.lr if lr is None else lr
-        if self.trainable is not None:
-            self._step_ranges(lr)
-            return
-        n = self.NW + self.NB
-        h.check(lib.rtn_sumsq(h.raw, self.grad.data_ptr(), self.gscale.data_ptr(), n, self.sumsq.data_ptr(), self.ss_ws.data_ptr(),
-                              self.ss_ws.numel()))
-        lr = self.lr if lr is None else lr
-        if not self.global_clip:
-            h.check(lib.rtn_sumsq_segments(h.raw, self.grad.data_ptr(), self.gscale.data_ptr(), self.seg_begin.data_ptr(), self.nseg,
-                                           self.sumsq_seg.data_ptr()))
-        for lo_, cnt, wf, code in ((0, self.NW, eng.wflat, eng.rdt), (self.NW, self.NB, eng.bflat, L.RTN_F32)):
-            off4 = lo_ * 4
-            if not self.global_clip:
-                h.check(lib.rtn_adam_clipnorm_step_segments(
-                    h.raw, self.master.data_ptr() + off4, self.m.data_ptr() + off4, self.v.data_ptr() + off4, self.grad.data_ptr() + off4,
-                    self.gscale.data_ptr() + off4, self.fold.data_ptr() + off4, wf.data_ptr(), code, cnt, self.step_count, lr, self.b1,
-                    self.b2, self.eps, self.seg_begin.data_ptr(), self.nseg, self.sumsq_seg.data_ptr(), lo_, self.clipnorm, 1.0))
-                continue
-            h.check(lib.rtn_adam_clipnorm_step(h.raw, self.master.data_ptr() + off4, self.m.data_ptr() + off4, self.v.data_ptr() + off4,
-                                               self.grad.data_ptr() + off4, self.gscale.data_ptr() + off4, self.fold.data_ptr() + off4,
-                                               wf.data_ptr(), code, cnt, self.step_count, lr, self.b1, self.b2, self.eps,
-                                               self.sumsq.data_ptr(), self.clipnorm, 1.0))
-        self._repack_dgrad()
-        eng.weights_version += 1                        # fused inference copies of the filters are stale now
-
-    def _range_tables(self):
-        """Element ranges of the trainable tensors (one per weight tensor, one per bias vector): device tables for the whole flat
-        vector (the norms), the weights and the biases (relative to NW), built once per trainable set."""
-        if self._ranges is None:
-            dev = self.eng.device
-            wr = [(lo["woff"], lo["woff"] + lo["rows"] * lo["K"]) for name, lo in self.eng.layout.items() if self._is_trainable(name)]
-            br = [(lo["boff"], lo["boff"] + lo["rows"]) for name, lo in self.eng.layout.items()
-                  if lo["has_bias"] and self._is_trainable(name)]
-            allr = wr + [(self.NW + a, self.NW + b) for a, b in br]
-            self._ranges = {"all": L.ranges_table(allr, dev), "w": L.ranges_table(wr, dev), "b": L.ranges_table(br, dev),
-                            "each": torch.zeros(max(1, len(allr)), dtype=torch.float64, device=dev)}
-        return self._ranges
-
-    def _step_ranges(self, lr):
-        """optimizer_step over the trainable layers only (rtn_sumsq_ranges + rtn_adam_clipnorm_step_ranges[_pertensor]): frozen slots
-        of master / m / v / grad and of the forward weights are never read or written."""
-        eng, lib, h = self.eng, L.lib, self.eng.h
         rt = self._range_tables()
         tab, nr, span = rt["all"]
         if nr == 0:                                     # nothing trains: no kernel, the weights and their copies stay
@@ -713,7 +683,24 @@ class Trainer:
             else:
                 h.check(lib.rtn_adam_clipnorm_step_ranges_pertensor(*args, each.data_ptr() + sums * 8, self.clipnorm, 1.0))
         self._repack_dgrad()
-        eng.weights_version += 1
+        eng.weights_version += 1                        # fused inference copies of the filters are stale now
+
+    def _range_tables(self):
+        """Element ranges of the trainable tensors (one per weight tensor, one per bias vector of a layer that owns a Keras bias):
+        device tables for the whole flat vector (the norms), the weights and the biases (relative to NW), built once per trainable
+        set and clipping mode.  Under global clipping no kernel asks which tensor an element belongs to, so adjacent tensors share
+        a row (the full step: one row for all weights): the same elements in the same order, and next to no table search."""
+        if self._ranges is None or self._ranges["global_clip"] != self.global_clip:
+            dev = self.eng.device
+            wr = [(lo["woff"], lo["woff"] + lo["rows"] * lo["K"]) for name, lo in self.eng.layout.items() if self._is_trainable(name)]
+            br = [(lo["boff"], lo["boff"] + lo["rows"]) for name, lo in self.eng.layout.items()
+                  if lo["has_bias"] and self._is_trainable(name)]
+            allr = wr + [(self.NW + a, self.NW + b) for a, b in br]
+            if self.global_clip:
+                wr, br, allr = merge_adjacent(wr), merge_adjacent(br), merge_adjacent(allr)
+            self._ranges = {"all": L.ranges_table(allr, dev), "w": L.ranges_table(wr, dev), "b": L.ranges_table(br, dev),
+                            "each": torch.zeros(max(1, len(allr)), dtype=torch.float64, device=dev), "global_clip": self.global_clip}
+        return self._ranges
 
     def train_on_batch(self, images, regression_batch, labels_batch, lr=None):
         """Keras-style step. Returns (total, regression_loss, classification_loss) as Python floats (one host sync)."""

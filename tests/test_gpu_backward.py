@@ -499,12 +499,15 @@ def test_adam_clipnorm_matches_keras_formula(pkg, handle, fwd):
     ss = torch.zeros(1, dtype=torch.float64, device=DEV)
     wsb = L.lib.rtn_sumsq_workspace_bytes()
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+    tab, nr, span = L.ranges_table([(0, n)], DEV)        # the whole vector as one range
     # float64 restatement of keras.optimizers.Adam.get_updates + clip_norm (global norm)
     w, m, v = w0.double(), torch.zeros(n, dtype=torch.float64), torch.zeros(n, dtype=torch.float64)
     for step in (1, 2, 3):
-        handle.check(L.lib.rtn_sumsq(handle.raw, gd.data_ptr(), gsd.data_ptr(), n, ss.data_ptr(), ws.data_ptr(), wsb))
-        handle.check(L.lib.rtn_adam_clipnorm_step(handle.raw, wd.data_ptr(), md.data_ptr(), vd.data_ptr(), gd.data_ptr(), gsd.data_ptr(),
-                                                  fd.data_ptr(), wf.data_ptr(), code, n, step, lr, b1, b2, eps, ss.data_ptr(), clipnorm, gm))
+        handle.check(L.lib.rtn_sumsq_ranges(handle.raw, gd.data_ptr(), gsd.data_ptr(), n, tab.data_ptr(), nr, span, ss.data_ptr(), None,
+                                            ws.data_ptr(), wsb))
+        handle.check(L.lib.rtn_adam_clipnorm_step_ranges(handle.raw, wd.data_ptr(), md.data_ptr(), vd.data_ptr(), gd.data_ptr(),
+                                                         gsd.data_ptr(), fd.data_ptr(), wf.data_ptr(), code, n, tab.data_ptr(), nr, span,
+                                                         step, lr, b1, b2, eps, ss.data_ptr(), clipnorm, gm))
         ge = grad.double() * gscale.double() * gm
         norm = float(torch.sqrt((ge ** 2).sum()))
         assert abs(float(ss.item()) - float(((grad.double() * gscale.double()) ** 2).sum())) <= 1e-6 * float(ss.item())

@@ -178,6 +178,35 @@ def test_frozen_steps_leave_frozen_slots_and_repeat(pkg, dtype):
         assert torch.equal(a[i], b[i]), "run-to-run difference in item %d" % i
 
 
+@pytest.mark.parametrize("dtype", ["bf16", "f32"])
+@pytest.mark.parametrize("global_clip", [True, False])
+def test_trainable_none_equals_every_layer_named(pkg, dtype, global_clip):
+    """One optimizer family: Trainer(trainable=None) and Trainer(trainable=<every layer>) mean the same thing and, from the same state
+    and the same three batches, end with the same bits in the parameters, the moments and the forward weights."""
+    E, Wt, T, L = mods(pkg)
+    state = Wt.init_state("resnet50", 1, 9, seed=6, randomize_bn=True, cls_bias=-2.0, tame=True)
+    batches = [make_batch(2, seed=50 + i) for i in range(3)]
+    runs = []
+    for named in (False, True):
+        eng = E.Engine("resnet50", 1, 9, dtype=dtype)
+        eng.load_state(state)
+        tr = T.Trainer(eng, lr=1e-4, clipnorm=0.001, global_clip=global_clip, trainable=frozenset(eng.layout) if named else None)
+        assert (tr.trainable is None) == (not named)
+        w0 = tr.master.clone()
+        losses = []
+        for x, reg, lab in batches:
+            tr.train_on_batch(x, reg, lab)
+            losses.append(tr.norm_sums.cpu().numpy().tolist())
+        torch.cuda.synchronize()
+        assert not torch.equal(tr.master, w0)                         # the steps did move the weights
+        runs.append((losses, {"master": tr.master.clone(), "m": tr.m.clone(), "v": tr.v.clone(), "wflat": eng.wflat.clone(),
+                              "bflat": eng.bflat.clone()}))
+    (loss_a, a), (loss_b, b) = runs
+    assert loss_a == loss_b
+    for k in a:
+        assert torch.equal(a[k], b[k]), "%s differs between trainable=None and every layer named" % k
+
+
 def random_ranges(rng, n):
     """Sorted, disjoint ranges inside [0, n): empty, one-element, unaligned and long ones, with gaps."""
     out, pos = [], int(rng.randint(0, 5))

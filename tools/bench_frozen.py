@@ -38,8 +38,6 @@ CONFIGS = {
 
 def optimizer_launches(tr):
     """Library calls of Trainer.optimizer_step: the norm, one Adam per part (weights / biases), the dgrad repack."""
-    if tr.trainable is None:
-        return 1 + 2 + 1
     rt = tr._range_tables()
     if rt["all"][1] == 0:
         return 0

@@ -48,14 +48,15 @@ for b in bp["bops"]:
         finish_bytes += slabs + 2 * NK * 4
 padcast = sum(b[3] * (b[4] * 4 + b[5] * 2) for b in bp["bops"] if b[0] == "padcast")
 packd = 2.0 * sum(w.numel() for w in tr.wd.values()) * 2
+nb_live = sum(lo["rows"] for lo in eng.layout.values() if lo["has_bias"])      # the optimizer's bias ranges: layers with a Keras bias (bench.py's byte model counts all NB slots)
 entries = [   # (kernel, where, bytes per step, launches per step or None = from the stats)
     ("stem_pack_kernel<0, 0>", "train", B * (H * W * 3 * 2 + xi["Hp"] * xi["Wp"] * 4 * 2)),
     ("anchor_targets_kernel", "train", rows * (5 + 2) * 4),
     ("loss_fwd_kernel", "train", rows * (2 + 5 + 1 + 4) * 4),
     ("loss_bwd_kernel", "train", rows * ((2 + 5 + 1 + 4) * 4 + 5 * 4)),
-    ("sumsq_kernel", "train", (tr.NW + tr.NB) * 4 * 2),
-    ("adam_kernel<2>", "train", tr.NW * (6 * 4 + 3 * 4 + 2)),
-    ("adam_kernel<4>", "train", tr.NB * (6 * 4 + 3 * 4 + 4)),
+    ("sumsq_ranges_kernel<true>", "train", (tr.NW + nb_live) * 4 * 2),
+    ("adam_ranges_kernel<2, true, false>", "train", tr.NW * (6 * 4 + 3 * 4 + 2)),
+    ("adam_ranges_kernel<4, true, false>", "train", nb_live * (6 * 4 + 3 * 4 + 4)),
     ("maxpool_bwd_idx_kernel<2>", "train", B * (Hp * Wp * 64 * (2 + 1 + 2) + H1 * W1 * 64 * 2)),
     ("pad_cast_rows8_kernel", "train", padcast),
     ("wgrad_finish_kernel (all instances)", "train", finish_bytes),
