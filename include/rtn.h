@@ -632,6 +632,29 @@ int rtn_jpeg_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const in
                     const int32_t* components, const int32_t* subsampling, const int32_t* quality, uint8_t* out,
                     const int64_t* out_offsets, int64_t* out_bytes, int32_t* status, void* workspace, size_t workspace_bytes);
 
+/* ---- PNG encode (lossless, on the device) ------------------------------------------------------------------------------
+ * Output: signature, IHDR (8-bit, colour type 2 = R,G,B or 0 = gray, non-interlaced), one IDAT per deflate chunk, IEND; no other
+ * chunk.  Row filters None, Sub and Up only.  The filtered stream (height rows of 1 + width * components bytes) is cut into chunks of
+ * RTN_PNG_CHUNK raw bytes; chunk k is deflated on its own (a fresh block, no match before its first byte), ends byte-aligned on an
+ * empty stored block and is IDAT number k, so IDAT k inflated alone as raw deflate gives raw bytes [k CHUNK, (k + 1) CHUNK).  IDAT 0
+ * starts with the 2-byte zlib header; the last IDAT ends with a final empty stored block and the stream's Adler-32.  Any PNG reader
+ * reads the file.  Input: uint8 (H, W, 3) B,G,R or (H, W) gray.  Sides: >= 1, with height * (1 + width * components) < 2^31.
+ *
+ * rtn_png_encode_bound (host only): the largest file one page can give, exactly: no chunk is written longer than its stored form, so
+ *   56 + stream bytes + 22 per chunk; 0 for an invalid page.  rtn_png_encode_workspace_bytes: device scratch for the n pages; 0 for an
+ *   invalid page.
+ * rtn_png_encode: n pages in one batch on the handle's stream, sizes and component counts mixed (host arrays of n).  pages: host array
+ *   of device pointers.  out: device memory; page i's slot is [out_offsets[i], out_offsets[i+1]) (host, n + 1 entries) and must hold
+ *   rtn_png_encode_bound bytes (RTN_EINVAL otherwise).  out_bytes (device, n int64): the file length.  status (device, n int32): 0 for
+ *   every page the call accepted; a size never sets it, and there is no host path to fall back to.  workspace: 256-byte aligned,
+ *   >= rtn_png_encode_workspace_bytes.  RTN_EINVAL for a NULL argument or an invalid page. */
+#define RTN_PNG_CHUNK 32768
+size_t rtn_png_encode_bound(int width, int height, int components);
+size_t rtn_png_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components);
+int rtn_png_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* widths, const int32_t* heights,
+                   const int32_t* components, uint8_t* out, const int64_t* out_offsets, int64_t* out_bytes, int32_t* status,
+                   void* workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

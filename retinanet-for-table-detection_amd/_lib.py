@@ -199,6 +199,9 @@ SIGNATURES = {
     "rtn_jpeg_encode_bound": (_SZ, [_I, _I, _I, _I]),
     "rtn_jpeg_encode_workspace_bytes": (_SZ, [_I, _P, _P, _P, _P]),
     "rtn_jpeg_encode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_png_encode_bound": (_SZ, [_I, _I, _I]),
+    "rtn_png_encode_workspace_bytes": (_SZ, [_I, _P, _P, _P]),
+    "rtn_png_encode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
 }
 
 

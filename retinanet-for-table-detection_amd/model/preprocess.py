@@ -33,15 +33,18 @@ def preprocess_pages(pages, return_binary=False):
     return (out, bo) if return_binary else out
 
 
-def preprocess_files(src_paths, dst_paths, quality=95):
+def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
     """DetectTablesUtils.preProcessSampleImages / preProcessTrainValImages as a batch: read every page (csv_generator.read_images_bgr:
     baseline JPEGs decoded on the device), run rtn_preprocess_dt3 on the device (one call per page size), and write the distance
     maps (model.utils.write_images_bgr: .jpg / .jpeg / .jpe names encoded on the device at `quality`, 4:2:0, other names through
-    write_image).  On the JPEG -> JPEG path the pixels never come to the host.  A page wider than rtn_preprocess_dt3 takes raises
-    what preprocess_pages raises for it."""
+    write_image; png="device" encodes the .png names on the device too, model.utils.encode_png_bgr).  On the JPEG -> JPEG path, and
+    with png="device" on the JPEG -> PNG and PNG -> PNG paths, the processed pixels never come to the host.  A page wider than
+    rtn_preprocess_dt3 takes raises what preprocess_pages raises for it."""
     import importlib
     from .utils import write_images_bgr
     src_paths, dst_paths = list(src_paths), list(dst_paths)
+    if png not in ("host", "device"):
+        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
     if len(src_paths) != len(dst_paths):
         raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
     if not src_paths:
@@ -64,7 +67,7 @@ def preprocess_files(src_paths, dst_paths, quality=95):
             h.check(L.lib.rtn_preprocess_dt3(h.raw, src.data_ptr(), 3, B, H, W, dst.data_ptr(), None, ws.data_ptr(), wsb))
             for k, i in enumerate(part):
                 out[i] = dst[k]
-    write_images_bgr(dst_paths, out, quality=quality)
+    write_images_bgr(dst_paths, out, quality=quality, png=png)
 
 
 def resize_cubic(img, scale):

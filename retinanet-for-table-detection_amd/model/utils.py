@@ -224,7 +224,7 @@ JPEG_MAX_SIDE = 65500                                   # libjpeg's JPEG_MAX_DIM
 
 
 def _check_page(i, p):
-    """(H, W, components) of one page for encode_jpeg_bgr, or ValueError."""
+    """(H, W, components) of one page for encode_jpeg_bgr / encode_png_bgr, or ValueError."""
     if not isinstance(p, (torch.Tensor, np.ndarray)):
         p = np.asarray(p)
     dtype, shape = p.dtype, tuple(p.shape)
@@ -233,7 +233,7 @@ def _check_page(i, p):
     if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
         raise ValueError("page %d: shape (H,W,3) B,G,R or (H,W) gray expected, got %s" % (i, shape))
     if not (1 <= shape[0] <= JPEG_MAX_SIDE and 1 <= shape[1] <= JPEG_MAX_SIDE):
-        raise ValueError("page %d: %dx%d: sides must be 1..%d for JPEG" % (i, shape[0], shape[1], JPEG_MAX_SIDE))
+        raise ValueError("page %d: %dx%d: sides must be 1..%d (the image writers' limit, JPEG's)" % (i, shape[0], shape[1], JPEG_MAX_SIDE))
     return shape[0], shape[1], 1 if len(shape) == 2 else 3
 
 
@@ -268,6 +268,24 @@ def _pillow_jpeg(page, quality, subsampling):
     b = io.BytesIO()
     Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(b, "JPEG", quality=int(quality), subsampling=subsampling)
     return b.getvalue()
+
+
+def _files_to_host(out, offs, nb, ok, n):
+    """The files of pages `ok` (slot offsets offs, lengths nb in the device buffer out) as bytes, through one copy of the used
+    bytes to pinned host memory; None for every other page."""
+    files = [None] * n
+    if ok:
+        used = torch.cat([out[int(offs[i]):int(offs[i]) + int(nb[i])] for i in ok]) if len(ok) > 1 else \
+            out[int(offs[ok[0]]):int(offs[ok[0]]) + int(nb[ok[0]])]
+        host = torch.empty(used.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(used, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        buf = host.numpy()
+        pos = 0
+        for i in ok:
+            files[i] = buf[pos:pos + int(nb[i])].tobytes()
+            pos += int(nb[i])
+    return files
 
 
 def encode_jpeg_bgr(pages, quality=95, subsampling=2):
@@ -307,39 +325,78 @@ def encode_jpeg_bgr(pages, quality=95, subsampling=2):
     stream.synchronize()
     nb = nb.numpy().copy()                                              # 0 = flagged (status != 0)
     ok = [i for i in range(n) if nb[i] > 0]
-    files = [None] * n
-    if ok:
-        used = torch.cat([out[int(offs[i]):int(offs[i]) + int(nb[i])] for i in ok]) if len(ok) > 1 else \
-            out[int(offs[ok[0]]):int(offs[ok[0]]) + int(nb[ok[0]])]
-        host = torch.empty(used.numel(), dtype=torch.uint8, pin_memory=True)
-        host.copy_(used, non_blocking=True)
-        stream.synchronize()
-        buf = host.numpy()
-        pos = 0
-        for i in ok:
-            files[i] = buf[pos:pos + int(nb[i])].tobytes()
-            pos += int(nb[i])
+    files = _files_to_host(out, offs, nb, ok, n)
     for i in range(n):
         if files[i] is None:
             files[i] = _pillow_jpeg(pages[i], qs[i], ss[i])
     return files
 
 
-def write_images_bgr(paths, pages, quality=95, subsampling=2):
+def encode_png_bgr(pages):
+    """PNG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), lossless, in the chunked layout of
+    DESIGN §3.4d that every PNG reader reads: one batched rtn_png_encode on the current stream (csrc/rtn_png_enc.hip), one small
+    copy of the n file lengths, then one copy of the used bytes to pinned host memory.  There is no host path: a valid page
+    always fits its slot (rtn_png_encode_bound).  Returns list[bytes]."""
+    import ctypes as C
+    pages = list(pages)
+    n = len(pages)
+    dims = [_check_page(i, p) for i, p in enumerate(pages)]
+    if n == 0:
+        return []
+    h = _rt.handle()
+    dev = []
+    for p in pages:
+        t = p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
+        dev.append(t.to(device="cuda", non_blocking=True).contiguous())
+    arr = lambda v: np.ascontiguousarray(v, np.int32)                    # noqa: E731
+    H, W, Cc = arr([d[0] for d in dims]), arr([d[1] for d in dims]), arr([d[2] for d in dims])
+    bounds = [int(L.lib.rtn_png_encode_bound(int(w), int(hh), int(c))) for w, hh, c in zip(W, H, Cc)]
+    for i, b in enumerate(bounds):
+        if b == 0:
+            raise ValueError("page %d: %dx%d is too large for one PNG stream" % (i, H[i], W[i]))
+    offs = np.zeros(n + 1, np.int64)
+    offs[1:] = np.cumsum([(b + 255) & ~255 for b in bounds])
+    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda")
+    lengths = torch.empty(n, dtype=torch.int64, device="cuda")
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    wsb = int(L.lib.rtn_png_encode_workspace_bytes(n, W.ctypes.data, H.ctypes.data, Cc.ctypes.data))
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in dev])
+    h.check(L.lib.rtn_png_encode(h.raw, n, ptrs, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, out.data_ptr(), offs.ctypes.data,
+                                 lengths.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb))
+    nb = torch.empty(n, dtype=torch.int64, pin_memory=True)
+    nb.copy_(lengths, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    nb = nb.numpy().copy()
+    if not all(0 < int(nb[i]) <= bounds[i] for i in range(n)):
+        raise RuntimeError("rtn_png_encode: file lengths %s outside (0, bound]" % nb.tolist())
+    return _files_to_host(out, offs, nb, list(range(n)), n)
+
+
+def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
     """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
-    .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged."""
+    .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged.
+    png="device" sends the .png files through one encode_png_bgr call instead (lossless, other bytes than write_image's);
+    png="host" (the default) leaves them with write_image."""
     import os
     paths, pages = list(paths), list(pages)
+    if png not in ("host", "device"):
+        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
     if len(paths) != len(pages):
         raise ValueError("%d paths for %d pages" % (len(paths), len(pages)))
     qs, ss = _check_settings(quality, subsampling, len(pages))
     for i, p in enumerate(pages):
         _check_page(i, p)
-    jpg = [i for i, path in enumerate(paths) if os.path.splitext(str(path))[1].lower() in JPEG_EXTENSIONS]
+    ext = [os.path.splitext(str(path))[1].lower() for path in paths]
+    jpg = [i for i, e in enumerate(ext) if e in JPEG_EXTENSIONS]
+    dpng = [i for i, e in enumerate(ext) if e == ".png"] if png == "device" else []
     for i, data in zip(jpg, encode_jpeg_bgr([pages[i] for i in jpg], quality=[qs[i] for i in jpg], subsampling=[ss[i] for i in jpg])):
         with open(paths[i], 'wb') as f:
             f.write(data)
-    for i in sorted(set(range(len(paths))) - set(jpg)):
+    for i, data in zip(dpng, encode_png_bgr([pages[i] for i in dpng])):
+        with open(paths[i], 'wb') as f:
+            f.write(data)
+    for i in sorted(set(range(len(paths))) - set(jpg) - set(dpng)):
         write_image(paths[i], _host_page(pages[i]))
 
 

@@ -1,0 +1,149 @@
+"""Measure the device PNG encoder (csrc/rtn_png_enc.hip) on sample-sized pages: the 2200x1712 distance map
+(tests/golden/sample_0717_023.jpg, what preprocess_files writes) or the page itself (--content page), 16 pages a batch.
+
+  python tools/bench_encode_png.py [--batch 16] [--iters 10] [--host-iters 3] [--content map|page]
+
+Reports medians and the min..max spread over the iterations after a warm-up, every path on the same machine:
+  (a) the parent commit's path for a .png name: model.utils.write_image (Pillow's default, compress level 6), one thread;
+  (b) Pillow at compress_level=1, the fastest lossless setting a host user has;
+  (c) model.utils.write_images_bgr(png="device") for the device-resident pages (encode, length read-back, one copy, file writes),
+      and the GPU time of the four kernels alone (events around rtn_png_encode);
+  (d) model.preprocess.preprocess_files of JPEG pages to .png names, png="host" against png="device";
+and the file sizes of (a), (b), (c).  The host paths take seconds per page, so they run --host-iters times.
+For the per-kernel split: rocprofv3 --kernel-trace --stats --output-format csv -d rocprof_out -o png_enc --
+  python tools/bench_encode_png.py --iters 3 --host-iters 0
+"""
+import argparse
+import ctypes as C
+import importlib
+import io
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "retinanet-for-table-detection_amd"
+L = importlib.import_module(PKG + "._lib")
+U = importlib.import_module(PKG + ".model.utils")
+P = importlib.import_module(PKG + ".model.preprocess")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def stat(v):
+    return (float(np.median(v)), float(np.min(v)), float(np.max(v))) if len(v) else (float("nan"),) * 3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--host-iters", type=int, default=3)
+    ap.add_argument("--content", choices=("map", "page"), default="map")
+    a = ap.parse_args()
+    n = a.batch
+    dev = torch.device("cuda", 0)
+    name = "sample_0717_023.jpg" if a.content == "map" else "sample_0717_023_orig.jpg"
+    page = np.ascontiguousarray(np.asarray(Image.open(os.path.join(GOLDEN, name)).convert("RGB"))[:, :, ::-1])
+    H, W = page.shape[:2]
+    tmp = tempfile.mkdtemp(prefix="bench_encode_png_")
+
+    def pillow_size(**kw):
+        b = io.BytesIO()
+        Image.fromarray(page[:, :, ::-1]).save(b, "PNG", **kw)
+        return len(b.getvalue())
+
+    pages = [torch.from_numpy(page).to(dev) for _ in range(n)]
+    host_pages = [page.copy() for _ in range(n)]
+    arr = lambda v: np.asarray([v] * n, np.int32)                        # noqa: E731
+    Wa, Ha, Ca = arr(W), arr(H), arr(3)
+    bound = int(L.lib.rtn_png_encode_bound(W, H, 3))
+    offs = np.arange(n + 1, dtype=np.int64) * ((bound + 255) & ~255)
+    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device=dev)
+    lengths = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    wsb = int(L.lib.rtn_png_encode_workspace_bytes(n, Wa.ctypes.data, Ha.ctypes.data, Ca.ctypes.data))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+    h = L.Handle(0)
+    h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def encode():
+        h.check(L.lib.rtn_png_encode(h.raw, n, ptrs, Wa.ctypes.data, Ha.ctypes.data, Ca.ctypes.data, out.data_ptr(), offs.ctypes.data,
+                                     lengths.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb))
+    for _ in range(3):
+        encode()
+    torch.cuda.synchronize()
+    assert int(status.abs().sum()) == 0
+    size_c = int(lengths[0])
+    got = np.asarray(Image.open(io.BytesIO(bytes(out[:size_c].cpu().numpy()))))
+    assert np.array_equal(got[:, :, ::-1], page)
+    size_a, size_b = pillow_size(), pillow_size(compress_level=1)
+    print("page: %s %dx%d B,G,R, %d chunks of %d B, bound %d B, workspace %.1f MB per page" %
+          (name, W, H, -(-H * (1 + 3 * W) // 32768), 32768, bound, wsb / n / 1e6))
+    print("file bytes: (a) Pillow default %d, (b) Pillow compress_level=1 %d, (c) device %d (%.3f of (b), %.3f of (a))" %
+          (size_a, size_b, size_c, size_c / size_b, size_c / size_a))
+
+    paths = [os.path.join(tmp, "out_%02d.png" % i) for i in range(n)]
+    ref_paths = [os.path.join(tmp, "ref_%02d.png" % i) for i in range(n)]
+    src = os.path.join(GOLDEN, "sample_0717_023_orig.jpg")
+    srcs = [shutil.copy(src, os.path.join(tmp, "src_%02d.jpg" % i)) for i in range(n)]
+    pre_dev = [os.path.join(tmp, "pred_%02d.png" % i) for i in range(n)]
+    pre_host = [os.path.join(tmp, "preh_%02d.png" % i) for i in range(n)]
+
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    k_ms, c_ms, a_ms, b_ms, pd_ms, ph_ms = [], [], [], [], [], []
+    for it in range(max(a.iters, a.host_iters) + 1):     # iteration 0 warms every path up
+        if it <= a.iters:
+            ev[0].record()
+            encode()
+            ev[1].record()
+            torch.cuda.synchronize()
+            k = ev[0].elapsed_time(ev[1])
+            c = wall_ms(lambda: U.write_images_bgr(paths, pages, png="device"))
+            pd = wall_ms(lambda: P.preprocess_files(srcs, pre_dev, png="device"))
+            if it:
+                k_ms.append(k); c_ms.append(c); pd_ms.append(pd)
+        if it <= a.host_iters and a.host_iters:
+            ta = wall_ms(lambda: [U.write_image(d, hp) for d, hp in zip(ref_paths, host_pages)])
+            tb = wall_ms(lambda: [Image.fromarray(hp[:, :, ::-1]).save(d, "PNG", compress_level=1) for d, hp in zip(ref_paths, host_pages)])
+            ph = wall_ms(lambda: P.preprocess_files(srcs, pre_host))
+            if it:
+                a_ms.append(ta); b_ms.append(tb); ph_ms.append(ph)
+    assert np.array_equal(np.asarray(Image.open(paths[-1]))[:, :, ::-1], page)
+    if a.host_iters:
+        assert np.array_equal(np.asarray(Image.open(pre_dev[-1])), np.asarray(Image.open(pre_host[-1])))
+    res = {"batch": n, "content": a.content, "bytes_pillow_default": size_a, "bytes_pillow_level1": size_b, "bytes_device": size_c}
+    for key, label, v in (("kernels_ms", "(c) encode kernels alone", k_ms), ("write_images_bgr_device_ms", "(c) write_images_bgr(png='device')", c_ms),
+                          ("write_image_ms", "(a) write_image (Pillow default), one thread", a_ms),
+                          ("pillow_level1_ms", "(b) Pillow compress_level=1, one thread", b_ms),
+                          ("preprocess_files_device_ms", "(d) preprocess_files JPEG -> PNG, png='device'", pd_ms),
+                          ("preprocess_files_host_ms", "(d) preprocess_files JPEG -> PNG, png='host'", ph_ms)):
+        m, lo, hi = stat(v)
+        print("%-52s %10.2f ms per %d pages (min %.2f, max %.2f, %d runs): %.1f pages/s" % (label, m, n, lo, hi, len(v), n / m * 1e3))
+        res[key] = round(m, 3)
+    if a_ms and c_ms:
+        print("(c) is %.0fx (a) and %.0fx (b); preprocess_files device is %.1fx host" %
+              (stat(a_ms)[0] / stat(c_ms)[0], stat(b_ms)[0] / stat(c_ms)[0], stat(ph_ms)[0] / stat(pd_ms)[0]))
+    print(json.dumps(res))
+    h.close()
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
