@@ -655,6 +655,46 @@ int rtn_png_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int
                    const int32_t* components, uint8_t* out, const int64_t* out_offsets, int64_t* out_bytes, int32_t* status,
                    void* workspace, size_t workspace_bytes);
 
+/* ---- PNG decode (files of the chunked layout above, on the device) --------------------------------------------------------
+ * Decodes the files rtn_png_encode writes, and any file of the same layout (tests/png_encode_ref.py builds them with zlib): IHDR
+ * 8-bit gray or R,G,B, non-interlaced; ceil(stream / RTN_PNG_CHUNK) IDATs and nothing else before IEND; IDAT k's deflate data inflates
+ * alone to filtered bytes [k CHUNK, (k + 1) CHUNK) and ends on an empty stored block; row filters None, Sub, Up.  Every other PNG
+ * (one zlib stream cut anywhere, Average / Paeth rows, 16-bit, palette, alpha, interlace, ancillary chunks) is for the host decoder.
+ * Output: uint8 (H, W, 3) B,G,R, bit-identical to Pillow's Image.open(f).convert("RGB") reversed; a gray file has its value in all
+ * three channels.
+ *
+ * rtn_png_inspect (host only; h may be NULL, rtn_last_error(NULL) then gives this thread's failure text): takes the file_bytes of one
+ *   file held in host memory apart, every step checked against file_bytes.  RTN_OK only for: the signature; a 13-byte IHDR with a
+ *   correct CRC, depth 8, colour type 0 or 2, compression 0, filter 0, interlace 0, sides >= 1, height * (1 + width * components)
+ *   < 2^31; then exactly ceil(stream / RTN_PNG_CHUNK) IDATs, an empty IEND and the end of the file; IDAT 0 starting with a zlib header
+ *   (CM 8, no dictionary, check bits); every IDAT's deflate data ending 00 00 FF FF; the last IDAT ending 01 00 00 FF FF + Adler-32.
+ *   Anything else: RTN_EINVAL and a reason.  It does not inflate and does not compute the IDAT CRCs: the device does both.  With
+ *   blob == NULL it only fills *info; otherwise it writes the blob (header: sides, components, chunks, stored Adler-32; a table of
+ *   offset, length and stored CRC per chunk; the deflate payloads), RTN_PNG_BLOB_BOUND(file_bytes) bytes at most, exactly
+ *   info->blob_bytes (a multiple of 16); a smaller blob_capacity is RTN_EINVAL.
+ * rtn_png_decode_workspace_bytes: device scratch for decoding the n blobs at host_blobs + offsets[i]; 0 if one is no blob.
+ * rtn_png_decode: n pages in one batch on the handle's stream, sizes and component counts mixed.  host_blobs and dev_blobs are the
+ *   same packed buffer on the host and on the device, offsets[i] (host, multiples of 16) the start of page i's blob in both; pages
+ *   (host array) the device outputs, H x W x 3 bytes each.  status (device, n int32) is 0 only if every chunk inflated as raw deflate
+ *   to exactly its slice, through non-final blocks, up to an empty stored block that ends at its payload's last byte, no match
+ *   reached before the chunk's first byte, every IDAT's CRC-32 and the joined Adler-32 equal the stored ones, and every row's filter
+ *   type was 0, 1 or 2.  Then the chunk-wise result equals an ordinary zlib decode of the concatenated IDATs; a page with any other
+ *   status holds unspecified bytes and the caller decodes that file on the host.  workspace: 256-byte aligned,
+ *   >= rtn_png_decode_workspace_bytes.
+ * rtn_png_inflate_chunk_host (host only, no handle): runs the device's inflate functions (csrc/rtn_png_inflate.h) on one chunk's
+ *   deflate payload on the CPU, so that they can be tested and fuzzed without a GPU.  *status = 0 and want_bytes bytes in out if the
+ *   payload passes the per-chunk rules above (1 <= want_bytes <= RTN_PNG_CHUNK); otherwise *status != 0 and out is not written. */
+typedef struct {
+    int32_t width, height, components, chunks;
+    int64_t blob_bytes, workspace_bytes, payload_bytes;   /* payload_bytes: deflate bytes of all chunks */
+} rtn_png_info_t;
+#define RTN_PNG_BLOB_BOUND(file_bytes) (128 + 2 * (size_t)(file_bytes))
+int rtn_png_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob, size_t blob_capacity);
+size_t rtn_png_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
+int rtn_png_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                   uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+int rtn_png_inflate_chunk_host(const void* in, size_t in_bytes, void* out, size_t want_bytes, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

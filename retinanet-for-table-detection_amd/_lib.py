@@ -103,6 +103,18 @@ class JpegInfo(C.Structure):
     ]
 
 
+class PngInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("chunks", C.c_int32),
+        ("blob_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("payload_bytes", C.c_int64),
+    ]
+
+
+def png_blob_bound(file_bytes):
+    """RTN_PNG_BLOB_BOUND of include/rtn.h: the most bytes rtn_png_inspect writes for a file of that size."""
+    return 128 + 2 * int(file_bytes)
+
+
 def jpeg_blob_bound(file_bytes):
     """RTN_JPEG_BLOB_BOUND of include/rtn.h: the most bytes rtn_jpeg_inspect writes for a file of that size."""
     return 16384 + 4 * int(file_bytes)
@@ -202,6 +214,10 @@ SIGNATURES = {
     "rtn_png_encode_bound": (_SZ, [_I, _I, _I]),
     "rtn_png_encode_workspace_bytes": (_SZ, [_I, _P, _P, _P]),
     "rtn_png_encode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_png_inspect": (_I, [_P, _P, _SZ, C.POINTER(PngInfo), _P, _SZ]),
+    "rtn_png_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_png_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_png_inflate_chunk_host": (_I, [_P, _SZ, _P, _SZ, C.POINTER(C.c_int32)]),
 }
 
 

@@ -25,6 +25,7 @@
 // final empty stored block (5) and the Adler-32 (4).  So a file is at most 56 + stream + 22 * chunks bytes, and the host path
 // has nothing to catch.
 #include "rtn_internal.h"
+#include "rtn_png_crc.h"
 
 namespace {
 
@@ -38,7 +39,6 @@ constexpr int PE_HASH = 1 << PE_HASH_BITS;
 constexpr int PE_MIN_MATCH = 3, PE_MAX_MATCH = 258;
 constexpr int PE_MAX_GRID = 1 << 20;           // workgroups along x of the filter launch: rows past it are looped over
 constexpr int PE_FAR = 4096;                   // a 3-byte match further back than this costs more than three literals
-constexpr uint32_t PE_POLY = 0xedb88320u;      // CRC-32, reflected
 constexpr uint32_t PE_ADLER = 65521u;
 static_assert(PE_CHUNK <= 32768 && PE_CHUNK % PE_THREADS == 0 && PE_CHUNK % 64 == 0, "chunk size");
 
@@ -84,30 +84,6 @@ inline PELayout pe_layout(int W, int H, int nc) {
     L.slots = L.file + pe_align((nk + 1) * 8 + 8);                     // file offset of every IDAT (int64), then the page's Adler-32
     L.total = L.slots + nk * PE_SLOT;
     return L;
-}
-
-// ---- CRC-32 arithmetic (zlib's representation: bit 31 is x^0) ------------------------------------------------------------------------
-__host__ __device__ inline uint32_t pe_crc_byte(uint32_t c, uint32_t b) {     // table-free update by one byte
-    c ^= b;
-    for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ PE_POLY : c >> 1;
-    return c;
-}
-__host__ __device__ inline uint32_t pe_mulmod(uint32_t a, uint32_t b) {       // a(x) b(x) mod P
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = (b & 1u) ? (b >> 1) ^ PE_POLY : b >> 1;
-    }
-    return p;
-}
-__host__ __device__ inline uint32_t pe_xpow8(uint32_t n) {                    // x^(8 n) mod P
-    uint32_t p = 0x80000000u, sq = 0x00800000u;
-    while (n) {
-        if (n & 1u) p = pe_mulmod(sq, p);
-        sq = pe_mulmod(sq, sq);
-        n >>= 1;
-    }
-    return p;
 }
 
 // ---- deflate symbol tables ----------------------------------------------------------------------------------------------------------

@@ -4,8 +4,9 @@ Same class names, constructor arguments and method names as the reference's Gene
 (:234-247) constructs it unchanged; what differs is where the work runs:
 
   host   CSV rows, grouping / shuffling, annotation filtering, the 3x3 augmentation matrices and box corners (a few flops),
-         parsing the page files (rtn_jpeg_inspect)
-  device per batch: rtn_jpeg_decode of the baseline-JPEG pages (read_images_bgr; other files are decoded by Pillow and uploaded)
+         parsing the page files (rtn_jpeg_inspect, rtn_png_inspect)
+  device per batch: rtn_jpeg_decode of the baseline-JPEG pages and rtn_png_decode of the chunked-layout PNG pages
+         (read_images_bgr; other files are decoded by Pillow and uploaded)
          per page: [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
          x/127.5-1 normalisation (preprocess_image 'custom_tf'), the INTER_CUBIC resize and the write into the zero-padded batch
          canvas of compute_inputs;  per batch: rtn_anchor_targets (anchors, IoU, assignment, box deltas) -> regression, labels
@@ -70,58 +71,105 @@ def jpeg_inspect(data):
     return info, blob[:info.blob_bytes]
 
 
-def _decode_batch(paths, device, handle, stream):
-    """read_images_bgr on an explicit handle and stream: every page that rtn_jpeg_inspect accepts is decoded in one batched
-    rtn_jpeg_decode after one host->device copy of the blobs; the status words are read once, on `stream`; the other pages (and
-    the pages whose status is non-zero) go through read_image_bgr and are uploaded."""
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def png_inspect(data):
+    """Parse one file's bytes with rtn_png_inspect (host only) -> (PngInfo, blob bytes) for a PNG of the chunked layout (DESIGN
+    §3.4d) that the device decodes, or (None, reason) for anything else."""
+    info = L.PngInfo()
+    blob = np.empty(L.png_blob_bound(len(data)), np.uint8)
+    rc = L.lib.rtn_png_inspect(None, data, len(data), C.byref(info), blob.ctypes.data, blob.size)
+    if rc != 0:
+        return None, L.lib.rtn_last_error(None).decode("utf-8", "replace")
+    return info, blob[:info.blob_bytes]
+
+
+def _decode_datas(datas, host_decode, device, handle, stream):
+    """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that rtn_jpeg_inspect or
+    rtn_png_inspect accepts is decoded on the device, each decoder running at most once, after ONE host->device copy of all
+    blobs; the status words of both are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
+    from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
+    (None where no device decoder took the file)."""
     from PIL import Image
-    out = [None] * len(paths)
-    on_host = []
-    datas = []
-    for i, path in enumerate(paths):
-        try:
-            with open(path, 'rb') as f:
-                datas.append((i, f.read()))
-        except OSError:
-            on_host.append(i)                       # read_image_bgr raises the same exception below, in page order
+    n_all = len(datas)
+    out = [None] * n_all
+    words = [None] * n_all
+    on_host = [i for i, d in enumerate(datas) if d is None]        # host_decode raises the file's exception below, in page order
     limit = Image.MAX_IMAGE_PIXELS
-    cap = sum(L.jpeg_blob_bound(len(d)) for _, d in datas)
+    # a file with the PNG signature fails rtn_jpeg_inspect at its first two bytes, before anything is written
+    cap = sum(L.png_blob_bound(len(d)) if d[:8] == PNG_SIGNATURE else L.jpeg_blob_bound(len(d)) for d in datas if d is not None)
     with torch.cuda.stream(stream):
         host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
         hp = host.data_ptr()
-        offsets, pages, which, pos = [], [], [], 0
-        for i, data in datas:
-            info = L.JpegInfo()
+        pos = 0
+        kinds = {"jpeg": ([], [], []), "png": ([], [], [])}          # blob offsets, pages, file indices
+        for i, data in enumerate(datas):
+            if data is None:
+                continue
+            info, kind = L.JpegInfo(), "jpeg"
             rc = L.lib.rtn_jpeg_inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
+            if rc != 0:
+                info, kind = L.PngInfo(), "png"
+                rc = L.lib.rtn_png_inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
             if rc != 0 or (limit and info.width * info.height > limit):
                 on_host.append(i)
                 continue
+            offsets, pages, which = kinds[kind]
             offsets.append(pos)
             pos += info.blob_bytes
             pages.append(torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=device))
             which.append(i)
-        if which:
-            n = len(which)
-            offs = np.asarray(offsets, np.int64)
+        n = len(kinds["jpeg"][2]) + len(kinds["png"][2])
+        if n:
             dev_blobs = host[:pos].to(device, non_blocking=True)
-            ws_bytes = int(L.lib.rtn_jpeg_workspace_bytes(n, hp, offs.ctypes.data))
-            ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
             status = torch.empty(n, dtype=torch.int32, device=device)
-            ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
             handle.set_stream(stream.cuda_stream)
-            handle.check(L.lib.rtn_jpeg_decode(handle.raw, n, hp, dev_blobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
-                                               ws.data_ptr(), ws_bytes))
+            keep = []                                                  # the workspaces live until the stream is synchronised
+            first = 0
+            for kind, ws_fn, decode in (("jpeg", L.lib.rtn_jpeg_workspace_bytes, L.lib.rtn_jpeg_decode),
+                                        ("png", L.lib.rtn_png_decode_workspace_bytes, L.lib.rtn_png_decode)):
+                offsets, pages, which = kinds[kind]
+                m = len(which)
+                if not m:
+                    continue
+                offs = np.asarray(offsets, np.int64)
+                ws_bytes = int(ws_fn(m, hp, offs.ctypes.data))
+                ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+                ptrs = (C.c_void_p * m)(*[p.data_ptr() for p in pages])
+                handle.check(decode(handle.raw, m, hp, dev_blobs.data_ptr(), offs.ctypes.data, ptrs,
+                                    status[first:first + m].data_ptr(), ws.data_ptr(), ws_bytes))
+                keep.append(ws)
+                first += m
             st = torch.empty(n, dtype=torch.int32, pin_memory=True)
             st.copy_(status, non_blocking=True)
             stream.synchronize()
-            for k, i in enumerate(which):
-                if int(st[k]) == 0:
-                    out[i] = pages[k]
-                else:
-                    on_host.append(i)
+            k = 0
+            for kind in ("jpeg", "png"):
+                _, pages, which = kinds[kind]
+                for page, i in zip(pages, which):
+                    words[i] = int(st[k])
+                    if words[i] == 0:
+                        out[i] = page
+                    else:
+                        on_host.append(i)
+                    k += 1
         for i in sorted(on_host):
-            out[i] = torch.from_numpy(read_image_bgr(paths[i])).to(device)
-    return out
+            out[i] = torch.from_numpy(host_decode(i)).to(device)
+    return out, words
+
+
+def _decode_batch(paths, device, handle, stream):
+    """read_images_bgr on an explicit handle and stream (see _decode_datas); a file that cannot be read is left to
+    read_image_bgr, which raises the same exception."""
+    datas = []
+    for path in paths:
+        try:
+            with open(path, 'rb') as f:
+                datas.append(f.read())
+        except OSError:
+            datas.append(None)
+    return _decode_datas(datas, lambda i: read_image_bgr(paths[i]), device, handle, stream)[0]
 
 
 _readers = {}
@@ -129,10 +177,14 @@ _readers_lock = threading.Lock()
 
 
 def read_images_bgr(paths, device=None):
-    """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits: baseline JPEGs (the files
-    cv2.imwrite writes for a .jpg name) are decoded on the device in one batched call (csrc/rtn_jpeg.hip) on the current stream;
-    every other file, and any JPEG whose stream the device decode flags, is decoded by read_image_bgr and uploaded.  A file
-    Pillow cannot open raises what read_image_bgr raises."""
+    """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits.  Baseline JPEGs (the files
+    cv2.imwrite writes for a .jpg name) and PNGs of the chunked layout of DESIGN §3.4d (the files write_images_bgr(png="device")
+    and preprocess_files(png="device") write) are decoded on the device, one batched call per format (csrc/rtn_jpeg.hip,
+    csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Every other file (any other
+    PNG among them: one zlib stream, Average or Paeth rows, 16-bit, palette, alpha, interlace, ancillary chunks), and any file
+    whose stream the device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset is converted once
+    with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises what read_image_bgr
+    raises."""
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())

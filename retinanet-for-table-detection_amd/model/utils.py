@@ -373,6 +373,34 @@ def encode_png_bgr(pages):
     return _files_to_host(out, offs, nb, list(range(n)), n)
 
 
+def decode_png_bgr(files, device=None, return_status=False):
+    """The pages of PNG files held in memory (list of bytes) as CUDA uint8 (H,W,3) B,G,R tensors with the bits Pillow gives:
+    the counterpart of encode_png_bgr, on read_images_bgr's path.  Files of the chunked layout are decoded in one
+    batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip); a file that is not in the layout, or that the device
+    flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
+    device's status word for file i (0 = the device's page was kept) or None where the device did not take the file."""
+    import importlib
+    import io
+    from PIL import Image
+    CG = importlib.import_module(_rt._pkg.__name__ + ".csv_generator")
+    files = [bytes(f) for f in files]
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+    def host_decode(i):
+        with Image.open(io.BytesIO(files[i])) as im:
+            rgb = np.asarray(im.convert("RGB"))
+        return np.ascontiguousarray(rgb[:, :, ::-1])
+
+    with CG._readers_lock:
+        h = CG._readers.get(dev.index)
+        if h is None:
+            h = CG._readers[dev.index] = L.Handle(dev.index)
+        pages, words = CG._decode_datas(files, host_decode, dev, h, torch.cuda.current_stream(dev))
+    return (pages, words) if return_status else pages
+
+
 def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
     """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
     .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged.

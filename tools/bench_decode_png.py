@@ -1,0 +1,190 @@
+"""Measure the device PNG decoder (csrc/rtn_png_dec.hip) on sample-sized pages: the 2200x1712 distance map
+(tests/golden/sample_0717_023.jpg, the file a training run reads), the page itself, or the gray page, written 16 times as PNG of
+the chunked layout by the device encoder (model.utils.encode_png_bgr).
+
+  python tools/bench_decode_png.py [--batch 16] [--iters 10] [--host-pages 4] [--content map|page|gray|all]
+
+Reports medians and the min..max spread over the iterations after a warm-up, every path on the same machine:
+  (a) GPU time of the four decode kernels per batch (events around rtn_png_decode, blobs already on the device);
+  (b) host time of rtn_png_inspect per page (parse and copy of the deflate payloads; the chunk CRCs are left to the device);
+  (c) wall time of read_images_bgr for the batch's files (read, inspect, one copy, decode, status read-back);
+  (d) read_image_bgr (Pillow) on one thread on the same files: the parent commit's path for them;
+  (e) one CSVGenerator batch of those files end to end, with the device decoder and with every page decoded by read_image_bgr.
+For the per-kernel split: rocprofv3 --kernel-trace --stats --output-format csv -d rocprof_out -o png_dec --
+  python tools/bench_decode_png.py --iters 3 --host-pages 0 --content map
+"""
+import argparse
+import ctypes as C
+import importlib
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+import warnings
+
+import numpy as np
+import torch
+from PIL import Image
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "retinanet-for-table-detection_amd"
+CG = importlib.import_module(PKG + ".csv_generator")
+L = importlib.import_module(PKG + "._lib")
+U = importlib.import_module(PKG + ".model.utils")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def stat(v):
+    return (float(np.median(v)), float(np.min(v)), float(np.max(v))) if len(v) else (float("nan"),) * 3
+
+
+def times_ms(fn, iters):
+    ts = []
+    for _ in range(iters):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return ts
+
+
+def load(content):
+    if content == "map":
+        return np.ascontiguousarray(np.asarray(Image.open(os.path.join(GOLDEN, "sample_0717_023.jpg")).convert("RGB"))[:, :, ::-1])
+    o = Image.open(os.path.join(GOLDEN, "sample_0717_023_orig.jpg"))
+    if content == "page":
+        return np.ascontiguousarray(np.asarray(o.convert("RGB"))[:, :, ::-1])
+    return np.ascontiguousarray(np.asarray(o.convert("L")))
+
+
+def bench(content, a):
+    n = a.batch
+    dev = torch.device("cuda", 0)
+    page = load(content)
+    (data,) = U.encode_png_bgr([page])
+    want = page if page.ndim == 3 else np.repeat(page[:, :, None], 3, axis=2)
+    tmp = tempfile.mkdtemp(prefix="bench_decode_png_")
+    paths = []
+    for i in range(n):
+        p = os.path.join(tmp, "page_%02d.png" % i)
+        with open(p, "wb") as f:
+            f.write(data)
+        paths.append(p)
+    info, blob = CG.png_inspect(data)
+    assert info is not None, blob
+    print("== %s: %dx%d, %d component(s), file %d B, %d chunks, deflate payload %d B, blob %d B, workspace %.1f MB per page" %
+          (content, info.width, info.height, info.components, len(data), info.chunks, info.payload_bytes, info.blob_bytes,
+           info.workspace_bytes / 1e6))
+
+    # (a) kernels alone
+    host = np.concatenate([blob] * n)
+    offs = np.arange(n, dtype=np.int64) * blob.size
+    dblobs = torch.from_numpy(host).to(dev)
+    wsb = int(L.lib.rtn_png_decode_workspace_bytes(n, host.ctypes.data, offs.ctypes.data))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    pages = [torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+    ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    h = L.Handle(0)
+    h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+
+    def decode():
+        h.check(L.lib.rtn_png_decode(h.raw, n, host.ctypes.data, dblobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
+                                     ws.data_ptr(), wsb))
+    for _ in range(3):
+        decode()
+    torch.cuda.synchronize()
+    assert int(status.abs().sum()) == 0
+    assert np.array_equal(pages[n - 1].cpu().numpy(), want)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    k_ms = []
+    for _ in range(a.iters):
+        ev[0].record()
+        decode()
+        ev[1].record()
+        torch.cuda.synchronize()
+        k_ms.append(ev[0].elapsed_time(ev[1]))
+
+    # (b) host inspect, per page
+    out = np.empty(L.png_blob_bound(len(data)), np.uint8)
+    pinfo = L.PngInfo()
+    i_ms = times_ms(lambda: L.lib.rtn_png_inspect(None, data, len(data), C.byref(pinfo), out.ctypes.data, out.size), max(a.iters, 5))
+
+    # (c) read_images_bgr, files to device pages
+    for _ in range(2):
+        got = CG.read_images_bgr(paths)
+    torch.cuda.synchronize()
+    assert np.array_equal(got[0].cpu().numpy(), want)
+
+    def read_all():
+        CG.read_images_bgr(paths)
+        torch.cuda.synchronize()
+    r_ms = times_ms(read_all, a.iters)
+
+    # (d) Pillow, one thread
+    p_ms = []
+    if a.host_pages:
+        CG.read_image_bgr(paths[0])
+        p_ms = times_ms(lambda: CG.read_image_bgr(paths[0]), a.host_pages)
+
+    # (e) one CSVGenerator batch from the files
+    csvf = os.path.join(tmp, "train.csv")
+    with open(csvf, "w") as f:
+        f.write("image_id,xmin,ymin,xmax,ymax,label\n")
+        for p in paths:
+            f.write("%s,100,120,900,700,table\n" % os.path.basename(p))
+
+    def gen_ms(device_decode, iters):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            gen = CG.CSVGenerator(csvf, tmp, {"table": 0}, batch_size=n, group_method="none", shuffle_groups=False)
+            if not device_decode:
+                gen.load_image_group = lambda group: CG.Generator.load_image_group(gen, group)
+            keep = []
+
+            def one():
+                x, (reg, lab) = gen[0]
+                torch.cuda.current_stream(dev).synchronize()
+                keep.append(x)
+            one()
+            ms = times_ms(one, iters)
+            gen.close()
+        return ms, keep[-1]
+    g_ms, x_dev = gen_ms(True, a.iters)
+    gh_ms = []
+    if a.host_pages:
+        gh_ms, x_host = gen_ms(False, 1)
+        assert torch.equal(x_dev, x_host)
+
+    res = {"content": content, "batch": n, "file_bytes": len(data)}
+    for key, label, v, per in (("kernels_ms", "(a) decode kernels alone", k_ms, n),
+                               ("inspect_ms_per_page", "(b) rtn_png_inspect on the host", i_ms, 1),
+                               ("read_images_bgr_ms", "(c) read_images_bgr", r_ms, n),
+                               ("pillow_ms_per_page", "(d) read_image_bgr (Pillow), one thread", p_ms, 1),
+                               ("generator_batch_ms_device", "(e) CSVGenerator batch, device decoder", g_ms, n),
+                               ("generator_batch_ms_pillow", "(e) CSVGenerator batch, read_image_bgr", gh_ms, n)):
+        m, lo, hi = stat(v)
+        print("%-44s %9.3f ms per %2d page(s) (min %.3f, max %.3f, %d runs): %.1f pages/s" % (label, m, per, lo, hi, len(v), per / m * 1e3))
+        res[key] = round(m, 3)
+    if p_ms:
+        print("(c) is %.0fx (d); the training step that has to hide (c) takes 25.9 ms" % (stat(p_ms)[0] * n / stat(r_ms)[0]))
+    print(json.dumps(res))
+    h.close()
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--host-pages", type=int, default=4)
+    ap.add_argument("--content", choices=("map", "page", "gray", "all"), default="all")
+    a = ap.parse_args()
+    for content in (("map", "page", "gray") if a.content == "all" else (a.content,)):
+        bench(content, a)
+
+
+if __name__ == "__main__":
+    main()
