@@ -41,22 +41,32 @@ def device_warp(pkg, handle, img, matrix, interp, border, cval):
     return dst.cpu().numpy()
 
 
-@pytest.mark.parametrize("interp", [0, 1])
-@pytest.mark.parametrize("border", [0, 1, 2, 3])
-def test_warp_affine_bit_exact(pkg, handle, interp, border):
-    rng = np.random.RandomState(10 * interp + border)
-    img = rng.randint(0, 256, (211, 173, 3)).astype(np.uint8)
+def check_warp_bit_exact(pkg, handle, rng, H, W, interp, border):
+    img = rng.randint(0, 256, (H, W, 3)).astype(np.uint8)
     prng = np.random.RandomState(3)
-    mats = [G.adjust_for_image(G.random_transform(prng, **TRAIN_KW), 211, 173) for _ in range(4)]
+    mats = [G.adjust_for_image(G.random_transform(prng, **TRAIN_KW), H, W) for _ in range(4)]
     mats.append(np.eye(3))
-    mats.append(G.adjust_for_image(G.random_transform(prng, min_rotation=1.0, max_rotation=2.0, min_scaling=(0.3, 0.4), max_scaling=(0.5, 0.6)), 211, 173))
+    mats.append(G.adjust_for_image(G.random_transform(prng, min_rotation=1.0, max_rotation=2.0, min_scaling=(0.3, 0.4), max_scaling=(0.5, 0.6)), H, W))
     mats.append(np.array([[1, 0, 400.0], [0, 1, -300.0], [0, 0, 1]]))            # everything off the page
     for m in mats:
         want = G.warp_affine_u8(img, m, interp, border, cval=77)
         got = device_warp(pkg, handle, img, m, interp, border, 77)
-        assert np.array_equal(got, want), "warp differs on %d bytes" % int((got != want).sum())
+        assert np.array_equal(got, want), "%dx%d: warp differs on %d bytes" % (H, W, int((got != want).sum()))
     gray = img[..., 0].copy()
     assert np.array_equal(device_warp(pkg, handle, gray, mats[0], interp, border, 5), G.warp_affine_u8(gray, mats[0], interp, border, cval=5))
+
+
+@pytest.mark.parametrize("interp", [0, 1])
+@pytest.mark.parametrize("border", [0, 1, 2, 3])
+def test_warp_affine_bit_exact(pkg, handle, interp, border):
+    rng = np.random.RandomState(10 * interp + border)
+    check_warp_bit_exact(pkg, handle, rng, 211, 173, interp, border)           # 173 * 3 % 4 != 0: every store is per byte
+    # W * 3 % 4 == 0: full 64-pixel blocks leave as packed dwords (dword_rows).  172 and 196: packed blocks, then a partial last
+    # block that takes the per-byte path; 64: one packed block and nothing else; 211, 9 and 6 rows: the last 4-row block of the
+    # grid is partial, so the packed store's own row guard decides
+    for H, W in ((211, 172), (9, 64), (6, 196)):
+        assert W * 3 % 4 == 0 and H % 4 != 0
+        check_warp_bit_exact(pkg, handle, np.random.RandomState(1000 * H + 10 * W + 10 * interp + border), H, W, interp, border)
 
 
 def test_warp_affine_rejects_bad_arguments(pkg, handle):

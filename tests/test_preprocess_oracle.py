@@ -6,6 +6,7 @@ import os
 import numpy as np
 
 from oracle import ref_preprocess as P
+import preprocess_cases as K
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -16,6 +17,15 @@ def test_vectorised_distance_transform_equals_literal_two_pass():
         b = (rng.uniform(size=shape) > p).astype(np.uint8) * 255
         for m in ("L2", "L1", "C"):
             assert np.array_equal(P.distance_transform(b, m), P.distance_transform_literal(b, m)), (shape, m)
+    # the patterns of tests/test_gpu_preprocess.py at widths past one wave and past 256 columns: a single zero pixel in each corner
+    # (the ramp crosses the whole row in both sweep directions) and zeros only at thread / wave seam columns on alternating rows
+    for H, W in ((5, 300), (3, 130)):
+        T, E = K.launch_shape(W)
+        pages = [K.corner_pages(H, W, k) for k in range(4)] + [K.seam_pages(H, W, T, E), K.seam_pages(H, W, 64, 2)]
+        for b in np.concatenate(pages):
+            assert (b == 0).any()
+            for m in ("L2", "L1", "C"):
+                assert np.array_equal(P.distance_transform(b, m), P.distance_transform_literal(b, m)), (H, W, m)
     # known answers: single zero pixel -> the metric's closed form
     b = np.full((9, 9), 255, np.uint8)
     b[4, 4] = 0
