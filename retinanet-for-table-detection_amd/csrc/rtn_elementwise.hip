@@ -46,7 +46,19 @@ extern "C" int rtn_set_stream(rtn_handle_t h, void* stream) {
     return RTN_OK;
 }
 
+static thread_local char g_host_err[256];
+const char* rtn_host_error_text() { return g_host_err[0] ? g_host_err : "null handle"; }
+void rtn_set_host_error(const char* text) { snprintf(g_host_err, sizeof(g_host_err), "%s", text); }
+
 extern "C" const char* rtn_last_error(rtn_handle_t h) { return h ? h->err : rtn_host_error_text(); }
+
+int rtn_fail_host(rtn_handle_t h, int code, const char* fmt, ...) {
+    va_list ap; va_start(ap, fmt);
+    if (h) vsnprintf(h->err, sizeof(h->err), fmt, ap);
+    else vsnprintf(g_host_err, sizeof(g_host_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
 
 namespace {
 

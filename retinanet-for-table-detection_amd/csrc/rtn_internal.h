@@ -85,10 +85,12 @@ int rtn_wgrad_finish(rtn_handle_t h, float* dW, const float* slab, int S, long l
 size_t rtn_wgrad_win_workspace_bytes(const rtn_conv_desc_t* d);
 int rtn_wgrad_win_try(rtn_handle_t h, const rtn_conv_desc_t* d, float* dW, float* db, int db_n, void* workspace, size_t workspace_bytes);
 
-// rtn_jpeg.hip: text of the calling thread's last failed host-only call made without a handle (rtn_last_error(NULL))
+// rtn_elementwise.hip: text of the calling thread's last failed host-only call made without a handle (rtn_last_error(NULL))
 const char* rtn_host_error_text();
-// ... and sets it (rtn_jpeg_enc.hip's host-only entry points)
+// ... and sets it (the host-only entry points of the page codecs)
 void rtn_set_host_error(const char* text);
+// rtn_fail with a handle; without one the formatted message becomes the calling thread's host-error text
+int rtn_fail_host(rtn_handle_t h, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 
 static inline int rtn_dtype_size(int dt) { return dt == RTN_F32 ? 4 : (dt == RTN_FP8 ? 1 : 2); }
 

@@ -14,12 +14,12 @@
 // A page whose stream breaks JPEG's rules, or whose IDCT leaves the range where libjpeg-turbo's C and SIMD IDCTs agree, gets a
 // non-zero status word: the caller decodes that page on the host.
 #include "rtn_internal.h"
+#include "rtn_codec.h"
 
 namespace {
 
 constexpr int JPG_MAGIC = 0x47504a52;          // "RJPG"
 constexpr int JPG_THREADS = 1024;              // huffman kernel workgroup: one page
-constexpr int JPG_BATCH = 32;                  // pages per launch (kernel-argument table)
 constexpr int JPG_MAX_PIXELS = 1 << 28;
 
 struct JHuff {                                 // 1440 bytes
@@ -48,9 +48,9 @@ constexpr int JB_SEG = JB_QUANT + 4 * 64 * 2;
 
 struct JBatch {
     int n, maxblocks, maxpix, pad_;
-    long long blob_off[JPG_BATCH];
-    long long ws_off[JPG_BATCH];
-    unsigned char* out[JPG_BATCH];
+    long long blob_off[RTN_CODEC_BATCH];
+    long long ws_off[RTN_CODEC_BATCH];
+    unsigned char* out[RTN_CODEC_BATCH];
 };
 
 __host__ __device__ constexpr int zz_natural(int k) {
@@ -486,19 +486,9 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
 }
 
 // ---- host parser ------------------------------------------------------------------------------------------------------------
-thread_local char g_host_err[256];
-
 struct RawHuff { bool defined; uint8_t bits[17]; uint8_t val[256]; int count; };
 
-int jfail(rtn_handle_t h, const char* fmt, ...) {
-    char buf[256];
-    va_list ap; va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) snprintf(h->err, sizeof(h->err), "%s", buf);
-    else snprintf(g_host_err, sizeof(g_host_err), "%s", buf);
-    return RTN_EINVAL;
-}
+#define jfail(h, ...) rtn_fail_host((h), RTN_EINVAL, __VA_ARGS__)      // a macro, so every message is format-checked
 
 inline int be16(const uint8_t* p) { return (p[0] << 8) | p[1]; }
 
@@ -797,9 +787,6 @@ extern "C" int rtn_jpeg_inspect(rtn_handle_t h, const void* file, size_t file_by
     return RTN_OK;
 }
 
-const char* rtn_host_error_text() { return g_host_err[0] ? g_host_err : "null handle"; }
-void rtn_set_host_error(const char* text) { snprintf(g_host_err, sizeof(g_host_err), "%s", text); }
-
 static bool jpeg_blob_ok(const uint8_t* b) {
     const JHdr* hd = reinterpret_cast<const JHdr*>(b);
     return hd->magic == JPG_MAGIC && hd->ws_bytes > 0 && hd->nseg > 0;
@@ -836,10 +823,10 @@ extern "C" int rtn_jpeg_decode(rtn_handle_t h, int n, const void* host_blobs, co
     if (workspace_bytes < need)
         return rtn_fail(h, RTN_ENOMEM, "rtn_jpeg_decode: workspace %zu < %zu bytes", workspace_bytes, need);
     long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += JPG_BATCH) {
+    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
         JBatch bt;
         memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < JPG_BATCH ? n - i0 : JPG_BATCH;
+        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
         long long maxpix = 0;
         int maxblocks = 0;
         for (int j = 0; j < bt.n; ++j) {

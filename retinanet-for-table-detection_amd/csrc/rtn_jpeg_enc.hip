@@ -3,8 +3,8 @@
 // Huffman tables, one interleaved scan, no restart markers, no optimisation pass.
 //
 // Host: the header (SOI .. SOS) is one __host__ __device__ function, so rtn_jpeg_encode_header and the device write the same bytes.
-// Device, five kernels per batch of up to JE_BATCH pages (each page's work stays inside its own workgroups; no workgroup waits on
-// another):
+// Device, five kernels per batch of up to RTN_CODEC_BATCH pages (each page's work stays inside its own workgroups; no workgroup
+// waits on another):
 //   1. jenc_transform_kernel: one thread per 8x8 block in scan order (MCU order, dummy blocks included): rgb_ycc_convert, edge
 //      replication, h2v1 / h2v2 downsampling, jpeg_fdct_islow, quantisation; writes the zig-zagged int16 coefficients.
 //   2. jenc_bits_kernel: the Huffman bit length of every block (its DC difference reads the predecessor's DC in scan order) and
@@ -17,10 +17,10 @@
 //      scans, and writes header + stuffed stream + EOI into the page's output slot, and the file length.
 // A page whose file would not fit its slot gets a non-zero status word and a length of 0: the caller encodes it on the host.
 #include "rtn_internal.h"
+#include "rtn_codec.h"
 
 namespace {
 
-constexpr int JE_BATCH = 32;                   // pages per launch (kernel-argument table)
 constexpr int JE_TILE = 256;                   // blocks per tile of the bit-offset scan (= workgroup of kernels 1, 2, 4)
 constexpr int JE_SCAN_THREADS = 1024;          // workgroup of kernels 3 and 5: one page
 constexpr int JE_BLOCK_BITS = 16 + 11 + 63 * (16 + 10);   // most bits one block can take: DC code + value, 63 x (AC code + value)
@@ -39,7 +39,7 @@ struct JEPage {
 
 struct JEBatch {
     int n, maxblocks, pad_[2];
-    JEPage p[JE_BATCH];
+    JEPage p[RTN_CODEC_BATCH];
 };
 
 __host__ __device__ constexpr int je_natural(int k) {
@@ -164,17 +164,15 @@ __host__ __device__ inline int je_write_header(uint8_t* o, int W, int H, int nc,
 // ---- per-page workspace ---------------------------------------------------------------------------------------------------
 struct JELayout { long long bits, tiles, stream, total, stream_words; int ntiles; };
 
-inline long long je_align(long long v) { return (v + 255) & ~255LL; }
-
 inline JELayout je_layout(const JEGeom& g) {
     JELayout L;
     L.ntiles = (g.nblocks + JE_TILE - 1) / JE_TILE;
     L.stream_words = ((long long)g.nblocks * JE_BLOCK_BITS + 31) / 32 + 1;
-    L.bits = je_align((long long)g.nblocks * 128);                     // coefficients: [nblocks][64] int16, zig-zag order
-    L.tiles = L.bits + je_align((long long)g.nblocks * 4);             // bits per block (int32)
+    L.bits = rtn_align256((long long)g.nblocks * 128);                 // coefficients: [nblocks][64] int16, zig-zag order
+    L.tiles = L.bits + rtn_align256((long long)g.nblocks * 4);         // bits per block (int32)
     // tile bit offsets (int64, ntiles + 1, the last one the page's total), tile sums (int32), the page's no-code flag (int32)
-    L.stream = L.tiles + je_align((long long)(L.ntiles + 1) * 8 + (long long)L.ntiles * 4 + 4);
-    L.total = L.stream + je_align((long long)L.stream_words * 4);
+    L.stream = L.tiles + rtn_align256((long long)(L.ntiles + 1) * 8 + (long long)L.ntiles * 4 + 4);
+    L.total = L.stream + rtn_align256((long long)L.stream_words * 4);
     return L;
 }
 
@@ -414,24 +412,6 @@ __global__ __launch_bounds__(JE_TILE) void jenc_bits_kernel(uint8_t* __restrict_
     }
 }
 
-// in-place exclusive scan of one value per thread over a workgroup of JE_SCAN_THREADS; returns the total
-template <typename T>
-__device__ inline T je_wg_exclusive_scan(T* sh, T& v) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < JE_SCAN_THREADS; d <<= 1) {
-        const T a = t >= d ? sh[t - d] : (T)0;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const T total = sh[JE_SCAN_THREADS - 1];
-    v = sh[t] - v;
-    __syncthreads();
-    return total;
-}
-
 __global__ __launch_bounds__(JE_SCAN_THREADS) void jenc_scan_kernel(uint8_t* __restrict__ ws, int32_t* __restrict__ status,
                                                                     long long* __restrict__ out_bytes, JEBatch bt) {
     __shared__ long long sh[JE_SCAN_THREADS];
@@ -445,7 +425,7 @@ __global__ __launch_bounds__(JE_SCAN_THREADS) void jenc_scan_kernel(uint8_t* __r
     for (int i0 = 0; i0 < pg.ntiles; i0 += JE_SCAN_THREADS) {
         const int i = i0 + threadIdx.x;
         long long v = i < pg.ntiles ? sums[i] : 0;
-        const long long tot = je_wg_exclusive_scan(sh, v);
+        const long long tot = rtn_wg_exclusive_scan<JE_SCAN_THREADS>(sh, v);
         if (i < pg.ntiles) off[i] = carry + v;
         carry += tot;
     }
@@ -553,7 +533,7 @@ __global__ __launch_bounds__(JE_SCAN_THREADS) void jenc_assemble_kernel(uint8_t*
         for (int k = 0; k < 4; ++k)
             if (wi * 4 + k < nbytes && byte_at(wi, k, wv) == 0xFFu) ++ff;
     }
-    const long long total_ff = je_wg_exclusive_scan(sh, ff);
+    const long long total_ff = rtn_wg_exclusive_scan<JE_SCAN_THREADS>(sh, ff);
     const int hb = je_header_bytes(pg.nc);
     const long long len = hb + nbytes + total_ff + 2;
     if (len > pg.cap) {
@@ -582,17 +562,12 @@ __global__ __launch_bounds__(JE_SCAN_THREADS) void jenc_assemble_kernel(uint8_t*
 }
 
 int je_check(rtn_handle_t h, int W, int H, int nc, int ss, int q, const char* who) {
-    char buf[160];
-    buf[0] = 0;
-    if (q < 1 || q > 100) snprintf(buf, sizeof(buf), "%s: quality %d outside 1..100", who, q);
-    else if (W < 1 || W > JE_MAX_DIM || H < 1 || H > JE_MAX_DIM)
-        snprintf(buf, sizeof(buf), "%s: %d x %d page: width and height must be 1..%d", who, W, H, JE_MAX_DIM);
-    else if (nc != 1 && nc != 3) snprintf(buf, sizeof(buf), "%s: %d components (1 or 3)", who, nc);
-    else if (ss < 0 || ss > 2) snprintf(buf, sizeof(buf), "%s: subsampling %d (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0)", who, ss);
-    if (!buf[0]) return RTN_OK;
-    if (h) return rtn_fail(h, RTN_EINVAL, "%s", buf);
-    rtn_set_host_error(buf);
-    return RTN_EINVAL;
+    if (q < 1 || q > 100) return rtn_fail_host(h, RTN_EINVAL, "%s: quality %d outside 1..100", who, q);
+    if (W < 1 || W > JE_MAX_DIM || H < 1 || H > JE_MAX_DIM)
+        return rtn_fail_host(h, RTN_EINVAL, "%s: %d x %d page: width and height must be 1..%d", who, W, H, JE_MAX_DIM);
+    if (nc != 1 && nc != 3) return rtn_fail_host(h, RTN_EINVAL, "%s: %d components (1 or 3)", who, nc);
+    if (ss < 0 || ss > 2) return rtn_fail_host(h, RTN_EINVAL, "%s: subsampling %d (0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0)", who, ss);
+    return RTN_OK;
 }
 
 }  // namespace
@@ -604,12 +579,8 @@ extern "C" int rtn_jpeg_encode_header(int width, int height, int components, int
     const int rc = je_check(nullptr, width, height, components, subsampling, quality, "rtn_jpeg_encode_header");
     if (rc) return rc;
     const int n = je_header_bytes(components);
-    if (!out || (size_t)n > capacity) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "rtn_jpeg_encode_header: %zu-byte buffer, %d bytes needed", out ? capacity : (size_t)0, n);
-        rtn_set_host_error(buf);
-        return RTN_EINVAL;
-    }
+    if (!out || (size_t)n > capacity)
+        return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_jpeg_encode_header: %zu-byte buffer, %d bytes needed", out ? capacity : (size_t)0, n);
     const int got = je_write_header(out, width, height, components, subsampling, quality);
     if (got != n) return RTN_EINVAL;
     if (written) *written = (size_t)n;
@@ -657,10 +628,10 @@ extern "C" int rtn_jpeg_encode(rtn_handle_t h, int n, const uint8_t* const* page
         return rtn_fail(h, RTN_ENOMEM, "rtn_jpeg_encode: workspace %zu < %zu bytes", workspace_bytes, need);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
     long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += JE_BATCH) {
+    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
         JEBatch bt;
         memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < JE_BATCH ? n - i0 : JE_BATCH;
+        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
         for (int k = 0; k < bt.n; ++k) {
             const int i = i0 + k;
             const JEGeom g = je_geom(widths[i], heights[i], components[i], subsampling[i]);

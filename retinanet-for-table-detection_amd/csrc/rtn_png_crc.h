@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 constexpr uint32_t PE_POLY = 0xedb88320u;      // CRC-32, reflected
+constexpr uint32_t PE_ADLER = 65521u;          // modulus of the Adler-32 sums (zlib's BASE)
 
 __host__ __device__ inline uint32_t pe_crc_byte(uint32_t c, uint32_t b) {     // table-free update by one byte
     c ^= b;

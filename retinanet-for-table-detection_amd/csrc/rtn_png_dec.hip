@@ -4,7 +4,7 @@
 // length, stored CRC).  It does not look into the deflate data beyond the bytes the layout fixes: the device vouches for the rest,
 // and a page whose status is not 0 is decoded by the caller on the host.
 //
-// Four kernels per batch of up to PD_BATCH pages; no workgroup waits on another:
+// Four kernels per batch of up to RTN_CODEC_BATCH pages; no workgroup waits on another:
 //   1. pdec_inflate_kernel: one workgroup of one wave per chunk.  Window (32 KiB) and decode tables in LDS; block loop, table build
 //      and symbol decode (csrc/rtn_png_inflate.h) uniform across the wave, payload words fetched 64 at a time into one register per
 //      lane, matches copied by all lanes.  Then the chunk's CRC-32 (slices per lane, joined like the encoder's), its Adler pair, the
@@ -20,19 +20,18 @@
 // a block boundary on a byte boundary wherever a payload ends, decodes the same blocks, and finds every match source inside the
 // same chunk: it produces the same bytes, and after the last payload the final block and the Adler-32 the page kernel compared.
 #include "rtn_internal.h"
+#include "rtn_codec.h"
 #include "rtn_png_crc.h"
 #include "rtn_png_inflate.h"
 #include <vector>
 
 namespace {
 
-constexpr int PD_BATCH = 32;                   // pages per launch (kernel-argument table)
 constexpr int PD_CHUNK = RTN_PNG_CHUNK;
 constexpr int PD_WAVE = 64;                    // workgroup of kernels 1 and 2: one wave
 constexpr int PD_THREADS = 256;                // workgroup of kernels 3 and 4
 constexpr int PD_MAX_GRID = 1 << 20;           // workgroups along x of the Sub launch: rows past it are looped over
 constexpr uint32_t PD_MAGIC = 0x444e5052u;     // "RPND"
-constexpr uint32_t PD_ADLER = 65521u;
 static_assert(PD_CHUNK == 32768 && PD_CHUNK % (16 * PD_WAVE) == 0, "chunk size");
 
 struct PDHdr {                                 // start of a blob; 64 bytes
@@ -57,22 +56,12 @@ struct PDPage {
 };
 struct PDBatch {
     int n, maxchunks, maxrows, maxcols;
-    PDPage p[PD_BATCH];
+    PDPage p[RTN_CODEC_BATCH];
 };
 
-inline long long pd_align(long long v) { return (v + 255) & ~255LL; }
-inline long long pd_ws_bytes(long long nchunks) { return nchunks * PD_CHUNK + pd_align(nchunks * (long long)sizeof(PDMeta)); }
+inline long long pd_ws_bytes(long long nchunks) { return nchunks * PD_CHUNK + rtn_align256(nchunks * (long long)sizeof(PDMeta)); }
 
-int pfail(rtn_handle_t h, const char* fmt, ...) {
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (h) return rtn_fail(h, RTN_EINVAL, "%s", buf);
-    rtn_set_host_error(buf);
-    return RTN_EINVAL;
-}
+#define pfail(h, ...) rtn_fail_host((h), RTN_EINVAL, __VA_ARGS__)      // a macro, so every message is format-checked
 
 inline uint32_t be32(const uint8_t* p) { return (uint32_t)p[0] << 24 | (uint32_t)p[1] << 16 | (uint32_t)p[2] << 8 | p[3]; }
 
@@ -218,8 +207,8 @@ __global__ __launch_bounds__(PD_WAVE) void pdec_inflate_kernel(const uint8_t* bl
             sb += (unsigned long long)(want - (p < want ? p : want)) * d;
         }
     }
-    const uint32_t A = (1u + pd_wave_sum(sa)) % PD_ADLER;
-    const uint32_t B = (want + pd_wave_sum((uint32_t)(sb % PD_ADLER))) % PD_ADLER;
+    const uint32_t A = (1u + pd_wave_sum(sa)) % PE_ADLER;
+    const uint32_t B = (want + pd_wave_sum((uint32_t)(sb % PE_ADLER))) % PE_ADLER;
 
     // ---- the filter-type bytes of the rows that start in this chunk
     {
@@ -253,20 +242,20 @@ __global__ __launch_bounds__(PD_WAVE) void pdec_page_kernel(uint8_t* ws, int32_t
         PDMeta m = {1u, 0u, 0u, 0u};
         if (k < pg.nchunks) m = meta[k];
         st |= m.status;
-        const uint32_t a1 = (m.a % PD_ADLER + PD_ADLER - 1u) % PD_ADLER;
+        const uint32_t a1 = (m.a % PE_ADLER + PE_ADLER - 1u) % PE_ADLER;
         uint32_t incl = a1;
         for (int o = 1; o < PD_WAVE; o <<= 1) {
             const uint32_t v = (uint32_t)__shfl_up((int)incl, o);
             if (ln >= o) incl += v;                                    // < 64 * 65521
         }
         const long long len = k < pg.nchunks ? (pg.stream - (long long)k * PD_CHUNK < PD_CHUNK ? pg.stream - (long long)k * PD_CHUNK : PD_CHUNK) : 0;
-        const unsigned long long before = (carry + incl - a1) % PD_ADLER;
-        const uint32_t term = k < pg.nchunks ? (uint32_t)((m.b % PD_ADLER + (unsigned long long)len * before) % PD_ADLER) : 0u;
-        bsum = (bsum + pd_wave_sum(term)) % PD_ADLER;
-        carry = (carry + (uint32_t)__shfl((int)incl, PD_WAVE - 1)) % PD_ADLER;
+        const unsigned long long before = (carry + incl - a1) % PE_ADLER;
+        const uint32_t term = k < pg.nchunks ? (uint32_t)((m.b % PE_ADLER + (unsigned long long)len * before) % PE_ADLER) : 0u;
+        bsum = (bsum + pd_wave_sum(term)) % PE_ADLER;
+        carry = (carry + (uint32_t)__shfl((int)incl, PD_WAVE - 1)) % PE_ADLER;
     }
     st = pd_wave_or(st);
-    const uint32_t adler = bsum << 16 | (1u + carry) % PD_ADLER;
+    const uint32_t adler = bsum << 16 | (1u + carry) % PE_ADLER;
     if (adler != pg.adler) st |= PI_ADLER;
     if (ln == 0) status[page] = (int32_t)st;
 }
@@ -514,10 +503,10 @@ extern "C" int rtn_png_decode(rtn_handle_t h, int n, const void* host_blobs, con
     const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
     long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += PD_BATCH) {
+    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
         PDBatch bt;
         memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < PD_BATCH ? n - i0 : PD_BATCH;
+        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
         long long maxcols = 0;
         for (int j = 0; j < bt.n; ++j) {
             const PDHdr* hd = pd_blob(host_blobs, offsets[i0 + j]);

@@ -4,7 +4,7 @@
 // empty stored block, so IDAT k inflated alone gives raw bytes [k CHUNK, (k + 1) CHUNK): the chunks compress in parallel now and
 // can be inflated in parallel later.
 //
-// Four kernels per batch of up to PE_BATCH pages; no workgroup waits on another:
+// Four kernels per batch of up to RTN_CODEC_BATCH pages; no workgroup waits on another:
 //   1. penc_filter_kernel: one workgroup per row (rows past PE_MAX_GRID are looped over).  Counts, for None, Sub and Up, the
 //      bytes of the filtered row that differ from the byte before them, keeps the filter with the fewest (ties: the lower type) and writes type byte + filtered row into the
 //      page's filtered stream.
@@ -25,11 +25,11 @@
 // final empty stored block (5) and the Adler-32 (4).  So a file is at most 56 + stream + 22 * chunks bytes, and the host path
 // has nothing to catch.
 #include "rtn_internal.h"
+#include "rtn_codec.h"
 #include "rtn_png_crc.h"
 
 namespace {
 
-constexpr int PE_BATCH = 32;                   // pages per launch (kernel-argument table)
 constexpr int PE_CHUNK = RTN_PNG_CHUNK;        // raw bytes per deflate chunk; <= 32768, so every match distance is legal
 constexpr int PE_THREADS = 256;                // workgroup of kernels 1, 2, 4; positions per sub-block of the matcher
 constexpr int PE_SCAN_THREADS = 1024;          // workgroup of kernel 3: one page
@@ -39,7 +39,6 @@ constexpr int PE_HASH = 1 << PE_HASH_BITS;
 constexpr int PE_MIN_MATCH = 3, PE_MAX_MATCH = 258;
 constexpr int PE_MAX_GRID = 1 << 20;           // workgroups along x of the filter launch: rows past it are looped over
 constexpr int PE_FAR = 4096;                   // a 3-byte match further back than this costs more than three literals
-constexpr uint32_t PE_ADLER = 65521u;
 static_assert(PE_CHUNK <= 32768 && PE_CHUNK % PE_THREADS == 0 && PE_CHUNK % 64 == 0, "chunk size");
 
 struct PEPage {
@@ -56,7 +55,7 @@ struct PEBatch {
     long long* out_bytes;
     int32_t* status;
     int n, maxrows, maxchunks, pad_;
-    PEPage p[PE_BATCH];
+    PEPage p[RTN_CODEC_BATCH];
 };
 
 struct PEMeta { uint32_t len, crc, a, b; };    // per chunk: slot bytes used, CRC state over "IDAT" (+ zlib header) + slot, Adler pair
@@ -75,13 +74,12 @@ inline long long pe_bound(int W, int H, int nc) {
 }
 
 struct PELayout { long long meta, file, slots, total; };
-inline long long pe_align(long long v) { return (v + 255) & ~255LL; }
 inline PELayout pe_layout(int W, int H, int nc) {
     const long long s = pe_stream(W, H, nc), nk = pe_chunks(s);
     PELayout L;
-    L.meta = pe_align(s + 8);                                          // filtered stream, padded for word reads
-    L.file = L.meta + pe_align(nk * (long long)sizeof(PEMeta));        // PEMeta per chunk
-    L.slots = L.file + pe_align((nk + 1) * 8 + 8);                     // file offset of every IDAT (int64), then the page's Adler-32
+    L.meta = rtn_align256(s + 8);                                      // filtered stream, padded for word reads
+    L.file = L.meta + rtn_align256(nk * (long long)sizeof(PEMeta));    // PEMeta per chunk
+    L.slots = L.file + rtn_align256((nk + 1) * 8 + 8);                 // file offset of every IDAT (int64), then the page's Adler-32
     L.total = L.slots + nk * PE_SLOT;
     return L;
 }
@@ -593,22 +591,6 @@ __global__ __launch_bounds__(PE_THREADS) void penc_deflate_kernel(PEBatch bt) {
 }
 
 // ---- kernel 3: one page's offsets, Adler-32 and fixed chunks ------------------------------------------------------------------------------
-__device__ inline long long pe_scan1024(long long* sh, long long& v) {            // exclusive scan in place; returns the total
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < PE_SCAN_THREADS; d <<= 1) {
-        const long long a = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const long long total = sh[PE_SCAN_THREADS - 1];
-    v = sh[t] - v;
-    __syncthreads();
-    return total;
-}
-
 __device__ inline void pe_put32(uint8_t* o, uint32_t v) { o[0] = (uint8_t)(v >> 24); o[1] = (uint8_t)(v >> 16); o[2] = (uint8_t)(v >> 8); o[3] = (uint8_t)v; }
 
 __global__ __launch_bounds__(PE_SCAN_THREADS) void penc_scan_kernel(PEBatch bt) {
@@ -626,15 +608,15 @@ __global__ __launch_bounds__(PE_SCAN_THREADS) void penc_scan_kernel(PEBatch bt) 
         PEMeta m = {0, 0, 1, 0};
         if (i < nk) m = meta[i];
         long long v = i < nk ? 12 + (long long)m.len + (i == 0 ? 2 : 0) + (i == nk - 1 ? 9 : 0) : 0;
-        const long long tot = pe_scan1024(sh, v);
+        const long long tot = rtn_wg_exclusive_scan<PE_SCAN_THREADS>(sh, v);
         if (i < nk) off[i] = fpos + v;
         fpos += tot;
         long long a = i < nk ? ((long long)m.a + PE_ADLER - 1) % PE_ADLER : 0;
-        const long long atot = pe_scan1024(sh, a);
+        const long long atot = rtn_wg_exclusive_scan<PE_SCAN_THREADS>(sh, a);
         // joining (A1, B1) with (A2, B2) over len2 bytes: A = A1 + A2 - 1, B = B1 + B2 + len2 (A1 - 1)
         const long long raw = i < nk ? (pg.stream - (long long)i * PE_CHUNK < PE_CHUNK ? pg.stream - (long long)i * PE_CHUNK : PE_CHUNK) : 0;
         long long b = i < nk ? ((long long)m.b + raw * ((asum + a) % PE_ADLER)) % PE_ADLER : 0;
-        bsum += pe_scan1024(sh, b);
+        bsum += rtn_wg_exclusive_scan<PE_SCAN_THREADS>(sh, b);
         asum += atot;
     }
     if (threadIdx.x == 0) {
@@ -698,12 +680,8 @@ __global__ __launch_bounds__(PE_THREADS) void penc_copy_kernel(PEBatch bt) {
 
 int pe_check(rtn_handle_t h, int W, int H, int nc, const char* who) {
     if (pe_valid(W, H, nc)) return RTN_OK;
-    char buf[200];
-    if (nc != 1 && nc != 3) snprintf(buf, sizeof(buf), "%s: %d components (1 or 3)", who, nc);
-    else snprintf(buf, sizeof(buf), "%s: %d x %d page: sides must be >= 1 and height * (1 + width * components) < 2^31", who, W, H);
-    if (h) return rtn_fail(h, RTN_EINVAL, "%s", buf);
-    rtn_set_host_error(buf);
-    return RTN_EINVAL;
+    if (nc != 1 && nc != 3) return rtn_fail_host(h, RTN_EINVAL, "%s: %d components (1 or 3)", who, nc);
+    return rtn_fail_host(h, RTN_EINVAL, "%s: %d x %d page: sides must be >= 1 and height * (1 + width * components) < 2^31", who, W, H);
 }
 
 }  // namespace
@@ -746,13 +724,13 @@ extern "C" int rtn_png_encode(rtn_handle_t h, int n, const uint8_t* const* pages
     }
     if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_png_encode: workspace %zu < %zu bytes", workspace_bytes, need);
     long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += PE_BATCH) {
+    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
         PEBatch bt;
         memset(&bt, 0, sizeof(bt));
         bt.ws = static_cast<uint8_t*>(workspace);
         bt.out_bytes = reinterpret_cast<long long*>(out_bytes + i0);
         bt.status = status + i0;
-        bt.n = n - i0 < PE_BATCH ? n - i0 : PE_BATCH;
+        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
         for (int k = 0; k < bt.n; ++k) {
             const int i = i0 + k;
             const PELayout L = pe_layout(widths[i], heights[i], components[i]);

@@ -6,7 +6,7 @@ Same class names, constructor arguments and method names as the reference's Gene
   host   CSV rows, grouping / shuffling, annotation filtering, the 3x3 augmentation matrices and box corners (a few flops),
          parsing the page files (rtn_jpeg_inspect, rtn_png_inspect)
   device per batch: rtn_jpeg_decode of the baseline-JPEG pages and rtn_png_decode of the chunked-layout PNG pages
-         (read_images_bgr; other files are decoded by Pillow and uploaded)
+         (read_images_bgr, re-exported here from model/page_io.py; other files are decoded by Pillow and uploaded)
          per page: [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
          x/127.5-1 normalisation (preprocess_image 'custom_tf'), the INTER_CUBIC resize and the write into the zero-padded batch
          canvas of compute_inputs;  per batch: rtn_anchor_targets (anchors, IoU, assignment, box deltas) -> regression, labels
@@ -33,11 +33,13 @@ try:                                    # as a module of the package ...
     from .model import anchors as _anchors
     from .model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
     from .model.utils import compute_resize_scale
+    from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, _decode_batch  # noqa: F401
 except ImportError:                     # ... or top-level, with the package directory on sys.path like the reference's layout
     from model import Parameters, _rt
     from model import anchors as _anchors
     from model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
     from model.utils import compute_resize_scale
+    from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, _decode_batch  # noqa: F401
 
 L = _rt.L
 
@@ -50,149 +52,6 @@ class ImageRecord:
         self.name, self.image_path, self.width, self.height = name, image_path, int(width), int(height)
         self.boxes = np.asarray(boxes, np.float64).reshape(-1, 4)
         self.class_names = list(class_names)
-
-
-def read_image_bgr(path):
-    """cv2.imread(path): uint8 (H,W,3) in B,G,R order.  Decoded with Pillow (OpenCV is not a dependency of this package)."""
-    from PIL import Image
-    with Image.open(path) as im:
-        rgb = np.asarray(im.convert("RGB"))
-    return np.ascontiguousarray(rgb[:, :, ::-1])
-
-
-def jpeg_inspect(data):
-    """Parse one file's bytes with rtn_jpeg_inspect (host only) -> (JpegInfo, blob bytes) for a baseline JPEG the device decodes,
-    or (None, reason) for anything else."""
-    info = L.JpegInfo()
-    blob = np.empty(L.jpeg_blob_bound(len(data)), np.uint8)
-    rc = L.lib.rtn_jpeg_inspect(None, data, len(data), C.byref(info), blob.ctypes.data, blob.size)
-    if rc != 0:
-        return None, L.lib.rtn_last_error(None).decode("utf-8", "replace")
-    return info, blob[:info.blob_bytes]
-
-
-PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-
-
-def png_inspect(data):
-    """Parse one file's bytes with rtn_png_inspect (host only) -> (PngInfo, blob bytes) for a PNG of the chunked layout (DESIGN
-    §3.4d) that the device decodes, or (None, reason) for anything else."""
-    info = L.PngInfo()
-    blob = np.empty(L.png_blob_bound(len(data)), np.uint8)
-    rc = L.lib.rtn_png_inspect(None, data, len(data), C.byref(info), blob.ctypes.data, blob.size)
-    if rc != 0:
-        return None, L.lib.rtn_last_error(None).decode("utf-8", "replace")
-    return info, blob[:info.blob_bytes]
-
-
-def _decode_datas(datas, host_decode, device, handle, stream):
-    """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that rtn_jpeg_inspect or
-    rtn_png_inspect accepts is decoded on the device, each decoder running at most once, after ONE host->device copy of all
-    blobs; the status words of both are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
-    from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
-    (None where no device decoder took the file)."""
-    from PIL import Image
-    n_all = len(datas)
-    out = [None] * n_all
-    words = [None] * n_all
-    on_host = [i for i, d in enumerate(datas) if d is None]        # host_decode raises the file's exception below, in page order
-    limit = Image.MAX_IMAGE_PIXELS
-    # a file with the PNG signature fails rtn_jpeg_inspect at its first two bytes, before anything is written
-    cap = sum(L.png_blob_bound(len(d)) if d[:8] == PNG_SIGNATURE else L.jpeg_blob_bound(len(d)) for d in datas if d is not None)
-    with torch.cuda.stream(stream):
-        host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
-        hp = host.data_ptr()
-        pos = 0
-        kinds = {"jpeg": ([], [], []), "png": ([], [], [])}          # blob offsets, pages, file indices
-        for i, data in enumerate(datas):
-            if data is None:
-                continue
-            info, kind = L.JpegInfo(), "jpeg"
-            rc = L.lib.rtn_jpeg_inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
-            if rc != 0:
-                info, kind = L.PngInfo(), "png"
-                rc = L.lib.rtn_png_inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
-            if rc != 0 or (limit and info.width * info.height > limit):
-                on_host.append(i)
-                continue
-            offsets, pages, which = kinds[kind]
-            offsets.append(pos)
-            pos += info.blob_bytes
-            pages.append(torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=device))
-            which.append(i)
-        n = len(kinds["jpeg"][2]) + len(kinds["png"][2])
-        if n:
-            dev_blobs = host[:pos].to(device, non_blocking=True)
-            status = torch.empty(n, dtype=torch.int32, device=device)
-            handle.set_stream(stream.cuda_stream)
-            keep = []                                                  # the workspaces live until the stream is synchronised
-            first = 0
-            for kind, ws_fn, decode in (("jpeg", L.lib.rtn_jpeg_workspace_bytes, L.lib.rtn_jpeg_decode),
-                                        ("png", L.lib.rtn_png_decode_workspace_bytes, L.lib.rtn_png_decode)):
-                offsets, pages, which = kinds[kind]
-                m = len(which)
-                if not m:
-                    continue
-                offs = np.asarray(offsets, np.int64)
-                ws_bytes = int(ws_fn(m, hp, offs.ctypes.data))
-                ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
-                ptrs = (C.c_void_p * m)(*[p.data_ptr() for p in pages])
-                handle.check(decode(handle.raw, m, hp, dev_blobs.data_ptr(), offs.ctypes.data, ptrs,
-                                    status[first:first + m].data_ptr(), ws.data_ptr(), ws_bytes))
-                keep.append(ws)
-                first += m
-            st = torch.empty(n, dtype=torch.int32, pin_memory=True)
-            st.copy_(status, non_blocking=True)
-            stream.synchronize()
-            k = 0
-            for kind in ("jpeg", "png"):
-                _, pages, which = kinds[kind]
-                for page, i in zip(pages, which):
-                    words[i] = int(st[k])
-                    if words[i] == 0:
-                        out[i] = page
-                    else:
-                        on_host.append(i)
-                    k += 1
-        for i in sorted(on_host):
-            out[i] = torch.from_numpy(host_decode(i)).to(device)
-    return out, words
-
-
-def _decode_batch(paths, device, handle, stream):
-    """read_images_bgr on an explicit handle and stream (see _decode_datas); a file that cannot be read is left to
-    read_image_bgr, which raises the same exception."""
-    datas = []
-    for path in paths:
-        try:
-            with open(path, 'rb') as f:
-                datas.append(f.read())
-        except OSError:
-            datas.append(None)
-    return _decode_datas(datas, lambda i: read_image_bgr(paths[i]), device, handle, stream)[0]
-
-
-_readers = {}
-_readers_lock = threading.Lock()
-
-
-def read_images_bgr(paths, device=None):
-    """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits.  Baseline JPEGs (the files
-    cv2.imwrite writes for a .jpg name) and PNGs of the chunked layout of DESIGN §3.4d (the files write_images_bgr(png="device")
-    and preprocess_files(png="device") write) are decoded on the device, one batched call per format (csrc/rtn_jpeg.hip,
-    csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Every other file (any other
-    PNG among them: one zlib stream, Average or Paeth rows, 16-bit, palette, alpha, interlace, ancillary chunks), and any file
-    whose stream the device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset is converted once
-    with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises what read_image_bgr
-    raises."""
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    with _readers_lock:
-        h = _readers.get(dev.index)
-        if h is None:
-            h = _readers[dev.index] = L.Handle(dev.index)
-        return _decode_batch(list(paths), dev, h, torch.cuda.current_stream(dev))
 
 
 def _image_size(path):

@@ -1,0 +1,357 @@
+"""Page files, read and written as cv2.imread / cv2.imwrite do, with the four device codecs behind them: baseline
+JPEG and chunked-layout PNG pages are decoded and encoded on the device, every other file by Pillow.  csv_generator.py,
+model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
+import contextlib
+import ctypes as C
+import io
+import os
+import threading
+from collections import namedtuple
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import _rt
+
+L = _rt.L
+
+
+def _pillow_bgr(fp):
+    with Image.open(fp) as im:
+        rgb = np.asarray(im.convert("RGB"))
+    return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def read_image_bgr(path):
+    """cv2.imread(path): uint8 (H,W,3) in B,G,R order.  Decoded with Pillow (OpenCV is not a dependency of this package)."""
+    return _pillow_bgr(path)
+
+
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+# One record per format the device decodes, in the order _decode_datas tries them: JPEG first, PNG second.
+_Format = namedtuple("_Format", "name Info inspect blob_bound workspace_bytes decode")
+_FORMATS = (
+    _Format("jpeg", L.JpegInfo, L.lib.rtn_jpeg_inspect, L.jpeg_blob_bound, L.lib.rtn_jpeg_workspace_bytes, L.lib.rtn_jpeg_decode),
+    _Format("png", L.PngInfo, L.lib.rtn_png_inspect, L.png_blob_bound, L.lib.rtn_png_decode_workspace_bytes, L.lib.rtn_png_decode),
+)
+_JPEG, _PNG = _FORMATS
+
+
+def _inspect(fmt, data):
+    info = fmt.Info()
+    blob = np.empty(fmt.blob_bound(len(data)), np.uint8)
+    rc = fmt.inspect(None, data, len(data), C.byref(info), blob.ctypes.data, blob.size)
+    if rc != 0:
+        return None, L.lib.rtn_last_error(None).decode("utf-8", "replace")
+    return info, blob[:info.blob_bytes]
+
+
+def jpeg_inspect(data):
+    """Parse one file's bytes with rtn_jpeg_inspect (host only) -> (JpegInfo, blob bytes) for a baseline JPEG the device decodes,
+    or (None, reason) for anything else."""
+    return _inspect(_JPEG, data)
+
+
+def png_inspect(data):
+    """Parse one file's bytes with rtn_png_inspect (host only) -> (PngInfo, blob bytes) for a PNG of the chunked layout (DESIGN
+    §3.4d) that the device decodes, or (None, reason) for anything else."""
+    return _inspect(_PNG, data)
+
+
+def _decode_datas(datas, host_decode, device, handle, stream):
+    """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that rtn_jpeg_inspect or
+    rtn_png_inspect accepts is decoded on the device, each decoder running at most once, after ONE host->device copy of all
+    blobs; the status words of both are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
+    from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
+    (None where no device decoder took the file)."""
+    out, words = [None] * len(datas), [None] * len(datas)
+    on_host = [i for i, d in enumerate(datas) if d is None]        # host_decode raises the file's exception below, in page order
+    limit = Image.MAX_IMAGE_PIXELS
+    # a file with the PNG signature fails rtn_jpeg_inspect at its first two bytes, before anything is written
+    cap = sum((_PNG if d[:8] == PNG_SIGNATURE else _JPEG).blob_bound(len(d)) for d in datas if d is not None)
+    with torch.cuda.stream(stream):
+        host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
+        hp = host.data_ptr()
+        pos = 0
+        kinds = {fmt.name: ([], [], []) for fmt in _FORMATS}         # blob offsets, pages, file indices
+        for i, data in enumerate(datas):
+            if data is None:
+                continue
+            for fmt in _FORMATS:
+                info = fmt.Info()
+                rc = fmt.inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
+                if rc == 0:
+                    break
+            if rc != 0 or (limit and info.width * info.height > limit):
+                on_host.append(i)
+                continue
+            offsets, pages, which = kinds[fmt.name]
+            offsets.append(pos)
+            pos += info.blob_bytes
+            pages.append(torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=device))
+            which.append(i)
+        taken = [(page, i) for _, pages, which in kinds.values() for page, i in zip(pages, which)]      # in the order of the status words
+        n = len(taken)
+        if n:
+            dev_blobs = host[:pos].to(device, non_blocking=True)
+            status = torch.empty(n, dtype=torch.int32, device=device)
+            handle.set_stream(stream.cuda_stream)
+            keep = []                                                  # the workspaces live until the stream is synchronised
+            first = 0
+            for fmt in _FORMATS:
+                offsets, pages, which = kinds[fmt.name]
+                m = len(which)
+                if not m:
+                    continue
+                offs = np.asarray(offsets, np.int64)
+                ws_bytes = int(fmt.workspace_bytes(m, hp, offs.ctypes.data))
+                ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=device)
+                ptrs = (C.c_void_p * m)(*[p.data_ptr() for p in pages])
+                handle.check(fmt.decode(handle.raw, m, hp, dev_blobs.data_ptr(), offs.ctypes.data, ptrs,
+                                        status[first:first + m].data_ptr(), ws.data_ptr(), ws_bytes))
+                keep.append(ws)
+                first += m
+            st = torch.empty(n, dtype=torch.int32, pin_memory=True)
+            st.copy_(status, non_blocking=True)
+            stream.synchronize()
+            for k, (page, i) in enumerate(taken):
+                words[i] = int(st[k])
+                if words[i] == 0:
+                    out[i] = page
+                else:
+                    on_host.append(i)
+        for i in sorted(on_host):
+            out[i] = torch.from_numpy(host_decode(i)).to(device)
+    return out, words
+
+
+def _decode_batch(paths, device, handle, stream):
+    """read_images_bgr on an explicit handle and stream (see _decode_datas); a file that cannot be read is left to
+    read_image_bgr, which raises the same exception."""
+    datas = []
+    for path in paths:
+        try:
+            with open(path, 'rb') as f:
+                datas.append(f.read())
+        except OSError:
+            datas.append(None)
+    return _decode_datas(datas, lambda i: read_image_bgr(paths[i]), device, handle, stream)[0]
+
+
+_readers = {}
+_readers_lock = threading.Lock()
+
+
+@contextlib.contextmanager
+def _reader(device):
+    """`device` (None, an int or a torch.device) as an indexed CUDA device, and that device's reader handle: (device, Handle).
+    _readers_lock is held while the caller is inside the `with`, that is for the whole decode."""
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with _readers_lock:
+        h = _readers.get(dev.index)
+        if h is None:
+            h = _readers[dev.index] = L.Handle(dev.index)
+        yield dev, h
+
+
+def read_images_bgr(paths, device=None):
+    """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits.  Baseline JPEGs (the files
+    cv2.imwrite writes for a .jpg name) and PNGs of the chunked layout of DESIGN §3.4d (the files write_images_bgr(png="device")
+    and preprocess_files(png="device") write) are decoded on the device, one batched call per format (csrc/rtn_jpeg.hip,
+    csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Every other file (any other
+    PNG among them: one zlib stream, Average or Paeth rows, 16-bit, palette, alpha, interlace, ancillary chunks), and any file
+    whose stream the device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset is converted once
+    with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises what read_image_bgr
+    raises."""
+    with _reader(device) as (dev, h):
+        return _decode_batch(list(paths), dev, h, torch.cuda.current_stream(dev))
+
+
+def decode_png_bgr(files, device=None, return_status=False):
+    """The pages of PNG files held in memory (list of bytes) as CUDA uint8 (H,W,3) B,G,R tensors with the bits Pillow gives:
+    the counterpart of encode_png_bgr, on read_images_bgr's path.  Files of the chunked layout are decoded in one
+    batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip); a file that is not in the layout, or that the device
+    flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
+    device's status word for file i (0 = the device's page was kept) or None where the device did not take the file."""
+    files = [bytes(f) for f in files]
+    with _reader(device) as (dev, h):
+        pages, words = _decode_datas(files, lambda i: _pillow_bgr(io.BytesIO(files[i])), dev, h, torch.cuda.current_stream(dev))
+    return (pages, words) if return_status else pages
+
+
+def write_image(path, image):
+    """cv2.imwrite of a uint8 (H,W[,3]) array whose channels the caller treats in OpenCV's B,G,R order."""
+    a = np.ascontiguousarray(image)
+    Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(path)
+
+
+JPEG_EXTENSIONS = ('.jpg', '.jpeg', '.jpe')
+JPEG_MAX_SIDE = 65500                                   # libjpeg's JPEG_MAX_DIMENSION
+
+
+def _check_page(i, p):
+    """(H, W, components) of one page for encode_jpeg_bgr / encode_png_bgr, or ValueError."""
+    if not isinstance(p, (torch.Tensor, np.ndarray)):
+        p = np.asarray(p)
+    dtype, shape = p.dtype, tuple(p.shape)
+    if dtype != (torch.uint8 if isinstance(p, torch.Tensor) else np.uint8):
+        raise ValueError("page %d: uint8 pixels expected, got %s" % (i, dtype))
+    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
+        raise ValueError("page %d: shape (H,W,3) B,G,R or (H,W) gray expected, got %s" % (i, shape))
+    if not (1 <= shape[0] <= JPEG_MAX_SIDE and 1 <= shape[1] <= JPEG_MAX_SIDE):
+        raise ValueError("page %d: %dx%d: sides must be 1..%d (the image writers' limit, JPEG's)" % (i, shape[0], shape[1], JPEG_MAX_SIDE))
+    return shape[0], shape[1], 1 if len(shape) == 2 else 3
+
+
+def _check_settings(quality, subsampling, n=None):
+    """(qualities, subsamplings) as lists of n, from ints or per-page sequences; ValueError for anything else."""
+    def per_page(v, name):
+        if isinstance(v, (list, tuple, np.ndarray)):
+            v = list(v)
+            if n is not None and len(v) != n:
+                raise ValueError("%d %s values for %d pages" % (len(v), name, n))
+            return v
+        return [v] * (n or 0)
+    qs, ss = per_page(quality, "quality"), per_page(subsampling, "subsampling")
+    for q in (qs if isinstance(quality, (list, tuple, np.ndarray)) else [quality]):
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= 100:
+            raise ValueError("quality must be an integer 1..100, got %r" % (q,))
+    for s in (ss if isinstance(subsampling, (list, tuple, np.ndarray)) else [subsampling]):
+        if isinstance(s, bool) or s not in (0, 1, 2):
+            raise ValueError("subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r" % (s,))
+    return [int(q) for q in qs], [int(s) for s in ss]
+
+
+def _host_page(p):
+    return p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
+
+
+def _pillow_jpeg(page, quality, subsampling):
+    """The host path: Pillow's JPEG of a B,G,R (or gray) page."""
+    a = np.ascontiguousarray(_host_page(page))
+    b = io.BytesIO()
+    Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(b, "JPEG", quality=int(quality), subsampling=subsampling)
+    return b.getvalue()
+
+
+def _encode_batch(pages, dims, *, extra, bound, slot, workspace_bytes, encode):
+    """The body encode_jpeg_bgr and encode_png_bgr share: upload the pages, lay out one slot of slot(bound(i, W, H, components))
+    bytes per page, run `encode` once on the current stream (`extra`: the format's own per-page int32 arrays) and copy the n file
+    lengths back.  Returns (device buffer, slot offsets, host lengths, bounds); length 0 = flagged (status != 0), and what
+    happens to such a page is the caller's policy."""
+    n = len(pages)
+    h = _rt.handle()
+    dev = []
+    for p in pages:
+        t = p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
+        dev.append(t.to(device="cuda", non_blocking=True).contiguous())
+    W, H, Cc = [np.ascontiguousarray([d[k] for d in dims], np.int32) for k in (1, 0, 2)]
+    bounds = [int(bound(i, int(w), int(hh), int(c))) for i, (w, hh, c) in enumerate(zip(W, H, Cc))]
+    offs = np.zeros(n + 1, np.int64)
+    offs[1:] = np.cumsum([slot(b) for b in bounds])
+    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda")
+    lengths = torch.empty(n, dtype=torch.int64, device="cuda")
+    status = torch.empty(n, dtype=torch.int32, device="cuda")
+    whc = (W.ctypes.data, H.ctypes.data, Cc.ctypes.data)
+    wsb = int(workspace_bytes(n, *whc))
+    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in dev])
+    h.check(encode(h.raw, n, ptrs, *whc, *[e.ctypes.data for e in extra], out.data_ptr(), offs.ctypes.data, lengths.data_ptr(),
+                   status.data_ptr(), ws.data_ptr(), wsb))
+    nb = torch.empty(n, dtype=torch.int64, pin_memory=True)
+    nb.copy_(lengths, non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return out, offs, nb.numpy().copy(), bounds
+
+
+def _files_to_host(out, offs, nb, ok, n):
+    """The files of pages `ok` (slot offsets offs, lengths nb in the device buffer out) as bytes, through one copy of the used
+    bytes to pinned host memory; None for every other page."""
+    files = [None] * n
+    if ok:
+        used = torch.cat([out[int(offs[i]):int(offs[i]) + int(nb[i])] for i in ok]) if len(ok) > 1 else \
+            out[int(offs[ok[0]]):int(offs[ok[0]]) + int(nb[ok[0]])]
+        host = torch.empty(used.numel(), dtype=torch.uint8, pin_memory=True)
+        host.copy_(used, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        buf = host.numpy()
+        pos = 0
+        for i in ok:
+            files[i] = buf[pos:pos + int(nb[i])].tobytes()
+            pos += int(nb[i])
+    return files
+
+
+def encode_jpeg_bgr(pages, quality=95, subsampling=2):
+    """Baseline JPEG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), byte-identical to
+    Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling): one batched rtn_jpeg_encode on the current
+    stream (csrc/rtn_jpeg_enc.hip), one small copy of the n file lengths, then one copy of the used bytes to pinned host
+    memory.  A page the device flags is encoded by Pillow.  The defaults are cv2.imwrite's for a .jpg name; quality and
+    subsampling may also be sequences of one value per page.  Returns list[bytes]."""
+    pages = list(pages)
+    n = len(pages)
+    qs, ss = _check_settings(quality, subsampling, n)
+    dims = [_check_page(i, p) for i, p in enumerate(pages)]
+    if n == 0:
+        return []
+    S, Q = np.ascontiguousarray(ss, np.int32), np.ascontiguousarray(qs, np.int32)
+    out, offs, nb, _ = _encode_batch(
+        pages, dims, extra=(S, Q), encode=L.lib.rtn_jpeg_encode,
+        bound=lambda i, w, hh, c: L.lib.rtn_jpeg_encode_bound(w, hh, c, ss[i]), slot=lambda b: b,
+        workspace_bytes=lambda m, w, hh, c: L.lib.rtn_jpeg_encode_workspace_bytes(m, w, hh, c, S.ctypes.data))
+    files = _files_to_host(out, offs, nb, [i for i in range(n) if nb[i] > 0], n)
+    return [f if f is not None else _pillow_jpeg(pages[i], qs[i], ss[i]) for i, f in enumerate(files)]
+
+
+def encode_png_bgr(pages):
+    """PNG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), lossless, in the chunked layout of
+    DESIGN §3.4d that every PNG reader reads: one batched rtn_png_encode on the current stream (csrc/rtn_png_enc.hip), one small
+    copy of the n file lengths, then one copy of the used bytes to pinned host memory.  There is no host path: a valid page
+    always fits its slot (rtn_png_encode_bound).  Returns list[bytes]."""
+    pages = list(pages)
+    n = len(pages)
+    dims = [_check_page(i, p) for i, p in enumerate(pages)]
+    if n == 0:
+        return []
+
+    def bound(i, w, hh, c):
+        b = L.lib.rtn_png_encode_bound(w, hh, c)
+        if b == 0:
+            raise ValueError("page %d: %dx%d is too large for one PNG stream" % (i, hh, w))
+        return b
+
+    out, offs, nb, bounds = _encode_batch(pages, dims, extra=(), encode=L.lib.rtn_png_encode, bound=bound, slot=lambda b: (b + 255) & ~255,
+                                          workspace_bytes=L.lib.rtn_png_encode_workspace_bytes)
+    if not all(0 < int(nb[i]) <= bounds[i] for i in range(n)):
+        raise RuntimeError("rtn_png_encode: file lengths %s outside (0, bound]" % nb.tolist())
+    return _files_to_host(out, offs, nb, list(range(n)), n)
+
+
+def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
+    """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
+    .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged.
+    png="device" sends the .png files through one encode_png_bgr call instead (lossless, other bytes than write_image's);
+    png="host" (the default) leaves them with write_image."""
+    paths, pages = list(paths), list(pages)
+    if png not in ("host", "device"):
+        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
+    if len(paths) != len(pages):
+        raise ValueError("%d paths for %d pages" % (len(paths), len(pages)))
+    qs, ss = _check_settings(quality, subsampling, len(pages))
+    for i, p in enumerate(pages):
+        _check_page(i, p)
+    ext = [os.path.splitext(str(path))[1].lower() for path in paths]
+    jpg = [i for i, e in enumerate(ext) if e in JPEG_EXTENSIONS]
+    dpng = [i for i, e in enumerate(ext) if e == ".png"] if png == "device" else []
+    for i, data in zip(jpg, encode_jpeg_bgr([pages[i] for i in jpg], quality=[qs[i] for i in jpg], subsampling=[ss[i] for i in jpg])):
+        with open(paths[i], 'wb') as f:
+            f.write(data)
+    for i, data in zip(dpng, encode_png_bgr([pages[i] for i in dpng])):
+        with open(paths[i], 'wb') as f:
+            f.write(data)
+    for i in sorted(set(range(len(paths))) - set(jpg) - set(dpng)):
+        write_image(paths[i], _host_page(pages[i]))

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _rt
+from .page_io import read_images_bgr, write_images_bgr
 
 L = _rt.L
 
@@ -34,14 +35,12 @@ def preprocess_pages(pages, return_binary=False):
 
 
 def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
-    """DetectTablesUtils.preProcessSampleImages / preProcessTrainValImages as a batch: read every page (csv_generator.read_images_bgr:
+    """DetectTablesUtils.preProcessSampleImages / preProcessTrainValImages as a batch: read every page (page_io.read_images_bgr:
     baseline JPEGs decoded on the device), run rtn_preprocess_dt3 on the device (one call per page size), and write the distance
-    maps (model.utils.write_images_bgr: .jpg / .jpeg / .jpe names encoded on the device at `quality`, 4:2:0, other names through
-    write_image; png="device" encodes the .png names on the device too, model.utils.encode_png_bgr).  On the JPEG -> JPEG path, and
+    maps (page_io.write_images_bgr: .jpg / .jpeg / .jpe names encoded on the device at `quality`, 4:2:0, other names through
+    write_image; png="device" encodes the .png names on the device too, page_io.encode_png_bgr).  On the JPEG -> JPEG path, and
     with png="device" on the JPEG -> PNG and PNG -> PNG paths, the processed pixels never come to the host.  A page wider than
     rtn_preprocess_dt3 takes raises what preprocess_pages raises for it."""
-    import importlib
-    from .utils import write_images_bgr
     src_paths, dst_paths = list(src_paths), list(dst_paths)
     if png not in ("host", "device"):
         raise ValueError("png must be 'host' or 'device', got %r" % (png,))
@@ -49,7 +48,6 @@ def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
         raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
     if not src_paths:
         return
-    read_images_bgr = importlib.import_module(_rt._pkg.__name__ + ".csv_generator").read_images_bgr
     pages = read_images_bgr(src_paths)
     h = _rt.handle()
     groups = {}

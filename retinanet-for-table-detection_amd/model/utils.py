@@ -6,6 +6,7 @@ import torch
 
 from . import _rt
 from .Parameters import image_scaling_factor, image_subtraction_factor
+from .page_io import write_image, write_images_bgr, encode_jpeg_bgr, encode_png_bgr, decode_png_bgr, JPEG_EXTENSIONS  # noqa: F401
 
 L = _rt.L
 
@@ -210,222 +211,6 @@ def draw_annotations(image, annotations, color=(0, 255, 0), label_to_name=None):
         c = color if color is not None else label_color(label)
         draw_caption(image, annotations['bboxes'][i], '{}'.format(label_to_name(label) if label_to_name else label))
         draw_box(image, annotations['bboxes'][i], color=c)
-
-
-def write_image(path, image):
-    """cv2.imwrite of a uint8 (H,W[,3]) array whose channels the caller treats in OpenCV's B,G,R order."""
-    from PIL import Image
-    a = np.ascontiguousarray(image)
-    Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(path)
-
-
-JPEG_EXTENSIONS = ('.jpg', '.jpeg', '.jpe')
-JPEG_MAX_SIDE = 65500                                   # libjpeg's JPEG_MAX_DIMENSION
-
-
-def _check_page(i, p):
-    """(H, W, components) of one page for encode_jpeg_bgr / encode_png_bgr, or ValueError."""
-    if not isinstance(p, (torch.Tensor, np.ndarray)):
-        p = np.asarray(p)
-    dtype, shape = p.dtype, tuple(p.shape)
-    if dtype != (torch.uint8 if isinstance(p, torch.Tensor) else np.uint8):
-        raise ValueError("page %d: uint8 pixels expected, got %s" % (i, dtype))
-    if not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
-        raise ValueError("page %d: shape (H,W,3) B,G,R or (H,W) gray expected, got %s" % (i, shape))
-    if not (1 <= shape[0] <= JPEG_MAX_SIDE and 1 <= shape[1] <= JPEG_MAX_SIDE):
-        raise ValueError("page %d: %dx%d: sides must be 1..%d (the image writers' limit, JPEG's)" % (i, shape[0], shape[1], JPEG_MAX_SIDE))
-    return shape[0], shape[1], 1 if len(shape) == 2 else 3
-
-
-def _check_settings(quality, subsampling, n=None):
-    """(qualities, subsamplings) as lists of n, from ints or per-page sequences; ValueError for anything else."""
-    def per_page(v, name):
-        if isinstance(v, (list, tuple, np.ndarray)):
-            v = list(v)
-            if n is not None and len(v) != n:
-                raise ValueError("%d %s values for %d pages" % (len(v), name, n))
-            return v
-        return [v] * (n or 0)
-    qs, ss = per_page(quality, "quality"), per_page(subsampling, "subsampling")
-    for q in (qs if isinstance(quality, (list, tuple, np.ndarray)) else [quality]):
-        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 1 <= q <= 100:
-            raise ValueError("quality must be an integer 1..100, got %r" % (q,))
-    for s in (ss if isinstance(subsampling, (list, tuple, np.ndarray)) else [subsampling]):
-        if isinstance(s, bool) or s not in (0, 1, 2):
-            raise ValueError("subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r" % (s,))
-    return [int(q) for q in qs], [int(s) for s in ss]
-
-
-def _host_page(p):
-    return p.cpu().numpy() if isinstance(p, torch.Tensor) else np.asarray(p)
-
-
-def _pillow_jpeg(page, quality, subsampling):
-    """The host path: Pillow's JPEG of a B,G,R (or gray) page."""
-    import io
-    from PIL import Image
-    a = np.ascontiguousarray(_host_page(page))
-    b = io.BytesIO()
-    Image.fromarray(a[:, :, ::-1] if a.ndim == 3 else a).save(b, "JPEG", quality=int(quality), subsampling=subsampling)
-    return b.getvalue()
-
-
-def _files_to_host(out, offs, nb, ok, n):
-    """The files of pages `ok` (slot offsets offs, lengths nb in the device buffer out) as bytes, through one copy of the used
-    bytes to pinned host memory; None for every other page."""
-    files = [None] * n
-    if ok:
-        used = torch.cat([out[int(offs[i]):int(offs[i]) + int(nb[i])] for i in ok]) if len(ok) > 1 else \
-            out[int(offs[ok[0]]):int(offs[ok[0]]) + int(nb[ok[0]])]
-        host = torch.empty(used.numel(), dtype=torch.uint8, pin_memory=True)
-        host.copy_(used, non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        buf = host.numpy()
-        pos = 0
-        for i in ok:
-            files[i] = buf[pos:pos + int(nb[i])].tobytes()
-            pos += int(nb[i])
-    return files
-
-
-def encode_jpeg_bgr(pages, quality=95, subsampling=2):
-    """Baseline JPEG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), byte-identical to
-    Image.fromarray(rgb).save(f, "JPEG", quality=quality, subsampling=subsampling): one batched rtn_jpeg_encode on the current
-    stream (csrc/rtn_jpeg_enc.hip), one small copy of the n file lengths, then one copy of the used bytes to pinned host
-    memory.  A page the device flags is encoded by Pillow.  The defaults are cv2.imwrite's for a .jpg name; quality and
-    subsampling may also be sequences of one value per page.  Returns list[bytes]."""
-    import ctypes as C
-    pages = list(pages)
-    n = len(pages)
-    qs, ss = _check_settings(quality, subsampling, n)
-    dims = [_check_page(i, p) for i, p in enumerate(pages)]
-    if n == 0:
-        return []
-    h = _rt.handle()
-    dev = []
-    for p in pages:
-        t = p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
-        dev.append(t.to(device="cuda", non_blocking=True).contiguous())
-    arr = lambda v: np.ascontiguousarray(v, np.int32)                    # noqa: E731
-    H, W, Cc = arr([d[0] for d in dims]), arr([d[1] for d in dims]), arr([d[2] for d in dims])
-    S, Q = arr(ss), arr(qs)
-    offs = np.zeros(n + 1, np.int64)
-    offs[1:] = np.cumsum([L.lib.rtn_jpeg_encode_bound(int(w), int(hh), int(c), int(s)) for w, hh, c, s in zip(W, H, Cc, S)])
-    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    lengths = torch.empty(n, dtype=torch.int64, device="cuda")
-    status = torch.empty(n, dtype=torch.int32, device="cuda")
-    wsb = int(L.lib.rtn_jpeg_encode_workspace_bytes(n, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, S.ctypes.data))
-    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in dev])
-    h.check(L.lib.rtn_jpeg_encode(h.raw, n, ptrs, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, S.ctypes.data, Q.ctypes.data,
-                                  out.data_ptr(), offs.ctypes.data, lengths.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb))
-    stream = torch.cuda.current_stream()
-    nb = torch.empty(n, dtype=torch.int64, pin_memory=True)
-    nb.copy_(lengths, non_blocking=True)
-    stream.synchronize()
-    nb = nb.numpy().copy()                                              # 0 = flagged (status != 0)
-    ok = [i for i in range(n) if nb[i] > 0]
-    files = _files_to_host(out, offs, nb, ok, n)
-    for i in range(n):
-        if files[i] is None:
-            files[i] = _pillow_jpeg(pages[i], qs[i], ss[i])
-    return files
-
-
-def encode_png_bgr(pages):
-    """PNG files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), lossless, in the chunked layout of
-    DESIGN §3.4d that every PNG reader reads: one batched rtn_png_encode on the current stream (csrc/rtn_png_enc.hip), one small
-    copy of the n file lengths, then one copy of the used bytes to pinned host memory.  There is no host path: a valid page
-    always fits its slot (rtn_png_encode_bound).  Returns list[bytes]."""
-    import ctypes as C
-    pages = list(pages)
-    n = len(pages)
-    dims = [_check_page(i, p) for i, p in enumerate(pages)]
-    if n == 0:
-        return []
-    h = _rt.handle()
-    dev = []
-    for p in pages:
-        t = p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p))
-        dev.append(t.to(device="cuda", non_blocking=True).contiguous())
-    arr = lambda v: np.ascontiguousarray(v, np.int32)                    # noqa: E731
-    H, W, Cc = arr([d[0] for d in dims]), arr([d[1] for d in dims]), arr([d[2] for d in dims])
-    bounds = [int(L.lib.rtn_png_encode_bound(int(w), int(hh), int(c))) for w, hh, c in zip(W, H, Cc)]
-    for i, b in enumerate(bounds):
-        if b == 0:
-            raise ValueError("page %d: %dx%d is too large for one PNG stream" % (i, H[i], W[i]))
-    offs = np.zeros(n + 1, np.int64)
-    offs[1:] = np.cumsum([(b + 255) & ~255 for b in bounds])
-    out = torch.empty(int(offs[-1]), dtype=torch.uint8, device="cuda")
-    lengths = torch.empty(n, dtype=torch.int64, device="cuda")
-    status = torch.empty(n, dtype=torch.int32, device="cuda")
-    wsb = int(L.lib.rtn_png_encode_workspace_bytes(n, W.ctypes.data, H.ctypes.data, Cc.ctypes.data))
-    ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in dev])
-    h.check(L.lib.rtn_png_encode(h.raw, n, ptrs, W.ctypes.data, H.ctypes.data, Cc.ctypes.data, out.data_ptr(), offs.ctypes.data,
-                                 lengths.data_ptr(), status.data_ptr(), ws.data_ptr(), wsb))
-    nb = torch.empty(n, dtype=torch.int64, pin_memory=True)
-    nb.copy_(lengths, non_blocking=True)
-    torch.cuda.current_stream().synchronize()
-    nb = nb.numpy().copy()
-    if not all(0 < int(nb[i]) <= bounds[i] for i in range(n)):
-        raise RuntimeError("rtn_png_encode: file lengths %s outside (0, bound]" % nb.tolist())
-    return _files_to_host(out, offs, nb, list(range(n)), n)
-
-
-def decode_png_bgr(files, device=None, return_status=False):
-    """The pages of PNG files held in memory (list of bytes) as CUDA uint8 (H,W,3) B,G,R tensors with the bits Pillow gives:
-    the counterpart of encode_png_bgr, on read_images_bgr's path.  Files of the chunked layout are decoded in one
-    batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip); a file that is not in the layout, or that the device
-    flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
-    device's status word for file i (0 = the device's page was kept) or None where the device did not take the file."""
-    import importlib
-    import io
-    from PIL import Image
-    CG = importlib.import_module(_rt._pkg.__name__ + ".csv_generator")
-    files = [bytes(f) for f in files]
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device or "cuda")
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-    def host_decode(i):
-        with Image.open(io.BytesIO(files[i])) as im:
-            rgb = np.asarray(im.convert("RGB"))
-        return np.ascontiguousarray(rgb[:, :, ::-1])
-
-    with CG._readers_lock:
-        h = CG._readers.get(dev.index)
-        if h is None:
-            h = CG._readers[dev.index] = L.Handle(dev.index)
-        pages, words = CG._decode_datas(files, host_decode, dev, h, torch.cuda.current_stream(dev))
-    return (pages, words) if return_status else pages
-
-
-def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
-    """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
-    .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged.
-    png="device" sends the .png files through one encode_png_bgr call instead (lossless, other bytes than write_image's);
-    png="host" (the default) leaves them with write_image."""
-    import os
-    paths, pages = list(paths), list(pages)
-    if png not in ("host", "device"):
-        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
-    if len(paths) != len(pages):
-        raise ValueError("%d paths for %d pages" % (len(paths), len(pages)))
-    qs, ss = _check_settings(quality, subsampling, len(pages))
-    for i, p in enumerate(pages):
-        _check_page(i, p)
-    ext = [os.path.splitext(str(path))[1].lower() for path in paths]
-    jpg = [i for i, e in enumerate(ext) if e in JPEG_EXTENSIONS]
-    dpng = [i for i, e in enumerate(ext) if e == ".png"] if png == "device" else []
-    for i, data in zip(jpg, encode_jpeg_bgr([pages[i] for i in jpg], quality=[qs[i] for i in jpg], subsampling=[ss[i] for i in jpg])):
-        with open(paths[i], 'wb') as f:
-            f.write(data)
-    for i, data in zip(dpng, encode_png_bgr([pages[i] for i in dpng])):
-        with open(paths[i], 'wb') as f:
-            f.write(data)
-    for i in sorted(set(range(len(paths))) - set(jpg) - set(dpng)):
-        write_image(paths[i], _host_page(pages[i]))
 
 
 def render_detections(processed_page, draw, boxes, scores, labels, image_scale, result_dir, image_name, labels_to_names=None,

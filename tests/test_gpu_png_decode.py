@@ -44,6 +44,11 @@ def P():
 
 
 @pytest.fixture(scope="module")
+def PIO():
+    return importlib.import_module("retinanet-for-table-detection_amd.model.page_io")
+
+
+@pytest.fixture(scope="module")
 def fixtures():
     """The three size fixtures, B,G,R (or gray): Pillow's decode of the golden JPEGs."""
     m = np.asarray(Image.open(os.path.join(GOLDEN, "sample_0717_023.jpg")).convert("RGB"))
@@ -210,12 +215,12 @@ def test_device_decode_is_bit_identical(CG, corpus):
         assert np.array_equal(g.cpu().numpy(), w), p
 
 
-def test_device_path_is_taken(CG, U, corpus, monkeypatch):
+def test_device_path_is_taken(CG, U, PIO, corpus, monkeypatch):
     paths, files, pages = corpus
 
     def no_host(path):
         raise AssertionError("host decode of %s" % path)
-    monkeypatch.setattr(CG, "read_image_bgr", no_host)
+    monkeypatch.setattr(PIO, "read_image_bgr", no_host)
     monkeypatch.setattr(Image, "open", no_host)
     out = CG.read_images_bgr(paths)
     assert len(out) == len(paths) and all(t.is_cuda for t in out)
@@ -247,6 +252,30 @@ def test_round_trip_with_the_device_encoder(U, fixtures):
         (alone,) = U.decode_png_bgr([f])
         assert torch.equal(alone, b)
     assert U.decode_png_bgr([]) == []
+
+
+def test_both_entry_points_share_one_reader(U, CG, PIO, tmp_path, monkeypatch):
+    """read_images_bgr (files) and decode_png_bgr (bytes) take the same per-device handle of page_io._readers: whichever runs
+    first creates it, the other finds it, and both give Pillow's pixels."""
+    rng = np.random.RandomState(11)
+    pages = [rng.randint(0, 256, (7, 5)).astype(np.uint8), rng.randint(0, 256, (33, 40, 3)).astype(np.uint8)]   # 5x7 gray, 40x33 colour
+    paths = [str(tmp_path / ("p%d.png" % i)) for i in range(len(pages))]
+    U.write_images_bgr(paths, pages, png="device")
+    files = [open(p, "rb").read() for p in paths]
+    want = [host_pixels(f) for f in files]
+    for w, page in zip(want, pages):
+        assert np.array_equal(w, bgr3(page))
+    dev = torch.cuda.current_device()
+    monkeypatch.setattr(PIO, "_readers", {})
+    from_bytes, status = U.decode_png_bgr(files, return_status=True)
+    assert status == [0, 0] and list(PIO._readers) == [dev]
+    h = PIO._readers[dev]
+    from_files = CG.read_images_bgr(paths)
+    assert list(PIO._readers) == [dev] and PIO._readers[dev] is h
+    for w, a, b in zip(want, from_bytes, from_files):
+        assert a.is_cuda and b.is_cuda and np.array_equal(a.cpu().numpy(), w) and np.array_equal(b.cpu().numpy(), w)
+    torch.cuda.synchronize()
+    h.close()
 
 
 def raw_decode(U, CG, handle, data):
@@ -434,7 +463,7 @@ def generator_batches(CG, csvf, d, augment):
 
 
 @pytest.mark.parametrize("augment", [False, True])
-def test_generator_over_layout_png_pages(CG, tmp_path, monkeypatch, augment):
+def test_generator_over_layout_png_pages(CG, PIO, tmp_path, monkeypatch, augment):
     csvf, d = make_png_dataset(tmp_path)
     device = generator_batches(CG, csvf, d, augment)
     with monkeypatch.context() as m:                                     # the same dataset decoded by read_image_bgr, page by page
@@ -447,14 +476,15 @@ def test_generator_over_layout_png_pages(CG, tmp_path, monkeypatch, augment):
 
     def no_host(path):
         raise AssertionError("host decode of %s" % path)
-    monkeypatch.setattr(CG, "read_image_bgr", no_host)
+    monkeypatch.setattr(PIO, "read_image_bgr", no_host)
+    monkeypatch.setattr(CG, "read_image_bgr", no_host)          # CSVGenerator.load_image looks the name up there
     again = generator_batches(CG, csvf, d, augment)
     for a, b in zip(again, host):
         for x, y in zip(a, b):
             assert np.array_equal(x, y)
 
 
-def test_preprocess_files_from_layout_png(U, CG, P, fixtures, tmp_path, monkeypatch):
+def test_preprocess_files_from_layout_png(PIO, P, fixtures, tmp_path, monkeypatch):
     pages = [np.ascontiguousarray(fixtures["page"][200:500, 100:340]), np.ascontiguousarray(fixtures["page"][900:1160, 600:1010]),
              np.ascontiguousarray(fixtures["map"][:260, :410])]
     src = []
@@ -467,8 +497,8 @@ def test_preprocess_files_from_layout_png(U, CG, P, fixtures, tmp_path, monkeypa
 
     def no_host(*a, **k):
         raise AssertionError("host image reader or writer")
-    monkeypatch.setattr(CG, "read_image_bgr", no_host)
-    monkeypatch.setattr(U, "write_image", no_host)
+    monkeypatch.setattr(PIO, "read_image_bgr", no_host)
+    monkeypatch.setattr(PIO, "write_image", no_host)
     P.preprocess_files(src, dst, png="device")
     for d, w in zip(dst, want):
         R.check_file(open(d, "rb").read(), w)

@@ -45,6 +45,11 @@ def P():
 
 
 @pytest.fixture(scope="module")
+def PIO():
+    return importlib.import_module("retinanet-for-table-detection_amd.model.page_io")
+
+
+@pytest.fixture(scope="module")
 def fixtures():
     """The three size fixtures, B,G,R (or gray): Pillow's decode of the golden JPEGs."""
     m = np.asarray(Image.open(os.path.join(GOLDEN, "sample_0717_023.jpg")).convert("RGB"))
@@ -133,7 +138,7 @@ def test_deterministic_and_input_kinds_agree(U, fixtures):
     assert U.encode_png_bgr([]) == []
 
 
-def test_no_host_fallback(U, fixtures, tmp_path, monkeypatch):
+def test_no_host_fallback(U, PIO, fixtures, tmp_path, monkeypatch):
     rng = np.random.RandomState(5)
     pages = [fixtures["map"][:300, :300], rng.randint(0, 256, (64, 64, 3)).astype(np.uint8), fixtures["gray"][:200, :500],
              np.zeros((1, 1, 3), np.uint8)]
@@ -142,7 +147,7 @@ def test_no_host_fallback(U, fixtures, tmp_path, monkeypatch):
 
     def no_host(*a, **k):
         raise AssertionError("host image writer")
-    monkeypatch.setattr(U, "write_image", no_host)
+    monkeypatch.setattr(PIO, "write_image", no_host)
     monkeypatch.setitem(Image.SAVE, "PNG", no_host)
     U.write_images_bgr(paths, [torch.from_numpy(p).cuda() for p in pages], png="device")
     for path, p in zip(paths, pages):
@@ -173,7 +178,7 @@ def test_default_routing_is_unchanged(U, CG, P, fixtures, tmp_path):
     assert not os.path.exists(tmp_path / "e.png")
 
 
-def test_preprocess_files_device_png(U, CG, P, fixtures, tmp_path, monkeypatch):
+def test_preprocess_files_device_png(PIO, CG, P, fixtures, tmp_path, monkeypatch):
     src = [os.path.join(GOLDEN, "sample_0717_023_orig.jpg"), os.path.join(GOLDEN, "sample_0717_023.jpg")]
     for i, crop in enumerate([fixtures["page"][200:500, 100:340], fixtures["map"][:260, :410], fixtures["page"][900:1160, 600:1010]]):
         p = tmp_path / ("src%d.png" % i)
@@ -184,7 +189,7 @@ def test_preprocess_files_device_png(U, CG, P, fixtures, tmp_path, monkeypatch):
     src.append(str(p))
     dst = [str(tmp_path / n) for n in ("o0.png", "o1.png", "o2.png", "o3.jpg", "o4.png", "o5.jpg")]
     want = [P.preprocess_pages(CG.read_image_bgr(s)) for s in src]
-    monkeypatch.setattr(U, "write_image", lambda *a, **k: (_ for _ in ()).throw(AssertionError("host image writer")))
+    monkeypatch.setattr(PIO, "write_image", lambda *a, **k: (_ for _ in ()).throw(AssertionError("host image writer")))
     P.preprocess_files(src, dst, png="device")
     for s, d, w in zip(src, dst, want):
         data = open(d, "rb").read()

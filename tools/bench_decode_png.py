@@ -1,6 +1,6 @@
 """Measure the device PNG decoder (csrc/rtn_png_dec.hip) on sample-sized pages: the 2200x1712 distance map
 (tests/golden/sample_0717_023.jpg, the file a training run reads), the page itself, or the gray page, written 16 times as PNG of
-the chunked layout by the device encoder (model.utils.encode_png_bgr).
+the chunked layout by the device encoder (model.page_io.encode_png_bgr).
 
   python tools/bench_decode_png.py [--batch 16] [--iters 10] [--host-pages 4] [--content map|page|gray|all]
 
@@ -33,7 +33,7 @@ sys.path.insert(0, ROOT)
 PKG = "retinanet-for-table-detection_amd"
 CG = importlib.import_module(PKG + ".csv_generator")
 L = importlib.import_module(PKG + "._lib")
-U = importlib.import_module(PKG + ".model.utils")
+PIO = importlib.import_module(PKG + ".model.page_io")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
@@ -63,7 +63,7 @@ def bench(content, a):
     n = a.batch
     dev = torch.device("cuda", 0)
     page = load(content)
-    (data,) = U.encode_png_bgr([page])
+    (data,) = PIO.encode_png_bgr([page])
     want = page if page.ndim == 3 else np.repeat(page[:, :, None], 3, axis=2)
     tmp = tempfile.mkdtemp(prefix="bench_decode_png_")
     paths = []
@@ -72,7 +72,7 @@ def bench(content, a):
         with open(p, "wb") as f:
             f.write(data)
         paths.append(p)
-    info, blob = CG.png_inspect(data)
+    info, blob = PIO.png_inspect(data)
     assert info is not None, blob
     print("== %s: %dx%d, %d component(s), file %d B, %d chunks, deflate payload %d B, blob %d B, workspace %.1f MB per page" %
           (content, info.width, info.height, info.components, len(data), info.chunks, info.payload_bytes, info.blob_bytes,
@@ -114,20 +114,20 @@ def bench(content, a):
 
     # (c) read_images_bgr, files to device pages
     for _ in range(2):
-        got = CG.read_images_bgr(paths)
+        got = PIO.read_images_bgr(paths)
     torch.cuda.synchronize()
     assert np.array_equal(got[0].cpu().numpy(), want)
 
     def read_all():
-        CG.read_images_bgr(paths)
+        PIO.read_images_bgr(paths)
         torch.cuda.synchronize()
     r_ms = times_ms(read_all, a.iters)
 
     # (d) Pillow, one thread
     p_ms = []
     if a.host_pages:
-        CG.read_image_bgr(paths[0])
-        p_ms = times_ms(lambda: CG.read_image_bgr(paths[0]), a.host_pages)
+        PIO.read_image_bgr(paths[0])
+        p_ms = times_ms(lambda: PIO.read_image_bgr(paths[0]), a.host_pages)
 
     # (e) one CSVGenerator batch from the files
     csvf = os.path.join(tmp, "train.csv")

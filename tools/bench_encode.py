@@ -7,7 +7,7 @@ Reports, device and host paths alternating inside every iteration, medians over 
   (1) GPU time of the five encode kernels per batch (events around rtn_jpeg_encode, pages resident on the device), and the
       achieved GB/s over the algorithmic bytes: pages read, coefficients written and read twice, the packed stream zeroed,
       written and read, the files written;
-  (2) wall time of model.utils.write_images_bgr for the 16 device pages (encode, length read-back, one copy, 16 file writes);
+  (2) wall time of model.page_io.write_images_bgr for the 16 device pages (encode, length read-back, one copy, 16 file writes);
   (3) the parent commit's path for the same files: Pillow save at the same quality and subsampling, one thread;
   (4) model.preprocess.preprocess_files of 16 JPEG pages (tests/golden/sample_0717_023_orig.jpg) against the parent's path:
       read_images_bgr + preprocess_pages + Pillow save.
@@ -33,9 +33,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PKG = "retinanet-for-table-detection_amd"
 L = importlib.import_module(PKG + "._lib")
-U = importlib.import_module(PKG + ".model.utils")
+PIO = importlib.import_module(PKG + ".model.page_io")
 P = importlib.import_module(PKG + ".model.preprocess")
-CG = importlib.import_module(PKG + ".csv_generator")
 Q, SS = 95, 2
 
 
@@ -112,7 +111,7 @@ def main():
     pre_ref = [os.path.join(tmp, "preref_%02d.jpg" % i) for i in range(n)]
 
     def parent_preprocess():
-        dp = CG.read_images_bgr(srcs)
+        dp = PIO.read_images_bgr(srcs)
         processed = P.preprocess_pages(torch.stack(dp).cpu().numpy())
         for p, d in zip(processed, pre_ref):
             pillow_save(d, p)
@@ -125,7 +124,7 @@ def main():
         ev[1].record()
         torch.cuda.synchronize()
         k = ev[0].elapsed_time(ev[1])
-        w = wall_ms(lambda: U.write_images_bgr(paths, pages))
+        w = wall_ms(lambda: PIO.write_images_bgr(paths, pages))
         p = wall_ms(lambda: [pillow_save(d, hp) for d, hp in zip(ref_paths, host_pages)])
         f = wall_ms(lambda: P.preprocess_files(srcs, pre_dst))
         r = wall_ms(parent_preprocess)

@@ -4,9 +4,9 @@
   python tools/bench_encode_png.py [--batch 16] [--iters 10] [--host-iters 3] [--content map|page]
 
 Reports medians and the min..max spread over the iterations after a warm-up, every path on the same machine:
-  (a) the parent commit's path for a .png name: model.utils.write_image (Pillow's default, compress level 6), one thread;
+  (a) the parent commit's path for a .png name: model.page_io.write_image (Pillow's default, compress level 6), one thread;
   (b) Pillow at compress_level=1, the fastest lossless setting a host user has;
-  (c) model.utils.write_images_bgr(png="device") for the device-resident pages (encode, length read-back, one copy, file writes),
+  (c) model.page_io.write_images_bgr(png="device") for the device-resident pages (encode, length read-back, one copy, file writes),
       and the GPU time of the four kernels alone (events around rtn_png_encode);
   (d) model.preprocess.preprocess_files of JPEG pages to .png names, png="host" against png="device";
 and the file sizes of (a), (b), (c).  The host paths take seconds per page, so they run --host-iters times.
@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PKG = "retinanet-for-table-detection_amd"
 L = importlib.import_module(PKG + "._lib")
-U = importlib.import_module(PKG + ".model.utils")
+PIO = importlib.import_module(PKG + ".model.page_io")
 P = importlib.import_module(PKG + ".model.preprocess")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -115,12 +115,12 @@ def main():
             ev[1].record()
             torch.cuda.synchronize()
             k = ev[0].elapsed_time(ev[1])
-            c = wall_ms(lambda: U.write_images_bgr(paths, pages, png="device"))
+            c = wall_ms(lambda: PIO.write_images_bgr(paths, pages, png="device"))
             pd = wall_ms(lambda: P.preprocess_files(srcs, pre_dev, png="device"))
             if it:
                 k_ms.append(k); c_ms.append(c); pd_ms.append(pd)
         if it <= a.host_iters and a.host_iters:
-            ta = wall_ms(lambda: [U.write_image(d, hp) for d, hp in zip(ref_paths, host_pages)])
+            ta = wall_ms(lambda: [PIO.write_image(d, hp) for d, hp in zip(ref_paths, host_pages)])
             tb = wall_ms(lambda: [Image.fromarray(hp[:, :, ::-1]).save(d, "PNG", compress_level=1) for d, hp in zip(ref_paths, host_pages)])
             ph = wall_ms(lambda: P.preprocess_files(srcs, pre_host))
             if it:
