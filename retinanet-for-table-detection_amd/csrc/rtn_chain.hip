@@ -22,7 +22,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned CH_OOB = 0xFFFF0000u;       // beyond every descriptor (< 2 GiB) even with the largest uniform offset added
 constexpr int IMG = 64 * 128;                  // one filter image: 64 rows x 128 B (64 K values), 16-byte slots XOR-swizzled by row & 7
@@ -47,10 +46,6 @@ __device__ __forceinline__ int perm_row(int rho) {     // MFMA row (16 f + 4 q +
 __device__ __forceinline__ float relu(float v) { return v > 0.f ? v : 0.f; }
 __device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
-
-// the store-data guard of rtn_bottleneck.hip (profiles/r3_store_hazard_isa.txt): the data registers of a 16-byte buffer store with
-// an SGPR offset stay live and unmodified for four wait states whatever the compiler schedules behind it
-#define CH_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
 
 // CM = mid / 64 (K images of branch2c), NCH = 4 mid / 64 (chunks), N3 = next / 64 (row images of the next branch2a),
 // PX = 16-pixel column fragments per wave, eight waves; DEPTH = chunks the shortcut fragments are requested ahead (the kernel moves
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(512) void chain1x1_kernel(const ChParams p) {
                                           pack2(relu(hi[0] + bf_lo(rv.z)), relu(hi[1] + bf_hi(rv.z))),
                                           pack2(relu(hi[2] + bf_lo(rv.w)), relu(hi[3] + bf_hi(rv.w)))};
                         if (!(dbg & 2)) __builtin_amdgcn_raw_buffer_store_b128(ov, o_rsrc, (int)xoff[u], g * 128 + s * 64, 0);
-                        CH_STORE_GUARD(ov)
+                        RTN_STORE_GUARD(ov)
                         xo[s][u] = __builtin_bit_cast(uint4, ov);
                     }
 #pragma unroll
@@ -219,7 +214,7 @@ __global__ __launch_bounds__(512) void chain1x1_kernel(const ChParams p) {
                     const u32x4 ov = {pack2(relu(lo[0]), relu(lo[1])), pack2(relu(lo[2]), relu(lo[3])),
                                       pack2(relu(hi[0]), relu(hi[1])), pack2(relu(hi[2]), relu(hi[3]))};
                     if (!(dbg & 32)) __builtin_amdgcn_raw_buffer_store_b128(ov, n_rsrc, (int)aoff[u], s * 64, 0);
-                    CH_STORE_GUARD(ov)
+                    RTN_STORE_GUARD(ov)
                 }
         }
     }

@@ -18,6 +18,7 @@
 // (identity or legacy-TF nearest upsample gather), ReLU / sigmoid fused.
 #include "rtn_internal.h"
 #include "rtn_device.h"
+#include "rtn_conv_epilogue.h"
 #include <cstdlib>
 
 namespace {
@@ -27,7 +28,6 @@ constexpr int NT = 256;
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;   // beyond every buffer: the hardware range check returns zeros
 
@@ -115,11 +115,6 @@ struct KParams {
     int korder_chunks, korder_kw;   // 256-row kernel: K-step visiting order (see KOrder in the kernel); {nkt, 1} = in order
 };
 
-__device__ __forceinline__ unsigned pack_bf16x2(float a, float b) {
-    bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-}
-
 // fp8 e4m3 x fp8 e4m3, K = 128 per instruction (twice the bf16 rate): a lane supplies 32 bytes of its row per operand.  Which 32 of
 // the row's 128 K positions a lane holds is free as long as A and B agree (the instruction pairs equal (lane group, byte) slots),
 // so the two 16-byte fragments are the ones the bf16 loop reads for ks = 0 and 1.  Block scales are 2^0 (E8M0 127).
@@ -130,13 +125,6 @@ __device__ __forceinline__ void mma_step_fp8(f32x4& acc, const uint4& a0, const 
     const i32x8 A = __builtin_shufflevector(__builtin_bit_cast(i32x4c, a0), __builtin_bit_cast(i32x4c, a1), 0, 1, 2, 3, 4, 5, 6, 7);
     const i32x8 B = __builtin_shufflevector(__builtin_bit_cast(i32x4c, b0), __builtin_bit_cast(i32x4c, b1), 0, 1, 2, 3, 4, 5, 6, 7);
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, B, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-}
-
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-    unsigned w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    return w;
 }
 
 template <int ES>
@@ -299,14 +287,8 @@ __device__ __forceinline__ void epilogue_finish8(const KParams& p, const KGroup&
     const long long oidx = (long long)r.b * G.out_img_stride + G.out_off + r.opix * p.out_ld + n;
     if constexpr (ES == 2) {
         if (p.out_fp8) {                               // bf16 layer feeding an fp8 layer: e4m3(clamp(y * out_scale)), vec_ok guaranteed
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float q = v[j] * p.out_scale;
-                v[j] = q > 448.f ? 448.f : (q < -448.f ? -448.f : q);
-            }
-            uint2 o;
-            o.x = pack_fp8x4(v[0], v[1], v[2], v[3]);
-            o.y = pack_fp8x4(v[4], v[5], v[6], v[7]);
+            const u32x2 q = epi_quant_fp8(v, p.out_scale);
+            const uint2 o = make_uint2(q.x, q.y);
             *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(G.out) + oidx) = o;
             return;
         }
@@ -324,10 +306,10 @@ __device__ __forceinline__ void epilogue_finish8(const KParams& p, const KGroup&
         unsigned short* op = reinterpret_cast<unsigned short*>(G.out) + oidx;
         if (p.vec_ok) {
             uint4 o;
-            o.x = pack_bf16x2(v[0], v[1]);
-            o.y = pack_bf16x2(v[2], v[3]);
-            o.z = pack_bf16x2(v[4], v[5]);
-            o.w = pack_bf16x2(v[6], v[7]);
+            o.x = pack2(v[0], v[1]);
+            o.y = pack2(v[2], v[3]);
+            o.z = pack2(v[4], v[5]);
+            o.w = pack2(v[6], v[7]);
             *reinterpret_cast<uint4*>(op) = o;
         } else {
             for (int j = 0; j < nvalid; ++j) {
@@ -348,21 +330,15 @@ __device__ __forceinline__ void epilogue_fp8(const KParams& p, const KGroup& G, 
     }
     const long long oidx = (long long)r.b * G.out_img_stride + G.out_off + r.opix * p.out_ld + n;
     if (p.out_fp8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float q = v[j] * p.out_scale;
-            v[j] = q > 448.f ? 448.f : (q < -448.f ? -448.f : q);
-        }
-        uint2 o;
-        o.x = pack_fp8x4(v[0], v[1], v[2], v[3]);
-        o.y = pack_fp8x4(v[4], v[5], v[6], v[7]);
+        const u32x2 q = epi_quant_fp8(v, p.out_scale);
+        const uint2 o = make_uint2(q.x, q.y);
         *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(G.out) + oidx) = o;
     } else {
         uint4 o;
-        o.x = pack_bf16x2(v[0], v[1]);
-        o.y = pack_bf16x2(v[2], v[3]);
-        o.z = pack_bf16x2(v[4], v[5]);
-        o.w = pack_bf16x2(v[6], v[7]);
+        o.x = pack2(v[0], v[1]);
+        o.y = pack2(v[2], v[3]);
+        o.z = pack2(v[4], v[5]);
+        o.w = pack2(v[6], v[7]);
         *reinterpret_cast<uint4*>(reinterpret_cast<unsigned short*>(G.out) + oidx) = o;
     }
 }

@@ -38,6 +38,7 @@
 // the sync block (first 4 KiB of the workspace) is zero before and after every launch.
 #include "rtn_internal.h"
 #include "rtn_device.h"
+#include "rtn_conv_epilogue.h"
 
 namespace {
 
@@ -55,8 +56,6 @@ __device__ unsigned long long g_g8_stamps[1024][8];
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 constexpr unsigned G8_OOB = 0xFFFF0000u;              // beyond every descriptor even with the largest uniform offset (K bytes) added
 constexpr int G8_THREADS = 512;
@@ -102,13 +101,6 @@ struct G8Params {
     unsigned* sk_flags;
 };
 constexpr int SK_ERR_WORD = 1023;
-
-// A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
-// them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
-// fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
-// inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
-// offset; tools/scan_store_hazard.py checks the built library.
-#define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
 
 // EPI: bit 0 = residual add (the `Add` closing a bottleneck block; accumulated gradient contributions in training), bit 1 = ReLU mask
 // of the tensor being differentiated (rtn_conv2d_dgrad): 16 bytes per lane and row, loaded one row fragment ahead of their use.
@@ -372,8 +364,7 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
             u += k1 - k0;
             constexpr unsigned SLOTS = MI * 4 * 2;                                 // 16-byte slots per thread of a partial tile
             constexpr unsigned SLAB = SLOTS * G8_THREADS * 16u;                    // bytes per workgroup
-            const __amdgpu_buffer_rsrc_t slab_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)p.sk_slab, 0, (int)__builtin_amdgcn_readfirstlane((int)p.sk_slab_bytes), 0x00020000);
+            const __amdgpu_buffer_rsrc_t slab_rsrc = epi_rsrc(p.sk_slab, p.sk_slab_bytes);
             if (k0 != 0) {
                 // ---- a tail / middle piece of the tile: publish the partial sums (write-through), then the flag
                 const unsigned base = (unsigned)Lw * SLAB + (unsigned)t * 16u;
@@ -381,14 +372,8 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        u32x4 o0, o1;
-                        o0.x = __float_as_uint(acc[i][0][r]); o0.y = __float_as_uint(acc[i][1][r]); o0.z = __float_as_uint(acc[i][2][r]); o0.w = __float_as_uint(acc[i][3][r]);
-                        o1.x = __float_as_uint(acc[i][4][r]); o1.y = __float_as_uint(acc[i][5][r]); o1.z = __float_as_uint(acc[i][6][r]); o1.w = __float_as_uint(acc[i][7][r]);
                         const unsigned slot = (unsigned)((i * 4 + r) * 2);
-                        __builtin_amdgcn_raw_buffer_store_b128(o0, slab_rsrc, (int)(base + slot * (G8_THREADS * 16u)), 0, 16);            // aux 16 = sc1
-                        RTN_STORE_GUARD(o0)
-                        __builtin_amdgcn_raw_buffer_store_b128(o1, slab_rsrc, (int)(base + (slot + 1) * (G8_THREADS * 16u)), 0, 16);
-                        RTN_STORE_GUARD(o1)
+                        epi_store_f32x8<16>(acc[i], r, slab_rsrc, base + slot * (G8_THREADS * 16u), base + (slot + 1) * (G8_THREADS * 16u));      // 16 = sc1
                     }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // EVERY storing wave drains before the flag may go up
                 // ... and says so in LDS; the wave whose add comes last raises the flag.  No barrier: the two wave groups keep their offset
@@ -443,12 +428,9 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
         G8_STAMP(4)
         // ---- epilogue: [mask] [+ residual] [mask] ReLU, bf16, 4 MI stores of 16 B per lane
         if (run_epilogue) {
-            const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)p.out, 0, (int)__builtin_amdgcn_readfirstlane((int)p.out_bytes), 0x00020000);
-            const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 1) ? p.res : p.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 1) ? p.res_bytes : 0u)), 0x00020000);
-            const __amdgpu_buffer_rsrc_t mask_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 2) ? p.mask : p.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 2) ? p.mask_bytes : 0u)), 0x00020000);
+            const __amdgpu_buffer_rsrc_t out_rsrc = epi_rsrc(p.out, p.out_bytes);
+            const __amdgpu_buffer_rsrc_t res_rsrc = epi_rsrc(p.res, p.res_bytes, EPI & 1, p.out);
+            const __amdgpu_buffer_rsrc_t mask_rsrc = epi_rsrc(p.mask, p.mask_bytes, EPI & 2, p.out);
             const int ncol = n0 + wn * (16 * NW) + NW * lrow;
             const bool col_ok = ncol < p.N;
             auto scatter_pix = [&](int m) -> unsigned {        // pixel of GEMM row m in out / res / mask
@@ -460,7 +442,6 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
             };
             // residual / mask rows of every row fragment: all MI x 4 loads of a wave go out before the first is used (these layers are
             // bound by their pixel traffic: more loads in flight per wave).  NW = 4: 8 bytes per lane and row instead of 16.
-            constexpr int NWD = NW / 2;                       // dwords per lane and row
             u32x4 rq[MI][4], mq[(EPI & 2) ? MI : 1][4];
             auto fetch = [&](int i) {
                 const int par = i, parm = (EPI & 2) ? i : 0;
@@ -480,15 +461,9 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
                             sx_ = sx_ < p.Wres - 1 ? sx_ : p.Wres - 1;
                             rrow = (unsigned)b * p.res_img_stride + (unsigned)(sy_ * p.Wres + sx_) * (unsigned)p.res_ld;
                         }
-                        const int roff = (int)(ok ? (rrow + (unsigned)ncol) * 2u : G8_OOB);
-                        if (NW == 8) rq[par][r] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, roff, 0, 0);
-                        else { const u32x2 t2 = __builtin_amdgcn_raw_buffer_load_b64(res_rsrc, roff, 0, 0); rq[par][r] = (u32x4){t2.x, t2.y, 0u, 0u}; }
+                        rq[par][r] = epi_load_row<NW>(res_rsrc, ok ? (rrow + (unsigned)ncol) * 2u : G8_OOB);
                     }
-                    if (EPI & 2) {
-                        const int moff = (int)(ok ? (pm * (unsigned)p.mask_ld + (unsigned)ncol) * 2u : G8_OOB);
-                        if (NW == 8) mq[parm][r] = __builtin_amdgcn_raw_buffer_load_b128(mask_rsrc, moff, 0, 0);
-                        else { const u32x2 t2 = __builtin_amdgcn_raw_buffer_load_b64(mask_rsrc, moff, 0, 0); mq[parm][r] = (u32x4){t2.x, t2.y, 0u, 0u}; }
-                    }
+                    if (EPI & 2) mq[parm][r] = epi_load_row<NW>(mask_rsrc, ok ? (pm * (unsigned)p.mask_ld + (unsigned)ncol) * 2u : G8_OOB);
                 }
             };
             if (EPI) {
@@ -503,33 +478,9 @@ __global__ __launch_bounds__(G8_THREADS, 2) void conv_gemm8_kernel(const G8Param
                     float v[NW];
 #pragma unroll
                     for (int j = 0; j < NW; ++j) v[j] = acc[i][j][r];
-                    if (EPI) {
-                        const u32x4 rw = rq[i][r], mw = mq[(EPI & 2) ? i : 0][r];
-#pragma unroll
-                        for (int j = 0; j < NWD; ++j) {
-                            const unsigned mj = (EPI & 2) ? mw[j] : 0x3f803f80u, rj = (EPI & 1) ? rw[j] : 0u;
-                            const bool keep_lo = __uint_as_float(mj << 16) > 0.f, keep_hi = __uint_as_float(mj & 0xffff0000u) > 0.f;
-                            if ((EPI & 2) && p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                            if (EPI & 1) { v[2 * j] += __uint_as_float(rj << 16); v[2 * j + 1] += __uint_as_float(rj & 0xffff0000u); }
-                            if ((EPI & 2) && !p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                        }
-                    }
-                    if (p.relu) {
-#pragma unroll
-                        for (int j = 0; j < NW; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
-                    }
-                    const unsigned off = (col_ok && m < p.M) ? (scatter_pix(m < p.M ? m : 0) * (unsigned)p.out_ld + (unsigned)ncol) * 2u : G8_OOB;
-                    if constexpr (NW == 8) {
-                        u32x4 o;
-                        o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
-                        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, (int)off, 0, 0);
-                        RTN_STORE_GUARD(o)
-                    } else {
-                        u32x2 o;
-                        o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]);
-                        __builtin_amdgcn_raw_buffer_store_b64(o, out_rsrc, (int)off, 0, 0);
-                        asm volatile("s_nop 3" :: "v"(o.x), "v"(o.y));
-                    }
+                    if (EPI) epi_mask_res<NW, EPI>(v, rq[i][r], mq[(EPI & 2) ? i : 0][r], p.mask_pre);
+                    if (p.relu) epi_relu(v);
+                    epi_store_bf16<NW>(v, out_rsrc, (col_ok && m < p.M) ? (scatter_pix(m < p.M ? m : 0) * (unsigned)p.out_ld + (unsigned)ncol) * 2u : G8_OOB);
                 }
             }
         }
@@ -549,28 +500,21 @@ template <int MI, bool ST, bool DU, int EP, int NW = 8, bool SK = false>
 int g8_go(rtn_handle_t h, int grid, const G8Params& p) {
     return rtn_launch_lds<conv_gemm8_kernel<MI, ST, DU, EP, NW, SK>>(h, dim3((unsigned)grid), dim3(G8_THREADS), G8_LDS, G8_LDS, p);
 }
-// run-time values -> kernel instance, one rung per instance: the stream-K, the 128-column and the full-width instances
+// run-time values -> kernel instance: the stream-K, the 128-column and the full-width instances
 template <int MI>
 int g8_pick_sk(rtn_handle_t h, int grid, const G8Params& p, bool dual, int epi) {
     if (dual) return g8_go<MI, true, true, 0, 8, true>(h, grid, p);
-    if (epi == 0) return g8_go<MI, true, false, 0, 8, true>(h, grid, p);
-    return g8_go<MI, true, false, 1, 8, true>(h, grid, p);
+    return rtn_with_epi<1>(epi, [&](auto e) { return g8_go<MI, true, false, decltype(e)::value, 8, true>(h, grid, p); });
 }
 template <int MI>
 int g8_pick_narrow(rtn_handle_t h, int grid, const G8Params& p, int epi) {
-    if (epi == 0) return g8_go<MI, true, false, 0, 4>(h, grid, p);
-    if (epi == 1) return g8_go<MI, true, false, 1, 4>(h, grid, p);
-    if (epi == 2) return g8_go<MI, true, false, 2, 4>(h, grid, p);
-    return g8_go<MI, true, false, 3, 4>(h, grid, p);
+    return rtn_with_epi<3>(epi, [&](auto e) { return g8_go<MI, true, false, decltype(e)::value, 4>(h, grid, p); });
 }
 template <int MI>
 int g8_pick(rtn_handle_t h, int grid, const G8Params& p, bool dual, bool stagger, int epi) {
     if (dual) return stagger ? g8_go<MI, true, true, 0>(h, grid, p) : g8_go<MI, false, true, 0>(h, grid, p);
     if (!stagger && epi == 0) return g8_go<MI, false, false, 0>(h, grid, p);      // lockstep variant: A/B only
-    if (epi == 0) return g8_go<MI, true, false, 0>(h, grid, p);
-    if (epi == 1) return g8_go<MI, true, false, 1>(h, grid, p);
-    if (epi == 2) return g8_go<MI, true, false, 2>(h, grid, p);
-    return g8_go<MI, true, false, 3>(h, grid, p);
+    return rtn_with_epi<3>(epi, [&](auto e) { return g8_go<MI, true, false, decltype(e)::value>(h, grid, p); });
 }
 }  // namespace
 

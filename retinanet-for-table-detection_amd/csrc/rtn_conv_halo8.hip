@@ -25,6 +25,7 @@
 // LDS (160 KiB, all of it): B ring 3 x 32 KiB at 0, halos 2 x 32 KiB at 96 KiB.  One workgroup (512 threads) per CU.
 #include "rtn_internal.h"
 #include "rtn_device.h"
+#include "rtn_conv_epilogue.h"
 
 #ifndef RTN_H8_ABLATE
 #define RTN_H8_ABLATE 0
@@ -49,7 +50,6 @@ __device__ unsigned long long g_h8_stamps[2][64];
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned OOB = 0xFFFFFF00u;                 // beyond every descriptor: loads return zeros, stores are dropped
 constexpr int H8_THREADS = 512;
@@ -91,13 +91,6 @@ struct H8Params {
     int out_fp8;
 };
 
-// A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
-// them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
-// fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
-// inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
-// offset; tools/scan_store_hazard.py checks the built library.
-#define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
-
 // fp8 e4m3 x e4m3, K = 128 per instruction at twice the bf16 rate: a lane supplies 32 bytes of its row per operand - the two 16-byte
 // fragments the bf16 loop reads for k halves 0 and 1 (which 32 of the row's 128 K positions a lane holds is free as long as A and
 // B agree).  Block scales 2^0.
@@ -108,12 +101,6 @@ __device__ __forceinline__ void mma_fp8(f32x4& acc, const uint4& a0, const uint4
     const i32x8 A = __builtin_shufflevector(__builtin_bit_cast(i32x4, a0), __builtin_bit_cast(i32x4, a1), 0, 1, 2, 3, 4, 5, 6, 7);
     const i32x8 B = __builtin_shufflevector(__builtin_bit_cast(i32x4, b0), __builtin_bit_cast(i32x4, b1), 0, 1, 2, 3, 4, 5, 6, 7);
     acc = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, B, acc, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-}
-__device__ __forceinline__ unsigned pack_fp8x4(float a, float b, float c, float d) {
-    unsigned w = 0;
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
-    w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
-    return w;
 }
 
 // MI = row fragments (16 rows) per wave: tiles of R = 64 MI rows (256 or 192).  The host picks the height that needs the fewest
@@ -499,12 +486,11 @@ __global__ __launch_bounds__(H8_THREADS, 2) void conv_halo8_kernel(const H8Param
             kh = kh1; cc = cc1;
         }
         kh0 = kh; cc0 = cc;                            // the next item starts at the group the cursor already points to
-        // ---- epilogue: [mask] [+ residual] [mask] ReLU, bf16, 4 MI stores of 16 B per lane (rows beyond TM / M go to an out-of-range
-        // offset and are dropped)
+        // ---- epilogue (rtn_conv_epilogue.h): [mask] [+ residual] [mask] ReLU, bf16, 4 MI stores of 2 NW bytes per lane (rows beyond
+        // TM / M go to an out-of-range offset and are dropped)
         if constexpr (ES == 1) {
             const H8Group& Gc = p.g[gi];
-            const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)Gc.out, 0, (int)__builtin_amdgcn_readfirstlane((int)Gc.out_bytes), 0x00020000);
+            const __amdgpu_buffer_rsrc_t out_rsrc = epi_rsrc(Gc.out, Gc.out_bytes);
             const int ncol = wn * 128 + 8 * lrow;
             const bool col_ok = ncol < p.N;
 #pragma unroll
@@ -520,83 +506,12 @@ __global__ __launch_bounds__(H8_THREADS, 2) void conv_halo8_kernel(const H8Param
                         v[j] = acc[i][j][r] * p.acc_scale + bias8[j];
                         if (p.relu) v[j] = v[j] > 0.f ? v[j] : 0.f;
                     }
-                    if (p.out_fp8) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) {
-                            const float q = v[j] * p.out_scale;
-                            v[j] = q > 448.f ? 448.f : (q < -448.f ? -448.f : q);
-                        }
-                        typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-                        u32x2 o;
-                        o.x = pack_fp8x4(v[0], v[1], v[2], v[3]); o.y = pack_fp8x4(v[4], v[5], v[6], v[7]);
-                        __builtin_amdgcn_raw_buffer_store_b64(o, out_rsrc, (int)(ok ? (unsigned)m * (unsigned)p.out_ld + (unsigned)ncol : OOB), 0, 0);
-                        asm volatile("s_nop 3" :: "v"(o.x), "v"(o.y));
-                    } else {
-                        u32x4 o;
-                        o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
-                        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, (int)(ok ? ((unsigned)m * (unsigned)p.out_ld + (unsigned)ncol) * 2u : OOB), 0, 0);
-                        RTN_STORE_GUARD(o)
-                    }
-                }
-        } else if constexpr (NW == 4) {
-            // 4 consecutive channels per lane and row: 8-byte stores (and 8-byte residual / mask loads, all of a wave's in flight first)
-            const H8Group& Gc = p.g[gi];
-            const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)Gc.out, 0, (int)__builtin_amdgcn_readfirstlane((int)Gc.out_bytes), 0x00020000);
-            const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 1) ? Gc.res : Gc.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 1) ? Gc.res_bytes : 0u)), 0x00020000);
-            const __amdgpu_buffer_rsrc_t mask_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 2) ? Gc.mask : Gc.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 2) ? Gc.mask_bytes : 0u)), 0x00020000);
-            const int ncol = wn * 64 + 4 * lrow;
-            const bool col_ok = ncol < p.N;
-            typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-            u32x2 rq[(EPI & 1) ? MI : 1][4], mq[(EPI & 2) ? MI : 1][4];
-            if (EPI) {
-#pragma unroll
-                for (int i = 0; i < MI; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int rloc = wm * (16 * MI) + i * 16 + kq * 4 + r;
-                        const int m = m0 + rloc;
-                        const bool ok = col_ok && rloc < TM && m < Gc.M;
-                        if (EPI & 1) rq[i][r] = __builtin_amdgcn_raw_buffer_load_b64(res_rsrc, (int)(ok ? ((unsigned)m * (unsigned)p.res_ld + (unsigned)ncol) * 2u : OOB), 0, 0);
-                        if (EPI & 2) mq[i][r] = __builtin_amdgcn_raw_buffer_load_b64(mask_rsrc, (int)(ok ? ((unsigned)m * (unsigned)p.mask_ld + (unsigned)ncol) * 2u : OOB), 0, 0);
-                    }
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rloc = wm * (16 * MI) + i * 16 + kq * 4 + r;
-                    const int m = m0 + rloc;
-                    float v[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = acc[i][j][r];
-                    if (EPI) {
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const unsigned mj = (EPI & 2) ? mq[(EPI & 2) ? i : 0][r][j] : 0x3f803f80u, rj = (EPI & 1) ? rq[(EPI & 1) ? i : 0][r][j] : 0u;
-                            const bool keep_lo = __uint_as_float(mj << 16) > 0.f, keep_hi = __uint_as_float(mj & 0xffff0000u) > 0.f;
-                            if ((EPI & 2) && p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                            if (EPI & 1) { v[2 * j] += __uint_as_float(rj << 16); v[2 * j + 1] += __uint_as_float(rj & 0xffff0000u); }
-                            if ((EPI & 2) && !p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                        }
-                    }
-                    if (p.relu) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
-                    }
-                    u32x2 o;
-                    o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]);
-                    const bool ok = col_ok && rloc < TM && m < Gc.M;
-                    const unsigned off = ok ? ((unsigned)m * (unsigned)p.out_ld + (unsigned)ncol) * 2u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b64(o, out_rsrc, (int)off, 0, 0);
-                    asm volatile("s_nop 3" :: "v"(o.x), "v"(o.y));
+                    if (p.out_fp8) epi_store8(epi_quant_fp8(v, p.out_scale), out_rsrc, ok ? (unsigned)m * (unsigned)p.out_ld + (unsigned)ncol : OOB);
+                    else epi_store_bf16<8>(v, out_rsrc, ok ? ((unsigned)m * (unsigned)p.out_ld + (unsigned)ncol) * 2u : OOB);
                 }
         } else if (SPLIT && p.S > 1) {
             // f32 partial sums of this K slice -> slab[sl][m][256 cb + channel], 2 x 16 B per lane and row
-            const __amdgpu_buffer_rsrc_t slab_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((char*)p.slab + (size_t)sl * p.slab_slice_bytes), 0, (int)__builtin_amdgcn_readfirstlane((int)p.slab_slice_bytes), 0x00020000);
+            const __amdgpu_buffer_rsrc_t slab_rsrc = epi_rsrc((char*)p.slab + (size_t)sl * p.slab_slice_bytes, p.slab_slice_bytes);
             const int gcol = cb * 256 + wn * 128 + 8 * lrow;
             const int Mg = p.g[gi].M;
 #pragma unroll
@@ -607,23 +522,14 @@ __global__ __launch_bounds__(H8_THREADS, 2) void conv_halo8_kernel(const H8Param
                     const int m = m0 + rloc;
                     const bool ok = gcol < p.slab_ld && rloc < TM && m < Mg;
                     const unsigned off = ok ? ((unsigned)m * (unsigned)p.slab_ld + (unsigned)gcol) * 4u : OOB;
-                    u32x4 o0, o1;
-                    o0.x = __float_as_uint(acc[i][0][r]); o0.y = __float_as_uint(acc[i][1][r]); o0.z = __float_as_uint(acc[i][2][r]); o0.w = __float_as_uint(acc[i][3][r]);
-                    o1.x = __float_as_uint(acc[i][4][r]); o1.y = __float_as_uint(acc[i][5][r]); o1.z = __float_as_uint(acc[i][6][r]); o1.w = __float_as_uint(acc[i][7][r]);
-                    __builtin_amdgcn_raw_buffer_store_b128(o0, slab_rsrc, (int)off, 0, 0);
-                    RTN_STORE_GUARD(o0)
-                    __builtin_amdgcn_raw_buffer_store_b128(o1, slab_rsrc, (int)(ok ? off + 16u : OOB), 0, 0);
-                    RTN_STORE_GUARD(o1)
+                    epi_store_f32x8<0>(acc[i], r, slab_rsrc, off, ok ? off + 16u : OOB);
                 }
         } else {
             const H8Group& Gc = p.g[gi];
-            const __amdgpu_buffer_rsrc_t out_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)Gc.out, 0, (int)__builtin_amdgcn_readfirstlane((int)Gc.out_bytes), 0x00020000);
-            const __amdgpu_buffer_rsrc_t res_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 1) ? Gc.res : Gc.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 1) ? Gc.res_bytes : 0u)), 0x00020000);
-            const __amdgpu_buffer_rsrc_t mask_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((EPI & 2) ? Gc.mask : Gc.out), 0, (int)__builtin_amdgcn_readfirstlane((int)((EPI & 2) ? Gc.mask_bytes : 0u)), 0x00020000);
-            const int ncol = (SPLIT ? cb * 256 : 0) + wn * 128 + 8 * lrow;
+            const __amdgpu_buffer_rsrc_t out_rsrc = epi_rsrc(Gc.out, Gc.out_bytes);
+            const __amdgpu_buffer_rsrc_t res_rsrc = epi_rsrc(Gc.res, Gc.res_bytes, EPI & 1, Gc.out);
+            const __amdgpu_buffer_rsrc_t mask_rsrc = epi_rsrc(Gc.mask, Gc.mask_bytes, EPI & 2, Gc.out);
+            const int ncol = (SPLIT ? cb * 256 : 0) + wn * (16 * NW) + NW * lrow;
             const bool col_ok = ncol < p.N;
             float bias_e[8];                        // SPLIT: the accumulators started at zero
 #pragma unroll
@@ -636,54 +542,40 @@ __global__ __launch_bounds__(H8_THREADS, 2) void conv_halo8_kernel(const H8Param
             }
             // residual / mask rows of the row fragments: with ONE of the two (the data gradients of the towers, P3, res4 branch2b take
             // the mask only) every fragment's rows are requested before the first is used - one round trip per tile instead of one per
-            // fragment (the loop's fragment and address registers are dead here); with both, two fragments are in flight (ping-pong)
-            constexpr int EDEPTH = (EPI == 3 || (EPI == 1 && MI == 4)) ? 2 : MI;     // (residual only, 256 rows: four fragments in flight spill)
+            // fragment (the loop's fragment and address registers are dead here); with both, two fragments are in flight (ping-pong).
+            // The 128-column instance (8 bytes per lane and row) always requests all of them first.
+            constexpr int EDEPTH = NW == 8 && (EPI == 3 || (EPI == 1 && MI == 4)) ? 2 : MI;     // (residual only, 256 rows: four fragments in flight spill)
             u32x4 rq[EDEPTH][4], mq[EDEPTH][4];
-            auto fetch = [&](int i, int par) {
+            const unsigned res_ld = (unsigned)p.res_ld, mask_ld = (unsigned)p.mask_ld;      // read once, ahead of the row loops
+            // one software-pipelined loop: step f requests the rows of fragment f and finishes fragment f - (EDEPTH - 1)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rloc = wm * (16 * MI) + i * 16 + kq * 4 + r;
-                    const int m = m0 + rloc;
-                    const bool ok = col_ok && rloc < TM && m < Gc.M;
-                    if (EPI & 1) rq[par][r] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, (int)(ok ? ((unsigned)m * (unsigned)p.res_ld + (unsigned)ncol) * 2u : OOB), 0, 0);
-                    if (EPI & 2) mq[par][r] = __builtin_amdgcn_raw_buffer_load_b128(mask_rsrc, (int)(ok ? ((unsigned)m * (unsigned)p.mask_ld + (unsigned)ncol) * 2u : OOB), 0, 0);
+            for (int f = 0; f < MI + EDEPTH - 1; ++f) {
+                if (EPI && f < MI) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int rloc = wm * (16 * MI) + f * 16 + kq * 4 + r;
+                        const int m = m0 + rloc;
+                        const bool ok = col_ok && rloc < TM && m < Gc.M;
+                        if (EPI & 1) rq[f % EDEPTH][r] = epi_load_row<NW>(res_rsrc, ok ? ((unsigned)m * res_ld + (unsigned)ncol) * 2u : OOB);
+                        if (EPI & 2) mq[f % EDEPTH][r] = epi_load_row<NW>(mask_rsrc, ok ? ((unsigned)m * mask_ld + (unsigned)ncol) * 2u : OOB);
+                    }
                 }
-            };
-            if (EPI) {
-#pragma unroll
-                for (int i = 0; i < EDEPTH - 1; ++i) fetch(i, i);
-            }
-#pragma unroll
-            for (int i = 0; i < MI; ++i) {
-                if (EPI && i + EDEPTH - 1 < MI) fetch(i + EDEPTH - 1, (i + EDEPTH - 1) % EDEPTH);
+                const int i = f - (EDEPTH - 1);
+                if (i < 0) continue;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int rloc = wm * (16 * MI) + i * 16 + kq * 4 + r;
                     const int m = m0 + rloc;
-                    float v[8];
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = acc[i][j][r] + (SPLIT ? bias_e[j] : 0.f);
-                    if (EPI) {
-                        const u32x4 rw = rq[i % EDEPTH][r], mw = mq[i % EDEPTH][r];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const unsigned mj = (EPI & 2) ? mw[j] : 0x3f803f80u, rj = (EPI & 1) ? rw[j] : 0u;
-                            const bool keep_lo = __uint_as_float(mj << 16) > 0.f, keep_hi = __uint_as_float(mj & 0xffff0000u) > 0.f;
-                            if ((EPI & 2) && p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                            if (EPI & 1) { v[2 * j] += __uint_as_float(rj << 16); v[2 * j + 1] += __uint_as_float(rj & 0xffff0000u); }
-                            if ((EPI & 2) && !p.mask_pre) { if (!keep_lo) v[2 * j] = 0.f; if (!keep_hi) v[2 * j + 1] = 0.f; }
-                        }
-                    }
-                    if (p.relu) {
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) v[j] = v[j] > 0.f ? v[j] : 0.f;
-                    }
-                    u32x4 o;
-                    o.x = pack2(v[0], v[1]); o.y = pack2(v[2], v[3]); o.z = pack2(v[4], v[5]); o.w = pack2(v[6], v[7]);
                     const bool ok = col_ok && rloc < TM && m < Gc.M;
                     const unsigned off = ok ? ((unsigned)m * (unsigned)p.out_ld + (unsigned)ncol) * 2u : OOB;
-                    __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, (int)off, 0, 0);
-                    RTN_STORE_GUARD(o)
+                    float v[NW];
+#pragma unroll
+                    // (a quirk kept for the sake of identical bits, not a requirement: the full-width instances have always added 0.f
+                    // without SPLIT, which turns -0.f into 0.f; the 128-column instance never did.  bias_e is dead code there.)
+                    for (int j = 0; j < NW; ++j) v[j] = NW == 8 ? acc[i][j][r] + (SPLIT ? bias_e[j] : 0.f) : acc[i][j][r];
+                    if (EPI) epi_mask_res<NW, EPI>(v, rq[i % EDEPTH][r], mq[i % EDEPTH][r], p.mask_pre);
+                    if (p.relu) epi_relu(v);
+                    epi_store_bf16<NW>(v, out_rsrc, off);
                 }
             }
         }
@@ -710,22 +602,14 @@ template <int MI, bool ST, int EP, bool SP, int NW = 8, int ES = 2>
 int h8_go(rtn_handle_t h, int grid, const H8Params& p) {
     return rtn_launch_lds<conv_halo8_kernel<3, MI, ST, EP, SP, NW, ES>>(h, dim3((unsigned)grid), dim3(H8_THREADS), H8_LDS, H8_LDS, p);
 }
-// run-time values -> kernel instance, one rung per instance
+// run-time values -> kernel instance
 template <int MI>
 int h8_pick(rtn_handle_t h, int grid, const H8Params& p, bool fp8, bool half, bool split, bool stagger, int epi) {
     if (fp8) return h8_go<3, true, 0, false, 8, 1>(h, grid, p);
-    if (half) {
-        if (epi == 0) return h8_go<MI, true, 0, false, 4>(h, grid, p);
-        if (epi == 1) return h8_go<MI, true, 1, false, 4>(h, grid, p);
-        if (epi == 2) return h8_go<MI, true, 2, false, 4>(h, grid, p);
-        return h8_go<MI, true, 3, false, 4>(h, grid, p);
-    }
+    if (half) return rtn_with_epi<3>(epi, [&](auto e) { return h8_go<MI, true, decltype(e)::value, false, 4>(h, grid, p); });
     if (split) return h8_go<MI, true, 0, true>(h, grid, p);
     if (!stagger && epi == 0) return h8_go<MI, false, 0, false>(h, grid, p);      // lockstep variant: A/B only
-    if (epi == 0) return h8_go<MI, true, 0, false>(h, grid, p);
-    if (epi == 1) return h8_go<MI, true, 1, false>(h, grid, p);
-    if (epi == 2) return h8_go<MI, true, 2, false>(h, grid, p);
-    return h8_go<MI, true, 3, false>(h, grid, p);
+    return rtn_with_epi<3>(epi, [&](auto e) { return h8_go<MI, true, decltype(e)::value, false>(h, grid, p); });
 }
 }  // namespace
 

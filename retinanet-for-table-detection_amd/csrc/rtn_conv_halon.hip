@@ -22,7 +22,6 @@ namespace {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 constexpr unsigned HN_OOB = 0xFFFFFF00u;              // beyond every descriptor: loads return zeros, stores are dropped
 constexpr int HN_THREADS = 512;
@@ -59,25 +58,6 @@ struct HNParams {
     int ngroups, ntiles;
     int N, Kbytes, nchunk, pad_t, pad_l, relu, sigmoid, out_ld, pix_b, vec, xcd, kh_fast;
 };
-
-// 64 lanes x 16 B from (descriptor, per-lane byte offset `voff` + uniform `soff`) to LDS bytes [lds_addr, lds_addr + 1024).
-// asm so that hipcc neither counts nor drains it; the kernel's own counted waits cover it.
-__device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
-    unsigned keep;
-    const unsigned la = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr), so = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(la), "s"(srd), "s"(so)
-                 : "memory");
-}
-
-// A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
-// them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
-// fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
-// inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
-// offset; tools/scan_store_hazard.py checks the built library.
-#define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
-#define RTN_STORE_GUARD1(V) asm volatile("s_nop 1" :: "v"(V));
 
 template <int NF>
 __global__ __launch_bounds__(HN_THREADS, 2) void conv_halon_kernel(const HNParams p) {
@@ -154,12 +134,12 @@ __global__ __launch_bounds__(HN_THREADS, 2) void conv_halon_kernel(const HNParam
         const int dy_ = st_kh - p.pad_t;                                                                       \
         const unsigned delta_ = (unsigned)(dy_ * st_row_b + st_cc * 128);                                      \
         const bool ok_ = (unsigned)(hiy[(I) & 3] + dy_) < (unsigned)st_Hin;                                    \
-        dma16(in_srd, ok_ ? hbase[(I) & 3] + delta_ : HN_OOB, 0u, lds_base + st_ring + (unsigned)(wave * 1024 + ((I) & 3) * 8192)); \
+        dma16_uniform(in_srd, ok_ ? hbase[(I) & 3] + delta_ : HN_OOB, 0u, lds_base + st_ring + (unsigned)(wave * 1024 + ((I) & 3) * 8192)); \
     } else if ((I) < Cfg::PP) {                                                                                \
         constexpr int d_ = (I) >= 4 && (I) - 4 < Cfg::BPW ? (I) - 4 : 0;                                       \
         const unsigned kcol_ = (unsigned)((st_kh * 3 * nchunk + st_cc) * 128);                                 \
         const int P_ = d_ * 8 + wave;                                                                          \
-        dma16(w_srd, wvoff[d_], kcol_, lds_base + (P_ < Cfg::BP ? st_ring + HN_HALO + (unsigned)P_ * 1024u : Cfg::DUMP)); \
+        dma16_uniform(w_srd, wvoff[d_], kcol_, lds_base + (P_ < Cfg::BP ? st_ring + HN_HALO + (unsigned)P_ * 1024u : Cfg::DUMP)); \
     }
     auto advance_stage = [&]() {
         st_ring = st_ring == 2 * Cfg::STAGE ? 0u : st_ring + Cfg::STAGE;

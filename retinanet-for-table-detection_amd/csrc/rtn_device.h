@@ -4,6 +4,8 @@
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
+typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 
 // Buffer descriptor words in SGPRs (raw buffer, stride 0, range = `bytes`); every input is made wave-uniform.
 __device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
@@ -25,6 +27,23 @@ __device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned 
                  : "v"(voff), "s"(lds_addr), "s"(srd), "s"(soff)
                  : "memory");
 }
+// The same with `soff` and `lds_addr` forced into SGPRs (readfirstlane): for callers whose uniform operands the compiler cannot prove
+// uniform (rtn_conv_halon.hip derives them from a ring cursor inside its K loop).
+__device__ __forceinline__ void dma16_uniform(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
+    const unsigned la = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr), so = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
+    dma16(srd, voff, so, la);
+}
+
+// A 16-byte buffer store whose data registers the following VALU instructions rewrite needs two wait states on gfx940+; LLVM pads
+// them except when the store's soffset is an SGPR (its hazard table treats that form as immune), which left ZERO wait states in the
+// fused bottleneck kernel and corrupted dword 0 of such stores (profiles/r3_store_hazard_isa.txt).  Naming the data registers as
+// inputs of an asm statement keeps them intact for four wait states whatever the compiler schedules next or wherever it keeps the
+// offset; tools/scan_store_hazard.py checks the built library.  The guard goes directly behind EVERY raw buffer store of a kernel
+// that computes on after it: 16-byte, 8-byte (RTN_STORE_GUARD2) and 4-byte (RTN_STORE_GUARD1, two wait states) data.  The guarded
+// stores of rtn_conv_epilogue.h are the way to issue one; a kernel that writes its own store writes the guard next to it.
+#define RTN_STORE_GUARD(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y), "v"(V.z), "v"(V.w));
+#define RTN_STORE_GUARD2(V) asm volatile("s_nop 3" :: "v"(V.x), "v"(V.y));
+#define RTN_STORE_GUARD1(V) asm volatile("s_nop 1" :: "v"(V));
 
 // f / d for 0 <= f < 2^24 with inv = 1.0f / d: the float product is within one of the quotient
 __device__ __forceinline__ void divmod24(int f, int d, float inv, int& q, int& r) {

@@ -1,10 +1,14 @@
-// rtn_internal.h — shared by the librtn.so translation units (not part of the C-ABI).
+// rtn_internal.h — shared by the librtn.so translation units (not part of the C-ABI): the handle, error and launch helpers
+// (rtn_launch_lds, rtn_with_epi), environment knobs and the entry points one translation unit offers the others.  Device-only
+// helpers are in rtn_device.h (descriptors, LDS-DMA, packers, the store-data guard) and rtn_conv_epilogue.h (the register epilogue
+// of the persistent convolution kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include "rtn.h"
 
 struct rtn_ctx {
@@ -57,6 +61,18 @@ inline int rtn_launch_lds(rtn_ctx* h, dim3 grid, dim3 block, unsigned lds, int l
     }
     hipLaunchKernelGGL(Kernel, grid, block, lds, h->stream, p);
     return RTN_OK;
+}
+
+// Run-time epilogue mode `epi` (bit 0 = residual, bit 1 = mask) -> compile-time constant: calls f(std::integral_constant<int, E>) for
+// E = epi; `epi` >= LAST takes LAST (the instances a launcher has are E = 0 .. LAST, no others are emitted).
+template <int LAST, int E = 0, class F>
+inline int rtn_with_epi(int epi, F&& f) {
+    if constexpr (E < LAST) {
+        if (epi == E) return f(std::integral_constant<int, E>{});
+        return rtn_with_epi<LAST, E + 1>(epi, f);
+    } else {
+        return f(std::integral_constant<int, LAST>{});
+    }
 }
 
 // integer environment knob (name must be a string literal): cached per thread, re-read when the environment changed, so one process

@@ -506,6 +506,183 @@ def test_gemm8_narrow_instance_for_128_columns(pkg, handle, monkeypatch, levels,
 
 
 
+EPI_MODES = ["none", "res", "mask", "mask_pre", "res+mask", "res+mask_pre"]
+EPI_FORMS = {
+    # name: (impl, k, cin, cout, levels, form)
+    "h8": (4, 3, 64, 136, [(12, 11), (2, 3)], None),       # generation 4 full width: 264 + 12 rows = two tiles at both tile heights, a group
+                                                           # boundary inside the second; columns 136..255 of the tile are never stored
+    "h8-128": (4, 3, 64, 72, [(12, 11), (2, 3)], None),    # ... its 128-column instance (8-byte accesses)
+    "g8": (5, 1, 128, 256, [(11, 13)], None),              # generation 5 full width: 286 rows = 3 / 2 tiles, the last one part full
+    "g8-128": (5, 1, 128, 128, [(11, 13)], None),          # ... its narrow instance
+    "h8-kslice": (4, 3, 64, 136, [(12, 11)], "kslice"),    # generation 4, three K slices (one kernel row each) through the f32 slabs
+    "g8-scatter": (5, 1, 128, 256, [(5, 4)], "scatter"),   # generation 5: rows land on every second pixel of a 9 x 7 grid (out_step 2)
+    "g8-up": (5, 1, 128, 256, [(7, 9)], "up"),             # ... residual = the coarser level (4 x 5: ratios 0.571 / 0.556)
+    "g8-sk": (5, 1, 128, 256, [(11, 13)], "sk"),           # ... stream-K: two K steps per tile, tiles cut between workgroups
+}
+_EPI_REF = {}
+
+
+def epi_exact_operands(form):
+    """Small-integer operands of one EPI_FORMS entry and the float64 convolution + bias of every level, computed once per form:
+    inputs and `other` in [-3, 3], filters in [-2, 2], bias in [-8, 8] - every partial sum is an integer below 2^24, exact in f32
+    in any order, so the only rounding on the device is the final one to bf16."""
+    if form not in _EPI_REF:
+        impl, k, cin, cout, levels, kind = EPI_FORMS[form]
+        g = torch.Generator().manual_seed(4000 + sorted(EPI_FORMS).index(form))
+        w = torch.randint(-2, 3, (k, k, cin, cout), generator=g).double()
+        bias = torch.randint(-8, 9, (cout,), generator=g).double()
+        B, lv = 2, []
+        for H, W in levels:
+            x = torch.randint(-3, 4, (B, H, W, cin), generator=g).double()
+            Hg, Wg = (2 * H - 1, 2 * W - 1) if kind == "scatter" else (H, W)         # the grid `out`, `other` and `act` live on
+            other = torch.randint(-3, 4, (B, (H + 1) // 2, (W + 1) // 2, cout) if kind == "up" else (B, Hg, Wg, cout), generator=g).double()
+            act = torch.randint(-3, 4, (B, Hg, Wg, cout), generator=g).double()
+            act[0, 0, 0, :8] = torch.tensor([0.0, -0.0, 1e-30, -1e-30, 1.0, -1.0, 0.5, 0.0])     # zeros of either sign do not pass
+            act = q(act, "bf16")
+            lv.append((x, other, act, ref_conv(x, w, bias, 1, (k - 1) // 2, (k - 1) // 2, H, W)))
+        _EPI_REF[form] = (w, bias, lv)
+    return _EPI_REF[form]
+
+
+def run_epi_exact(pkg, handle, form, mode, relu):
+    """One launch of an EPI_FORMS entry; returns [(got, want)] per level as float64 on the pixels the launch writes."""
+    L = pkg._lib
+    dev = torch.device("cuda")
+    impl, k, cin, cout, levels, kind = EPI_FORMS[form]
+    w, bias, lv = epi_exact_operands(form)
+    wk, rows = pack_w(w, "bf16", dev)
+    bk = torch.zeros(rows, dtype=torch.float32)
+    bk[:cout] = bias.float()
+    bk = bk.to(dev)
+    B = 2
+    d = L.ConvDesc()
+    d.ngroups, d.batch, d.dtype = len(levels), B, DT["bf16"][1]
+    d.w, d.bias, d.w_rows, d.N, d.KH, d.KW = wk.data_ptr(), bk.data_ptr(), rows, cout, k, k
+    d.Crun = d.pix_stride = cin
+    d.sy = d.sx = 1
+    d.pad_t = d.pad_l = (k - 1) // 2
+    d.out_ld = cout
+    d.flags = (L.CONV_RELU if relu else 0) | (L.CONV_RELU_MASK if "mask" in mode else 0) | (L.CONV_MASK_PRE if "pre" in mode else 0) | \
+        ((L.CONV_RES_UPSAMPLE if kind == "up" else L.CONV_RES_SAME) if "res" in mode else 0)
+    keep, outs, res = [], [], []
+    for gi, ((H, W), (x, other, act, y)) in enumerate(zip(levels, lv)):
+        step = 2 if kind == "scatter" else 1
+        Hg, Wg = act.shape[1], act.shape[2]
+        xd = x.to(torch.bfloat16).to(dev).contiguous()
+        od = torch.full((B, Hg, Wg, cout), -77.0, dtype=torch.bfloat16, device=dev)
+        rd = other.to(torch.bfloat16).to(dev).contiguous()
+        ad = act.to(torch.bfloat16).to(dev).contiguous()
+        grp = L.ConvGroup()
+        grp.in_, grp.in_elems = xd.data_ptr(), xd.numel()
+        grp.in_img_stride, grp.in_row_stride = H * W * cin, W * cin
+        grp.Hin, grp.Win, grp.Hout, grp.Wout = H, W, H, W
+        grp.out, grp.out_elems, grp.out_img_stride = od.data_ptr(), od.numel(), Hg * Wg * cout
+        if kind == "scatter":
+            grp.out_step, grp.out_pix_w = 2, Wg
+        if "res" in mode:
+            grp.res, grp.res_elems, grp.res_img_stride, grp.res_ld = rd.data_ptr(), rd.numel(), rd.numel() // B, cout
+            grp.Hres, grp.Wres = rd.shape[1], rd.shape[2]
+        if "mask" in mode:
+            grp.mask, grp.mask_elems, grp.mask_img_stride, grp.mask_ld = ad.data_ptr(), ad.numel(), Hg * Wg * cout, cout
+        d.g[gi] = grp
+        keep += [xd, rd, ad]
+        outs.append(od)
+        # the float64 reference on the written pixels: [mask] [+ other] [mask], ReLU, one rounding to bf16
+        keepm = (act[:, ::step, ::step] > 0) if "mask" in mode else torch.ones_like(y, dtype=torch.bool)
+        o = upsample_nearest_legacy(other, H, W) if kind == "up" else other[:, ::step, ::step]
+        want = y
+        if "pre" in mode:
+            want = want * keepm
+        if "res" in mode:
+            want = want + o
+        if "mask" in mode and "pre" not in mode:
+            want = want * keepm
+        res.append((step, torch.relu(want) if relu else want))
+    L.attach_conv_workspace(handle, d)
+    handle.check(L.lib.rtn_conv2d_fwd(handle.raw, C.byref(d)))
+    torch.cuda.synchronize()
+    LAST["d"], LAST["keep"] = d, keep
+    assert L.lib.rtn_debug_last_conv_impl(handle.raw) == impl
+    pairs = []
+    for od, (step, want) in zip(outs, res):
+        got = od.cpu().double()
+        if step > 1:                                   # off the stride grid nothing is written
+            rest = torch.ones(got.shape[1], got.shape[2], dtype=torch.bool)
+            rest[::step, ::step] = False
+            assert torch.all(got[:, rest] == -77.0)
+        pairs.append((got[:, ::step, ::step], want))
+    return pairs
+
+
+def assert_epi_exact(pairs):
+    for got, want in pairs:
+        wq = q(want, "bf16")
+        assert torch.equal(got, wq), "exact operands: %d values differ, worst %.3e" % (int((got != wq).sum()), float((got - wq).abs().max()))
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("mode", EPI_MODES)
+@pytest.mark.parametrize("mi", [3, 4])
+@pytest.mark.parametrize("form", ["h8", "h8-128"])
+def test_register_epilogue_exact_generation4(pkg, handle, monkeypatch, form, mi, mode, relu):
+    """The shared register epilogue (csrc/rtn_conv_epilogue.h) on generation 4, full width and 128 columns, every mode, both tile
+    heights, on operands whose sums are exact: the output must EQUAL the float64 reference rounded once to bf16 - a mask on the wrong
+    side of the add, swapped halves of a packed pair or a wrong row of the residual at one column in eight cannot hide in that."""
+    monkeypatch.setenv("RTN_CONV_IMPL", "4")
+    monkeypatch.setenv("RTN_CONV_H8_MI", str(mi))
+    monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
+    assert_epi_exact(run_epi_exact(pkg, handle, form, mode, relu))
+    assert pkg._lib.lib.rtn_debug_last_conv_tile(handle.raw) == ((64 * mi) << 16) | (256 if form == "h8" else 128)
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("mi", [3, 4])
+def test_register_epilogue_exact_generation4_k_slices(pkg, handle, monkeypatch, mi, relu):
+    """... generation 4's K-slice branch: the f32 partial sums of three slices through the guarded slab stores."""
+    monkeypatch.setenv("RTN_CONV_IMPL", "4")
+    monkeypatch.setenv("RTN_CONV_H8_MI", str(mi))
+    monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
+    slabs = 3 * 2 * 12 * 11 * 256 * 4                  # three f32 slabs [M = 264][256]: what the launch asks of the caller ONLY when it slices
+    monkeypatch.setenv("RTN_CONV_H8_KSPLIT", "1")
+    assert_epi_exact(run_epi_exact(pkg, handle, "h8-kslice", "none", relu))
+    assert LAST["d"].workspace_bytes < slabs, "unsliced launch asked for slabs"
+    monkeypatch.setenv("RTN_CONV_H8_KSPLIT", "3")
+    assert_epi_exact(run_epi_exact(pkg, handle, "h8-kslice", "none", relu))
+    assert LAST["d"].workspace_bytes >= slabs and LAST["d"].workspace, "the K-slice branch did not run: no slabs attached"
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("mode", EPI_MODES)
+@pytest.mark.parametrize("mi", [2, 3])
+@pytest.mark.parametrize("form", ["g8", "g8-128"])
+def test_register_epilogue_exact_generation5(pkg, handle, monkeypatch, form, mi, mode, relu):
+    """... on generation 5, full width and the narrow instance."""
+    monkeypatch.setenv("RTN_CONV_IMPL", "5")
+    monkeypatch.setenv("RTN_CONV_G8_MI", str(mi))
+    monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
+    monkeypatch.setenv("RTN_CONV_G8_SK", "0")
+    assert_epi_exact(run_epi_exact(pkg, handle, form, mode, relu))
+    assert pkg._lib.lib.rtn_debug_last_conv_tile(handle.raw) == ((64 * mi) << 16) | (256 if form == "g8" else 128)
+
+
+@pytest.mark.parametrize("form,mode,relu", [
+    ("g8-scatter", "res+mask", 0),         # data gradient of a stride-2 1x1 'valid' convolution: out / res / mask on the stride grid
+    ("g8-up", "res", 1),                   # FPN lateral: the residual is the coarser level at a non-integer ratio
+    ("g8-sk", "res", 1),                   # stream-K with a residual: the tile's owner adds the published slabs, then the epilogue
+])
+def test_register_epilogue_exact_generation5_other_forms(pkg, handle, monkeypatch, form, mode, relu):
+    """... generation 5's scattered rows, upsampled residual and stream-K hand-off."""
+    monkeypatch.setenv("RTN_CONV_IMPL", "5")
+    monkeypatch.setenv("RTN_CONV_G8_MI", "2")
+    monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
+    monkeypatch.setenv("RTN_CONV_G8_SK", "1" if form == "g8-sk" else "0")
+    assert_epi_exact(run_epi_exact(pkg, handle, form, mode, relu))
+    assert (pkg._lib.lib.rtn_debug_last_conv_streamk(handle.raw) > 0) == (form == "g8-sk")
+    if form == "g8-sk":
+        assert sk_timeouts(pkg, handle) == 0
+
+
+
 def test_persistent_8phase_kernel_repeats_bit_for_bit(pkg, handle, monkeypatch):
     """A race between an LDS-DMA piece and a fragment read shows up as a tile that changes from launch to launch: 6 launches of a
     head-tower-sized layer (five levels, 700 tiles, every CU walking 2-3 of them) must give the same bits, staggered and not."""
