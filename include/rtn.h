@@ -695,6 +695,35 @@ int rtn_png_decode(rtn_handle_t h, int n, const void* host_blobs, const void* de
                    uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_png_inflate_chunk_host(const void* in, size_t in_bytes, void* out, size_t want_bytes, int32_t* status);
 
+/* ---- stream PNG decode (ordinary PNG files, on the device) ------------------------------------------------------------------
+ * Decodes the PNG files other programs write: one zlib stream cut into any number of IDATs, row filters None, Sub, Up, Average and
+ * Paeth.  It takes the files rtn_png_inspect refuses; output and blob / offsets / pages / status / workspace conventions are those
+ * of rtn_png_decode.
+ *
+ * rtn_png_stream_inspect (host only; h may be NULL): RTN_OK only for: the signature; a 13-byte IHDR with a correct CRC, depth 8,
+ *   colour type 0 or 2, compression 0, filter 0, interlace 0, sides >= 1, height * (1 + width * components) < 2^31; one or more
+ *   consecutive IDATs (empty ones allowed); before or after them only pHYs, tEXt, zTXt, iTXt, tIME, gAMA, cHRM, sRGB, iCCP or eXIf
+ *   chunks, each with a correct CRC; an empty IEND and the end of the file; the concatenated IDAT data starting with a zlib header
+ *   (CM 8, CINFO <= 7, no dictionary, check bits).  Anything else: RTN_EINVAL and a reason.  It does not inflate and computes no
+ *   IDAT CRC.  The blob (at most rtn_png_stream_blob_bound(file_bytes) bytes, exactly info->blob_bytes, a multiple of 16) holds the
+ *   sides, the components, the stored Adler-32, a table of offset, length and stored CRC per IDAT, and the concatenated stream.
+ *   info->chunks is the number of segments of RTN_PNG_SEGMENT compressed bytes (environment, 256 .. 2^24, default 16384) the
+ *   stream is cut into; info->workspace_bytes follows from the segments and height * (1 + width * components) alone.
+ * rtn_png_stream_decode: status (device, n int32) is 0 only if the chain of block runs from the stream's first bit decoded the final
+ *   block, that block ended in the last byte before the Adler-32, the runs gave exactly height * (1 + width * components) bytes, no
+ *   match reached before the stream's first byte, every IDAT's CRC-32 and the Adler-32 equal the stored ones and every row's filter
+ *   type was 0 .. 4 (PI_* bits of csrc/rtn_png_inflate.h otherwise); a page with any other status holds unspecified bytes.
+ * rtn_png_stream_inflate_host (host only, no handle): the device's find, count, chain, marker decode, window walk and resolve
+ *   functions run one after the other on the CPU over an rtn_png_stream_inspect blob, cut into segments of segment_bytes (0: the
+ *   blob's own).  want_bytes must be height * (1 + width * components).  *status = 0 and the filtered stream in out, or *status != 0
+ *   (filter types are not looked at) and out not written. */
+size_t rtn_png_stream_blob_bound(size_t file_bytes);
+int rtn_png_stream_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob, size_t blob_capacity);
+size_t rtn_png_stream_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
+int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                          uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+int rtn_png_stream_inflate_host(const void* blob, size_t segment_bytes, void* out, size_t want_bytes, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif

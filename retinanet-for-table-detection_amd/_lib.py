@@ -218,6 +218,11 @@ SIGNATURES = {
     "rtn_png_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_png_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_png_inflate_chunk_host": (_I, [_P, _SZ, _P, _SZ, C.POINTER(C.c_int32)]),
+    "rtn_png_stream_blob_bound": (_SZ, [_SZ]),
+    "rtn_png_stream_inspect": (_I, [_P, _P, _SZ, C.POINTER(PngInfo), _P, _SZ]),
+    "rtn_png_stream_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_png_stream_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_png_stream_inflate_host": (_I, [_P, _SZ, _P, _SZ, C.POINTER(C.c_int32)]),
 }
 
 

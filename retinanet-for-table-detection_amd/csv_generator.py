@@ -33,13 +33,13 @@ try:                                    # as a module of the package ...
     from .model import anchors as _anchors
     from .model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
     from .model.utils import compute_resize_scale
-    from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, _decode_batch  # noqa: F401
+    from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
 except ImportError:                     # ... or top-level, with the package directory on sys.path like the reference's layout
     from model import Parameters, _rt
     from model import anchors as _anchors
     from model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
     from model.utils import compute_resize_scale
-    from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, _decode_batch  # noqa: F401
+    from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
 
 L = _rt.L
 

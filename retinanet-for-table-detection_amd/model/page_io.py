@@ -1,5 +1,6 @@
-"""Page files, read and written as cv2.imread / cv2.imwrite do, with the four device codecs behind them: baseline
-JPEG and chunked-layout PNG pages are decoded and encoded on the device, every other file by Pillow.  csv_generator.py,
+"""Page files, read and written as cv2.imread / cv2.imwrite do, with the five device codecs behind them: baseline
+JPEG and chunked-layout PNG pages are decoded and encoded on the device, ordinary 8-bit gray and R,G,B PNG pages (one zlib stream,
+all five row filters) are decoded there in calls of at least RTN_PNG_STREAM_MIN files (default 4), every other file is left to Pillow.  csv_generator.py,
 model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
 import contextlib
 import ctypes as C
@@ -30,13 +31,31 @@ def read_image_bgr(path):
 
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
 
-# One record per format the device decodes, in the order _decode_datas tries them: JPEG first, PNG second.
-_Format = namedtuple("_Format", "name Info inspect blob_bound workspace_bytes decode")
+PNG_STREAM_MIN_DEFAULT = 4
+
+
+def png_stream_min():
+    """RTN_PNG_STREAM_MIN: the fewest files in one call for which its ordinary (single-stream) PNGs are decoded on the device (DESIGN §3.4f);
+    0 leaves them all to Pillow.  The default, 4, is the batch at which the device first beat Pillow on one thread on both kinds
+    of sample-sized page (profiles/png_stream_decode_bench.txt)."""
+    try:
+        return max(0, int(os.environ.get("RTN_PNG_STREAM_MIN", "") or PNG_STREAM_MIN_DEFAULT))
+    except ValueError:
+        return PNG_STREAM_MIN_DEFAULT
+
+
+# One record per format the device decodes, in the order _decode_datas tries them: JPEG first, then PNG of the chunked layout,
+# then any other PNG.  min_files(): the fewest files in one call for which the format is tried at all (0: never).
+_Format = namedtuple("_Format", "name Info inspect blob_bound workspace_bytes decode min_files")
 _FORMATS = (
-    _Format("jpeg", L.JpegInfo, L.lib.rtn_jpeg_inspect, L.jpeg_blob_bound, L.lib.rtn_jpeg_workspace_bytes, L.lib.rtn_jpeg_decode),
-    _Format("png", L.PngInfo, L.lib.rtn_png_inspect, L.png_blob_bound, L.lib.rtn_png_decode_workspace_bytes, L.lib.rtn_png_decode),
+    _Format("jpeg", L.JpegInfo, L.lib.rtn_jpeg_inspect, L.jpeg_blob_bound, L.lib.rtn_jpeg_workspace_bytes, L.lib.rtn_jpeg_decode,
+            lambda: 1),
+    _Format("png", L.PngInfo, L.lib.rtn_png_inspect, L.png_blob_bound, L.lib.rtn_png_decode_workspace_bytes, L.lib.rtn_png_decode,
+            lambda: 1),
+    _Format("png_stream", L.PngInfo, L.lib.rtn_png_stream_inspect, L.lib.rtn_png_stream_blob_bound,
+            L.lib.rtn_png_stream_decode_workspace_bytes, L.lib.rtn_png_stream_decode, png_stream_min),
 )
-_JPEG, _PNG = _FORMATS
+_JPEG, _PNG, _PNG_STREAM = _FORMATS
 
 
 def _inspect(fmt, data):
@@ -60,10 +79,17 @@ def png_inspect(data):
     return _inspect(_PNG, data)
 
 
+def png_stream_inspect(data):
+    """Parse one file's bytes with rtn_png_stream_inspect (host only) -> (PngInfo, blob bytes) for an ordinary 8-bit gray or R,G,B
+    PNG (one zlib stream over any number of IDATs, harmless ancillary chunks) that the device can decode, or
+    (None, reason) for anything else.  PngInfo.chunks counts the segments of RTN_PNG_SEGMENT compressed bytes."""
+    return _inspect(_PNG_STREAM, data)
+
+
 def _decode_datas(datas, host_decode, device, handle, stream):
-    """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that rtn_jpeg_inspect or
-    rtn_png_inspect accepts is decoded on the device, each decoder running at most once, after ONE host->device copy of all
-    blobs; the status words of both are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
+    """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that the inspector of one
+    of _FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
+    words of all are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
     from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
     (None where no device decoder took the file)."""
     out, words = [None] * len(datas), [None] * len(datas)
@@ -76,10 +102,11 @@ def _decode_datas(datas, host_decode, device, handle, stream):
         hp = host.data_ptr()
         pos = 0
         kinds = {fmt.name: ([], [], []) for fmt in _FORMATS}         # blob offsets, pages, file indices
+        formats = [fmt for fmt in _FORMATS if 1 <= fmt.min_files() <= len(datas)]
         for i, data in enumerate(datas):
             if data is None:
                 continue
-            for fmt in _FORMATS:
+            for fmt in formats:
                 info = fmt.Info()
                 rc = fmt.inspect(None, data, len(data), C.byref(info), hp + pos, cap - pos)
                 if rc == 0:
@@ -162,11 +189,13 @@ def read_images_bgr(paths, device=None):
     """read_image_bgr for a list of files, as CUDA uint8 (H,W,3) B,G,R tensors with the same bits.  Baseline JPEGs (the files
     cv2.imwrite writes for a .jpg name) and PNGs of the chunked layout of DESIGN §3.4d (the files write_images_bgr(png="device")
     and preprocess_files(png="device") write) are decoded on the device, one batched call per format (csrc/rtn_jpeg.hip,
-    csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Every other file (any other
-    PNG among them: one zlib stream, Average or Paeth rows, 16-bit, palette, alpha, interlace, ancillary chunks), and any file
-    whose stream the device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset is converted once
-    with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises what read_image_bgr
-    raises."""
+    csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Ordinary PNGs (what Pillow,
+    libpng and cv2.imwrite write: 8-bit gray or R,G,B, one zlib stream, any of the five row filters, harmless ancillary chunks)
+    take the same road through csrc/rtn_png_stream.hip when the call holds at least RTN_PNG_STREAM_MIN files
+    (default 4; 0: never).  Every other file (16-bit, palette, alpha and interlaced PNGs, PNGs with tRNS or unknown chunks, BMP, ...),
+    and any file whose stream a device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset can
+    also be converted once with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises
+    what read_image_bgr raises."""
     with _reader(device) as (dev, h):
         return _decode_batch(list(paths), dev, h, torch.cuda.current_stream(dev))
 
@@ -174,8 +203,9 @@ def read_images_bgr(paths, device=None):
 def decode_png_bgr(files, device=None, return_status=False):
     """The pages of PNG files held in memory (list of bytes) as CUDA uint8 (H,W,3) B,G,R tensors with the bits Pillow gives:
     the counterpart of encode_png_bgr, on read_images_bgr's path.  Files of the chunked layout are decoded in one
-    batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip); a file that is not in the layout, or that the device
-    flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
+    batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip), ordinary 8-bit gray and R,G,B PNGs in one batched
+    rtn_png_stream_decode (csrc/rtn_png_stream.hip, DESIGN §3.4f) when the call holds at least RTN_PNG_STREAM_MIN files (default 4;
+    0: never); any other file, or one that the device flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
     device's status word for file i (0 = the device's page was kept) or None where the device did not take the file."""
     files = [bytes(f) for f in files]
     with _reader(device) as (dev, h):

@@ -12,6 +12,13 @@ Reports medians and the min..max spread over the iterations after a warm-up, eve
   (e) one CSVGenerator batch of those files end to end, with the device decoder and with every page decoded by read_image_bgr.
 For the per-kernel split: rocprofv3 --kernel-trace --stats --output-format csv -d rocprof_out -o png_dec --
   python tools/bench_decode_png.py --iters 3 --host-pages 0 --content map
+
+  python tools/bench_decode_png.py --stream [--iters 10] [--content map|page|gray|all] [--segments 16384,65536,262144]
+
+measures the stream PNG decoder (csrc/rtn_png_stream.hip) instead, on the same pages saved 16 times by Pillow with
+default settings: read_images_bgr with RTN_PNG_STREAM_MIN=1 at batch sizes 1, 2, 4, 8 and 16 for every RTN_PNG_SEGMENT value asked
+for, the decode kernels alone at batch 16, and the yardsticks on the same files: read_image_bgr (Pillow) on one thread, which is
+what read_images_bgr does with these files without the device path, and the same decode spread over 16 host threads.
 """
 import argparse
 import ctypes as C
@@ -175,15 +182,98 @@ def bench(content, a):
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def bench_stream(content, a):
+    from concurrent.futures import ThreadPoolExecutor
+    dev = torch.device("cuda", 0)
+    page = load(content)
+    want = page if page.ndim == 3 else np.repeat(page[:, :, None], 3, axis=2)
+    tmp = tempfile.mkdtemp(prefix="bench_decode_png_stream_")
+    paths = []
+    for i in range(16):
+        p = os.path.join(tmp, "page_%02d.png" % i)
+        if i == 0:
+            PIO.write_image(p, page)
+        else:
+            shutil.copy(paths[0], p)
+        paths.append(p)
+    data = open(paths[0], "rb").read()
+    res = {"content": content, "file_bytes": len(data)}
+
+    def line(key, label, v, per):
+        m, lo, hi = stat(v)
+        print("%-58s %9.3f ms per %2d page(s) (min %.3f, max %.3f, %d runs): %.1f pages/s" % (label, m, per, lo, hi, len(v), per / m * 1e3))
+        res[key] = round(m, 3)
+        return m
+
+    os.environ["RTN_PNG_STREAM_MIN"] = "0"
+    PIO.read_image_bgr(paths[0])
+    one = line("pillow_ms_per_page", "read_image_bgr (Pillow), one thread", times_ms(lambda: PIO.read_image_bgr(paths[0]), a.iters), 1)
+    with ThreadPoolExecutor(16) as pool:
+        list(pool.map(PIO.read_image_bgr, paths))
+        line("pillow_16_threads_ms", "read_image_bgr (Pillow), 16 threads", times_ms(lambda: list(pool.map(PIO.read_image_bgr, paths)), a.iters), 16)
+
+    def read_n(n):
+        PIO.read_images_bgr(paths[:n])
+        torch.cuda.synchronize()
+    read_n(16)
+    line("parent_read_images_bgr_ms", "read_images_bgr, device path off (the parent's path)", times_ms(lambda: read_n(16), max(2, a.iters // 3)), 16)
+    os.environ["RTN_PNG_STREAM_MIN"] = "1"
+    for seg in a.segments:
+        os.environ["RTN_PNG_SEGMENT"] = str(seg)
+        info, blob = PIO.png_stream_inspect(data)
+        assert info is not None, blob
+        print("== %s, RTN_PNG_SEGMENT=%d: %dx%d, %d component(s), file %d B, %d segments, blob %d B, workspace %.1f MB per page" %
+              (content, seg, info.width, info.height, info.components, len(data), info.chunks, info.blob_bytes, info.workspace_bytes / 1e6))
+        got, words = PIO.decode_png_bgr([data], return_status=True)
+        assert words == [0] and np.array_equal(got[0].cpu().numpy(), want)
+        for n in (1, 2, 4, 8, 16):
+            read_n(n)
+            m = line("read_images_bgr_ms_S%d_B%d" % (seg, n), "read_images_bgr, device path, batch %d" % n, times_ms(lambda: read_n(n), a.iters), n)
+            print("    %.2fx the one-thread Pillow decode of the same files" % (one * n / m))
+        # the kernels alone, batch 16
+        n = 16
+        host = np.concatenate([blob] * n)
+        offs = np.arange(n, dtype=np.int64) * blob.size
+        dblobs = torch.from_numpy(host).to(dev)
+        wsb = int(L.lib.rtn_png_stream_decode_workspace_bytes(n, host.ctypes.data, offs.ctypes.data))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        pages = [torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        h = L.Handle(0)
+        h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        k_ms = []
+        for it in range(a.iters + 2):
+            ev[0].record()
+            h.check(L.lib.rtn_png_stream_decode(h.raw, n, host.ctypes.data, dblobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
+                                                ws.data_ptr(), wsb))
+            ev[1].record()
+            torch.cuda.synchronize()
+            if it >= 2:
+                k_ms.append(ev[0].elapsed_time(ev[1]))
+        assert int(status.abs().sum()) == 0 and np.array_equal(pages[n - 1].cpu().numpy(), want)
+        line("kernels_ms_S%d" % seg, "decode kernels alone, batch 16", k_ms, n)
+        pinfo = L.PngInfo()
+        out = np.empty(L.png_blob_bound(len(data)), np.uint8)
+        line("inspect_ms_per_page_S%d" % seg, "rtn_png_stream_inspect on the host",
+             times_ms(lambda: L.lib.rtn_png_stream_inspect(None, data, len(data), C.byref(pinfo), out.ctypes.data, out.size), max(a.iters, 5)), 1)
+        h.close()
+    print(json.dumps(res))
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--host-pages", type=int, default=4)
     ap.add_argument("--content", choices=("map", "page", "gray", "all"), default="all")
+    ap.add_argument("--stream", action="store_true", help="measure the stream PNG decoder on Pillow-written files")
+    ap.add_argument("--segments", type=lambda v: [int(x) for x in v.split(",")], default=[16384], help="RTN_PNG_SEGMENT values (--stream)")
     a = ap.parse_args()
     for content in (("map", "page", "gray") if a.content == "all" else (a.content,)):
-        bench(content, a)
+        (bench_stream if a.stream else bench)(content, a)
 
 
 if __name__ == "__main__":
