@@ -594,7 +594,14 @@ int rtn_preprocess_image(rtn_handle_t h, const void* src, int src_dtype, float* 
  *   copy), offsets[i] (host, multiples of 16) the start of page i's blob in both; pages (host array) the device outputs, each
  *   H x W x 3 bytes; status (device, n int32) is written 0 for a decoded page and non-zero where the stream breaks JPEG's rules or
  *   leaves the range the device decode reproduces exactly: the caller decodes those pages on the host.  workspace: 256-byte
- *   aligned, >= rtn_jpeg_workspace_bytes. */
+ *   aligned, >= rtn_jpeg_workspace_bytes.
+ * rtn_jpeg_decode_host (host only, no handle): the device's decode functions run on the CPU over one rtn_jpeg_inspect blob: the
+ *   Huffman kernel's algorithm for `threads` (1 .. 65536; the device has 1024) virtual threads one after another (the same bit
+ *   ranges, synchronisation passes, segmented scan and writing pass), then the IDCT per block and the colour step per pixel, every
+ *   position checked against the blob's and the page's sizes (one outside them aborts the process).  out_bytes must be
+ *   height * width * 3.  RTN_OK with *status = the device's status word (0: the page is in out_bgr; 1, 2: out_bgr not written);
+ *   RTN_EINVAL for a blob the inspector cannot have written.  rtn_jpeg_decode_host_counters: of this thread's last call, the
+ *   synchronisation passes it ran and the threads whose bit range was not empty. */
 typedef struct {
     int32_t width, height, components, h_samp, v_samp;   /* h_samp / v_samp: luma sampling factors (2, 2 = 4:2:0) */
     int32_t restart_interval;                             /* MCUs per restart segment, 0 = none */
@@ -606,6 +613,8 @@ int rtn_jpeg_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_jp
 size_t rtn_jpeg_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
 int rtn_jpeg_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+int rtn_jpeg_decode_host(const void* blob, int threads, uint8_t* out_bgr, size_t out_bytes, int32_t* status);
+void rtn_jpeg_decode_host_counters(int32_t* passes, int32_t* busy_threads);
 
 /* ---- baseline JPEG encode (Pillow's Image.save(f, "JPEG", quality=q, subsampling=s), on the device) ------------------------------
  * Output: byte-identical to what Pillow 12 / libjpeg-turbo 3 writes with quality q (1..100) and subsampling s (0 = 4:4:4,

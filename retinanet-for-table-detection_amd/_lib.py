@@ -207,6 +207,8 @@ SIGNATURES = {
     "rtn_jpeg_inspect": (_I, [_P, _P, _SZ, C.POINTER(JpegInfo), _P, _SZ]),
     "rtn_jpeg_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_jpeg_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_jpeg_decode_host": (_I, [_P, _I, _P, _SZ, C.POINTER(C.c_int32)]),
+    "rtn_jpeg_decode_host_counters": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "rtn_jpeg_encode_header": (_I, [_I, _I, _I, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
     "rtn_jpeg_encode_bound": (_SZ, [_I, _I, _I, _I]),
     "rtn_jpeg_encode_workspace_bytes": (_SZ, [_I, _P, _P, _P, _P]),

@@ -128,22 +128,23 @@ def coefficients(page, quality, subsampling):
     return np.array(out)
 
 
-def _codes(t):
+def _codes(t, huff=None):
+    bits, vals = (HUFF_BITS[t], HUFF_VALS[t]) if huff is None else huff[t]
     codes, code, k = {}, 0, 0
-    for length, count in enumerate(HUFF_BITS[t], 1):
+    for length, count in enumerate(bits, 1):
         for _ in range(count):
-            codes[HUFF_VALS[t][k]] = (code, length)
+            codes[vals[k]] = (code, length)
             code, k = code + 1, k + 1
         code <<= 1
     return codes
 
 
-def scan(coefs, components, subsampling):
+def scan(coefs, components, subsampling, huff=None):
     """The entropy-coded segment of the blocks in scan order: DC prediction per component, Huffman coding with the standard
-    tables, 1-bit padding, 0xFF stuffing."""
+    tables (or huff: four (bits, vals) pairs in the order of HUFF_BITS), 1-bit padding, 0xFF stuffing."""
     hm, vm = (1, 1) if components == 1 or subsampling == 0 else ((2, 1) if subsampling == 1 else (2, 2))
     comp = [0] if components == 1 else [0] * (hm * vm) + [1, 2]
-    tabs = [(_codes(0), _codes(1)), (_codes(2), _codes(3))]
+    tabs = [(_codes(0, huff), _codes(1, huff)), (_codes(2, huff), _codes(3, huff))]
     bits = []
     pred = [0, 0, 0]
 
