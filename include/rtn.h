@@ -733,6 +733,47 @@ int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blobs, const v
                           uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_png_stream_inflate_host(const void* blob, size_t segment_bytes, void* out, size_t want_bytes, int32_t* status);
 
+/* ---- detection rendering (render_detections' outlines, captions and crops, on the device) ----------------------------------
+ * Every output image of a batch (crops and annotated pages alike) is a rectangle of one source page with some of that page's
+ * operations painted over it.  Page p owns the operations op_begin[p] .. op_begin[p + 1] - 1 (at most RTN_RENDER_MAX_OPS), in drawing
+ * order.  Operation j is a box outline (draw_box: the four bands of `thickness` pixels centred on the edges of the int box, corners
+ * sorted, in 0,0,0) followed by a caption (draw_caption: the set bits of a one-bit-per-pixel mask whose top-left pixel sits at
+ * (x, y) of the caption rectangle, in B,G,R = 0,0,255); both are clipped to the page.  An output image with `outlines` = a and
+ * `captions` = c shows outlines 0 .. a - 1 and captions 0 .. c - 1 of its page in the order outline 0, caption 0, outline 1, ...: the
+ * value of a pixel is that of the last operation covering it, else the source pixel.
+ *
+ * Host arrays: pages (n_pages device pointers to uint8 (H, W, 3) pages, sides 1 .. 65500), heights, widths, op_begin (n_pages + 1,
+ *   non-decreasing, op_begin[n_pages] <= n_ops); boxes ([n_ops][4]: x1, y1, x2, y2), captions ([n_ops][4]: x, y of the mask's first
+ *   pixel on the page, mask width and height; width or height 0: no caption), mask_bits (bit offset of the mask's first pixel in
+ *   `masks`; pixel (mx, my) of the mask is bit mask_bits + my * mask_pitch + mx, bit b being bit b & 7 of byte b >> 3), mask_pitch
+ *   (bits per mask row, >= the mask width); coordinates within +-2^30.  out_page, out_rects ([n_out][4]: x0, y0, w, h on the page,
+ *   w, h >= 1, inside the page), out_outlines, out_captions (0 .. the page's operations), out_offsets (byte offset of the contiguous
+ *   (h, w, 3) image in `out`).  Device memory: the pages, masks (mask_bytes bytes), out (out_bytes bytes; output images must not
+ *   overlap each other or a page) and workspace (256-byte aligned, >= rtn_render_workspace_bytes).  thickness: 0 .. 65536.
+ * rtn_render_pages: one launch on the handle's stream for all n_out images, after one copy of the tables into the workspace, for
+ *   which the call waits on the stream.  The pages are only read.  RTN_EINVAL with a reason for anything outside the rules above.
+ * rtn_render_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers; the kernel's per-pixel function (csrc/rtn_render.h) looped over every pixel of every output image.
+ * rtn_render_tiles_host: the same again through the kernel's tile walk (operations collected per tile, 16-byte destination units,
+ *   aligned 4-byte source words), one tile after another on the CPU. */
+#define RTN_RENDER_MAX_OPS 1024
+size_t rtn_render_workspace_bytes(int n_pages, int n_ops, int n_out);
+int rtn_render_pages(rtn_handle_t h, int n_pages, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                     const int32_t* op_begin, int n_ops, const int32_t* boxes, const int32_t* captions, const int64_t* mask_bits,
+                     const int32_t* mask_pitch, const uint8_t* masks, size_t mask_bytes, int n_out, const int32_t* out_page,
+                     const int32_t* out_rects, const int32_t* out_outlines, const int32_t* out_captions, const int64_t* out_offsets,
+                     int thickness, uint8_t* out, size_t out_bytes, void* workspace, size_t workspace_bytes);
+int rtn_render_host(int n_pages, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* op_begin,
+                    int n_ops, const int32_t* boxes, const int32_t* captions, const int64_t* mask_bits, const int32_t* mask_pitch,
+                    const uint8_t* masks, size_t mask_bytes, int n_out, const int32_t* out_page, const int32_t* out_rects,
+                    const int32_t* out_outlines, const int32_t* out_captions, const int64_t* out_offsets, int thickness, uint8_t* out,
+                    size_t out_bytes);
+int rtn_render_tiles_host(int n_pages, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                          const int32_t* op_begin, int n_ops, const int32_t* boxes, const int32_t* captions, const int64_t* mask_bits,
+                          const int32_t* mask_pitch, const uint8_t* masks, size_t mask_bytes, int n_out, const int32_t* out_page,
+                          const int32_t* out_rects, const int32_t* out_outlines, const int32_t* out_captions,
+                          const int64_t* out_offsets, int thickness, uint8_t* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

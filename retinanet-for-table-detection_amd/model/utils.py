@@ -162,18 +162,24 @@ def draw_box(image, box, color, thickness=5):
     band(y1 - lo, y2 + hi, x2 - lo, x2 + hi)
 
 
-def draw_caption(image, box, caption, font_size=5, font_thickness=5):
-    """ model/utils.py:310-318: `caption` above the box's top-left corner in (0, 0, 255), drawn in place (Pillow's built-in font
-    scaled by font_size in place of FONT_HERSHEY_PLAIN)."""
+def _caption_mask(caption, font_size=5):
+    """The pixels draw_caption paints for `caption`, as a bool (h, w) mask whose top-left pixel goes to (x1, y1 - 10 - h): Pillow's
+    built-in font, every font pixel blown up to a square of round(0.9 font_size) pixels."""
     from PIL import Image, ImageDraw, ImageFont
-    b = np.array(box).astype(int)
     font = ImageFont.load_default()
     probe = ImageDraw.Draw(Image.new("L", (1, 1)))
     l, t, r, btm = probe.textbbox((0, 0), caption, font=font)
     tile = Image.new("L", (max(r, 1), max(btm, 1)), 0)
     ImageDraw.Draw(tile).text((0, 0), caption, fill=255, font=font)
     s = max(1, int(round(font_size * 0.9)))
-    mask = np.kron(np.asarray(tile) > 127, np.ones((s, s), bool))
+    return np.kron(np.asarray(tile) > 127, np.ones((s, s), bool))
+
+
+def draw_caption(image, box, caption, font_size=5, font_thickness=5):
+    """ model/utils.py:310-318: `caption` above the box's top-left corner in (0, 0, 255), drawn in place (Pillow's built-in font
+    scaled by font_size in place of FONT_HERSHEY_PLAIN)."""
+    b = np.array(box).astype(int)
+    mask = _caption_mask(caption, font_size)
     x0, y0 = int(b[0]), int(b[1]) - 10 - mask.shape[0]
     H, W = image.shape[:2]
     ys, xs = max(y0, 0), max(x0, 0)
@@ -213,6 +219,35 @@ def draw_annotations(image, annotations, color=(0, 255, 0), label_to_name=None):
         draw_box(image, annotations['bboxes'][i], color=c)
 
 
+def _kept_detections(boxes, scores, labels, image_scale, score_threshold):
+    """The detections render_detections keeps of one page's (1,300,.) outputs: the boxes divided by image_scale in float32, walked
+    until the first score below score_threshold, truncated to int.  Returns (list of (box int[4], score, label), the score that
+    ended the walk or None)."""
+    boxes = np.asarray(boxes, np.float32) / np.float32(image_scale)
+    kept = []
+    for box, score, label in zip(boxes[0], np.asarray(scores)[0], np.asarray(labels)[0]):
+        if score < score_threshold:
+            return kept, score
+        kept.append((box.astype(int), float(score), int(label)))
+    return kept, None
+
+
+def _caption_text(labels_to_names, score, label):
+    return "{} {:.3f}".format(labels_to_names[int(label)], score)
+
+
+def _render_names(result_dir, image_name):
+    """render_detections' directories (created) and file names: (crop(k), no_detection(score), page)."""
+    import os
+    head, tail = os.path.splitext(image_name)
+    cropped, in_image = os.path.join(result_dir, "detections_cropped"), os.path.join(result_dir, "detections_inImage")
+    os.makedirs(cropped, exist_ok=True)
+    os.makedirs(in_image, exist_ok=True)
+    return (lambda k: os.path.join(cropped, "{}_{}{}".format(head, k, tail)),
+            lambda score: os.path.join(cropped, "{}_{}_{}{}".format(head, "noDete_minScore-", score, tail)),
+            os.path.join(in_image, image_name))
+
+
 def render_detections(processed_page, draw, boxes, scores, labels, image_scale, result_dir, image_name, labels_to_names=None,
                       score_threshold=0.6):
     """The output step of test_image (RetinaNet.py:366-402) for one page.  boxes/scores/labels: the (1,300,·) detections of the
@@ -221,23 +256,202 @@ def render_detections(processed_page, draw, boxes, scores, labels, image_scale, 
     result_dir/detections_cropped/<head>_<k><tail> per table (cropped AFTER the box outline is drawn, as the reference does),
     <head>_noDete_minScore-_<score><tail> when the first detection already fails, and result_dir/detections_inImage/<image_name>.
     Returns the list of kept (box int[4], score, label)."""
-    import os
     labels_to_names = labels_to_names or {0: 'table'}
-    head, tail = os.path.splitext(image_name)
-    os.makedirs(os.path.join(result_dir, "detections_cropped"), exist_ok=True)
-    os.makedirs(os.path.join(result_dir, "detections_inImage"), exist_ok=True)
-    boxes = np.asarray(boxes, np.float32) / np.float32(image_scale)
-    kept, k = [], 0
-    for box, score, label in zip(boxes[0], np.asarray(scores)[0], np.asarray(labels)[0]):
-        if score < score_threshold:
-            if k == 0:
-                write_image(os.path.join(result_dir, "detections_cropped", "{}_{}_{}{}".format(head, "noDete_minScore-", score, tail)), draw)
-            break
-        b = box.astype(int)
-        draw_box(draw, b, color=label_color(int(label)))
-        write_image(os.path.join(result_dir, "detections_cropped", "{}_{}{}".format(head, k, tail)), extract_box(draw, b))
-        draw_caption(draw, b, "{} {:.3f}".format(labels_to_names[int(label)], score))
-        kept.append((b, float(score), int(label)))
-        k += 1
-    write_image(os.path.join(result_dir, 'detections_inImage', image_name), draw)
+    crop_name, none_name, page_name = _render_names(result_dir, image_name)
+    kept, ended = _kept_detections(boxes, scores, labels, image_scale, score_threshold)
+    if not kept and ended is not None:
+        write_image(none_name(ended), draw)
+    for k, (b, score, label) in enumerate(kept):
+        draw_box(draw, b, color=label_color(label))
+        write_image(crop_name(k), extract_box(draw, b))
+        draw_caption(draw, b, _caption_text(labels_to_names, score, label))
+    write_image(page_name, draw)
+    return kept
+
+
+# ---- the same step on the device (DESIGN §3.4g): csrc/rtn_render.hip paints every crop and annotated page of a batch in one launch,
+# write_images_bgr's encoders turn them into files ------------------------------------------------------------------------------------
+_RENDER_COORD = 1 << 30          # rtn_render_pages' coordinate range: far outside any page, so clamping to it changes no pixel
+
+
+def _render_plan(shapes, kept, labels_to_names=None, thickness=5, font_size=5):
+    """The tables of one rtn_render_pages / rtn_render_host call.  shapes: (H, W) per page; kept: per page the list
+    _kept_detections returns.  A page without kept detections gets no output image.  A page with J of them gets, in this order,
+    crop k (the page rectangle [max(x1,0), min(x2,W)) x [max(y1,0), min(y2,H)) with outlines 0..k and captions 0..k-1) for every k
+    whose rectangle is not empty, then the whole page with all J outlines and captions.  Returns a dict: the int32 / int64 arrays
+    in the C-ABI's order, `masks` (uint8: the captions' masks, one bit per pixel, rows padded to whole bytes, equal captions
+    shared), `images` (per output: (page, k or None for the page, h, w, byte offset)) and `out_bytes`."""
+    labels_to_names = labels_to_names or {0: 'table'}
+    op_begin, boxes, captions, mask_bits, mask_pitch = [0], [], [], [], []
+    out_page, out_rects, out_outlines, out_captions, out_offsets, images = [], [], [], [], [], []
+    blob, seen, pos = [], {}, 0
+
+    def clamp(v):
+        return int(min(max(int(v), -_RENDER_COORD), _RENDER_COORD))
+
+    def image(p, k, x0, y0, w, h, outlines, caps):
+        nonlocal pos
+        out_page.append(p)
+        out_rects.append((x0, y0, w, h))
+        out_outlines.append(outlines)
+        out_captions.append(caps)
+        out_offsets.append(pos)
+        images.append((p, k, h, w, pos))
+        pos += (h * w * 3 + 255) & ~255
+
+    for p, ((H, W), dets) in enumerate(zip(shapes, kept)):
+        for k, (b, score, label) in enumerate(dets):
+            text = _caption_text(labels_to_names, score, label)
+            if text not in seen:
+                mask = _caption_mask(text, font_size)
+                packed = np.packbits(mask, axis=1, bitorder="little")
+                seen[text] = (8 * sum(len(x) for x in blob), 8 * packed.shape[1], mask.shape[1], mask.shape[0])
+                blob.append(packed.tobytes())
+            bit, pitch, mw, mh = seen[text]
+            x1, y1, x2, y2 = (clamp(v) for v in b)
+            boxes.append((x1, y1, x2, y2))
+            captions.append((x1, clamp(int(b[1]) - 10 - mh), mw, mh))
+            mask_bits.append(bit)
+            mask_pitch.append(pitch)
+            cx0, cy0, cx1, cy1 = max(x1, 0), max(y1, 0), min(x2, W), min(y2, H)
+            if cx0 < cx1 and cy0 < cy1:
+                image(p, k, cx0, cy0, cx1 - cx0, cy1 - cy0, k + 1, k)
+        if dets:
+            image(p, None, 0, 0, W, H, len(dets), len(dets))
+        op_begin.append(len(boxes))
+    i32 = lambda v, shape: np.ascontiguousarray(v, np.int32).reshape(shape)
+    return {
+        "heights": i32([s[0] for s in shapes], (-1,)), "widths": i32([s[1] for s in shapes], (-1,)), "op_begin": i32(op_begin, (-1,)),
+        "boxes": i32(boxes, (-1, 4)), "captions": i32(captions, (-1, 4)), "mask_bits": np.ascontiguousarray(mask_bits, np.int64),
+        "mask_pitch": i32(mask_pitch, (-1,)), "masks": np.frombuffer(b"".join(blob), np.uint8),
+        "out_page": i32(out_page, (-1,)), "out_rects": i32(out_rects, (-1, 4)), "out_outlines": i32(out_outlines, (-1,)),
+        "out_captions": i32(out_captions, (-1,)), "out_offsets": np.ascontiguousarray(out_offsets, np.int64),
+        "thickness": int(thickness), "images": images, "out_bytes": pos,
+    }
+
+
+def _render_args(plan, page_ptrs, masks_ptr, out_ptr):
+    """The arguments rtn_render_pages (behind the handle, before the workspace), rtn_render_host and rtn_render_tiles_host share."""
+    import ctypes as C
+    n = len(page_ptrs)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    return [n, (C.c_void_p * max(n, 1))(*page_ptrs), ptr(plan["heights"]), ptr(plan["widths"]), plan["op_begin"].ctypes.data,
+            len(plan["boxes"]), ptr(plan["boxes"]), ptr(plan["captions"]), ptr(plan["mask_bits"]), ptr(plan["mask_pitch"]),
+            masks_ptr, plan["masks"].size, len(plan["images"]), ptr(plan["out_page"]), ptr(plan["out_rects"]),
+            ptr(plan["out_outlines"]), ptr(plan["out_captions"]), ptr(plan["out_offsets"]), plan["thickness"], out_ptr,
+            plan["out_bytes"]]
+
+
+def _render_files(plan, kept, ended, sources, rendered, result_dir, image_names):
+    """(paths, images) of the files render_detections writes for the pages of a plan, in its order: `sources` the pages as they
+    came, `rendered` the output images of plan["images"].  A crop whose rectangle is empty has no file."""
+    by_page = {}
+    for (p, k, _h, _w, _off), img in zip(plan["images"], rendered):
+        by_page.setdefault(p, {})[k] = img
+    paths, images = [], []
+    for p, name in enumerate(image_names):
+        crop_name, none_name, page_name = _render_names(result_dir, name)
+        mine = by_page.get(p, {})
+        if not kept[p] and ended[p] is not None:
+            paths.append(none_name(ended[p]))
+            images.append(sources[p])
+        for k in range(len(kept[p])):
+            if k in mine:
+                paths.append(crop_name(k))
+                images.append(mine[k])
+        paths.append(page_name)
+        images.append(mine[None] if kept[p] else sources[p])
+    return paths, images
+
+
+def _render_device(plan, pages):
+    """One rtn_render_pages launch on the current stream for the plan's images over the CUDA pages -> (the output buffer, its
+    (h, w, 3) views in the order of plan["images"]); (None, []) for a plan without images."""
+    if not plan["images"]:
+        return None, []
+    h = _rt.handle()
+    out = torch.empty(plan["out_bytes"], dtype=torch.uint8, device=pages[0].device)
+    masks = torch.from_numpy(plan["masks"].copy()).to(out.device) if plan["masks"].size else None
+    wsb = int(L.lib.rtn_render_workspace_bytes(len(pages), len(plan["boxes"]), len(plan["images"])))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=out.device)
+    args = _render_args(plan, [p.data_ptr() for p in pages], masks.data_ptr() if masks is not None else None, out.data_ptr())
+    h.check(L.lib.rtn_render_pages(h.raw, *args, ws.data_ptr(), wsb))
+    return out, [out[off:off + hh * ww * 3].view(hh, ww, 3) for (_p, _k, hh, ww, off) in plan["images"]]
+
+
+def render_detections_device(draw_pages, boxes, scores, labels, image_scales, result_dir, image_names, labels_to_names=None,
+                             score_threshold=0.6, png="host", return_pages=False):
+    """render_detections for a batch of pages that live on the device.  draw_pages: list of CUDA uint8 (H,W,3) B,G,R pages (what
+    read_images_bgr returns; sizes may differ; never written); boxes, scores, labels: the (B,300,·) detections, CUDA or host;
+    image_scales and image_names: one per page.  The detections come to the host in one copy, the kept list of every page is
+    render_detections' (the same helper), one rtn_render_pages launch paints all crops and annotated pages of the batch into one
+    buffer (csrc/rtn_render.hip), and one write_images_bgr(..., png=png) call writes all files of the batch under
+    render_detections' names: .jpg names at cv2.imwrite's quality 95, 4:2:0 through the device encoder.  A page without a kept
+    detection is written as it came.  One difference from render_detections: crop k is the page rectangle
+    [max(x1,0), min(x2,W)) x [max(y1,0), min(y2,H)); where that is empty no file is written for k (render_detections raises inside
+    Pillow) and the numbering of the others stays.  Returns the kept list per page; with return_pages=True also, per page, (list
+    of the crops as CUDA tensors, None for an empty one; the annotated page), the source page itself where nothing was kept."""
+    pages = list(draw_pages)
+    image_names = list(image_names)
+    for i, p in enumerate(pages):
+        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.uint8 and p.dim() == 3 and p.shape[2] == 3
+                and p.shape[0] >= 1 and p.shape[1] >= 1):
+            raise ValueError("page %d: a CUDA uint8 (H,W,3) tensor expected, got %s" % (
+                i, "%s %s" % (p.dtype, tuple(p.shape)) if isinstance(p, torch.Tensor) else type(p).__name__))
+    host3 = []
+    if any(isinstance(a, torch.Tensor) and a.is_cuda for a in (boxes, scores, labels)):
+        torch.cuda.synchronize()                    # Engine.detect may have run on a stream of its own (in_flight > 1)
+    for a in (boxes, scores, labels):
+        host3.append(a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a))
+    boxes, scores, labels = host3
+    if not (len(pages) == len(image_names) == len(image_scales) == len(boxes) == len(scores) == len(labels)):
+        raise ValueError("%d pages, %d names, %d scales, %d / %d / %d detection rows" % (
+            len(pages), len(image_names), len(image_scales), len(boxes), len(scores), len(labels)))
+    kept, ended = [], []
+    for i in range(len(pages)):
+        k, e = _kept_detections(boxes[i:i + 1], scores[i:i + 1], labels[i:i + 1], image_scales[i], score_threshold)
+        kept.append(k)
+        ended.append(e)
+    pages = [p.contiguous() for p in pages]
+    plan = _render_plan([(p.shape[0], p.shape[1]) for p in pages], kept, labels_to_names)
+    rendered = _render_device(plan, pages)[1]
+    paths, images = _render_files(plan, kept, ended, pages, rendered, result_dir, image_names)
+    write_images_bgr(paths, images, png=png)
+    if not return_pages:
+        return kept
+    per_page = [([None] * len(k), p) for k, p in zip(kept, pages)]
+    for (p, k, _h, _w, _off), img in zip(plan["images"], rendered):
+        if k is None:
+            per_page[p] = (per_page[p][0], img)
+        else:
+            per_page[p][0][k] = img
+    return kept, per_page
+
+
+def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
+                 min_side=800, max_side=1333):
+    """The loop of RetinaNet.py's test() over files, in batches of batch_size, with every pixel on the device: read_images_bgr of
+    the preprocessed pages (src_paths) and of the pages to draw on (orig_paths), compute_inputs_device, the inference model's
+    engine().detect, render_detections_device with image_names = basename(src_paths).  `model`: a retinanet_bbox model (ValueError
+    otherwise).  Returns the kept list of every file."""
+    import os
+    from . import preprocess
+    from .page_io import read_images_bgr
+    if not getattr(model, "bbox", False):
+        raise ValueError("detect_files: the inference model (retinanet_bbox) is required")
+    src_paths, orig_paths = list(src_paths), list(orig_paths)
+    if len(src_paths) != len(orig_paths):
+        raise ValueError("%d preprocessed pages for %d pages to draw on" % (len(src_paths), len(orig_paths)))
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    dtype = torch.float32 if model._root().dtype == "f32" else torch.bfloat16
+    eng = model.engine()
+    kept = []
+    for i in range(0, len(src_paths), int(batch_size)):
+        src, orig = src_paths[i:i + int(batch_size)], orig_paths[i:i + int(batch_size)]
+        canvas, scales = preprocess.compute_inputs_device(read_images_bgr(src), min_side=min_side, max_side=max_side, dtype=dtype)
+        boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
+        kept += render_detections_device(read_images_bgr(orig), boxes, scores, labels, scales, result_dir,
+                                         [os.path.basename(p) for p in src], labels_to_names=labels_to_names,
+                                         score_threshold=score_threshold, png=png)
     return kept
