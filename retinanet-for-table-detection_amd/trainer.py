@@ -468,8 +468,17 @@ class Trainer:
         fu = plan["fusion"]
         h1s = [blk["b2"] for blk in fu["blocks64"]] + [fb["b2"] for fb in fu["first_blocks"] if fb["f"] == 64]
         keep_fwd = (any(t.data_ptr() in reads for t in h1s), any(b[0] == "poolbwd" for b in bops))
+        # id(forward tensor) -> the tensor that holds its gradient after the backward pass: its own buffer, or the aliased sum's for a
+        # tensor whose only consumer is a residual add.  grad_src keeps those forward tensors alive, so the ids stay valid.
+        grad_of_map = dict(grads)
+        grad_of_map.update({t_: st_[1] for t_, st_ in gstate.items() if isinstance(st_, tuple)})
+        fwd = {}
+        for op in ops:
+            ts = (list(op[3]["xs"]) + list(op[3]["ys"]) + [r for r in op[3]["res"] if r is not None]) if op[0] == "conv" else \
+                [op[1], op[2]] if op[0] in ("pool", "relu") else []
+            fwd.update((tid(t), t) for t in ts)
         bp = {"bops": bops, "keep": keep, "last_bias_bop": bias_bops[-1] if bias_bops else -1, "wgrad_ws_bytes": max_ws,
-              "keep_fwd": keep_fwd,
+              "keep_fwd": keep_fwd, "grad_of": grad_of_map, "grad_src": [fwd[t_] for t_ in grad_of_map],
               "d_reg": d_reg, "d_cls": d_cls, "dyp_cls": dyp_cls, "loss_ws": loss_ws, "plan": plan, "rowinfo": {}}
         self.bplans[key] = bp
         return bp

@@ -28,6 +28,15 @@ without one there is nowhere for a partial sum to go.)  Weight and bias gradient
 pieces runs its own chain over ceil(P / splits) pixels (32 per MFMA for the weights; every 4th pixel per lane for the fused bias
 sums, then <= 16 lane partials), then the pieces are added in order: L = ceil(P / (splits x step)) + splits + 1 (+ 16 for the bias).
 
+GRADIENTS OF THE TRAINING STEP (test_gpu_backward_audit.py).  A weight gradient is one such sum over P pixels: wgrad_ref, with the
+chain lengths above.  The gradient of an activation T is m (.) sum_j c_j over its n consumers, m = (T > 0) where the model puts a
+ReLU on T: dgrad_ref for a consuming convolution (L_j = conv_L of its kh kw Cout products per element), the sum's own gradient for
+an identity add (L_j = 0), upsample_bwd_ref for UpsampleLike + Add (L_j = the destination pixels of one source pixel), maxpool_bwd_ref
+for the pool (L_j = 4 windows).  The device writes the c_j one launch after another into one buffer of the activation's dtype, so the
+running sum is rounded n - 1 times before the final rounding, each time by at most REL sum_j |c_j|:
+    |got - ref| <= REL |ref| + gamma(max_j L_j + n) sum_j A_j + (n - 1) REL sum_j |c_j|
+The mask distributes over the sum, so the reference does not depend on where a launch applies it.
+
 Intermediates that a fused launch rounds to bf16 but does not store (the bneck's branch2b output h1, the stem's conv1 output) are
 carried as an INTERVAL: the device's f32 value lies within gamma A of the float64 one, so its bf16 rounding lies between the
 roundings of the two ends.  Where those differ (a rounding midpoint inside the interval), the next layer's bound gets
@@ -243,26 +252,77 @@ def wgrad_ref(x, dy, kh, kw, stride, pad, out_rows=None):
     return D.t() @ P, D.abs().t() @ P.abs(), D.sum(0), D.abs().sum(0)
 
 
-def maxpool_bwd_ref(dy, xin, mode, pool_out=None):
+def dgrad_ref(dy, w, Hin, Win, stride, pad):
+    """Data gradient of a convolution at its input [B, Hin, Win, cin]: for every tap (i, j)
+        dx[b, oy*s - pt + i, ox*s - pl + j, :] += dy[b, oy, ox, :] @ w[:, i, j, :]
+    with positions outside the image dropped.  dy [B, Ho, Wo, cout] (any dtype), w [cout, kh, kw, cin] float64.  One matmul and one
+    masked index-add per tap.  Returns (dx, A) float64 on dy's device, A the same sum over absolute values."""
+    B, Ho, Wo, N = dy.shape
+    cout, kh, kw, cin = w.shape
+    assert cout == N, (cout, N)
+    dev = dy.device
+    w = w.to(dev)
+    D = dy.reshape(-1, N).double()
+    Da = D.abs()
+    r = torch.arange(B * Ho * Wo, device=dev)
+    b, oy, ox = r // (Ho * Wo), (r % (Ho * Wo)) // Wo, r % Wo
+    dx = torch.zeros(B * Hin * Win, cin, dtype=torch.float64, device=dev)
+    A = torch.zeros_like(dx)
+    for i in range(kh):
+        iy = oy * stride - pad[0] + i
+        for j in range(kw):
+            ix = ox * stride - pad[1] + j
+            ok = (iy >= 0) & (iy < Hin) & (ix >= 0) & (ix < Win)
+            tgt = (b * Hin * Win + iy * Win + ix)[ok]
+            dx.index_add_(0, tgt, D[ok] @ w[:, i, j, :])
+            A.index_add_(0, tgt, Da[ok] @ w[:, i, j, :].abs())
+    return dx.view(B, Hin, Win, cin), A.view(B, Hin, Win, cin)
+
+
+def upsample_bwd_ref(d_dst, Hs, Ws):
+    """Gradient of UpsampleLike at its source [B, Hs, Ws, C]: every destination pixel sends its gradient to the source pixel
+    tf_upsample_index reads it from (the scatter-add inverse of upsample_rows).  Returns (d_src, A) float64 on d_dst's device."""
+    B, Hd, Wd, Cc = d_dst.shape
+    dev = d_dst.device
+    iy = torch.as_tensor(tf_upsample_index(Hs, Hd), device=dev)
+    ix = torch.as_tensor(tf_upsample_index(Ws, Wd), device=dev)
+    r = torch.arange(B * Hd * Wd, device=dev)
+    tgt = (r // (Hd * Wd)) * Hs * Ws + iy[(r % (Hd * Wd)) // Wd] * Ws + ix[r % Wd]
+    g = d_dst.reshape(-1, Cc).double()
+    out = []
+    for gg in (g, g.abs()):
+        out.append(torch.zeros(B * Hs * Ws, Cc, dtype=torch.float64, device=dev).index_add_(0, tgt, gg).view(B, Hs, Ws, Cc))
+    return out[0], out[1]
+
+
+def pool_window_taps(xin):
+    """The nine taps of every MaxPool 3x3 / 2 TF 'same' window of xin [B,H,W,C], in scan order: views [B,Ho,Wo,C] float64, -inf
+    outside the image."""
+    B, H, W, Cc = xin.shape
+    Ho, Wo = (H + 1) // 2, (W + 1) // 2
+    pt, pl = same_pad_before(H, 3, 2), same_pad_before(W, 3, 2)
+    xpad = torch.full((B, H + 4, W + 4, Cc), -math.inf, dtype=torch.float64, device=xin.device)
+    xpad[:, pt:pt + H, pl:pl + W] = xin.double()
+    return [xpad[:, t // 3:t // 3 + 2 * Ho - 1:2, t % 3:t % 3 + 2 * Wo - 1:2] for t in range(9)]
+
+
+def maxpool_bwd_ref(dy, xin, mode, pool_out=None, arg=None):
     """Gradient of MaxPool 3x3 / 2 TF 'same' at its input [B,H,W,C]: every window sends dy to its FIRST maximum in scan order
-    (kh, kw) - TensorFlow's tie rule.  mode 1: dx = 0 where the input (a ReLU output) is <= 0; mode 2: a window passes its gradient
+    (kh, kw) - TensorFlow's tie rule - or to the tap `arg` [B,Ho,Wo,C] (kh * 3 + kw) where the caller has established the winners.  mode 1: dx = 0 where the input (a ReLU output) is <= 0; mode 2: a window passes its gradient
     only when the POOLED tensor `pool_out` (what the kernel reads as its mask) is > 0 there.  Returns (dx, A) float64 on dy's device:
     A = the same routing of |dy|, at most four terms per input pixel."""
     B, H, W, Cc = xin.shape
     Ho, Wo = dy.shape[1], dy.shape[2]
     pt, pl = same_pad_before(H, 3, 2), same_pad_before(W, 3, 2)
     dev = dy.device
-    best = torch.full((B, Ho, Wo, Cc), -math.inf, dtype=torch.float64, device=dev)
-    arg = torch.zeros(B, Ho, Wo, Cc, dtype=torch.uint8, device=dev)
-    xpad = torch.full((B, H + 4, W + 4, Cc), -math.inf, dtype=torch.float64, device=dev)
-    xpad[:, pt:pt + H, pl:pl + W] = xin.double()
-    for t in range(9):
-        i, j = t // 3, t % 3
-        v = xpad[:, i:i + 2 * Ho - 1:2, j:j + 2 * Wo - 1:2]
-        take = v > best                      # strict: the first maximum in scan order keeps its place
-        best = torch.where(take, v, best)
-        arg[take] = t
-    del xpad, best
+    if arg is None:
+        best = torch.full((B, Ho, Wo, Cc), -math.inf, dtype=torch.float64, device=dev)
+        arg = torch.zeros(B, Ho, Wo, Cc, dtype=torch.uint8, device=dev)
+        for t, v in enumerate(pool_window_taps(xin)):
+            take = v > best                      # strict: the first maximum in scan order keeps its place
+            best = torch.where(take, v, best)
+            arg[take] = t
+        del best
     g = dy.double()
     if mode == 2:
         g = torch.where(pool_out.to(dev) > 0, g, torch.zeros_like(g))

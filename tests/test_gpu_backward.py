@@ -330,6 +330,82 @@ def test_wgrad_window_kernel(pkg, handle, monkeypatch, levels, cin, cout, B, bia
     assert float((db0 - db1).abs().max()) <= 1e-3 * max(1.0, float(wantb.abs().max())) if bias else True
 
 
+@pytest.mark.parametrize("levels,cin,cout,B,concat", [
+    ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, 256, 4, False),
+    ([(40, 67)], 128, 128, 3, False),
+    ([(7, 250)], 64, 128, 1, False),
+    ([(40, 334)], 64, 64, 2, False),
+    ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, 64, 4, True),
+])
+def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypatch, levels, cin, cout, B, concat):
+    """x and dY are integers in [-2, 2] stored as bf16: every product and every partial sum is an integer below 2^24, so dW and db
+    must equal the float64 sums bit for bit whatever the summation order, the split count or the kernel - one pixel dropped or
+    counted twice changes an entry by at least 1.  The window kernel, then the general kernels under RTN_WGRAD_DMA unset / 2 / 0,
+    each with the launcher's own split count and with RTN_WGRAD_BLOCKS = 64 and 1024; the kernel that ran is asserted."""
+    L = pkg._lib
+    tdt, code = DT["bf16"]
+    total = sum(H * W for H, W in levels)
+    dyfull = torch.zeros(B, total, cout, dtype=tdt, device=DEV) if concat else None
+    g = torch.Generator().manual_seed(1300 + cin + cout)
+    w = torch.zeros(3, 3, cin, cout, dtype=torch.float64, requires_grad=True)
+    d = L.ConvDesc()
+    d.ngroups, d.batch, d.dtype = len(levels), B, code
+    d.w_rows, d.N, d.KH, d.KW = cout, cout, 3, 3
+    d.Crun = d.pix_stride = cin
+    d.sy = d.sx = 1
+    d.pad_t = d.pad_l = 1
+    d.out_ld = cout
+    keep, want, wantb, off, tiles = [], 0, 0, 0, 0
+    for gi, (H, W) in enumerate(levels):
+        x = torch.randint(-2, 3, (B, H, W, cin), generator=g).double()
+        dy = torch.randint(-2, 3, (B, H, W, cout), generator=g).double()
+        want = want + torch.autograd.grad(fwd_ref(x, w, 1, 1, 1, H, W), w, dy)[0]
+        wantb = wantb + dy.sum(dim=(0, 1, 2))
+        xd, dyd = x.to(tdt).to(DEV).contiguous(), dy.to(tdt).to(DEV).contiguous()
+        keep += [xd, dyd]
+        grp = L.ConvGroup()
+        grp.in_, grp.in_elems = xd.data_ptr(), xd.numel()
+        grp.in_img_stride, grp.in_row_stride = H * W * cin, W * cin
+        grp.Hin, grp.Win, grp.Hout, grp.Wout = H, W, H, W
+        if concat:
+            dyfull[:, off:off + H * W, :] = dyd.reshape(B, H * W, cout)
+            grp.out, grp.out_elems, grp.out_img_stride, grp.out_off = dyfull.data_ptr(), dyfull.numel(), total * cout, off * cout
+            off += H * W
+        else:
+            grp.out, grp.out_elems, grp.out_img_stride = dyd.data_ptr(), dyd.numel(), H * W * cout
+        d.g[gi] = grp
+        tiles += -(-B * H * W // 64)
+    wantm = want.permute(3, 0, 1, 2).reshape(cout, -1)
+    assert float(wantm.abs().max()) < 2 ** 24 and float(wantm.abs().max()) > 64
+    wantm, wantb = wantm.float(), wantb.float()
+    big = cout > 128                                       # the 256 x 256 LDS-DMA kernel needs more than 128 filters (K = 9 cin >= 256 here)
+    runs = [({"RTN_WGRAD_WIN": "1"}, 4)]
+    for dma, impl in ((None, 2 if (big and tiles >= 2048) else 3), ("2", 2 if big else 3), ("0", 0)):
+        for blocks in (None, "64", "1024"):
+            env = {"RTN_WGRAD_WIN": "0"}
+            if dma is not None:
+                env["RTN_WGRAD_DMA"] = dma
+            if blocks is not None:
+                env["RTN_WGRAD_BLOCKS"] = blocks
+            runs.append((env, impl))
+    for env, impl in runs:
+        for k in ("RTN_WGRAD_WIN", "RTN_WGRAD_DMA", "RTN_WGRAD_BLOCKS"):
+            if k in env:
+                monkeypatch.setenv(k, env[k])
+            else:
+                monkeypatch.delenv(k, raising=False)
+        wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(d))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
+        dW = torch.full((cout, 9 * cin), 3.0, dtype=torch.float32, device=DEV)
+        db = torch.full((cout,), 5.0, dtype=torch.float32, device=DEV)
+        handle.check(L.lib.rtn_conv2d_wgrad_bias(handle.raw, C.byref(d), dW.data_ptr(), db.data_ptr(), cout, ws.data_ptr(), wsb))
+        torch.cuda.synchronize()
+        assert L.lib.rtn_debug_last_wgrad_impl(handle.raw) == impl, (env, L.lib.rtn_debug_last_wgrad_impl(handle.raw), impl)
+        gw, gb = dW.cpu() - 3.0, db.cpu() - 5.0
+        assert torch.equal(gw, wantm), "%s: dW differs at %d entries, by up to %g" % (env, int((gw != wantm).sum()), float((gw - wantm).abs().max()))
+        assert torch.equal(gb, wantb), "%s: db differs by up to %g" % (env, float((gb - wantb).abs().max()))
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 @pytest.mark.parametrize("H,W,cin,cout,k,B,env", [
     (40, 67, 256, 64, 1, 4, {}),                           # 128 x 128 kernel, many pixel splits (XCD map)

@@ -208,3 +208,149 @@ def test_gradient_bounds_see_one_image_at_the_benched_training_size():
     w, b = emulate(skip=9)
     assert LA.compare(w, ref, A, Lw, "f32")["bad"] > 0
     assert LA.compare(b, bref, bA, Lb, "f32")["bad"] > 0
+
+
+# ------------------------------------------------------------------------------------------------- gradients of the training step
+def dgrad_f32(dy, w, Hin, Win, stride, pad, drop=None, odd=False):
+    """The device's data gradient emulated: f32 accumulation over the taps in K steps of 32 gradient channels, nothing rounded before
+    the caller's epilogue.  drop = (tap i, tap j, input column): that tap never reaches that column (a border test off by one);
+    odd: the stride grid starts at pixel 1 instead of pixel 0.  Returns [B, Hin, Win, cin] f32."""
+    Bn, Ho, Wo, N = dy.shape
+    cout, kh, kw, cin = w.shape
+    D = dy.reshape(-1, N).float()
+    r = torch.arange(Bn * Ho * Wo)
+    b, oy, ox = r // (Ho * Wo), (r % (Ho * Wo)) // Wo, r % Wo
+    dx = torch.zeros(Bn * Hin * Win, cin)
+    for i in range(kh):
+        iy = oy * stride - pad[0] + i + (1 if odd else 0)
+        for j in range(kw):
+            ix = ox * stride - pad[1] + j + (1 if odd else 0)
+            ok = (iy >= 0) & (iy < Hin) & (ix >= 0) & (ix < Win)
+            if drop is not None and (i, j) == drop[:2]:
+                ok = ok & (ix != drop[2])
+            wt = w[:, i, j, :].float()
+            for k in range(0, N, KS):
+                dx.index_add_(0, (b * Hin * Win + iy * Win + ix)[ok], D[ok][:, k:k + KS] @ wt[k:k + KS])
+    return dx.view(Bn, Hin, Win, cin)
+
+
+@pytest.fixture(scope="module")
+def gcase():
+    g = torch.Generator().manual_seed(21)
+    Bn, Hn, Wn, Cn = 2, 9, 11, 64
+    return {"B": Bn, "H": Hn, "W": Wn, "C": Cn,
+            "w3": bf(torch.randn(Cn, 3, 3, Cn, generator=g) * math.sqrt(2.0 / (9 * Cn))).double(),
+            "w1": bf(torch.randn(Cn, 1, 1, Cn, generator=g) * math.sqrt(2.0 / Cn)).double(),
+            "dy": bf(torch.randn(Bn, Hn, Wn, Cn, generator=g)),
+            "dy2": bf(torch.randn(Bn, (Hn + 1) // 2, (Wn + 1) // 2, Cn, generator=g)),
+            "ident": bf(torch.randn(Bn, Hn, Wn, Cn, generator=g)),
+            "act": bf(torch.relu(torch.randn(Bn, Hn, Wn, Cn, generator=g)))}
+
+
+def test_one_dropped_pixel_of_a_weight_gradient_is_flagged():
+    """A 3x3 layer at P = 2 x 80 x 112 pixels under the bound the GPU audit uses (splits = 1): the f32 reduction in 32-pixel steps
+    passes, and so does one cut into 7 ordered pieces; one pixel of 17920 left out of the sum is flagged."""
+    g = torch.Generator().manual_seed(17)
+    Bn, Hn, Wn, C1, C2 = 2, 80, 112, 16, 16
+    P = Bn * Hn * Wn
+    x = bf(torch.relu(torch.randn(Bn, Hn, Wn, C1, generator=g)))
+    dy = bf(torch.randn(Bn, Hn, Wn, C2, generator=g))
+    ref, A, bref, bA = LA.wgrad_ref(x, dy, 3, 3, 1, (1, 1))
+    Lw, Lb = LA.L_TABLE["wgrad_bf16"](P, 1), LA.L_TABLE["bgrad"](P, 1)
+    G = LA.gather(x, torch.arange(P), Hn, Wn, 3, 3, 1, (1, 1)).float()
+
+    def emulate(pieces, skip=None):
+        D = dy.reshape(-1, C2).float().clone()
+        if skip is not None:
+            D[skip] = 0
+        per = -(-P // pieces)
+        w, b = torch.zeros(C2, G.shape[1]), torch.zeros(C2)
+        for p0 in range(0, P, per):
+            pw, pb = torch.zeros(C2, G.shape[1]), torch.zeros(C2)
+            for lo in range(p0, min(P, p0 + per), 32):
+                hi = min(lo + 32, p0 + per)
+                pw = pw + D[lo:hi].t() @ G[lo:hi]
+                pb = pb + D[lo:hi].sum(0)
+            w, b = w + pw, b + pb
+        return w, b
+
+    for pieces in (1, 7):
+        w, b = emulate(pieces)
+        assert LA.compare(w, ref, A, Lw, "f32")["bad"] == 0 and LA.compare(b, bref, bA, Lb, "f32")["bad"] == 0, pieces
+    w, b = emulate(1, skip=Hn * Wn + 37 * Wn + 5)
+    assert LA.compare(w, ref, A, Lw, "f32")["bad"] > 0
+
+
+def test_dropped_border_tap_of_a_data_gradient_is_flagged(gcase):
+    c = gcase
+    ref, A = LA.dgrad_ref(c["dy"], c["w3"], c["H"], c["W"], 1, (1, 1))
+    L = LA.conv_L(9 * c["C"], "bf16")
+    good = bf(dgrad_f32(c["dy"], c["w3"], c["H"], c["W"], 1, (1, 1)))
+    assert LA.compare(good, ref, A, L, "bf16")["bad"] == 0
+    for col, tap in ((0, (1, 0)), (c["W"] - 1, (2, 2))):          # the tap that reaches the first / last column from inside the image
+        bad = bf(dgrad_f32(c["dy"], c["w3"], c["H"], c["W"], 1, (1, 1), drop=tap + (col,)))
+        r = LA.compare(bad, ref, A, L, "bf16")
+        assert r["bad"] > 0, (col, tap, r)
+        assert torch.equal(bad[:, :, 1:-1], good[:, :, 1:-1])     # the defect is confined to that one column
+
+
+def test_stride2_gradient_on_the_odd_grid_is_flagged(gcase):
+    """A stride-2 1x1 'valid' convolution: its data gradient lives on the even pixels; the same values one pixel off are flagged."""
+    c = gcase
+    ref, A = LA.dgrad_ref(c["dy2"], c["w1"], c["H"], c["W"], 2, (0, 0))
+    assert not bool(ref[:, 1::2].any()) and not bool(ref[:, :, 1::2].any()) and bool(ref[:, ::2, ::2].any())
+    L = LA.conv_L(c["C"], "bf16")
+    assert LA.compare(bf(dgrad_f32(c["dy2"], c["w1"], c["H"], c["W"], 2, (0, 0))), ref, A, L, "bf16")["bad"] == 0
+    assert LA.compare(bf(dgrad_f32(c["dy2"], c["w1"], c["H"], c["W"], 2, (0, 0), odd=True)), ref, A, L, "bf16")["bad"] > 0
+
+
+def test_relu_mask_on_one_contribution_only_is_flagged(gcase):
+    """A block input T = relu(.) with two consumers: the next block's identity add (its gradient arrives unmasked, as an alias of the
+    sum's gradient) and a 1x1 convolution.  dT = (T > 0) (ident + dgrad); masking the convolution's part alone leaves the identity
+    gradient alive where T = 0.  The bound of the GPU audit for a sum of n = 2 contributions."""
+    c = gcase
+    conv, Ac = LA.dgrad_ref(c["dy"], c["w1"], c["H"], c["W"], 1, (0, 0))
+    ident = c["ident"].double()
+    m = c["act"] > 0
+    zero = torch.zeros_like(conv)
+    ref, A = torch.where(m, conv + ident, zero), torch.where(m, Ac + ident.abs(), zero)
+    n = 2
+    L = LA.conv_L(c["C"], "bf16") + n
+    extra = (n - 1) * LA.REL["bf16"] * torch.where(m, conv.abs() + ident.abs(), zero)
+    f32 = dgrad_f32(c["dy"], c["w1"], c["H"], c["W"], 1, (0, 0))
+    good = bf(torch.where(m, f32 + c["ident"].float(), torch.zeros_like(f32)))
+    assert LA.compare(good, ref, A, L, "bf16", extra=extra)["bad"] == 0
+    # written in two launches: the identity part masked and rounded first, the convolution added to it
+    two = bf(torch.where(m, f32, torch.zeros_like(f32)) + bf(torch.where(m, c["ident"].float(), torch.zeros_like(f32))).float())
+    assert LA.compare(two, ref, A, L, "bf16", extra=extra)["bad"] == 0
+    bad = bf(torch.where(m, f32, torch.zeros_like(f32)) + c["ident"].float())
+    assert LA.compare(bad, ref, A, L, "bf16", extra=extra)["bad"] > 0
+
+
+def test_upsample_bwd_ref_inverts_the_forward_index():
+    g = torch.Generator().manual_seed(2)
+    Bn, Hs, Ws, Hd, Wd, Cn = 2, 5, 7, 10, 14, 3
+    d = torch.randn(Bn, Hd, Wd, Cn, generator=g)
+    src = torch.randn(Bn, Hs, Ws, Cn, generator=g).double()
+    up = LA.upsample_rows(src, torch.arange(Bn * Hd * Wd), Hd, Wd).view(Bn, Hd, Wd, Cn)
+    got, A = LA.upsample_bwd_ref(d, Hs, Ws)
+    assert abs(float((up * d.double()).sum()) - float((src * got).sum())) <= 1e-9          # <U s, d> = <s, U^T d>
+    assert torch.equal(A, LA.upsample_bwd_ref(d.abs(), Hs, Ws)[0])
+    got2, _ = LA.upsample_bwd_ref(d[:, :9, :13], Hs, Ws)                                   # odd extents: 9 x 13 over 5 x 7
+    assert abs(float(got2.sum()) - float(d[:, :9, :13].double().sum())) <= 1e-9
+
+
+@pytest.mark.parametrize("Hn,Wn,k,s", [(9, 11, 3, 1), (10, 13, 3, 2), (9, 12, 3, 2), (9, 11, 1, 2)])
+def test_dgrad_ref_is_the_adjoint_of_the_forward_reference(Hn, Wn, k, s):
+    """<conv(x), dy> = <x, dgrad(dy)> against conv_rows_ref, at even and odd extents of the stride-2 'same' padding."""
+    g = torch.Generator().manual_seed(Hn * Wn + k)
+    Bn, C1, C2 = 2, 5, 6
+    x = torch.randn(Bn, Hn, Wn, C1, generator=g).double()
+    w = torch.randn(C2, k, k, C1, generator=g).double()
+    Ho, Wo = -(-Hn // s), -(-Wn // s)
+    pad = (LA.same_pad_before(Hn, k, s), LA.same_pad_before(Wn, k, s))
+    dy = torch.randn(Bn, Ho, Wo, C2, generator=g).double()
+    y, _ = LA.conv_rows_ref(x, torch.arange(Bn * Ho * Wo), Ho, Wo, w, s, pad)
+    dx, A = LA.dgrad_ref(dy, w, Hn, Wn, s, pad)
+    assert abs(float((y * dy.reshape(-1, C2)).sum()) - float((x * dx).sum())) <= 1e-9 * float(A.sum())
+    assert bool((A >= dx.abs() - 1e-12).all())
