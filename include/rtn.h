@@ -774,6 +774,56 @@ int rtn_render_tiles_host(int n_pages, const uint8_t* const* pages, const int32_
                           const int32_t* out_rects, const int32_t* out_outlines, const int32_t* out_captions,
                           const int64_t* out_offsets, int thickness, uint8_t* out, size_t out_bytes);
 
+/* ---- header detection (HeaderDetect.py main() on the device: HSV k-means elbow sweep and patches) ---------------------
+ * A batch is n table crops.  Crop i, uint8 (heights[i], widths[i], 3) B,G,R with sides 1 .. 65500, is resampled to dst_heights[i] x
+ * RTN_HEADER_WIDTH (dst_heights[i] = int(h * (500 / w)) in doubles, >= 1, 500 * dst_heights[i] <= RTN_HEADER_MAX_POINTS) and owns the
+ * points offsets[i] .. offsets[i] + N_i - 1 (N_i = 500 * dst_heights[i]; offsets is the running sum of the N_i from 0) of the packed
+ * buffers: hsv (3 bytes per point: H in [0,180), S, V by OpenCV's 8-bit BGR2HSV) and labels (9 bytes per point: crop i's labels of
+ * the k-cluster fit are the N_i bytes at 9 * offsets[i] + (k - 1) * N_i).  heights, widths, dst_heights, offsets, ks and the patch
+ * tables are host arrays; on the device entries the crops, hsv, labels, the per-k outputs, hist, out and the workspace (256-byte
+ * aligned, >= rtn_header_workspace_bytes(n, n_patches)) are device memory, hsv and labels 4-byte aligned.  Each device entry is one
+ * launch on the handle's stream after one copy of its tables into the workspace, for which the call waits on the stream.
+ * rtn_header_sample: the exact box resample (destination pixel = (2 * sum(src * wx * wy) + w * h) / (2 * w * h) in 64-bit integers,
+ *   wx / wy the overlaps of source and destination pixels on the axes scaled by 500 * w and dst_height * h) and BGR2HSV into hsv.
+ * rtn_header_cluster: one workgroup per crop runs k-means for k = 1 .. RTN_HEADER_MAX_K in a chain (float32 centres and distances
+ *   ((H-c0)^2 + (S-c1)^2) + (V-c2)^2, integer sums, at most max_iter >= 1 assignment passes per k, a fit ends when no label changes,
+ *   k + 1 starts from k's fit with the cluster of the largest SSE split along its channel of the largest variance).  Outputs per crop
+ *   and k: centres [n][9][9][3] float, counts [n][9][9] uint32 (both 0 beyond cluster k - 1), passes [n][9] int32, distortion_fx
+ *   [n][9] uint64 (the sum over the points of llrintf(sqrtf(d to the nearest centre) * 65536)) and the labels.
+ * rtn_header_stats: hist [n][9][3][256] uint32, the histogram of every channel of every cluster of the ks[i]-cluster fit (1 .. 9).
+ * rtn_header_patches: patch j, of crop patch_crop[j], is the (dst_height, 500, 3) B,G,R image at out + out_offsets[j] (increasing,
+ *   not overlapping): a point keeps its H,S,V where any point of its 3x3 neighbourhood, clipped to the image, lies in
+ *   [low[j], high[j]] on all three channels and becomes 0,0,0 elsewhere, then OpenCV's 8-bit HSV2BGR.
+ * rtn_header_*_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers of any alignment and no workspace; the kernels' per-element functions (csrc/rtn_header.h), for the cluster twin in the
+ *   kernel's pass structure.  The results are the device's bit for bit. */
+#define RTN_HEADER_MAX_K 9
+#define RTN_HEADER_WIDTH 500
+#define RTN_HEADER_MAX_POINTS (1 << 21)
+size_t rtn_header_workspace_bytes(int n_crops, int n_patches);
+int rtn_header_sample(rtn_handle_t h, int n, const uint8_t* const* crops, const int32_t* heights, const int32_t* widths,
+                      const int32_t* dst_heights, const int64_t* offsets, uint8_t* hsv, size_t hsv_bytes, void* workspace,
+                      size_t workspace_bytes);
+int rtn_header_cluster(rtn_handle_t h, int n, const int32_t* dst_heights, const int64_t* offsets, const uint8_t* hsv, size_t hsv_bytes,
+                       int max_iter, float* centres, uint32_t* counts, int32_t* passes, uint64_t* distortion_fx, uint8_t* labels,
+                       size_t labels_bytes, void* workspace, size_t workspace_bytes);
+int rtn_header_stats(rtn_handle_t h, int n, const int32_t* dst_heights, const int64_t* offsets, const int32_t* ks, const uint8_t* hsv,
+                     size_t hsv_bytes, const uint8_t* labels, size_t labels_bytes, uint32_t* hist, void* workspace,
+                     size_t workspace_bytes);
+int rtn_header_patches(rtn_handle_t h, int n, const int32_t* dst_heights, const int64_t* offsets, const uint8_t* hsv, size_t hsv_bytes,
+                       int n_patches, const int32_t* patch_crop, const uint8_t* low, const uint8_t* high, const int64_t* out_offsets,
+                       uint8_t* out, size_t out_bytes, void* workspace, size_t workspace_bytes);
+int rtn_header_sample_host(int n, const uint8_t* const* crops, const int32_t* heights, const int32_t* widths,
+                           const int32_t* dst_heights, const int64_t* offsets, uint8_t* hsv, size_t hsv_bytes);
+int rtn_header_cluster_host(int n, const int32_t* dst_heights, const int64_t* offsets, const uint8_t* hsv, size_t hsv_bytes,
+                            int max_iter, float* centres, uint32_t* counts, int32_t* passes, uint64_t* distortion_fx, uint8_t* labels,
+                            size_t labels_bytes);
+int rtn_header_stats_host(int n, const int32_t* dst_heights, const int64_t* offsets, const int32_t* ks, const uint8_t* hsv,
+                          size_t hsv_bytes, const uint8_t* labels, size_t labels_bytes, uint32_t* hist);
+int rtn_header_patches_host(int n, const int32_t* dst_heights, const int64_t* offsets, const uint8_t* hsv, size_t hsv_bytes,
+                            int n_patches, const int32_t* patch_crop, const uint8_t* low, const uint8_t* high,
+                            const int64_t* out_offsets, uint8_t* out, size_t out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

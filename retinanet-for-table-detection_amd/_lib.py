@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("RTN_LIB_PATH") or os.path.join(_HERE, "librtn.so")   
 RTN_BF16, RTN_F32, RTN_U8, RTN_FP8, RTN_I32 = 0, 1, 2, 3, 4
 RTN_DET_CLASS_AGNOSTIC, RTN_DET_NO_NMS = 1, 2
 RTN_MAX_GROUPS, RTN_MAX_GT, RTN_MAX_DET = 5, 64, 300
+RTN_HEADER_MAX_K, RTN_HEADER_WIDTH, RTN_HEADER_MAX_POINTS = 9, 500, 1 << 21
 
 CONV_RELU, CONV_SIGMOID, CONV_RES_SAME, CONV_RES_UPSAMPLE, CONV_OUT_F32, CONV_RELU_MASK, CONV_MASK_PRE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 
@@ -229,6 +230,15 @@ SIGNATURES = {
     "rtn_render_pages": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _SZ]),
     "rtn_render_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ]),
     "rtn_render_tiles_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ]),
+    "rtn_header_workspace_bytes": (_SZ, [_I, _I]),
+    "rtn_header_sample": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_header_cluster": (_I, [_P, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_header_stats": (_I, [_P, _I, _P, _P, _P, _P, _SZ, _P, _SZ, _P, _P, _SZ]),
+    "rtn_header_patches": (_I, [_P, _I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_header_sample_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_header_cluster_host": (_I, [_I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_header_stats_host": (_I, [_I, _P, _P, _P, _P, _SZ, _P, _SZ, _P]),
+    "rtn_header_patches_host": (_I, [_I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ]),
 }
 
 

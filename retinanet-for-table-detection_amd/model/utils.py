@@ -1,5 +1,6 @@
 """model/utils.py of the reference: image utilities (:19-211) and model utilities (:218-259) on the device."""
 import sys
+import warnings
 
 import numpy as np
 import torch
@@ -429,11 +430,14 @@ def render_detections_device(draw_pages, boxes, scores, labels, image_scales, re
 
 
 def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
-                 min_side=800, max_side=1333):
+                 min_side=800, max_side=1333, headers=False):
     """The loop of RetinaNet.py's test() over files, in batches of batch_size, with every pixel on the device: read_images_bgr of
     the preprocessed pages (src_paths) and of the pages to draw on (orig_paths), compute_inputs_device, the inference model's
     engine().detect, render_detections_device with image_names = basename(src_paths).  `model`: a retinanet_bbox model (ValueError
-    otherwise).  Returns the kept list of every file."""
+    otherwise).  headers=True also runs HeaderDetect.py's step on the crops of every batch while they are on the device
+    (model/header.py detect_headers) and writes its files under result_dir/headerResults/test_<crop file name without extension>/;
+    a crop too tall for detect_headers' point limit is skipped with a warning.
+    Returns the kept list of every file."""
     import os
     from . import preprocess
     from .page_io import read_images_bgr
@@ -451,7 +455,27 @@ def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_t
         src, orig = src_paths[i:i + int(batch_size)], orig_paths[i:i + int(batch_size)]
         canvas, scales = preprocess.compute_inputs_device(read_images_bgr(src), min_side=min_side, max_side=max_side, dtype=dtype)
         boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
-        kept += render_detections_device(read_images_bgr(orig), boxes, scores, labels, scales, result_dir,
-                                         [os.path.basename(p) for p in src], labels_to_names=labels_to_names,
-                                         score_threshold=score_threshold, png=png)
+        names = [os.path.basename(p) for p in src]
+        got = render_detections_device(read_images_bgr(orig), boxes, scores, labels, scales, result_dir, names,
+                                       labels_to_names=labels_to_names, score_threshold=score_threshold, png=png,
+                                       return_pages=headers)
+        if headers:
+            from . import header
+            got, per_page = got
+            crops, crop_names = [], []
+            for name, (page_crops, _page) in zip(names, per_page):
+                crop_name = _render_names(result_dir, name)[0]
+                for k, crop in enumerate(page_crops):
+                    if crop is not None:
+                        crops.append(crop)
+                        crop_names.append(crop_name(k))
+            out_dir = os.path.join(result_dir, "headerResults")
+            fits = [header.sampled_points(c.shape[0], c.shape[1]) <= header.MAX_POINTS for c in crops]
+            for c, name, ok in zip(crops, crop_names, fits):
+                if not ok:                          # a sliver of a box: 500 x dh points past the limit; its OrigImage.png alone is written
+                    warnings.warn("header detection skipped for %s: %d x %d is too tall for a width of 500" % (name, c.shape[0], c.shape[1]))
+            found = iter(header.detect_headers([c for c, ok in zip(crops, fits) if ok]))
+            paths, images = header._header_outputs(crops, crop_names, [next(found) if ok else None for ok in fits], out_dir)
+            write_images_bgr(paths, images, png=png)
+        kept += got
     return kept
