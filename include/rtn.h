@@ -824,6 +824,58 @@ int rtn_header_patches_host(int n, const int32_t* dst_heights, const int64_t* of
                             int n_patches, const int32_t* patch_crop, const uint8_t* low, const uint8_t* high,
                             const int64_t* out_offsets, uint8_t* out, size_t out_bytes);
 
+/* ---- scan analysis (connectedComponentAnalysis.py on the device: line removal and component heights) ------------------
+ * A batch is n images with sides RTN_CCA_MIN_SIDE .. RTN_CCA_MAX_SIDE, at most 65535 of them.  Pages are uint8 (heights[i], widths[i],
+ * channels[i]) with 3 channels in B,G,R order or 1 (gray); masks are uint8 (h, w), 0 or 255, page i's at offsets[i] (increasing, not
+ * overlapping) of every packed mask buffer of mask_bytes.  heights, widths, channels, offsets, capacity, box_offsets, box_page and the
+ * boxes of rtn_cca_paint are host arrays; on the device entries the pages, masks, counts, boxes and the workspace (256-byte aligned,
+ * >= rtn_cca_workspace_bytes(n, heights, widths, n_boxes) for the same n, sizes and n_boxes, 0 where the entry takes no boxes) are
+ * device memory.  Every device entry queues its launches on the handle's stream after copying its tables into the workspace, for
+ * which the call waits on the stream.  All arithmetic is integer: the same arguments give the same bytes, whatever the buffers held.
+ * rtn_cca_lines_mask: process_graphical_lines up to its two masks.  g = 255 - gray (gray = (1868 b + 9617 g + 4899 r + 8192) >> 14,
+ *   a gray page as it is); S the 15x15 box sum of g with replicated borders; bw = 255 where g - (2 S + 225) / 450 > 2; horizontal =
+ *   bw eroded then dilated along x by the window [x - L / 2, x - L / 2 + L - 1] cut to the image, L = w / 30; vertical the same along
+ *   y with L = h / 30.  No step loops over the window.
+ * rtn_cca_text_mask: process_image up to its closed mask.  The 3-tap blur (27, 202, 27) / 256 with reflected (101) borders, 16 bits
+ *   kept between the passes, (sum + 32768) >> 16; the gray close along x with the window [x - 2, x + 1]; black-hat; > 10; dilate by
+ *   [x - 18, x + 9]; twice dilate then erode by [x - 5, x + 4].
+ * rtn_cca_label: the connected components of n binary images (non-zero is foreground, 8-connected), in the order of the raster
+ *   index y * w + x of their first pixels.  With external_only != 0 only those with a pixel 4-adjacent to the 4-connected background
+ *   region that contains a one-pixel frame around the image (findContours(RETR_EXTERNAL)).  counts[i] receives image i's number of
+ *   components; its first capacity[i] boxes (x, y, w, h, int32) go to boxes + 4 * box_offsets[i] (in boxes; increasing, not
+ *   overlapping; boxes_bytes the size of the buffer).  Where counts[i] > capacity[i] the call returns RTN_EINVAL after writing the
+ *   true counts and the boxes that fit.  The call waits for the counts.  Launches: tiles in LDS, merge across tile borders, flatten,
+ *   frame and external flags, count, scan, rank, boxes, finish; none waits on another workgroup.
+ * rtn_cca_paint: box j (x, y, w, h, all within 0 .. 16384) of page box_page[j], clipped to the page, is painted into the page:
+ *   mode 0 fills [y, y + h) x [x, x + w) with 255; mode 1 draws the outline of thickness 2 from (x, y) to (x + w, y + h) (bands of
+ *   rows / columns [e - 1, e + 1) around every edge e, draw_box of model/utils.py) in (0, 255, 0), 255 on a gray page.
+ * rtn_cca_*_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host pointers
+ *   and no workspace, through the per-element functions of csrc/rtn_cca.h; the results are the device's bit for bit.  The mask twins
+ *   take one more buffer, which may be NULL: bw (as the masks) receives the thresholded image; stages (4 * mask_bytes, page i's four
+ *   planes of h * w from 4 * offsets[i]) receives the blurred, black-hat, thresholded and dilated images. */
+#define RTN_CCA_MIN_SIDE 30
+#define RTN_CCA_MAX_SIDE 16384
+size_t rtn_cca_workspace_bytes(int n, const int32_t* heights, const int32_t* widths, int n_boxes);
+int rtn_cca_lines_mask(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                       const int32_t* channels, const int64_t* offsets, uint8_t* horizontal, uint8_t* vertical, size_t mask_bytes,
+                       void* workspace, size_t workspace_bytes);
+int rtn_cca_text_mask(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                      const int32_t* channels, const int64_t* offsets, uint8_t* closed, size_t mask_bytes, void* workspace,
+                      size_t workspace_bytes);
+int rtn_cca_label(rtn_handle_t h, int n, const uint8_t* const* images, const int32_t* heights, const int32_t* widths, int external_only,
+                  const int32_t* capacity, const int64_t* box_offsets, int32_t* counts, int32_t* boxes, size_t boxes_bytes,
+                  void* workspace, size_t workspace_bytes);
+int rtn_cca_paint(rtn_handle_t h, int n, uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                  int n_boxes, const int32_t* box_page, const int32_t* boxes, int mode, void* workspace, size_t workspace_bytes);
+int rtn_cca_lines_mask_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                            const int64_t* offsets, uint8_t* horizontal, uint8_t* vertical, size_t mask_bytes, uint8_t* bw);
+int rtn_cca_text_mask_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                           const int64_t* offsets, uint8_t* closed, size_t mask_bytes, uint8_t* stages);
+int rtn_cca_label_host(int n, const uint8_t* const* images, const int32_t* heights, const int32_t* widths, int external_only,
+                       const int32_t* capacity, const int64_t* box_offsets, int32_t* counts, int32_t* boxes, size_t boxes_bytes);
+int rtn_cca_paint_host(int n, uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels, int n_boxes,
+                       const int32_t* box_page, const int32_t* boxes, int mode);
+
 #ifdef __cplusplus
 }
 #endif

@@ -239,6 +239,15 @@ SIGNATURES = {
     "rtn_header_cluster_host": (_I, [_I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ]),
     "rtn_header_stats_host": (_I, [_I, _P, _P, _P, _P, _SZ, _P, _SZ, _P]),
     "rtn_header_patches_host": (_I, [_I, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_cca_workspace_bytes": (_SZ, [_I, _P, _P, _I]),
+    "rtn_cca_lines_mask": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_cca_text_mask": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_cca_label": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_cca_paint": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _SZ]),
+    "rtn_cca_lines_mask_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rtn_cca_text_mask_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "rtn_cca_label_host": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _SZ]),
+    "rtn_cca_paint_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _I]),
 }
 
 

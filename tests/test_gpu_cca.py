@@ -1,0 +1,178 @@
+"""GPU tests of scan analysis (csrc/rtn_cca.hip): every device output against its CPU twin's bytes on one mixed batch,
+the inputs untouched, a second call on the same buffers, analyse_scan against the NumPy / scipy oracle (tests/cca_ref.py) and
+analyse_files on two small files."""
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+import cca_cases as K
+
+pytestmark = pytest.mark.gpu
+CCA = K.CCA
+L = CCA.L
+
+
+def cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a).copy()).cuda()
+
+
+def test_labelling_equals_the_twins_on_every_binary_image_in_one_batch(pkg):
+    names = list(K.binaries())
+    imgs = [K.binaries()[nm] for nm in names]
+    dev = [cuda(a) for a in imgs]
+    be = CCA._Device(dev[0].device)
+    sizes = [a.shape for a in imgs]
+    for external in (True, False):
+        got = CCA._label(be, dev, sizes, external_only=external)
+        want = CCA._label(CCA._Twins(), imgs, sizes, external_only=external)
+        for nm, g, w in zip(names, got, want):
+            assert np.array_equal(g, w), (nm, external)
+            assert np.array_equal(g, K.oracle_components(nm, external)), (nm, external)
+    assert all(np.array_equal(d.cpu().numpy(), a) for d, a in zip(dev, imgs))                  # the images are only read
+
+
+def test_label_overflow_reports_the_true_count(pkg):
+    img = K.binaries()["isolated_pixels"]
+    true = len(K.oracle_components("isolated_pixels", True))
+    be = CCA._Device(torch.device("cuda", torch.cuda.current_device()))
+    hs, ws = np.asarray([img.shape[0]], np.int32), np.asarray([img.shape[1]], np.int32)
+    cap, off = np.asarray([10], np.int32), np.zeros(1, np.int64)
+    d = cuda(img)
+    counts, boxes = torch.full((1,), -1, dtype=torch.int32, device="cuda"), torch.full((40,), -1, dtype=torch.int32, device="cuda")
+    wsb = int(L.lib.rtn_cca_workspace_bytes(1, hs.ctypes.data, ws.ctypes.data, 0))
+    wsp = torch.empty(wsb, dtype=torch.uint8, device="cuda")
+    ptrs = (CCA.C.c_void_p * 1)(d.data_ptr())
+    rc = L.lib.rtn_cca_label(be.h.raw, 1, ptrs, hs.ctypes.data, ws.ctypes.data, 1, cap.ctypes.data, off.ctypes.data, counts.data_ptr(),
+                             boxes.data_ptr(), 160, wsp.data_ptr(), wsb)
+    assert rc == -1                                                             # RTN_EINVAL
+    assert int(counts.cpu()[0]) == true > 10
+    assert np.array_equal(boxes.cpu().numpy().reshape(10, 4), K.oracle_components("isolated_pixels", True)[:10])
+
+
+def stages(be, pages, shapes):
+    """Every entry once through one backend -> name -> buffer."""
+    hor, ver, off = CCA._lines_mask(be, pages, shapes)
+    cleaned, line_boxes = CCA._remove(be, pages, shapes)
+    closed, _off = CCA._text_mask(be, cleaned, shapes)
+    heights, drawn = CCA._heights(be, cleaned, shapes, True)
+    out = {"horizontal": hor, "vertical": ver, "closed": closed}
+    for i in range(len(pages)):
+        out["cleaned_%d" % i], out["annotated_%d" % i] = cleaned[i], drawn[i]
+    return out, line_boxes, heights
+
+
+def test_every_device_output_equals_the_twins_on_the_mixed_batch(pkg):
+    names = list(K.pages())
+    pages = [K.pages()[nm] for nm in names]
+    assert len({p.shape for p in pages}) == len(pages) and any(p.ndim == 2 for p in pages)
+    dev = [cuda(p) for p in pages]
+    dev, shapes = CCA._check_batch(dev, True)
+    be = CCA._Device(dev[0].device)
+    got, boxes, heights = stages(be, dev, shapes)
+    torch.cuda.synchronize()
+    want, wboxes, wheights = stages(CCA._Twins(), pages, shapes)
+    assert all(np.array_equal(d.cpu().numpy(), p) for d, p in zip(dev, pages))                # the pages are only read
+    for key in want:
+        assert np.array_equal(got[key].cpu().numpy(), want[key]), key
+    for i, nm in enumerate(names):
+        assert np.array_equal(boxes[i], wboxes[i]) and np.array_equal(heights[i], wheights[i]), nm
+    assert sum(len(b) for b in boxes) > 0 and sum(len(h) for h in heights) > 0
+
+    # a second call of the mask and label entries on the same buffers (stale masks, labels and boxes in place): the same bytes
+    hs, ws, ch, off, total = CCA._layout(shapes)
+    n = len(dev)
+    wsb = int(L.lib.rtn_cca_workspace_bytes(2 * n, np.tile(hs, 2).ctypes.data, np.tile(ws, 2).ctypes.data, 0))
+    wsp = torch.full((wsb,), 0xA5, dtype=torch.uint8, device="cuda")
+    first = {k: got[k].clone() for k in ("horizontal", "vertical", "closed")}
+    ptrs = CCA._pointers(be, dev)
+    for _ in range(2):
+        be.check(L.lib.rtn_cca_lines_mask(be.h.raw, n, ptrs, hs.ctypes.data, ws.ctypes.data, ch.ctypes.data, off.ctypes.data,
+                                          got["horizontal"].data_ptr(), got["vertical"].data_ptr(), total, wsp.data_ptr(), wsb))
+    cleaned = [got["cleaned_%d" % i] for i in range(n)]
+    be.check(L.lib.rtn_cca_text_mask(be.h.raw, n, CCA._pointers(be, cleaned), hs.ctypes.data, ws.ctypes.data, ch.ctypes.data,
+                                     off.ctypes.data, got["closed"].data_ptr(), total, wsp.data_ptr(), wsb))
+    torch.cuda.synchronize()
+    for k in first:
+        assert torch.equal(got[k], first[k]), k
+    images = CCA._mask_views(be, got["horizontal"], off, shapes) + CCA._mask_views(be, got["vertical"], off, shapes)
+    hs2, ws2 = np.tile(hs, 2), np.tile(ws, 2)
+    cap = np.asarray([CCA.max_components(h, w) for h, w in zip(hs2, ws2)], np.int32)
+    box_off = np.concatenate([[0], np.cumsum(cap.astype(np.int64))]).astype(np.int64)
+    counts = torch.full((2 * n,), -7, dtype=torch.int32, device="cuda")
+    out = torch.full((4 * int(box_off[-1]),), -7, dtype=torch.int32, device="cuda")
+    results = []
+    for _ in range(2):
+        be.check(L.lib.rtn_cca_label(be.h.raw, 2 * n, CCA._pointers(be, images), hs2.ctypes.data, ws2.ctypes.data, 1, cap.ctypes.data,
+                                     box_off.ctypes.data, counts.data_ptr(), out.data_ptr(), 16 * int(box_off[-1]), wsp.data_ptr(), wsb))
+        results.append((counts.cpu().numpy().copy(), out.cpu().numpy().copy()))
+    assert np.array_equal(results[0][0], results[1][0]) and np.array_equal(results[0][1], results[1][1])
+    for i in range(n):
+        both = [results[1][1][4 * int(box_off[j]):4 * (int(box_off[j]) + int(results[1][0][j]))].reshape(-1, 4) for j in (i, n + i)]
+        assert np.array_equal(np.concatenate(both), boxes[i]), names[i]
+
+
+def test_pages_of_the_largest_side_equal_the_twins(pkg):
+    """30 x 16384 and 16384 x 30: a thread of a row kernel owns 64 pixels, the line windows are 546 long."""
+    pages = list(K.long_pages().values())
+    dev, shapes = CCA._check_batch([cuda(p) for p in pages], True)
+    got, boxes, heights = stages(CCA._Device(dev[0].device), dev, shapes)
+    want, wboxes, wheights = stages(CCA._Twins(), pages, shapes)
+    for key in want:
+        assert np.array_equal(got[key].cpu().numpy(), want[key]), key
+    for i in range(len(pages)):
+        assert np.array_equal(boxes[i], wboxes[i]) and np.array_equal(heights[i], wheights[i]) and len(boxes[i]) > 0, i
+
+
+def assert_analysis(res, want, where, host):
+    for key in ("line_boxes", "heights", "histogram"):
+        assert np.array_equal(res[key], want[key]), (where, key)
+    assert tuple(res["mode_bin"]) == tuple(want["mode_bin"]), where
+    for key in ("cleaned", "annotated"):
+        assert np.array_equal(host(res[key]), want[key]), (where, key)
+
+
+def test_analyse_scan_equals_the_oracle(pkg):
+    names = list(K.pages())
+    dev = [cuda(K.pages()[nm]) for nm in names]
+    res = CCA.analyse_scan(dev, annotate=True)
+    for nm, r in zip(names, res):
+        assert r["cleaned"].is_cuda and r["annotated"].is_cuda
+        assert_analysis(r, K.oracle(nm), nm, lambda t: t.cpu().numpy())
+    for nm, boxes in zip(names, CCA.text_components(dev)):
+        assert np.array_equal(boxes, K.R.text_boxes(K.pages()[nm])), nm
+    with pytest.raises(ValueError, match="page 1"):
+        CCA.analyse_scan([dev[0], torch.zeros((29, 40, 3), dtype=torch.uint8, device="cuda")])
+    with pytest.raises(ValueError, match="page 0"):
+        CCA.remove_graphical_lines([K.pages()[names[0]]])                      # a host array: CUDA tensors are required
+    assert CCA.analyse_scan([]) == []
+
+
+def read_bgr(path):
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"))[:, :, ::-1]
+
+
+def test_analyse_files_writes_the_cleaned_and_the_annotated_page(pkg, tmp_path):
+    IO = __import__("importlib").import_module("retinanet-for-table-detection_amd.model.page_io")
+    names = ["ruled_table", "gray_page"]
+    paths = []
+    for nm in names:
+        p = str(tmp_path / (nm + ".png"))
+        page = K.pages()[nm]
+        Image.fromarray(page[:, :, ::-1] if page.ndim == 3 else page).save(p)
+        paths.append(p)
+    out = tmp_path / "Temp"
+    res = CCA.analyse_files(paths, str(out))
+    for nm, path, r in zip(names, paths, res):
+        page = IO.read_image_bgr(path)                                          # a gray file is read as B,G,R
+        want = K.R.analyse(page)
+        assert_analysis(r, want, nm, lambda t: t.cpu().numpy())
+        for suffix, key in (("_3.Final.jpg", "cleaned"), ("_9.Final.jpg", "annotated")):
+            f = str(out / (nm + ".png" + suffix))
+            enc = str(tmp_path / ("expected_" + nm + suffix))
+            IO.write_images_bgr([enc], [torch.from_numpy(want[key].copy()).cuda()])
+            assert np.array_equal(read_bgr(f), read_bgr(enc)), f
+    assert sorted(p.name for p in out.iterdir()) == sorted(nm + ".png" + s for nm in names for s in ("_3.Final.jpg", "_9.Final.jpg"))
+    quiet = CCA.analyse_files(paths[:1])
+    assert "annotated" not in quiet[0] and np.array_equal(quiet[0]["heights"], res[0]["heights"])
