@@ -158,7 +158,7 @@ int rtn_debug_conv_sync_timeouts(rtn_handle_t h, const void* workspace, unsigned
 /* Which kernel generation the last convolution launch on this handle ran (1: 128-row register-staged, 2: 256-row LDS-DMA per tap,
  * 3: 256-row shared halo, 4: persistent 8-phase halo kernel, 5: persistent 1x1 kernel, 6: narrow-N head-output kernel).  For tests and profiles: proves which native path executed. */
 int rtn_debug_last_conv_impl(rtn_handle_t h);
-/* Which weight-gradient kernel the last wgrad call of this handle ran: 2 the 256 x 256
+/* Which weight-gradient kernel the last wgrad call of this handle ran (csrc/rtn_wgrad.hip chooses): 2 the 256 x 256
  * LDS-DMA kernel, 3 the 128 x 128 LDS-DMA kernel, 4 the nine-tap window kernel (csrc/rtn_wgrad_win.hip: stride-1 3x3 'same' layers
  * with 64 or a multiple of 128 filters), 0 the register-staged kernel (fp32 and odd shapes). */
 int rtn_debug_last_wgrad_impl(rtn_handle_t h);
@@ -286,7 +286,7 @@ int rtn_pack_dgrad_weights(rtn_handle_t h, const void* w_fwd, void* w_dgrad, int
  * the concatenation of all w_dgrad arrays, 0}; total_elems = sum of w_rows_dgrad * KH*KW*Cout_run. */
 int rtn_pack_dgrad_weights_multi(rtn_handle_t h, const int64_t* table_dev, int nlayers, int64_t total_elems, int dtype);
 
-/* Weight gradient (Conv2DBackpropFilter).  `d` describes the FORWARD convolution with two re-interpretations:
+/* Weight gradient (Conv2DBackpropFilter; csrc/rtn_wgrad.hip).  `d` describes the FORWARD convolution with two re-interpretations:
  * g[i].out / out_elems / out_img_stride / out_off and out_ld describe dY (same dtype as `in`; N and out_ld must span whole
  * 16-byte chunks — the head outputs' 36- and 9-channel gradients are padded to 64 channels with rtn_pad_cast_rows), and
  * w / bias are ignored.  dW is f32 [w_rows][KH*KW*Crun] in the forward weight layout and is ACCUMULATED into (zero it
@@ -323,7 +323,7 @@ int rtn_maxpool3x3s2_tfsame_fwd_idx(rtn_handle_t h, const void* in, void* out, u
 int rtn_maxpool3x3s2_tfsame_bwd_idx(rtn_handle_t h, const void* dy, const uint8_t* idx, const void* x, void* dx, int dtype,
                                     int B, int Hin, int Win, int C, int relu_mask);
 
-/* ---- optimizer: Adam(lr, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=0.001)  (RetinaNet.py:130) ---------------
+/* ---- optimizer (csrc/rtn_optimizer.hip): Adam(lr, beta_1=0.9, beta_2=0.999, epsilon=1e-7, clipnorm=0.001)  (RetinaNet.py:130) ----
  * Parameters live in ONE flat f32 buffer (forward weight layout per layer).  gscale[i] multiplies the raw gradient
  * (frozen-BN fold factor of the layer's output channel; 0 for structurally-zero slots), fold[i] re-creates the forward
  * weight w_fwd[i] = cast(w[i] * fold[i]).  grad_mul rescales g (e.g. 1/world_size).

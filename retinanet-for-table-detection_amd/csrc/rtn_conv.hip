@@ -31,23 +31,8 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr unsigned OOB_OFFSET = 0xFFFFFF00u;   // beyond every buffer: the hardware range check returns zeros
 
-__device__ __forceinline__ uint4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-
-// LDS-DMA: 64 lanes x 16 B land at LDS byte address `lds_addr` (wave-uniform) + lane*16; lanes whose `voff` is outside
-// the descriptor range write zeros.  Issued from asm so that hipcc's waitcnt insertion does not see it (it would
-// drain it with vmcnt(0) before the next ds_read and lose the overlap with the MFMAs); the kernel waits for it itself
-// (dma_wait_all) before the barrier that publishes the buffer.  M0 is saved/restored inside the statement.
-__device__ __forceinline__ void dma16_to_lds(const i32x4& srd, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(lds_addr), "s"(srd)
-                 : "memory");
-}
+// The LDS-DMA pieces (dma16, rtn_device.h) are invisible to hipcc's waitcnt insertion: the kernel waits for them itself before the
+// barrier that publishes the buffer.
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // Wait until at most `stages` x PIECES of this wave's newest vector-memory operations are still in flight (vmcnt
 // retires in order): the older stages' LDS-DMA pieces have landed.  `stages` is wave-uniform.
@@ -717,14 +702,14 @@ __global__ __launch_bounds__(NT2, 2) void conv_igemm2_kernel(const KParams p) {
             const int iy_ = iy0[(D) & 3] + kh_, ix_ = ix0[(D) & 3] + kw_;                                           \
             const bool ok_ = (unsigned)iy_ < (unsigned)Hin && (unsigned)ix_ < (unsigned)Win;                        \
             if (DUAL && src2_)                                                                                      \
-                dma16_to_lds(in2_srd, iy0[(D) & 3] > -(1 << 27) ? rowbase2[DUAL ? ((D) & 3) : 0] + delta2_ : OOB_OFFSET,    \
-                             lds_base + (unsigned)((BUF) * SB + wave * 1024 + ((D) & 3) * 8192));                   \
+                dma16(in2_srd, iy0[(D) & 3] > -(1 << 27) ? rowbase2[DUAL ? ((D) & 3) : 0] + delta2_ : OOB_OFFSET,           \
+                      lds_base + (unsigned)((BUF) * SB + wave * 1024 + ((D) & 3) * 8192));                          \
             else                                                                                                    \
-            dma16_to_lds(in_srd, ok_ ? rowbase[(D) & 3] + delta_ : OOB_OFFSET,                                      \
-                         lds_base + (unsigned)((BUF) * SB + wave * 1024 + ((D) & 3) * 8192));                       \
+            dma16(in_srd, ok_ ? rowbase[(D) & 3] + delta_ : OOB_OFFSET,                                             \
+                  lds_base + (unsigned)((BUF) * SB + wave * 1024 + ((D) & 3) * 8192));                              \
         } else {                                                                                                    \
-            dma16_to_lds(w_srd, wk_ + (unsigned)((D) - 4) * wstep,                                                  \
-                         lds_base + (unsigned)((BUF) * SB + A_BYTES + wave * 1024 + ((D) - 4) * 8192));             \
+            dma16(w_srd, wk_ + (unsigned)((D) - 4) * wstep,                                                         \
+                  lds_base + (unsigned)((BUF) * SB + A_BYTES + wave * 1024 + ((D) - 4) * 8192));                    \
         }                                                                                                           \
     }
 
@@ -1042,16 +1027,16 @@ __global__ __launch_bounds__(NT2, 2) void conv_igemm3_kernel(const KParams p) {
         const unsigned delta_ = (unsigned)(dy_ * in_row_stride_b + (CC_) * 128);                                    \
         _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_) {                                                          \
             const bool ok_ = (unsigned)(hiy[i_] + dy_) < (unsigned)Hin;                                             \
-            dma16_to_lds(in_srd, ok_ ? hbase[i_] + delta_ : OOB_OFFSET,                                             \
-                         lds_base + (unsigned)((ABUF) * A_BYTES + wave * 1024 + i_ * 8192));                        \
+            dma16(in_srd, ok_ ? hbase[i_] + delta_ : OOB_OFFSET,                                                    \
+                  lds_base + (unsigned)((ABUF) * A_BYTES + wave * 1024 + i_ * 8192));                               \
         }                                                                                                           \
     }
 #define RTN_B_STAGE(BBUF, KH_, CC_, KW_)                                                                            \
     {                                                                                                               \
         const unsigned wk_ = wbase + (unsigned)((((KH_) * KWn + (KW_)) * nchunk + (CC_)) * 128);                    \
         _Pragma("unroll") for (int d_ = 0; d_ < NBI; ++d_)                                                          \
-            dma16_to_lds(w_srd, wk_ + (unsigned)d_ * wstep,                                                         \
-                         lds_base + (unsigned)(B_BASE + (BBUF) * B_BYTES + wave * 1024 + d_ * 8192));               \
+            dma16(w_srd, wk_ + (unsigned)d_ * wstep,                                                                \
+                  lds_base + (unsigned)(B_BASE + (BBUF) * B_BYTES + wave * 1024 + d_ * 8192));                      \
     }
 
     // B ring of `nbst` stages (2 or 3): the B tile of step kt + nbst - 1 is staged while step kt is multiplied.
@@ -1246,13 +1231,6 @@ __global__ __launch_bounds__(NT2, 2) void conv_igemm3_kernel(const KParams p) {
 int rtn_conv_impl_override() {
     const int v = rtn_env_int("RTN_CONV_IMPL", 0);
     return (v >= 1 && v <= 6) ? v : 0;                 // 4 / 5 / 6 = the persistent kernels (rtn_conv_halo8.hip / rtn_conv_gemm8.hip / rtn_conv_halon.hip) where they apply
-}
-
-int ilog2_exact(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int s = 0;
-    while ((1 << s) < v) ++s;
-    return s;
 }
 
 }  // namespace

@@ -18,8 +18,29 @@ __device__ __forceinline__ i32x4 make_srd(const void* ptr, unsigned bytes) {
     return r;
 }
 
-// 64 lanes x 16 B from (descriptor, per-lane byte offset `voff` + uniform `soff`) to LDS bytes [lds_addr, lds_addr + 1024).
-// asm so that hipcc neither counts nor drains it; the kernel's own counted waits cover it.
+// 16 bytes per lane through a raw buffer resource (lanes whose `voff` is outside its range read zeros)
+__device__ __forceinline__ uint4 buffer_load16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 0);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// LDS-DMA: 64 lanes x 16 B from (descriptor, per-lane byte offset `voff`) to LDS bytes [lds_addr, lds_addr + 1024), lane-linear;
+// `lds_addr` is wave-uniform, lanes whose `voff` is outside the descriptor range write zeros.  Issued from asm so that hipcc's
+// waitcnt insertion neither counts nor drains it (it would wait for vmcnt(0) before the next ds_read and lose the overlap with the
+// MFMAs): the kernel's own counted waits cover it.  M0 is saved / restored inside the statement.  The literal 0 offset is a form of
+// its own: a zero passed to the `soff` overload below occupies an SGPR and moves the callers' register allocation.
+__device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned lds_addr) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(lds_addr), "s"(srd)
+                 : "memory");
+}
+// ... with `lds_addr` forced into an SGPR (readfirstlane), for callers whose address the compiler cannot prove uniform
+__device__ __forceinline__ void dma16_uniform(const i32x4& srd, unsigned voff, unsigned lds_addr) {
+    dma16(srd, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr));
+}
+// ... with a wave-uniform byte offset `soff` added to every lane's `voff`
 __device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned soff, unsigned lds_addr) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"

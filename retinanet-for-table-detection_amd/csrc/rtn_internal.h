@@ -94,6 +94,7 @@ int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
 int rtn_conv_ksplit_finish(rtn_handle_t h, const float* slab, int S, long long M, int N, int ld, const float* bias, int relu, void* out,
                            int out_ld);
 
+// rtn_wgrad.hip: the ordered reduction of the pixel splits of every weight-gradient kernel
 struct rtn_wgrad_frag_t { int ncb, C, Ktot, wpt, co_tile; };   // slabs in the accumulator-fragment order of rtn_wgrad_win.hip (ncb > 0): waves per tile in the slab (8 / 4), filters per tile (128 / 64)
 int rtn_wgrad_finish(rtn_handle_t h, float* dW, const float* slab, int S, long long NK, float* db, const float* bslab, int N, int db_n,
                      int bS = 0 /* parts of bslab when not S */, const rtn_wgrad_frag_t* frag = nullptr);
@@ -109,6 +110,22 @@ void rtn_set_host_error(const char* text);
 int rtn_fail_host(rtn_handle_t h, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 
 static inline int rtn_dtype_size(int dt) { return dt == RTN_F32 ? 4 : (dt == RTN_FP8 ? 1 : 2); }
+
+// log2 of a power of two, -1 for anything else
+static inline int ilog2_exact(int v) {
+    if (v <= 0 || (v & (v - 1))) return -1;
+    int s = 0;
+    while ((1 << s) < v) ++s;
+    return s;
+}
+
+// workgroups of 256 threads for `work` items of a grid-stride loop: at least one, at most `cap`
+static inline unsigned rtn_grid_for(long long work, int cap = 4096) {
+    long long g = (work + 255) / 256;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
 
 // bf16 helpers on raw bits (device + host)
 __host__ __device__ static inline float rtn_bf16_to_f32(unsigned short b) {

@@ -4,7 +4,7 @@
 //
 //     dW[n][(kh, kw, c)] += sum over pixels m of  dY[m][n] * X[m + (kh - 1) * W + (kw - 1)][c]
 //
-// The per-tap kernels (rtn_backward.hip: 256 x 256 tile per tap; rtn_wgrad_halo.hip: one kernel row per tile) stage 7.6 / 5.3 KB of
+// The per-tap kernels (rtn_wgrad.hip: 256 x 256 tile per tap; rtn_wgrad_halo.hip: one kernel row per tile) stage 7.6 / 5.3 KB of
 // operands per MFLOP and read 0.75 / 0.83 transposed fragments per MFMA.  Here a workgroup owns 128 filters x 64 channels x 9 taps
 // (288 KB of f32 accumulators = 144 registers per lane in 8 waves) and walks the pixels ONCE:
 //   * the pixel stream of a level is PADDED with one non-existent pixel after every image row and one non-existent row after every
@@ -79,15 +79,6 @@ struct WWParams {
     int pix_b, dy_ld_b;
     unsigned xring;               // bytes of the X ring
 };
-
-__device__ __forceinline__ void dma16(const i32x4& srd, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    const unsigned la = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(la), "s"(srd)
-                 : "memory");
-}
 
 // transposed fragment: 4 + 4 reduction rows x 16 columns; the addresses are LDS byte offsets (the kernel's dynamic LDS starts at 0)
 __device__ __forceinline__ s16x8 read_tr_at(unsigned lo, unsigned hi) {
@@ -184,14 +175,14 @@ __global__ __launch_bounds__(WW_THREADS) void conv_wgrad_win_kernel(const WWPara
         const int s = lc.k - 2 * lc.D;
         const bool dy_live = live && s >= lc.s_lo;
         const unsigned v0 = slot_offset(s * WW_SP + dy_row, dy_live, g_dyimg, (unsigned)p.dy_ld_b, dy_col);
-        dma16(ys, v0, DY_BASE + dyl_ring + (unsigned)wave * 1024u);
+        dma16_uniform(ys, v0, DY_BASE + dyl_ring + (unsigned)wave * 1024u);
         if (!PS) {
             const unsigned v1 = slot_offset(s * WW_SP + 32 + dy_row, dy_live, g_dyimg, (unsigned)p.dy_ld_b, dy_col);
-            dma16(ys, v1, DY_BASE + dyl_ring + 8192u + (unsigned)wave * 1024u);
+            dma16_uniform(ys, v1, DY_BASE + dyl_ring + 8192u + (unsigned)wave * 1024u);
         }
         const unsigned vx = slot_offset((lc.k - lc.D) * WW_SP + x_row, live, g_ximg, (unsigned)p.pix_b, x_col);
-        dma16(xs, vx, xl_ring + (unsigned)wave * 1024u);
-        if (xl_ring == 0) dma16(xs, vx, XRING + (unsigned)wave * 1024u);
+        dma16_uniform(xs, vx, xl_ring + (unsigned)wave * 1024u);
+        if (xl_ring == 0) dma16_uniform(xs, vx, XRING + (unsigned)wave * 1024u);
         xl_ring = xl_ring == XRING - WW_XBLK ? 0u : xl_ring + WW_XBLK;
         dyl_ring = dyl_ring == (WW_NDY - 1) * WW_DYST ? 0u : dyl_ring + WW_DYST;
         if (live && ++lc.k == lc.k_end) {

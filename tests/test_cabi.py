@@ -2,6 +2,7 @@
 the ctypes structs match the header's layout, and host-only entry points give reference answers.
 No kernel is launched here."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -66,24 +67,86 @@ def test_error_paths_without_gpu(pkg):
     assert L.lib.rtn_generate_anchors(32.0, bad, 0, bad, 1, bad) == -1
 
 
+def wgrad_desc(L, levels, cin, cout, k, B=8, dtype=None, stride=1, out_ld=None, shared_dy=False, first_cell=0):
+    """Weight-gradient descriptor of a k x k 'same' conv over `levels` = [(Hin, Win), ...], one group per level.  shared_dy: the levels'
+    dY lie one after the other inside ONE [B][cells of all levels + first_cell][out_ld] tensor (the head outputs)."""
+    d = L.ConvDesc()
+    d.ngroups, d.batch, d.dtype = len(levels), B, L.RTN_BF16 if dtype is None else dtype
+    d.w_rows, d.N, d.KH, d.KW = cout, cout, k, k
+    d.Crun = d.pix_stride = cin
+    d.sy = d.sx = stride
+    d.pad_t = d.pad_l = k // 2
+    d.out_ld = out_ld = out_ld or cout
+    outs = [((H + stride - 1) // stride, (W + stride - 1) // stride) for H, W in levels]
+    cells_total = first_cell + sum(h * w for h, w in outs)
+    cell_off = first_cell
+    for g, (H, W), (Ho, Wo) in zip(d.g, levels, outs):
+        g.Hin, g.Win, g.Hout, g.Wout = H, W, Ho, Wo
+        g.in_row_stride, g.in_img_stride = W * cin, H * W * cin
+        g.in_elems = B * H * W * cin
+        if shared_dy:
+            g.out_img_stride, g.out_off, g.out_elems = cells_total * out_ld, cell_off * out_ld, B * cells_total * out_ld
+            cell_off += Ho * Wo
+        else:
+            g.out_img_stride, g.out_elems = Ho * Wo * out_ld, B * Ho * Wo * out_ld
+    return d
+
+
+PYRAMID = [(100, 167), (50, 84), (25, 42), (13, 21), (7, 11)]      # P3..P7 of an 800 x 1333 page
+
+
+def wgrad_golden_descs(L):
+    """The descriptors of tests/golden/wgrad_workspace_bytes.json (values recorded from the library before its wgrad launcher was
+    split into check / plan / launch steps: the planning must not have moved)."""
+    return {
+        "res3_1x1_256to64": wgrad_desc(L, [(50, 84)], 256, 64, 1),
+        "res4_branch2b_3x3": wgrad_desc(L, [(50, 84)], 256, 256, 3),
+        "res2_branch2b_3x3_64": wgrad_desc(L, [(200, 334)], 64, 64, 3),
+        "P5_3x3": wgrad_desc(L, [(25, 42)], 256, 256, 3),
+        "wide_rows_3x3": wgrad_desc(L, [(8, 400)], 128, 128, 3),
+        "res3_1x1_128to512": wgrad_desc(L, [(100, 167)], 128, 512, 1),
+        "P6_3x3_stride2": wgrad_desc(L, [(25, 42)], 2048, 256, 3, stride=2),
+        "f32_1x1_256to64": wgrad_desc(L, [(50, 84)], 256, 64, 1, dtype=L.RTN_F32),
+        "f32_P5_3x3": wgrad_desc(L, [(25, 42)], 256, 256, 3, dtype=L.RTN_F32),
+        "f32_P6_3x3_stride2": wgrad_desc(L, [(25, 42)], 256, 256, 3, dtype=L.RTN_F32, stride=2),
+        "head_tower_5_levels": wgrad_desc(L, PYRAMID, 256, 256, 3),
+        "head_tower_5_levels_batch2": wgrad_desc(L, PYRAMID, 256, 256, 3, B=2),
+        "head_output_5_levels_64": wgrad_desc(L, PYRAMID, 256, 64, 3, B=2, shared_dy=True),
+        "head_output_P4_40_of_64": wgrad_desc(L, [(50, 84)], 256, 40, 3, B=2, out_ld=64, shared_dy=True, first_cell=100 * 167),
+        "small_3x3_64to128": wgrad_desc(L, [(17, 21)], 64, 128, 3, B=2),
+        "small_3x3_64to256": wgrad_desc(L, [(17, 21)], 64, 256, 3, B=2),
+        "small_f32_3x3_64to128": wgrad_desc(L, [(9, 13)], 64, 128, 3, B=2, dtype=L.RTN_F32),
+    }
+
+
+WGRAD_KNOBS = ("RTN_WGRAD_WIN", "RTN_WGRAD_DMA", "RTN_WGRAD_BLOCKS", "RTN_WGRAD_SLAB")
+WGRAD_GOLDEN_SETTINGS = [{}, {"RTN_WGRAD_WIN": "0"}, {"RTN_WGRAD_WIN": "1"}, {"RTN_WGRAD_DMA": "0"}, {"RTN_WGRAD_DMA": "2"},
+                         {"RTN_WGRAD_BLOCKS": "64"}, {"RTN_WGRAD_BLOCKS": "1024"}, {"RTN_WGRAD_SLAB": "0"}]
+
+
+def wgrad_workspace_table(L, setenv, delenv):
+    """{descriptor: {knob setting: bytes}} of rtn_conv2d_wgrad_workspace_bytes over the golden descriptors and settings"""
+    table = {}
+    for setting in WGRAD_GOLDEN_SETTINGS:
+        for k in WGRAD_KNOBS:
+            delenv(k, None)
+        for k, v in setting.items():
+            setenv(k, v)
+        label = ",".join("%s=%s" % kv for kv in setting.items()) or "default"
+        for name, d in wgrad_golden_descs(L).items():
+            table.setdefault(name, {})[label] = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(d))
+    for k in WGRAD_KNOBS:
+        delenv(k, None)
+    return table
+
+
 def test_wgrad_workspace_sizes_without_gpu(pkg, monkeypatch):
     """rtn_conv2d_wgrad_workspace_bytes is a host function: the row-info table (16 B per 64-padded pixel) plus, unless RTN_WGRAD_SLAB=0,
     the per-split slabs of the ordered (atomic-free) reduction, or the nine-tap window kernel's slabs where that kernel is taken - always BEHIND the table."""
     L = pkg._lib
 
     def desc(H, W, cin, cout, k, B=8):
-        d = L.ConvDesc()
-        d.ngroups, d.batch, d.dtype = 1, B, L.RTN_BF16
-        d.w_rows, d.N, d.KH, d.KW = cout, cout, k, k
-        d.Crun = d.pix_stride = cin
-        d.sy = d.sx = 1
-        d.pad_t = d.pad_l = k // 2
-        d.out_ld = cout
-        g = d.g[0]
-        g.Hin, g.Win, g.Hout, g.Wout = H, W, H, W
-        g.in_row_stride, g.in_img_stride, g.out_img_stride = W * cin, H * W * cin, H * W * cout
-        g.in_elems, g.out_elems = B * H * W * cin, B * H * W * cout
-        return d
+        return wgrad_desc(L, [(H, W)], cin, cout, k, B)
 
     d = desc(50, 84, 256, 64, 1)
     table = ((8 * 50 * 84 + 63) // 64) * 64 * 16
@@ -115,6 +178,13 @@ def test_wgrad_workspace_sizes_without_gpu(pkg, monkeypatch):
     forced = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(wide))
     monkeypatch.setenv("RTN_WGRAD_WIN", "0")
     assert L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(wide)) == forced
+    # kernel choice, pixel splits and workspace layout have ONE owner (csrc/rtn_wgrad.hip: WgradPlan); what it answers is pinned
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "wgrad_workspace_bytes.json")))
+    got = wgrad_workspace_table(L, monkeypatch.setenv, monkeypatch.delenv)
+    assert sorted(got) == sorted(want) and len(got) >= 17
+    for name in got:
+        assert got[name] == want[name], name
+        assert len(got[name]) == len(WGRAD_GOLDEN_SETTINGS) and min(got[name].values()) > 0, name
 
 
 def test_product_does_not_import_oracle():

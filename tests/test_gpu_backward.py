@@ -455,6 +455,58 @@ def test_wgrad_general_kernels_repeat_bit_for_bit(pkg, handle, monkeypatch, dtyp
     assert float((w0 - w1).abs().max()) <= 1e-4 * scale and float((b0 - b1).abs().max()) <= 1e-4 * max(1.0, float(b0.abs().max()))
 
 
+@pytest.mark.parametrize("H,W,cout,dtype,env,impl", [
+    (17, 21, 128, "bf16", {"RTN_WGRAD_WIN": "1"}, 4),       # window kernel: 13 stages, 8 splits - the smallest grid it takes with room to spare
+    (17, 21, 128, "bf16", {"RTN_WGRAD_WIN": "0", "RTN_WGRAD_BLOCKS": "64"}, 3),      # 12 tiles, XCD map: 8 splits, 6 own tiles, partial last tile
+    (17, 21, 256, "bf16", {"RTN_WGRAD_WIN": "0", "RTN_WGRAD_DMA": "2"}, 2),          # the 256 x 256 LDS-DMA kernel
+    (9, 13, 128, "f32", {}, 0),                             # register-staged kernel: 4 tiles, the last one of 42 pixels
+])
+def test_wgrad_rowinfo_then_prepared_equals_the_one_call_form(pkg, handle, monkeypatch, H, W, cout, dtype, env, impl):
+    """rtn_conv2d_wgrad_rowinfo + rtn_conv2d_wgrad_prepared (what the trainer calls) against rtn_conv2d_wgrad_bias on the same
+    descriptor: the same kernel runs (rtn_debug_last_wgrad_impl) and dW / db come out with the same bits.  Both forms read ONE
+    plan of the workspace (csrc/rtn_wgrad.hip: WgradPlan); the workspaces start out as garbage, so the table must have been built."""
+    L = pkg._lib
+    tdt, code = DT[dtype]
+    for kk, v in env.items():
+        monkeypatch.setenv(kk, v)
+    B, cin, k = 2, 64, 3
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(B, H, W, cin, generator=g).to(tdt).to(DEV).contiguous()
+    dy = torch.randn(B, H, W, cout, generator=g).to(tdt).to(DEV).contiguous()
+    d = L.ConvDesc()
+    d.ngroups, d.batch, d.dtype = 1, B, code
+    d.w_rows, d.N, d.KH, d.KW = cout, cout, k, k
+    d.Crun = d.pix_stride = cin
+    d.sy = d.sx = 1
+    d.pad_t = d.pad_l = k // 2
+    d.out_ld = cout
+    grp = L.ConvGroup()
+    grp.in_, grp.in_elems, grp.in_img_stride, grp.in_row_stride = x.data_ptr(), x.numel(), H * W * cin, W * cin
+    grp.Hin, grp.Win, grp.Hout, grp.Wout = H, W, H, W
+    grp.out, grp.out_elems, grp.out_img_stride = dy.data_ptr(), dy.numel(), H * W * cout
+    d.g[0] = grp
+    wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(d))
+
+    def run(two_calls):
+        ws = torch.full((wsb,), 0xFF, dtype=torch.uint8, device=DEV)
+        dW = torch.full((cout, k * k * cin), 0.5, dtype=torch.float32, device=DEV)
+        db = torch.full((cout,), 0.25, dtype=torch.float32, device=DEV)
+        if two_calls:
+            handle.check(L.lib.rtn_conv2d_wgrad_rowinfo(handle.raw, C.byref(d), ws.data_ptr(), wsb))
+            handle.check(L.lib.rtn_conv2d_wgrad_prepared(handle.raw, C.byref(d), dW.data_ptr(), db.data_ptr(), cout, ws.data_ptr(), wsb))
+        else:
+            handle.check(L.lib.rtn_conv2d_wgrad_bias(handle.raw, C.byref(d), dW.data_ptr(), db.data_ptr(), cout, ws.data_ptr(), wsb))
+        torch.cuda.synchronize()
+        return dW.cpu(), db.cpu(), L.lib.rtn_debug_last_wgrad_impl(handle.raw)
+
+    w1, b1, impl1 = run(False)
+    w2, b2, impl2 = run(True)
+    print("wgrad impl: one call %d, rowinfo + prepared %d, expected %d" % (impl1, impl2, impl))
+    assert impl1 == impl2 == impl
+    assert torch.equal(w1, w2) and torch.equal(b1, b2)
+    assert float((w1 - 0.5).abs().max()) > 1.0 and float((b1 - 0.25).abs().max()) > 1.0     # a gradient was added at all
+
+
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_wgrad_grouped_levels_and_padded_head_output(pkg, handle, dtype):
     """Shared head weights: one wgrad launch over five pyramid levels; dY of the 36-channel output padded to 64."""

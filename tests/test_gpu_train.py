@@ -172,7 +172,7 @@ def test_trainer_follows_engine_load_state(pkg):
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_training_steps_repeat_bit_for_bit(pkg, dtype):
     """No float atomics in the step: every weight-gradient kernel stores its pixel splits into slabs and adds them in split order
-    (csrc/rtn_backward.hip, rtn_wgrad_halo.hip).  Two trainers started from the same state and fed the same two batches end with
+    (csrc/rtn_wgrad.hip, rtn_wgrad_win.hip).  Two trainers started from the same state and fed the same two batches end with
     the same bits in the flat gradient, the Adam moments and the master weights; the wgrad lanes run on side streams meanwhile."""
     E, Wt, T = mods(pkg)
     state = Wt.init_state("resnet50", 1, 9, seed=3, randomize_bn=True, cls_bias=-2.0, tame=True)

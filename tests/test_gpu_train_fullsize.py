@@ -121,7 +121,7 @@ def test_fp32_training_step_800x1333_batch2_against_float64_autograd(pkg):
 # Which kernel each backward op takes at batch 16 x 800 x 1333 in bf16 (rtn_debug_last_conv_impl / rtn_debug_last_wgrad_impl;
 # dgrad: 2 = 256-row LDS-DMA per tap, 4 = persistent 8-phase 3x3, 5 = persistent 1x1; wgrad: 2 = 256 x 256
 # LDS-DMA, 3 = 128 x 128 LDS-DMA, 4 = the nine-tap window kernel).  The cost models that choose are in csrc/rtn_conv.hip
-# (conv_choose, the *_try launchers) and rtn_backward.hip (wgrad_plan, wgrad_takes_win); DESIGN.md §3.3.
+# (conv_choose, the *_try launchers) and rtn_wgrad.hip (wgrad_plan, wgrad_takes_win); DESIGN.md §3.3.
 EXPECTED_IMPLS = {
     # data gradients: the tower / pyramid / bottleneck 3x3 layers on the persistent 8-phase kernel, the 1x1 layers with >= 128
     # output channels on the persistent 1x1 kernel (residual + ReLU-mask epilogues), the 64-channel and stride-2 forms on generations 1-2
