@@ -876,6 +876,36 @@ int rtn_cca_label_host(int n, const uint8_t* const* images, const int32_t* heigh
 int rtn_cca_paint_host(int n, uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels, int n_boxes,
                        const int32_t* box_page, const int32_t* boxes, int mode);
 
+/* ---- colour effects (VisualEffect of model/transform.py on the device: contrast, brightness, hue, saturation) ----------
+ * A batch is n pages (at most 65535), uint8 (heights[i], widths[i], 3) in B,G,R order with sides 1 .. 65500.  pages, heights, widths,
+ * params, flags and outs are host arrays; the pages, the outputs and the workspace (256-byte aligned, >=
+ * rtn_visual_effect_workspace_bytes(n, heights, widths)) are device memory.  outs[i] may be pages[i] (in place); otherwise no output
+ * may overlap a page or another output.  Pages and outputs of any alignment are taken; those that are 16-byte aligned move as 16-byte
+ * words.  params[4 * i ..] = page i's contrast factor, brightness delta, hue delta and saturation factor (finite).  A step whose
+ * parameter is 0 does not run, unless its RTN_EFFECT_FORCE_* flag asks for it; flags may be NULL (all 0).
+ *   contrast    x -> clip((x - mean_c) * factor + mean_c, 0, 255), truncated; mean_c the mean of the channel's column means, the
+ *               columns added from x = 0 upwards (image.mean(axis=0).mean(axis=0))
+ *   brightness  x -> clip(x + delta * 255, 0, 255), truncated
+ *   hue, saturation: cv2's 8-bit BGR2HSV; H -> mod(H + delta * 180, 180) with the sign of the divisor (180 itself can result), S ->
+ *               clip(S * factor, 0, 255), both truncated; cv2's 8-bit HSV2BGR.  The round trip runs whenever one of the two does, and
+ *               changes bytes by itself.  With RTN_EFFECT_RAW_HSV the bytes of the page are taken as H,S,V and neither conversion runs.
+ *   All arithmetic is float64, one rounding per operation; the results are the NumPy text's bit for bit.
+ * rtn_visual_effect_u8 copies its page table into the workspace (for which the call waits on the stream), then queues a fixed number of
+ *   launches for the whole batch on the handle's stream: the integer column sums (only where contrast runs), one table of 256 entries
+ *   per step and page, the pixels.  Nothing returns to the host.
+ * rtn_visual_effect_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers and no workspace, through the per-element functions of csrc/rtn_effect.h; the results are the device's bit for bit. */
+#define RTN_EFFECT_RAW_HSV           1u
+#define RTN_EFFECT_FORCE_CONTRAST    16u
+#define RTN_EFFECT_FORCE_BRIGHTNESS  32u
+#define RTN_EFFECT_FORCE_HUE         64u
+#define RTN_EFFECT_FORCE_SATURATION  128u
+size_t rtn_visual_effect_workspace_bytes(int n, const int32_t* heights, const int32_t* widths);
+int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                         const double* params, const uint32_t* flags, uint8_t* const* outs, void* workspace, size_t workspace_bytes);
+int rtn_visual_effect_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const double* params,
+                           const uint32_t* flags, uint8_t* const* outs);
+
 #ifdef __cplusplus
 }
 #endif

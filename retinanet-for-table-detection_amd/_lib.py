@@ -19,6 +19,7 @@ RTN_BF16, RTN_F32, RTN_U8, RTN_FP8, RTN_I32 = 0, 1, 2, 3, 4
 RTN_DET_CLASS_AGNOSTIC, RTN_DET_NO_NMS = 1, 2
 RTN_MAX_GROUPS, RTN_MAX_GT, RTN_MAX_DET = 5, 64, 300
 RTN_HEADER_MAX_K, RTN_HEADER_WIDTH, RTN_HEADER_MAX_POINTS = 9, 500, 1 << 21
+RTN_EFFECT_RAW_HSV, RTN_EFFECT_FORCE_CONTRAST, RTN_EFFECT_FORCE_BRIGHTNESS, RTN_EFFECT_FORCE_HUE, RTN_EFFECT_FORCE_SATURATION = 1, 16, 32, 64, 128
 
 CONV_RELU, CONV_SIGMOID, CONV_RES_SAME, CONV_RES_UPSAMPLE, CONV_OUT_F32, CONV_RELU_MASK, CONV_MASK_PRE = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x40
 
@@ -248,6 +249,9 @@ SIGNATURES = {
     "rtn_cca_text_mask_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "rtn_cca_label_host": (_I, [_I, _P, _P, _P, _I, _P, _P, _P, _P, _SZ]),
     "rtn_cca_paint_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _I]),
+    "rtn_visual_effect_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_visual_effect_u8": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_visual_effect_host": (_I, [_I, _P, _P, _P, _P, _P, _P]),
 }
 
 

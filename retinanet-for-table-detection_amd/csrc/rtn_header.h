@@ -46,14 +46,20 @@ struct HAcc {
 
 // ---- stage 1: sample ------------------------------------------------------------------------------------------------------------
 // cv2 BGR2HSV, 8 bit, H in [0, 180): sdiv = cvRound((255 << 12) / v), hdiv = cvRound((180 << 12) / (6 * diff)), both 0 at 0
-__host__ __device__ inline void hdr_bgr2hsv(int b, int g, int r, uint8_t* out) {
+__host__ __device__ inline int hdr_sdiv(int v) { return v ? (int)rint(1044480.0 / (double)v) : 0; }
+__host__ __device__ inline int hdr_hdiv(int diff) { return diff ? (int)rint(737280.0 / (6.0 * (double)diff)) : 0; }
+
+__host__ __device__ inline void hdr_value_range(int b, int g, int r, int* v_out, int* diff_out) {
     int v = b > g ? b : g;
     v = v > r ? v : r;
     int vmin = b < g ? b : g;
     vmin = vmin < r ? vmin : r;
-    const int diff = v - vmin;
-    const int sdiv = v ? (int)rint(1044480.0 / (double)v) : 0;
-    const int hdiv = diff ? (int)rint(737280.0 / (6.0 * (double)diff)) : 0;
+    *v_out = v;
+    *diff_out = v - vmin;
+}
+
+// the integer half of the rule: sdiv = hdr_sdiv(v) and hdiv = hdr_hdiv(diff), computed or read from a table of them
+__host__ __device__ inline void hdr_bgr2hsv_div(int b, int g, int r, int v, int diff, int sdiv, int hdiv, uint8_t* out) {
     const int s = (diff * sdiv + 2048) >> 12;
     int h = v == r ? g - b : (v == g ? b - r + 2 * diff : r - g + 4 * diff);
     h = (h * hdiv + 2048) >> 12;                   // arithmetic shift of a negative h, as in OpenCV
@@ -61,6 +67,12 @@ __host__ __device__ inline void hdr_bgr2hsv(int b, int g, int r, uint8_t* out) {
     out[0] = (uint8_t)(h > 255 ? 255 : h);
     out[1] = (uint8_t)s;
     out[2] = (uint8_t)v;
+}
+
+__host__ __device__ inline void hdr_bgr2hsv(int b, int g, int r, uint8_t* out) {
+    int v, diff;
+    hdr_value_range(b, g, r, &v, &diff);
+    hdr_bgr2hsv_div(b, g, r, v, diff, hdr_sdiv(v), hdr_hdiv(diff), out);
 }
 
 // destination pixel (Y, X) of the dh x 500 box resample of an (h, w, 3) image: source pixel i covers [500 i, 500 (i + 1)) of the

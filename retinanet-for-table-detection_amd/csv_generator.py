@@ -7,6 +7,7 @@ Same class names, constructor arguments and method names as the reference's Gene
          parsing the page files (rtn_jpeg_inspect, rtn_png_inspect)
   device per batch: rtn_jpeg_decode of the baseline-JPEG pages and rtn_png_decode of the chunked-layout PNG pages
          (read_images_bgr, re-exported here from model/page_io.py; other files are decoded by Pillow and uploaded)
+         per batch, with apply_visual_effect=True: rtn_visual_effect_u8, the colour effects of the whole group in one call
          per page: [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
          x/127.5-1 normalisation (preprocess_image 'custom_tf'), the INTER_CUBIC resize and the write into the zero-padded batch
          canvas of compute_inputs;  per batch: rtn_anchor_targets (anchors, IoU, assignment, box deltas) -> regression, labels
@@ -31,13 +32,13 @@ import torch
 try:                                    # as a module of the package ...
     from .model import Parameters, _rt
     from .model import anchors as _anchors
-    from .model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
+    from .model.transform import adjust_transform_for_image, invert_affine, transform_aabb, visual_effect_batch, warp_codes
     from .model.utils import compute_resize_scale
     from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
 except ImportError:                     # ... or top-level, with the package directory on sys.path like the reference's layout
     from model import Parameters, _rt
     from model import anchors as _anchors
-    from model.transform import adjust_transform_for_image, invert_affine, transform_aabb, warp_codes
+    from model.transform import adjust_transform_for_image, invert_affine, transform_aabb, visual_effect_batch, warp_codes
     from model.utils import compute_resize_scale
     from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
 
@@ -92,7 +93,7 @@ class Generator:
     def __init__(self, transform_generator=None, visual_effect_generator=None, batch_size=1, group_method='random',
                  shuffle_groups=True, image_min_side=800, image_max_side=1333, transform_parameters=None,
                  compute_anchor_targets=None, compute_shapes=None, preprocess_image=None, config=False,
-                 dtype=torch.bfloat16, output='device', device=None):
+                 dtype=torch.bfloat16, output='device', device=None, apply_visual_effect=False):
         if compute_anchor_targets not in (None, _anchors.anchor_targets_bbox) or compute_shapes not in (None, _anchors.guess_shapes) \
                 or preprocess_image is not None:
             raise ValueError("the device generator implements the reference's default handlers (anchor_targets_bbox, guess_shapes, "
@@ -102,7 +103,10 @@ class Generator:
         if not torch.cuda.is_available():
             raise RuntimeError("csv_generator runs its batch work on a ROCm GPU through librtn.so: no CPU fallback exists")
         self.transform_generator = transform_generator
-        self.visual_effect_generator = visual_effect_generator        # accepted and unused, like the reference (csv_generator.py:385)
+        # stored and never advanced by default, like the reference, whose call is commented out (csv_generator.py:385);
+        # apply_visual_effect=True puts the call back where the reference has it
+        self.visual_effect_generator = visual_effect_generator
+        self.apply_visual_effect = bool(apply_visual_effect)
         self.batch_size = int(batch_size)
         self.group_method = group_method
         self.shuffle_groups = shuffle_groups
@@ -209,6 +213,23 @@ class Generator:
             raise ValueError("pages must be uint8 (H,W,3)")
         return t.contiguous()
 
+    def random_visual_effect_group_entry(self, image, annotations):
+        """csv_generator.py:221-227 for one page: the next effect of the generator, through the batched entry."""
+        images, annotations_group = self.random_visual_effect_group([image], [annotations])
+        return images[0], annotations_group[0]
+
+    def random_visual_effect_group(self, image_group, annotations_group):
+        """csv_generator.py:230-245 on device pages: one effect per page drawn in group order, then the whole group in one call of
+        rtn_visual_effect_u8 on this generator's handle and stream.  Without an effect generator the group passes through."""
+        assert len(image_group) == len(annotations_group)
+        if not self.visual_effect_generator or len(image_group) == 0:
+            return image_group, annotations_group
+        effects = [next(self.visual_effect_generator) for _ in image_group]
+        params = [(float(e.contrast_factor), float(e.brightness_delta), float(e.hue_delta), float(e.saturation_factor)) for e in effects]
+        with torch.cuda.stream(self._stream):                 # the workspace is allocated on the stream the kernels run on
+            pages = [self._upload(im) for im in image_group]
+            return visual_effect_batch(pages, params, handle=self._h), annotations_group
+
     def random_transform_group_entry(self, image, annotations, transform=None):
         """csv_generator.py:248-265 on a device page: warp the pixels with rtn_warp_affine_u8, move the box corners on the host."""
         if transform is None and not self.transform_generator:
@@ -292,6 +313,8 @@ class Generator:
             image_group = self.load_image_group(group)
             annotations_group = self.load_annotations_group(group)
             image_group, annotations_group = self.filter_annotations(image_group, annotations_group, group)
+            if self.apply_visual_effect:
+                image_group, annotations_group = self.random_visual_effect_group(image_group, annotations_group)
             image_group, annotations_group = self.random_transform_group(image_group, annotations_group)
             pages = [self._upload(im) for im in image_group]
             scales = [compute_resize_scale(p.shape, self.image_min_side, self.image_max_side) for p in pages]

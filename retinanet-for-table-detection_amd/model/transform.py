@@ -1,11 +1,16 @@
-"""Augmentation geometry of the reference's model/transform.py behind the same names.
+"""The augmentation of the reference's model/transform.py behind the same names: geometry and colour effects.
 
 The 3x3 homogeneous matrices are host NumPy (float64, a handful of flops per image); the draws come from the caller's PRNG in the
 reference's order (rotation, translation x/y, shear, scaling x/y, flip x, flip y - model/transform.py:190-234), so a seeded
 RandomState yields the reference's matrices bit for bit (tests/golden/ref_generator_golden.npz holds matrices produced by the
 reference module itself).  apply_transform - cv2.warpAffine in the reference (model/transform.py:343-362) - runs on the device
-through rtn_warp_affine_u8.  The colour effects (VisualEffect, model/transform.py:397-511) are not mirrored: the reference never
-applies them (the call is commented out at csv_generator.py:385).
+through rtn_warp_affine_u8.
+
+The colour effects (VisualEffect, random_visual_effect_generator, adjust_*: model/transform.py:365-512) run on the device through
+rtn_visual_effect_u8: the four parameters are np.random.uniform draws from the global NumPy state in the
+reference's order (contrast, brightness, hue, saturation), the pixels are the reference's NumPy text bit for bit around a
+restatement of cv2's 8-bit BGR2HSV / HSV2BGR (recalled, not verifiable offline).  visual_effect_batch is the batched form the
+generator uses: every page of a group in one call.
 """
 import numpy as np
 
@@ -184,3 +189,143 @@ def apply_transform(matrix, image, params):
     if image.ndim == 2:
         dst = dst[..., 0]
     return dst if on_device else _rt.host(dst)
+
+
+# ---- colour effects (model/transform.py:365-512) on the device: rtn_visual_effect_u8, DESIGN §3.4j -----------------------------------
+_CONTRAST, _BRIGHTNESS, _HUE, _SATURATION = 0, 1, 2, 3                          # the order of a page's four parameters
+
+
+def _uniform(val_range):
+    """One draw from the global NumPy state (model/transform.py:365-370)."""
+    return np.random.uniform(val_range[0], val_range[1])
+
+
+def _check_range(val_range, min_val=None, max_val=None):
+    """model/transform.py:373-385."""
+    if val_range[0] > val_range[1]:
+        raise ValueError('interval lower bound > upper bound')
+    if min_val is not None and val_range[0] < min_val:
+        raise ValueError('invalid interval lower bound')
+    if max_val is not None and val_range[1] > max_val:
+        raise ValueError('invalid interval upper bound')
+
+
+def _clip(image):
+    """model/transform.py:388-394, host NumPy (the device steps clip inside their tables)."""
+    return np.clip(image, 0, 255).astype(np.uint8)
+
+
+def visual_effect_batch(pages, params, flags=None, handle=None, in_place=False):
+    """Every page of a group through rtn_visual_effect_u8 in one call.  pages: contiguous uint8 (H,W,3) CUDA tensors of any sizes;
+    params: one (contrast_factor, brightness_delta, hue_delta, saturation_factor) per page; flags: None or one RTN_EFFECT_* word per
+    page.  Runs on `handle` and its stream (default: the package's handle on the current stream) and returns the new pages, or the
+    pages themselves with in_place."""
+    import ctypes
+    import torch
+    from . import _rt
+    L = _rt.L
+    n = len(pages)
+    if n == 0:
+        return []
+    for p in pages:
+        if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 3 or p.shape[2] != 3 or not p.is_contiguous():
+            raise ValueError("visual_effect_batch: contiguous uint8 (H,W,3) CUDA tensors expected")
+    h = _rt.handle() if handle is None else handle
+    par = np.ascontiguousarray(np.asarray(params, np.float64).reshape(n, 4))
+    fl = np.zeros(n, np.uint32) if flags is None else np.ascontiguousarray(np.asarray(flags, np.uint32).reshape(n))
+    heights = np.array([p.shape[0] for p in pages], np.int32)
+    widths = np.array([p.shape[1] for p in pages], np.int32)
+    outs = list(pages) if in_place else [torch.empty_like(p) for p in pages]
+    src = (ctypes.c_void_p * n)(*[p.data_ptr() for p in pages])
+    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
+    wsb = int(L.lib.rtn_visual_effect_workspace_bytes(n, heights.ctypes.data, widths.ctypes.data))
+    if wsb == 0:
+        raise ValueError("visual_effect_batch: at most 65535 pages with sides 1 .. 65500")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=pages[0].device)
+    h.check(L.lib.rtn_visual_effect_u8(h.raw, n, src, heights.ctypes.data, widths.ctypes.data, par.ctypes.data, fl.ctypes.data, dst,
+                                       ws.data_ptr(), wsb))
+    return outs
+
+
+def _effect_one(image, params, flags, in_place=False):
+    """One page through the device entry: a uint8 (H,W,3) NumPy array (returns NumPy) or CUDA tensor (returns a CUDA tensor, no host
+    round trip), as apply_transform."""
+    import torch
+    from . import _rt
+    on_device = isinstance(image, torch.Tensor)
+    if (image.dtype != torch.uint8) if on_device else (np.asarray(image).dtype != np.uint8):
+        raise ValueError("the colour effects take uint8 pages (what cv2.imread hands the generator)")
+    if image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError("the colour effects take (H,W,3) pages")
+    if on_device:
+        if in_place and image.is_contiguous():
+            return visual_effect_batch([image], [params], [flags], in_place=True)[0]
+        out = visual_effect_batch([image.contiguous()], [params], [flags])[0]
+        return image.copy_(out) if in_place else out
+    out = _rt.host(visual_effect_batch([_rt.dev(image, torch.uint8)], [params], [flags])[0])
+    if in_place:
+        image[...] = out
+        return image
+    return out
+
+
+class VisualEffect:
+    """model/transform.py:397-440: the four parameters, and __call__ applying them to a page.  A parameter that is 0 skips its step;
+    the HSV round trip runs when hue or saturation does."""
+
+    def __init__(self, contrast_factor, brightness_delta, hue_delta, saturation_factor):
+        self.contrast_factor = contrast_factor
+        self.brightness_delta = brightness_delta
+        self.hue_delta = hue_delta
+        self.saturation_factor = saturation_factor
+
+    def params(self):
+        return (float(self.contrast_factor), float(self.brightness_delta), float(self.hue_delta), float(self.saturation_factor))
+
+    def __call__(self, image):
+        return _effect_one(image, self.params(), 0)
+
+
+def random_visual_effect_generator(contrast_range=(0.9, 1.1), brightness_range=(-.1, .1), hue_range=(-0.05, 0.05),
+                                   saturation_range=(0.95, 1.05)):
+    """Endless stream of VisualEffect with parameters drawn uniformly from the given intervals (model/transform.py:443-472); the
+    intervals are checked by the call itself."""
+    _check_range(contrast_range, 0)
+    _check_range(brightness_range, -1, 1)
+    _check_range(hue_range, -1, 1)
+    _check_range(saturation_range, 0)
+
+    def _generate():
+        while True:
+            yield VisualEffect(contrast_factor=_uniform(contrast_range), brightness_delta=_uniform(brightness_range),
+                               hue_delta=_uniform(hue_range), saturation_factor=_uniform(saturation_range))
+
+    return _generate()
+
+
+def _one_step(image, step, value, raw_hsv, in_place=False):
+    from . import _rt
+    params = [0.0, 0.0, 0.0, 0.0]
+    params[step] = float(value)
+    flags = (_rt.L.RTN_EFFECT_FORCE_CONTRAST << step) | (_rt.L.RTN_EFFECT_RAW_HSV if raw_hsv else 0)
+    return _effect_one(image, params, flags, in_place)
+
+
+def adjust_contrast(image, factor):
+    """clip((image - mean) * factor + mean) with the per-channel mean (model/transform.py:475-482)."""
+    return _one_step(image, _CONTRAST, factor, False)
+
+
+def adjust_brightness(image, delta):
+    """clip(image + delta * 255) (model/transform.py:485-491)."""
+    return _one_step(image, _BRIGHTNESS, delta, False)
+
+
+def adjust_hue(image, delta):
+    """H = mod(H + delta * 180, 180) of an H,S,V image, in place as in the reference (model/transform.py:494-502)."""
+    return _one_step(image, _HUE, delta, True, in_place=True)
+
+
+def adjust_saturation(image, factor):
+    """S = clip(S * factor, 0, 255) of an H,S,V image, in place as in the reference (model/transform.py:505-512)."""
+    return _one_step(image, _SATURATION, factor, True, in_place=True)
