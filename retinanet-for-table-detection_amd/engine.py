@@ -15,12 +15,24 @@ import numpy as np
 import os
 import torch
 
+from typing import Any, NamedTuple, Optional
+
 from . import _lib as L
+from . import ops as O
 from . import weights as Wt
+from .ops import SRC_DT as _SRC_DT
 
 _TORCH_DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 _RTN_DT = {"bf16": L.RTN_BF16, "f32": L.RTN_F32}
-_SRC_DT = {torch.bfloat16: 0, torch.float32: 1, torch.uint8: 2}
+
+
+class Block(NamedTuple):
+    """One bottleneck block of a plan: what _variant() needs to substitute its fused forms.  x: the block's input, sc: its shortcut
+    (x itself in an identity block, branch1's output in a stage's first block), a / b2: the outputs of branch2a / branch2b, y: the
+    block's output; i_*: indices of the block's convs in plan["ops"] (i_2a / i_2b None where the fp8 pairing owns them, i_b1 None in
+    an identity block); step: the stride of branch2a and branch1."""
+    stage: int; block: int; f: int; step: int; key: str; n2a: str; n2b: str; n2c: str; n1: Optional[str]
+    x: Any; a: Any; b2: Any; sc: Any; y: Any; i_2a: Optional[int]; i_2b: Optional[int]; i_b1: Optional[int]; i_2c: int; Ho: int; Wo: int
 
 
 def same_pad_before(n, k, s):
@@ -100,6 +112,32 @@ def schedule_lanes(lanes, io):
     joins = sorted(i for ln, i in last.items() if ln != 0)
     events = set(j for w in waits for j in w) | set(joins)
     return {"lanes": lanes, "waits": waits, "events": events, "joins": joins, "nlanes": max(lanes) + 1}
+
+
+def run_lanes(handle, streams, sched, events, fork, launch):
+    """Run an op list on its lanes.  streams: one per lane, [0] the launch stream; sched: schedule_lanes' result; events: {op index:
+    event} for sched["events"].  The side lanes start behind `fork`, recorded on the launch stream now; every op waits for its
+    cross-lane events, runs as launch(index, stream) with the handle bound to its lane's stream (re-bound only when the stream
+    changes) and records its event if another lane or the join waits for it; the last op of every side lane is joined into the
+    launch stream, to which the handle is bound again."""
+    main = streams[0]
+    fork.record(main)
+    for st in streams[1:sched["nlanes"]]:
+        st.wait_event(fork)
+    bound = None
+    for i, (ln, waits) in enumerate(zip(sched["lanes"], sched["waits"])):
+        st = streams[ln]
+        for j in waits:
+            st.wait_event(events[j])
+        if bound is not st:
+            handle.set_stream(st.cuda_stream)
+            bound = st
+        launch(i, st)
+        if i in events:
+            events[i].record(st)
+    for j in sched["joins"]:
+        main.wait_event(events[j])
+    handle.set_stream(main.cuda_stream)
 
 
 class Engine:
@@ -286,20 +324,11 @@ class Engine:
         """One fp8 layer (rtn_conv2d_fp8_fwd): bias (+ ReLU), fp8 or bf16 output."""
         wq, sw = self._fp8_weights()[name]
         _, bk, kh, kw, cin, cout = self.w[name]
-        d = L.ConvDesc()
-        for i, g in enumerate(groups):
-            d.g[i] = g
-        d.ngroups, d.batch, d.dtype = len(groups), B, L.RTN_FP8
-        d.w, d.bias = wq.data_ptr(), bk.data_ptr()
-        d.w_rows, d.N, d.KH, d.KW = wq.shape[0], cout, kh, kw
-        d.Crun = d.pix_stride = cin
-        d.sy = d.sx = 1
-        d.pad_t, d.pad_l = (kh - 1) // 2, (kw - 1) // 2
-        d.out_ld, d.flags = cout, (L.CONV_RELU if relu else 0)
+        d = self._desc(groups, B, L.RTN_FP8, wq, bk, cout, kh, kw, cin, pad=((kh - 1) // 2, (kw - 1) // 2), flags=L.CONV_RELU if relu else 0)
         q = L.ConvFp8(acc_scale=1.0 / (s_in * sw), out_scale=s_out, out_dtype=L.RTN_FP8 if out_fp8 else L.RTN_BF16)
         meta = {"name": name, "xs": [g._x for g in groups], "ys": [g._out for g in groups], "res": [None] * len(groups),
                 "kh": kh, "kw": kw, "cin": cin, "cout": cout, "B": B, "fp8": True, "s_in": s_in, "sw": sw}
-        return ("conv8", d, name, meta, q)
+        return O.Conv8("conv8", d, name, meta, q)
 
     # ------------------------------------------------------------------ descriptors
     def _group(self, x, out, Hout, Wout, res=None, out_off=0, out_img_stride=None, res_hw=None):
@@ -320,113 +349,87 @@ class Engine:
         g._x, g._out, g._res, g._off = x, out, res, out_off       # python-side refs for the backward graph
         return g
 
-    def _conv(self, name, groups, B, stride=1, pad=(0, 0), flags=0, out_ld=None):
-        """One fused conv launch; the torch tensors behind the groups are kept in the op's meta for the backward graph."""
-        wk, bk, kh, kw, cin, cout = self.w[name]
+    def _desc(self, groups, B, dtype, w, bias, N, kh, kw, cin, stride=1, pad=(0, 0), flags=0, out_ld=None):
+        """A conv descriptor over `groups`: filters w [rows][kh * kw * cin], N output channels, `cin`-element pixels."""
         d = L.ConvDesc()
         for i, g in enumerate(groups):
             d.g[i] = g
-        d.ngroups, d.batch, d.dtype = len(groups), B, self.rdt
-        d.w, d.bias = wk.data_ptr(), bk.data_ptr()
-        d.w_rows, d.N, d.KH, d.KW = wk.shape[0], cout, kh, kw
-        d.Crun, d.pix_stride = cin, cin
+        d.ngroups, d.batch, d.dtype = len(groups), B, dtype
+        d.w, d.bias = w.data_ptr(), bias.data_ptr()
+        d.w_rows, d.N, d.KH, d.KW = w.shape[0], N, kh, kw
+        d.Crun = d.pix_stride = cin
         d.sy = d.sx = stride
         d.pad_t, d.pad_l = pad
-        d.out_ld = cout if out_ld is None else out_ld
-        d.flags = flags
+        d.out_ld, d.flags = N if out_ld is None else out_ld, flags
+        return d
+
+    def _conv(self, name, groups, B, stride=1, pad=(0, 0), flags=0, out_ld=None):
+        """One fused conv launch; the torch tensors behind the groups are kept in the op's meta for the backward graph."""
+        wk, bk, kh, kw, cin, cout = self.w[name]
+        d = self._desc(groups, B, self.rdt, wk, bk, cout, kh, kw, cin, stride, pad, flags, out_ld)
         L.attach_conv_workspace(self.h, d)                 # split-K / tail-split slabs (P6, P7, res4-sized grids): caller-owned
         meta = {"name": name, "xs": [g._x for g in groups], "ys": [g._out for g in groups], "res": [g._res for g in groups],
                 "offs": [g._off for g in groups], "stride": stride, "pad": pad, "flags": flags,
                 "relu": bool(flags & L.CONV_RELU), "kh": kh, "kw": kw, "cin": cin, "cout": cout, "B": B,
                 "out_ld": d.out_ld}
-        return ("conv", d, name, meta)
+        return O.Conv("conv", d, name, meta)
 
     def _dual_op(self, fb, B):
         """First block of a stage with the projection shortcut folded into branch2c: y = relu([W2c | W1] . [b2 ; x(step)] + b)."""
-        wd, bd = self._dual_weights()[fb["key"]]
-        f = fb["f"]
-        d = L.ConvDesc()
-        d.g[0] = self._group(fb["b2"], fb["y"], fb["Ho"], fb["Wo"])
-        d.ngroups, d.batch, d.dtype = 1, B, self.rdt
-        d.w, d.bias = wd.data_ptr(), bd.data_ptr()
-        d.w_rows, d.N, d.KH, d.KW = wd.shape[0], 4 * f, 1, 1
-        d.Crun = d.pix_stride = f
-        d.sy = d.sx = 1
-        d.pad_t = d.pad_l = 0
-        d.out_ld, d.flags = 4 * f, L.CONV_RELU
-        x = fb["x"]
+        wd, bd = self._dual_weights()[fb.key]
+        d = self._desc([self._group(fb.b2, fb.y, fb.Ho, fb.Wo)], B, self.rdt, wd, bd, 4 * fb.f, 1, 1, fb.f, flags=L.CONV_RELU)
+        x = fb.x
         s2 = L.ConvSrc2()
         s2.in_, s2.in_elems = x.data_ptr(), x.numel()
         s2.in_img_stride, s2.in_row_stride, s2.pix_stride = x.shape[1] * x.shape[2] * x.shape[3], x.shape[2] * x.shape[3], x.shape[3]
-        s2.Hin, s2.Win, s2.C, s2.step = x.shape[1], x.shape[2], x.shape[3], fb["step"]
+        s2.Hin, s2.Win, s2.C, s2.step = x.shape[1], x.shape[2], x.shape[3], fb.step
         L.attach_conv_workspace(self.h, d, s2)             # stream-K slabs of the small-M stages (res5a): caller-owned
-        return ("dual", d, fb["key"] + "_branch2c+1", s2, {"xs": [fb["b2"], x], "ys": [fb["y"]]})
-
-    def _bneck_proj_op(self, fb, B, keep_h1=False, nxt=None):
-        """The FIRST block of the 64-channel stage as one launch: branch2b, then branch2c and the projection shortcut as one product
-        over the K-concatenated filters of _dual_weights() (rtn_bottleneck64_fwd with p_in / wproj), and branch2a of the following
-        identity block `nxt` when there is one."""
-        wd, bd = self._dual_weights()[fb["key"]]
-        w2b, b2b = self.w[fb["n2b"]][:2]
-        a, x, y = fb["a"], fb["x"], fb["y"]
-        d = L.BottleneckDesc()
-        d.a_in, d.a_in_elems = a.data_ptr(), a.numel()
-        d.p_in, d.p_in_elems = x.data_ptr(), x.numel()
-        d.x_out, d.x_out_elems = y.data_ptr(), y.numel()
-        d.w2b, d.b2b, d.w2c, d.b2c = w2b.data_ptr(), b2b.data_ptr(), wd.data_ptr(), bd.data_ptr()
-        d.wproj, d.w2c_ld = wd.data_ptr() + 64 * wd.element_size(), wd.shape[1]
-        d.batch, d.H, d.W, d.mid, d.dtype = B, fb["Ho"], fb["Wo"], 64, self.rdt
-        outs = [y]
-        if nxt is not None:
-            w2a, b2a = self.w[nxt["n2a"]][:2]
-            d.a_out, d.a_out_elems = nxt["a"].data_ptr(), nxt["a"].numel()
-            d.w2a, d.b2a = w2a.data_ptr(), b2a.data_ptr()
-            outs.append(nxt["a"])
-        if keep_h1:                                      # training: branch2b's activation is an input of the backward pass
-            d.h1_out, d.h1_out_elems = fb["b2"].data_ptr(), fb["b2"].numel()
-            outs.append(fb["b2"])
-        return ("bneck", d, fb["n2b"] + "+2c+1" + ("+next2a" if nxt is not None else ""),
-                {"xs": [a, x], "ys": outs, "B": B, "H": fb["Ho"], "W": fb["Wo"], "tail": nxt is not None, "proj": True, "h1": keep_h1})
+        return O.Dual("dual", d, fb.key + "_branch2c+1", s2, {"xs": [fb.b2, x], "ys": [fb.y]})
 
     def _bneck_op(self, blk, nxt, B, keep_h1=False, xq=None, yq=None):
-        """An identity block of the 64-channel stage as one launch (rtn_bottleneck64_fwd): branch2b + branch2c + Add + ReLU of
-        `blk`, and branch2a of the following identity block `nxt` when there is one.  xq / yq: compact quarter tensors (the even
-        pixels) that stand in for the shortcut / the block output (the library's x_in_step / x_out_step = 2)."""
-        w2b, b2b = self.w[blk["n2b"]][:2]
-        w2c, b2c = self.w[blk["n2c"]][:2]
-        a, x, y = blk["a"], blk["x"] if xq is None else xq, blk["y"] if yq is None else yq
+        """A block of the 64-channel stage as one launch (rtn_bottleneck64_fwd): branch2b + branch2c + Add + ReLU of `blk`, and
+        branch2a of the following identity block `nxt` when there is one.  The stage's FIRST block takes branch2c and its projection
+        shortcut as one product over the K-concatenated filters of _dual_weights() (p_in / wproj).  xq / yq (identity blocks): compact
+        quarter tensors (the even pixels) that stand in for the shortcut / the block output (the library's x_in_step / x_out_step = 2)."""
+        proj = blk.block == 0
+        w2b, b2b = self.w[blk.n2b][:2]
+        w2c, b2c = self._dual_weights()[blk.key] if proj else self.w[blk.n2c][:2]
+        a, x, y = blk.a, blk.x if xq is None else xq, blk.y if yq is None else yq
         d = L.BottleneckDesc()
         d.a_in, d.a_in_elems = a.data_ptr(), a.numel()
-        d.x_in, d.x_in_elems = x.data_ptr(), x.numel()
         d.x_out, d.x_out_elems = y.data_ptr(), y.numel()
         d.w2b, d.b2b, d.w2c, d.b2c = w2b.data_ptr(), b2b.data_ptr(), w2c.data_ptr(), b2c.data_ptr()
-        outs = [y]
+        d.batch, d.H, d.W, d.mid, d.dtype = B, blk.Ho, blk.Wo, 64, self.rdt
+        meta = {"xs": [a, x], "ys": [y], "B": B, "H": blk.Ho, "W": blk.Wo, "tail": nxt is not None, "h1": keep_h1}
+        if proj:
+            d.p_in, d.p_in_elems = x.data_ptr(), x.numel()
+            d.wproj, d.w2c_ld = w2c.data_ptr() + 64 * w2c.element_size(), w2c.shape[1]
+            meta["proj"] = True
+        else:
+            d.x_in, d.x_in_elems = x.data_ptr(), x.numel()
+            d.x_in_step, d.x_out_step = meta["x_in_step"], meta["x_out_step"] = 1 if xq is None else 2, 1 if yq is None else 2
         if nxt is not None:
-            w2a, b2a = self.w[nxt["n2a"]][:2]
-            d.a_out, d.a_out_elems = nxt["a"].data_ptr(), nxt["a"].numel()
+            w2a, b2a = self.w[nxt.n2a][:2]
+            d.a_out, d.a_out_elems = nxt.a.data_ptr(), nxt.a.numel()
             d.w2a, d.b2a = w2a.data_ptr(), b2a.data_ptr()
-            outs.append(nxt["a"])
-        d.batch, d.H, d.W, d.mid, d.dtype = B, blk["Ho"], blk["Wo"], 64, self.rdt
-        d.x_in_step, d.x_out_step = 1 if xq is None else 2, 1 if yq is None else 2
-        if keep_h1:
-            d.h1_out, d.h1_out_elems = blk["b2"].data_ptr(), blk["b2"].numel()
-            outs.append(blk["b2"])
-        name = blk["n2b"] + "+2c" + ("+next2a" if nxt is not None else "")
-        return ("bneck", d, name, {"xs": [a, x], "ys": outs, "B": B, "H": blk["Ho"], "W": blk["Wo"], "tail": nxt is not None, "h1": keep_h1,
-                                   "x_in_step": int(d.x_in_step), "x_out_step": int(d.x_out_step)})
+            meta["ys"].append(nxt.a)
+        if keep_h1:                                      # training: branch2b's activation is an input of the backward pass
+            d.h1_out, d.h1_out_elems = blk.b2.data_ptr(), blk.b2.numel()
+            meta["ys"].append(blk.b2)
+        return O.Bneck("bneck", d, blk.n2b + ("+2c+1" if proj else "+2c") + ("+next2a" if nxt is not None else ""), meta)
 
-    def _chain_op(self, sm):
+    def _chain_op(self, blk, nxt):
         """The seam between two identity blocks of the 128- / 256-channel stages as one launch (rtn_chain1x1_fwd): branch2c + Add +
-        ReLU of the first, branch2a + ReLU of the second."""
-        w2c, b2c = self.w[sm["n2c"]][:2]
-        w2a, b2a = self.w[sm["n2a"]][:2]
-        h, x, y, a = sm["b2"], sm["x"], sm["y"], sm["a"]
+        ReLU of `blk`, branch2a + ReLU of `nxt`."""
+        w2c, b2c = self.w[blk.n2c][:2]
+        w2a, b2a = self.w[nxt.n2a][:2]
+        h, x, y, a, f = blk.b2, blk.sc, blk.y, nxt.a, blk.f
         d = L.ChainDesc()
         d.h_in, d.h_in_elems, d.x_in, d.x_in_elems = h.data_ptr(), h.numel(), x.data_ptr(), x.numel()
         d.x_out, d.x_out_elems, d.a_out, d.a_out_elems = y.data_ptr(), y.numel(), a.data_ptr(), a.numel()
         d.w2c, d.b2c, d.w2a, d.b2a = w2c.data_ptr(), b2c.data_ptr(), w2a.data_ptr(), b2a.data_ptr()
-        d.pixels, d.mid, d.out, d.next, d.dtype = y.numel() // y.shape[3], sm["f"], 4 * sm["f"], sm["f"], self.rdt
-        return ("chain", d, sm["n2c"] + "+next2a", {"xs": [h, x], "ys": [y, a], "pixels": int(d.pixels), "mid": sm["f"]})
+        d.pixels, d.mid, d.out, d.next, d.dtype = y.numel() // y.shape[3], f, 4 * f, f, self.rdt
+        return O.Chain("chain", d, blk.n2c + "+next2a", {"xs": [h, x], "ys": [y, a], "pixels": int(d.pixels), "mid": f})
 
     # ------------------------------------------------------------------ plan
     def _plan(self, B, H, W, slot=0):
@@ -466,90 +469,59 @@ class Engine:
         keep.append(xp)
         c1 = buf(B, H1, W1, 64)
         wk, bk, *_ = self.w["conv1"]
-        d = L.ConvDesc()
         g = L.ConvGroup()
         g.in_ = xp.data_ptr(); g.in_elems = xp.numel()
         g.out = c1.data_ptr(); g.out_elems = c1.numel()
         g.in_img_stride, g.in_row_stride = Hp * Wp * 4, Wp * 4
         g.Hin, g.Win, g.Hout, g.Wout = Hp, Wp, H1, W1
         g.out_img_stride = H1 * W1 * 64
-        d.g[0] = g
-        d.ngroups, d.batch, d.dtype = 1, B, self.rdt
-        d.w, d.bias, d.w_rows, d.N = wk.data_ptr(), bk.data_ptr(), wk.shape[0], 64
-        d.KH, d.KW, d.Crun, d.pix_stride = 8, 1, 32, 4
-        d.sy = d.sx = 2
-        d.pad_t = d.pad_l = 0
-        d.out_ld, d.flags = 64, L.CONV_RELU
-        ops.append(("pack", xp, xin))
-        ops.append(("conv", d, "conv1", {"name": "conv1", "xs": [xp], "ys": [c1], "res": [None], "offs": [0], "stride": 2,
-                                          "pad": (0, 0), "flags": L.CONV_RELU, "relu": True, "kh": 8, "kw": 1, "cin": 32,
-                                          "cout": 64, "B": B, "out_ld": 64, "stem": True}))
+        d = self._desc([g], B, self.rdt, wk, bk, 64, 8, 1, 32, stride=2, flags=L.CONV_RELU)
+        d.pix_stride = 4                                   # a 32-element run spans eight packed pixels
+        ops.append(O.Pack("pack", xp, xin))
+        ops.append(O.Conv("conv", d, "conv1", {"name": "conv1", "xs": [xp], "ys": [c1], "res": [None], "offs": [0], "stride": 2,
+                                               "pad": (0, 0), "flags": L.CONV_RELU, "relu": True, "kh": 8, "kw": 1, "cin": 32,
+                                               "cout": 64, "B": B, "out_ld": 64, "stem": True}))
         # ---- pool1
         H2, W2 = (H1 + 1) // 2, (W1 + 1) // 2
         x = buf(B, H2, W2, 64)
         pool_idx = torch.empty(B * H2 * W2 * 64, dtype=torch.uint8, device=dev)     # winning taps (training mode only)
         keep.append(pool_idx)
-        ops.append(("pool", c1, x, (B, H1, W1, 64), pool_idx))
-        # inference, bf16: the three stem ops above collapse into one kernel (rtn_stem_conv_pool)
-        stem_fused = ("stem", x, (B, H, W), wk, bk, xp, (Hp, Wp), None, pool_idx)       # [7]: (a_out, w2a, b2a) with fuse_stem == 2
+        ops.append(O.Pool("pool", c1, x, (B, H1, W1, 64), pool_idx))
+        # inference, bf16: the three stem ops above collapse into one kernel (rtn_stem_conv_pool); tail: set with fuse_stem == 2
+        stem_fused = O.Stem("stem", x, (B, H, W), wk, bk, xp, (Hp, Wp), None, pool_idx)
         n_stem_ops = len(ops)
         # ---- bottleneck stages
         feats = []
-        first_blocks = []
-        blocks64 = []                    # identity blocks of the 64-channel stage: candidates for the fused bottleneck kernel
-        seams = []                       # identity block -> next block in the 128- / 256-channel stages: branch2c + next branch2a as one launch
-        prev_blk = None
+        blocks = []                      # one Block per bottleneck block: what _variant() fuses
         a_acts = {}
         for stage, nblocks in enumerate(Wt.STAGE_BLOCKS[self.backbone]):
             f = 64 * 2 ** stage
             for block in range(nblocks):
-                s, bname = str(stage + 2), Wt.block_name(self.backbone, stage, block)
+                res = "res%d%s" % (stage + 2, Wt.block_name(self.backbone, stage, block))
                 st = 2 if (block == 0 and stage > 0) else 1
                 Hi, Wi = x.shape[1], x.shape[2]
                 Ho, Wo = (Hi - 1) // st + 1, (Wi - 1) // st + 1
-                n2a, n2b = "res%s%s_branch2a" % (s, bname), "res%s%s_branch2b" % (s, bname)
-                if fp8_on and ("a", n2a) in self.fp8_scales:      # branch2a -> e4m3 -> fp8 branch2b -> bf16
-                    a = buf(B, Ho, Wo, f, dtype=torch.uint8)
+                n2a, n2b, n2c, n1 = res + "_branch2a", res + "_branch2b", res + "_branch2c", res + "_branch1" if block == 0 else None
+                fp8_pair = fp8_on and ("a", n2a) in self.fp8_scales
+                a = buf(B, Ho, Wo, f, dtype=torch.uint8 if fp8_pair else None)
+                c2a = self._conv(n2a, [self._group(x, a, Ho, Wo)], B, stride=st, flags=L.CONV_RELU)
+                b2 = buf(B, Ho, Wo, f)
+                if fp8_pair:                                      # branch2a -> e4m3 -> fp8 branch2b -> bf16
                     sa = self.fp8_scales[("a", n2a)]
-                    ops.append(("convq",) + self._conv(n2a, [self._group(x, a, Ho, Wo)], B, stride=st, flags=L.CONV_RELU)[1:] + (sa,))
-                    b2 = buf(B, Ho, Wo, f)
-                    ops.append(self._conv8(n2b, [self._group(a, b2, Ho, Wo)], B, sa, 1.0, out_fp8=False))
+                    ops += [O.ConvQ("convq", *c2a[1:], sa), self._conv8(n2b, [self._group(a, b2, Ho, Wo)], B, sa, 1.0, out_fp8=False)]
                 else:
-                    a = buf(B, Ho, Wo, f)
-                    ops.append(self._conv(n2a, [self._group(x, a, Ho, Wo)], B, stride=st, flags=L.CONV_RELU))
-                    i_2a = len(ops) - 1
-                    b2 = buf(B, Ho, Wo, f)
-                    ops.append(self._conv(n2b, [self._group(a, b2, Ho, Wo)], B, pad=(1, 1), flags=L.CONV_RELU))
-                    i_2b_cur = len(ops) - 1
+                    ops += [c2a, self._conv(n2b, [self._group(a, b2, Ho, Wo)], B, pad=(1, 1), flags=L.CONV_RELU)]
                     if f >= 128:
                         a_acts[n2a] = a
-                    if f == 64 and block > 0:
-                        blocks64.append({"block": block, "i_2a": i_2a, "i_2b": len(ops) - 1, "a": a, "x": x, "b2": b2, "n2a": n2a, "n2b": n2b,
-                                         "n2c": "res%s%s_branch2c" % (s, bname), "Ho": Ho, "Wo": Wo})
+                i_2b = len(ops) - 1
+                sc = x
                 if block == 0:
                     sc = buf(B, Ho, Wo, 4 * f)
-                    ops.append(self._conv("res%s%s_branch1" % (s, bname), [self._group(x, sc, Ho, Wo)], B, stride=st))
-                    i_b1 = len(ops) - 1
-                else:
-                    sc = x
+                    ops.append(self._conv(n1, [self._group(x, sc, Ho, Wo)], B, stride=st))
                 y = buf(B, Ho, Wo, 4 * f)
-                ops.append(self._conv("res%s%s_branch2c" % (s, bname), [self._group(b2, y, Ho, Wo, res=sc)], B,
-                                      flags=L.CONV_RELU | L.CONV_RES_SAME))
-                if not (fp8_on and ("a", n2a) in self.fp8_scales):
-                    cur_blk = {"stage": stage, "block": block, "i_2a": i_2a, "i_2c": len(ops) - 1, "a": a, "b2": b2, "x": sc, "y": y, "f": f,
-                               "n2a": n2a, "n2c": "res%s%s_branch2c" % (s, bname)}
-                    if prev_blk is not None and prev_blk["stage"] == stage and prev_blk["block"] >= 1 and prev_blk["block"] + 1 == block \
-                            and L.lib.rtn_chain1x1_supported(f, 4 * f, f):
-                        seams.append({"i_2c": prev_blk["i_2c"], "i_2a": i_2a, "b2": prev_blk["b2"], "x": prev_blk["x"], "y": prev_blk["y"],
-                                      "a": a, "f": f, "n2c": prev_blk["n2c"], "n2a": n2a})
-                    prev_blk = cur_blk
-                if block == 0:
-                    first_blocks.append({"key": "res%s%s" % (s, bname), "i_b1": i_b1, "i_2c": len(ops) - 1, "x": x, "b2": b2, "y": y,
-                                         "Ho": Ho, "Wo": Wo, "step": st, "f": f, "a": a, "n2b": n2b, "n2a": n2a,
-                                         "i_2a": None if (fp8_on and ("a", n2a) in self.fp8_scales) else i_2a,
-                                         "i_2b": None if (fp8_on and ("a", n2a) in self.fp8_scales) else i_2b_cur})
-                if blocks64 and blocks64[-1].get("y") is None and blocks64[-1]["n2c"] == "res%s%s_branch2c" % (s, bname):
-                    blocks64[-1].update({"i_2c": len(ops) - 1, "y": y})
+                ops.append(self._conv(n2c, [self._group(b2, y, Ho, Wo, res=sc)], B, flags=L.CONV_RELU | L.CONV_RES_SAME))
+                blocks.append(Block(stage, block, f, st, res, n2a, n2b, n2c, n1, x, a, b2, sc, y, None if fp8_pair else i_2b - 1,
+                                    None if fp8_pair else i_2b, i_2b + 1 if block == 0 else None, len(ops) - 1, Ho, Wo))
                 x = y
             feats.append(x)
         C3, C4, C5 = feats[1], feats[2], feats[3]
@@ -565,24 +537,22 @@ class Engine:
         P4 = buf(B, *hw(C4), 256)
         ops.append(self._conv("P4", [self._group(P4m, P4, *hw(C4))], B, pad=(1, 1)))
         p3_fp8 = fp8_on and ("a", "C3_reduced") in self.fp8_scales
+        P3m = buf(B, *hw(C3), 256, dtype=torch.uint8 if p3_fp8 else None)
+        c3r = self._conv("C3_reduced", [self._group(C3, P3m, *hw(C3), res=P4m)], B, flags=L.CONV_RES_UPSAMPLE)
+        P3 = buf(B, *hw(C3), 256, dtype=torch.uint8 if p3_fp8 else None)
         if p3_fp8:        # P3's input has no other reader and P3 itself only feeds the towers: C3_reduced -> e4m3 -> fp8 P3 -> e4m3
             s3 = self.fp8_scales[("a", "C3_reduced")]
-            P3m = buf(B, *hw(C3), 256, dtype=torch.uint8)
-            ops.append(("convq",) + self._conv("C3_reduced", [self._group(C3, P3m, *hw(C3), res=P4m)], B, flags=L.CONV_RES_UPSAMPLE)[1:] + (s3,))
-            P3 = buf(B, *hw(C3), 256, dtype=torch.uint8)
-            ops.append(self._conv8("P3", [self._group(P3m, P3, *hw(C3))], B, s3, self.fp8_scales["in"], out_fp8=True, relu=False))
+            ops += [O.ConvQ("convq", *c3r[1:], s3),
+                    self._conv8("P3", [self._group(P3m, P3, *hw(C3))], B, s3, self.fp8_scales["in"], out_fp8=True, relu=False)]
         else:
-            P3m = buf(B, *hw(C3), 256)
-            ops.append(self._conv("C3_reduced", [self._group(C3, P3m, *hw(C3), res=P4m)], B, flags=L.CONV_RES_UPSAMPLE))
-            P3 = buf(B, *hw(C3), 256)
-            ops.append(self._conv("P3", [self._group(P3m, P3, *hw(C3))], B, pad=(1, 1)))
+            ops += [c3r, self._conv("P3", [self._group(P3m, P3, *hw(C3))], B, pad=(1, 1))]
             a_acts["C3_reduced"] = P3m
         H6, W6 = (C5.shape[1] + 1) // 2, (C5.shape[2] + 1) // 2
         P6 = buf(B, H6, W6, 256)
         ops.append(self._conv("P6", [self._group(C5, P6, H6, W6)], B, stride=2,
                               pad=(same_pad_before(C5.shape[1], 3, 2), same_pad_before(C5.shape[2], 3, 2))))
         P6r = buf(B, H6, W6, 256)
-        ops.append(("relu", P6, P6r))
+        ops.append(O.Relu("relu", P6, P6r))
         H7, W7 = (H6 + 1) // 2, (W6 + 1) // 2
         P7 = buf(B, H7, W7, 256)
         ops.append(self._conv("P7", [self._group(P6r, P7, H7, W7)], B, stride=2,
@@ -602,7 +572,7 @@ class Engine:
             pyr8 = [p if p.dtype == torch.uint8 else buf(B, *hw(p), 256, dtype=torch.uint8) for p in pyr]
             for p, p8 in zip(pyr, pyr8):
                 if p8 is not p:
-                    ops.append(("quant", p, p8, self.fp8_scales["in"]))
+                    ops.append(O.Quant("quant", p, p8, self.fp8_scales["in"]))
         for prefix, out_t, per_anchor, last_flags in (("pyramid_regression", regression, 4, L.CONV_OUT_F32),
                                                       ("pyramid_classification", classification, self.K,
                                                        L.CONV_OUT_F32 | L.CONV_SIGMOID)):
@@ -627,7 +597,7 @@ class Engine:
             tower_ranges.append((tower_start, len(ops)))
         ws_bytes = L.lib.rtn_detect_workspace_bytes(B, N, self.K)
         # what _variant() substitutes: the fused ops of a fusion key are built on its first use
-        fusion = {"stem": stem_fused, "n_stem_ops": n_stem_ops, "first_blocks": first_blocks, "blocks64": blocks64, "seams": seams}
+        fusion = {"stem": stem_fused, "n_stem_ops": n_stem_ops, "blocks": blocks}
         plan = {"ops": ops, "towers": tower_ranges, "tower_acts": tower_acts, "a_acts": a_acts, "fp8": fp8_on, "sched": self._schedule(ops),
                 "keep": keep, "fusion": fusion, "variants": {}, "xin": xin, "cfg": cfg, "N": N, "regression": regression,
                 "classification": classification, "pyr": pyr, "feats": feats,
@@ -649,57 +619,55 @@ class Engine:
         else:
             fs, fd, fk, fc, fp, ft, fq = key
             fu, B = plan["fusion"], plan["xin"]["B"]
-            first_blocks, blocks64 = fu["first_blocks"], fu["blocks64"]
+            blocks = fu["blocks"]
+            first_blocks = [b for b in blocks if b.block == 0]
+            blocks64 = [b for b in blocks if b.f == 64 and b.block > 0 and b.i_2b is not None]      # identity blocks of the 64-channel stage
             v = list(plan["ops"])
-            if fc:
-                for sm in fu["seams"]:
-                    v[sm["i_2c"]] = self._chain_op(sm)
-                    v[sm["i_2a"]] = None
+            if fc:                                   # consecutive identity blocks of a stage: branch2c + the next branch2a as one launch
+                for blk, nxt in zip(blocks, blocks[1:]):
+                    if blk.stage == nxt.stage and blk.block >= 1 and blk.i_2a is not None and nxt.i_2a is not None \
+                            and L.lib.rtn_chain1x1_supported(blk.f, 4 * blk.f, blk.f):
+                        v[blk.i_2c] = self._chain_op(blk, nxt)
+                        v[nxt.i_2a] = None
             if fd:
                 # one set per plan, shared by its variants: dual ops run on lane 0, a plan's variants run in stream order, and every
                 # in-flight slot has a plan of its own
                 if "dual_ops" not in plan:
                     plan["dual_ops"] = [self._dual_op(fb, B) for fb in first_blocks]
                 for fb, op in zip(first_blocks, plan["dual_ops"]):
-                    v[fb["i_2c"]] = op
-                    v[fb["i_b1"]] = None
-            if fk and fd:                            # res2a: branch2b + [branch2c | branch1] + ReLU as one launch
-                for fb in first_blocks:
-                    if fb["f"] == 64 and fb["step"] == 1 and fb["i_2b"] is not None:
-                        nx0 = blocks64[0] if (blocks64 and fp) else None      # res2b's branch2a rides along
-                        v[fb["i_2b"]] = self._bneck_proj_op(fb, B, keep_h1=fk == 2, nxt=nx0)
-                        v[fb["i_2c"]] = None
-                        if nx0 is not None:
-                            v[nx0["i_2a"]] = None
-            if fk:
-                for bi, blk in enumerate(blocks64):
-                    nxt = blocks64[bi + 1] if bi + 1 < len(blocks64) else None      # its branch2a rides along
-                    v[blk["i_2b"]] = self._bneck_op(blk, nxt, B, keep_h1=fk == 2)
-                    v[blk["i_2c"]] = None
+                    v[fb.i_2c] = op
+                    v[fb.i_b1] = None
+            if fk:                                   # with fd, res2a too: branch2b + [branch2c | branch1] + ReLU as one launch
+                fused = [fb for fb in first_blocks if fd and fb.f == 64 and fb.step == 1 and fb.i_2b is not None] + blocks64
+                for blk in fused:
+                    # the next block's branch2a rides along (blocks64[k] is block k + 1; res2a takes res2b's only under fp)
+                    nxt = blocks64[blk.block] if blk.block < len(blocks64) and (blk.block or fp) else None
+                    v[blk.i_2b] = self._bneck_op(blk, nxt, B, keep_h1=fk == 2)
+                    v[blk.i_2c] = None
                     if nxt is not None:
-                        v[nxt["i_2a"]] = None
+                        v[nxt.i_2a] = None
             if fq:
                 # C2 is read at its even pixels only (res3a's branch2a and branch1: 1x1, stride 2).  The stage's last block computes
                 # and writes that quarter, the block before it stores the matching quarter of its output (whose only reader in
                 # memory is the last block's shortcut), and res3a reads the compact C2 with stride 1.
                 prev, last = blocks64[-2], blocks64[-1]
-                fb3 = [fb for fb in first_blocks if fb["x"] is last["y"]][0]
+                fb3 = [fb for fb in first_blocks if fb.x is last.y][0]
                 if "c2_quarter" not in plan:                  # two tensors a quarter of C2 each, shared by the variants like dual_ops
-                    hq, wq = (last["Ho"] + 1) // 2, (last["Wo"] + 1) // 2
+                    hq, wq = (last.Ho + 1) // 2, (last.Wo + 1) // 2
                     plan["c2_quarter"] = [torch.empty(B, hq, wq, 256, dtype=self.tdt, device=self.device) for _ in range(2)]
                     plan["keep"] += plan["c2_quarter"]
                     xq, c2q = plan["c2_quarter"]
                     plan["c2_quarter_ops"] = (self._bneck_op(prev, last, B, yq=xq), self._bneck_op(last, None, B, xq=xq, yq=c2q),
-                                              self._conv(fb3["n2a"], [self._group(c2q, fb3["a"], fb3["Ho"], fb3["Wo"])], B, flags=L.CONV_RELU),
-                                              self._dual_op(dict(fb3, x=c2q, step=1), B))
-                v[prev["i_2b"]], v[last["i_2b"]], v[fb3["i_2a"]], v[fb3["i_2c"]] = plan["c2_quarter_ops"]
+                                              self._conv(fb3.n2a, [self._group(c2q, fb3.a, fb3.Ho, fb3.Wo)], B, flags=L.CONV_RELU),
+                                              self._dual_op(fb3._replace(x=c2q, step=1), B))
+                v[prev.i_2b], v[last.i_2b], v[fb3.i_2a], v[fb3.i_2c] = plan["c2_quarter_ops"]
             if fs:
                 sf = fu["stem"]
                 fb0 = first_blocks[0]
-                if fs == 2 and fb0["f"] == 64 and fb0["step"] == 1 and fb0["i_2a"] is not None and v[fb0["i_2a"]] is not None:
-                    w2a, b2a = self.w[fb0["n2a"]][:2]             # the pooled pixels go through res2a_branch2a before they leave the registers
-                    sf = sf[:7] + ((fb0["a"], w2a, b2a), sf[8])
-                    v[fb0["i_2a"]] = None
+                if fs == 2 and fb0.f == 64 and fb0.step == 1 and fb0.i_2a is not None and v[fb0.i_2a] is not None:
+                    # the pooled pixels go through res2a_branch2a before they leave the registers
+                    sf = sf._replace(tail=(fb0.a,) + tuple(self.w[fb0.n2a][:2]))
+                    v[fb0.i_2a] = None
                 v = [v[0], sf] + v[fu["n_stem_ops"]:]              # pack, then conv1 + ReLU + pool1 as one launch
             ops = [op for op in v if op is not None]
             sched = self._schedule(ops)
@@ -707,55 +675,22 @@ class Engine:
         plan["variants"][key] = rec
         return rec
 
-    # ------------------------------------------------------------------ lanes
+    # ------------------------------------------------------------------ lanes: the records of ops.py say what an op reads, where it runs, how
     @staticmethod
     def _op_io(op):
         """(tensors read, tensors written) of a plan op, as data pointers."""
-        kind = op[0]
-        if kind in ("conv", "conv8", "convq"):
-            m = op[3]
-            reads = [t.data_ptr() for t in m["xs"]] + [t.data_ptr() for t in m["res"] if t is not None]
-            return reads, [t.data_ptr() for t in m["ys"]]
-        if kind == "quant":
-            return [op[1].data_ptr()], [op[2].data_ptr()]
-        if kind == "pack":
-            return [], [op[1].data_ptr()]
-        if kind == "stem":
-            return [op[5].data_ptr()], [op[1].data_ptr(), op[8].data_ptr()] + ([op[7][0].data_ptr()] if op[7] is not None else [])
-        if kind == "dual":
-            return [t.data_ptr() for t in op[4]["xs"]], [t.data_ptr() for t in op[4]["ys"]]
-        if kind in ("bneck", "chain"):
-            return [t.data_ptr() for t in op[3]["xs"]], [t.data_ptr() for t in op[3]["ys"]]
-        if kind == "pool":
-            return [op[1].data_ptr()], [op[2].data_ptr(), op[4].data_ptr()]
-        if kind == "relu":
-            return [op[1].data_ptr()], [op[2].data_ptr()]
-        raise RuntimeError("unknown op %r" % (kind,))
+        return op.io()
 
     @staticmethod
     def _lane_of(op):
-        """HIP stream lane of an op.  The graph is a chain except where the reference's model forks
-        (model/defineModel.py:183-249): the projection shortcut of a stage's first block (branch1, beside branch2a/2b),
-        the P6 -> P7 and P5 / P4 branches of the pyramid (beside the top-down C4/C3 path) and the two head towers.  Those
-        run on side lanes so that their launch latency and partly filled last rounds of workgroups overlap other work."""
-        if op[0] == "relu":
-            return 1                                              # between P6 and P7
-        if op[0] not in ("conv", "conv8", "convq"):
-            return 0
-        name = op[2]
-        if name.endswith("_branch1") or name in ("P6", "P7"):
-            return 1
-        if name in ("P5", "P4"):
-            return 2
-        if name.startswith("pyramid_classification"):
-            return 1
-        return 0
+        """HIP stream lane of an op: 0 except at the graph's forks (ops._conv_lane)."""
+        return op.lane()
 
     @staticmethod
     def _schedule(ops):
         """Lanes of a forward op list and their events (schedule_lanes).  Every tensor of a plan is written by exactly one op of a
         forward pass, so only read-after-write hazards arise inside a pass; passes are joined on lane 0."""
-        return schedule_lanes([Engine._lane_of(op) for op in ops], [Engine._op_io(op) for op in ops])
+        return schedule_lanes([op.lane() for op in ops], [op.io() for op in ops])
 
     # ------------------------------------------------------------------ run
     def _bind_stream(self):
@@ -789,30 +724,12 @@ class Engine:
             for op in ops:
                 self._run_op(op, images)
             return plan["regression"], plan["classification"]
-        sched, events = var["sched"], var["events"]
         main = torch.cuda.current_stream(self.device)
         if self._side is None:                               # three lanes that do not share a hardware queue with each other or with `main`
             self._side = self._concurrent_streams(3, beside=(main,))
-        streams = [main] + self._side
-        lanes, waits = sched["lanes"], sched["waits"]
-        fork = plan.setdefault("fork", torch.cuda.Event())
-        fork.record(main)                                    # side lanes start after everything queued before this pass
-        for st in streams[1:sched["nlanes"]]:
-            st.wait_event(fork)
-        bound = None
-        for i, op in enumerate(ops):
-            st = streams[lanes[i]]
-            for j in waits[i]:
-                st.wait_event(events[j])
-            if bound is not st:
-                self.h.set_stream(st.cuda_stream)
-                bound = st
-            self._run_op(op, images)
-            if i in events:
-                events[i].record(st)
-        for j in sched["joins"]:
-            main.wait_event(events[j])
-        self.h.set_stream(main.cuda_stream)
+        # the fork: side lanes start after everything queued before this pass
+        run_lanes(self.h, [main] + self._side, var["sched"], var["events"], plan.setdefault("fork", torch.cuda.Event()),
+                  lambda i, st: self._run_op(ops[i], images))
         return plan["regression"], plan["classification"]
 
     def _fused(self, private=False):
@@ -847,49 +764,7 @@ class Engine:
         return self._variant(plan, self._fused(private))["ops"]
 
     def _run_op(self, op, images):
-        lib, h = L.lib, self.h
-        kind = op[0]
-        if kind == "conv":
-            h.check(lib.rtn_conv2d_fwd(h.raw, C.byref(op[1])))
-        elif kind == "dual":
-            h.check(lib.rtn_conv1x1_dual_fwd(h.raw, C.byref(op[1]), C.byref(op[3])))
-        elif kind == "bneck":
-            h.check(lib.rtn_bottleneck64_fwd(h.raw, C.byref(op[1])))
-        elif kind == "chain":
-            h.check(lib.rtn_chain1x1_fwd(h.raw, C.byref(op[1])))
-        elif kind == "conv8":
-            h.check(lib.rtn_conv2d_fp8_fwd(h.raw, C.byref(op[1]), C.byref(op[4])))
-        elif kind == "convq":
-            h.check(lib.rtn_conv2d_fwd_fp8out(h.raw, C.byref(op[1]), op[4]))
-        elif kind == "quant":
-            h.check(lib.rtn_quantize_fp8(h.raw, op[1].data_ptr(), self.rdt, op[2].data_ptr(), op[1].numel(), op[3]))
-        elif kind == "stem":
-            Bn, Hn, Wn = op[2]
-            taps = self._taps()
-            if op[7] is not None or taps:                # + res2a_branch2a on the pooled pixels; training: + the pool's winning taps
-                a_out, w2a, b2a = op[7] if op[7] is not None else (None, None, None)
-                h.check(lib.rtn_stem_conv_pool_branch2a(h.raw, op[5].data_ptr(), op[6][0], op[6][1], op[3].data_ptr(), op[3].shape[0],
-                                                        op[4].data_ptr(), op[1].data_ptr(), Bn, Hn, Wn,
-                                                        w2a.data_ptr() if w2a is not None else None, b2a.data_ptr() if b2a is not None else None,
-                                                        a_out.data_ptr() if a_out is not None else None,
-                                                        op[8].data_ptr() if taps else None))
-            else:
-                h.check(lib.rtn_stem_conv_pool(h.raw, op[5].data_ptr(), op[6][0], op[6][1], op[3].data_ptr(), op[3].shape[0],
-                                               op[4].data_ptr(), op[1].data_ptr(), Bn, Hn, Wn))
-        elif kind == "pack":
-            xi = op[2]
-            h.check(lib.rtn_stem_pack(h.raw, images.data_ptr(), _SRC_DT[images.dtype], op[1].data_ptr(), self.rdt,
-                                      xi["B"], xi["H"], xi["W"], xi["Hp"], xi["Wp"]))
-        elif kind == "pool":
-            Bn, Hi, Wi, Cc = op[3]
-            if self._taps():
-                h.check(lib.rtn_maxpool3x3s2_tfsame_fwd_idx(h.raw, op[1].data_ptr(), op[2].data_ptr(), op[4].data_ptr(), self.rdt, Bn, Hi, Wi, Cc))
-            else:
-                h.check(lib.rtn_maxpool3x3s2_tfsame_fwd(h.raw, op[1].data_ptr(), op[2].data_ptr(), self.rdt, Bn, Hi, Wi, Cc))
-        elif kind == "relu":
-            h.check(lib.rtn_relu(h.raw, op[1].data_ptr(), op[2].data_ptr(), self.rdt, op[1].numel()))
-        else:
-            raise RuntimeError("unknown op %r" % (kind,))
+        op.launch(self, images)
 
     def profile_ops(self, images, reps=1):
         """Per-op device time: events recorded on the launch stream around every op of `reps` forward passes.
@@ -912,7 +787,7 @@ class Engine:
             torch.cuda.synchronize()
             for i in range(len(ops) + 1):
                 totals[i] += evs[i].elapsed_time(evs[i + 1])
-        return [(op[0], totals[i]) for i, op in enumerate(ops)] + [("detect", totals[-1])]
+        return [(op.kind, totals[i]) for i, op in enumerate(ops)] + [("detect", totals[-1])]
 
     def detect(self, images, score_threshold=0.05, nms_threshold=0.5, max_detections=300, nms=True, class_specific_filter=True):
         """Inference model outputs [boxes (B,300,4), scores (B,300), labels (B,300)] (model/defineModel.py:310-315).
@@ -974,7 +849,7 @@ class Engine:
             caller.wait_event(slot["consumed"])
         self.h.set_stream(caller.cuda_stream)
         first = 0
-        if ops and ops[0][0] == "pack":                      # the only reader of `images`: in the caller's stream order
+        if ops and ops[0].kind == "pack":                      # the only reader of `images`: in the caller's stream order
             self._run_op(ops[0], images)
             first = 1
         else:
@@ -1065,13 +940,6 @@ class Engine:
         """flags: detect_flags(nms, class_specific_filter); every mode fits the plan's workspace (rtn_detect_workspace_bytes)."""
         self._bind_stream()
         B = regression.shape[0]
-        if flags == 0:
-            self.h.check(L.lib.rtn_decode_filter_nms(self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(),
-                                                      classification.data_ptr(), H, W, score_threshold, nms_threshold,
-                                                      max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                                      ws.data_ptr(), ws.numel()))
-        else:
-            self.h.check(L.lib.rtn_decode_filter_nms_ex(self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(),
-                                                         classification.data_ptr(), H, W, score_threshold, nms_threshold,
-                                                         max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                                         ws.data_ptr(), ws.numel(), flags, None))
+        args = (self.h.raw, C.byref(cfg), B, classification.shape[2], regression.data_ptr(), classification.data_ptr(), H, W, score_threshold,
+                nms_threshold, max_detections, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), ws.data_ptr(), ws.numel())
+        self.h.check(L.lib.rtn_decode_filter_nms(*args) if flags == 0 else L.lib.rtn_decode_filter_nms_ex(*args, flags, None))

@@ -25,6 +25,7 @@ range tables hold the trainable layers only, the all-reduce runs over their segm
 stem and the 64-channel blocks in their inference form when the backward never reads their extra outputs (Engine.train_keep).
 """
 import ctypes as C
+import itertools
 
 import numpy as np
 import os
@@ -33,9 +34,10 @@ import weakref
 import torch
 
 from . import _lib as L
+from . import ops as O
 from . import weights as Wt
 from . import parallel as Par
-from .engine import schedule_lanes
+from .engine import run_lanes, schedule_lanes
 
 
 def _ceil128(v):
@@ -253,8 +255,8 @@ class Trainer:
         # producers / consumers
         prod, ncons, relu_src = {}, {}, {}
         for op in ops:
-            if op[0] == "conv":
-                me = op[3]
+            if op.kind == "conv":
+                me = op.meta
                 for y in me["ys"]:
                     prod[tid(y)] = me
                 for x in me["xs"]:
@@ -262,24 +264,24 @@ class Trainer:
                 for r in me["res"]:
                     if r is not None:
                         ncons[tid(r)] = ncons.get(tid(r), 0) + 1
-            elif op[0] == "pool":
-                ncons[tid(op[1])] = ncons.get(tid(op[1]), 0) + 1
-                prod[tid(op[2])] = {"relu": False, "name": "pool1"}
-            elif op[0] == "relu":
-                relu_src[tid(op[2])] = op[1]                       # P6r -> P6
+            elif op.kind == "pool":
+                ncons[tid(op.src)] = ncons.get(tid(op.src), 0) + 1
+                prod[tid(op.dst)] = {"relu": False, "name": "pool1"}
+            elif op.kind == "relu":
+                relu_src[tid(op.dst)] = op.src                     # P6r -> P6
         for t_, src in relu_src.items():                            # a consumer of relu(S) counts as a consumer of S
             ncons[tid(src)] = ncons.get(tid(src), 0) + ncons.pop(t_, 0)
         # needs-grad: a tensor needs a gradient iff its producer is a trainable layer or any input of its producer needs one.  Every
         # consumer of a tensor is pruned alike, so the first-writer / accumulate order below is the full backward's, minus whole tensors.
         need = set()
         for op in ops:
-            if op[0] == "conv":
-                me = op[3]
-                if self._is_trainable(op[2]) or any(tid(x) in need for x in me["xs"]) or \
+            if op.kind == "conv":
+                me = op.meta
+                if self._is_trainable(op.name) or any(tid(x) in need for x in me["xs"]) or \
                         any(r is not None and tid(r) in need for r in me["res"]):
                     need.update(tid(y) for y in me["ys"])
-            elif op[0] in ("pool", "relu") and tid(op[1]) in need:
-                need.add(tid(op[2]))
+            elif op.kind in ("pool", "relu") and tid(op.src) in need:
+                need.add(tid(op.dst))
 
         grads, gstate, done = {}, {}, {}
 
@@ -300,18 +302,13 @@ class Trainer:
         grads[tid(plan["regression"])] = dyp_reg
         grads[tid(plan["classification"])] = dyp_cls
         if tid(plan["regression"]) in need:
-            bops.append(("padcast", d_reg, dyp_reg, B * cells_total, eng.A * 4, cp_reg))
+            bops.append(O.PadCast("padcast", d_reg, dyp_reg, B * cells_total, eng.A * 4, cp_reg))
         if tid(plan["classification"]) in need:
-            bops.append(("padcast", d_cls, dyp_cls, B * cells_total, eng.A * eng.K, cp_cls))
+            bops.append(O.PadCast("padcast", d_cls, dyp_cls, B * cells_total, eng.A * eng.K, cp_cls))
 
-        def group_fwd_geom(g, x):
-            g.in_, g.in_elems = x.data_ptr(), x.numel()
-
-        max_ws = 0
         for op in reversed(ops):
-            kind = op[0]
-            if kind == "conv":
-                d_f, name, me = op[1], op[2], op[3]
+            if op.kind == "conv":
+                d_f, name, me = op.desc, op.name, op.meta
                 if tid(me["ys"][0]) not in need:             # frozen, and nothing below it trains
                     continue
                 lo = eng.layout[name]
@@ -346,9 +343,7 @@ class Trainer:
                     else:
                         g.out_img_stride, g.out_off = cells * crun, 0
                 if self._is_trainable(name):
-                    wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(dw))
-                    max_ws = max(max_ws, wsb)
-                    bops.append(("wgrad", dw, dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
+                    bops.append(O.Wgrad("wgrad", dw, dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
                 # ---------- residual inputs of the forward epilogue
                 for gi in range(ng):
                     r = me["res"][gi]
@@ -361,7 +356,7 @@ class Trainer:
                         gstate[tid(r)] = ("alias", dys[gi])
                     else:                                            # UpsampleLike + Add
                         acc = 1 if gstate.get(tid(r)) == "buf" else 0
-                        bops.append(("upbwd", dys[gi], gbuf(r), (B, dys[gi].shape[1], dys[gi].shape[2], r.shape[1], r.shape[2], r.shape[3]), acc))
+                        bops.append(O.UpBwd("upbwd", dys[gi], gbuf(r), (B, dys[gi].shape[1], dys[gi].shape[2], r.shape[1], r.shape[2], r.shape[3]), acc))
                         gstate[tid(r)] = "buf"
                 # ---------- dgrad into every input
                 if me.get("stem"):
@@ -415,7 +410,7 @@ class Trainer:
                         Hs, Ws = 2 * Ho - 1, 2 * Wo - 1
                         up = torch.zeros(B, Hs, Ws, crun, dtype=tdt, device=dev)
                         keep.append(up)
-                        bops.append(("zins", dy, up, (B, Ho, Wo, crun, Hs, Ws)))
+                        bops.append(O.Zins("zins", dy, up, (B, Ho, Wo, crun, Hs, Ws)))
                         src = up
                         dd.pad_t, dd.pad_l = lo["kh"] - 1 - pt, lo["kw"] - 1 - pl
                         g.Hout, g.Wout = Hx, Wx
@@ -449,89 +444,54 @@ class Trainer:
                 dd.ngroups = ngd
                 dd.flags = flags_all
                 L.attach_conv_workspace(eng.h, dd)                   # caller-owned K-split slabs, one buffer per launch
-                bops.append(("dgrad", dd, name))
-            elif kind == "pool":
-                x, y = op[1], op[2]
+                bops.append(O.Dgrad("dgrad", dd, name))
+            elif op.kind == "pool":
+                x, y = op.src, op.dst
                 if tid(x) not in need:
                     continue
                 dy = grads.get(tid(y))
                 done[tid(x)] = done.get(tid(x), 0) + 1
-                bops.append(("poolbwd", x, dy, gbuf(x), op[3], op[4], y))      # y: the pooled tensor (the fused stem's ReLU mask)
+                bops.append(O.PoolBwd("poolbwd", x, dy, gbuf(x), op.bhwc, op.idx, y))      # y: the pooled tensor (the fused stem's ReLU mask)
                 gstate[tid(x)] = "buf"
         loss_ws = torch.empty(L.lib.rtn_retina_loss_workspace_bytes(B * N), dtype=torch.uint8, device=dev)
-        bias_bops = [i for i, b in enumerate(bops) if b[0] == "wgrad" and b[4] is not None]
+        bias_bops = [i for i, b in enumerate(bops) if b.kind == "wgrad" and b.db is not None]
         # every weight-gradient op owns its workspace (row-info table + the slabs of its ordered split reduction: 130 MB for a head
-        # layer at batch 16 x 800 x 1333, 3.4 GB over the 107 layers), allocated at its first launch in forward_backward: ops on
+        # layer at batch 16 x 800 x 1333, 3.4 GB over the 107 layers), allocated at its first launch (ops.Wgrad.launch): ops on
         # different lanes never share scratch, and the table is built once per layer
         # what the pruned backward reads of the training forward's extra outputs: branch2b of the fused 64-channel blocks, the pool taps
-        reads = set(p_ for b in bops for p_ in Trainer._bop_io(b)[0])
-        fu = plan["fusion"]
-        h1s = [blk["b2"] for blk in fu["blocks64"]] + [fb["b2"] for fb in fu["first_blocks"] if fb["f"] == 64]
-        keep_fwd = (any(t.data_ptr() in reads for t in h1s), any(b[0] == "poolbwd" for b in bops))
+        reads = set(p_ for b in bops for p_ in b.io()[0])
+        keep_fwd = (any(blk.b2.data_ptr() in reads for blk in plan["fusion"]["blocks"] if blk.f == 64), any(b.kind == "poolbwd" for b in bops))
         # id(forward tensor) -> the tensor that holds its gradient after the backward pass: its own buffer, or the aliased sum's for a
         # tensor whose only consumer is a residual add.  grad_src keeps those forward tensors alive, so the ids stay valid.
         grad_of_map = dict(grads)
         grad_of_map.update({t_: st_[1] for t_, st_ in gstate.items() if isinstance(st_, tuple)})
         fwd = {}
         for op in ops:
-            ts = (list(op[3]["xs"]) + list(op[3]["ys"]) + [r for r in op[3]["res"] if r is not None]) if op[0] == "conv" else \
-                [op[1], op[2]] if op[0] in ("pool", "relu") else []
+            ts = (list(op.meta["xs"]) + list(op.meta["ys"]) + [r for r in op.meta["res"] if r is not None]) if op.kind == "conv" else \
+                [op.src, op.dst] if op.kind in ("pool", "relu") else []
             fwd.update((tid(t), t) for t in ts)
-        bp = {"bops": bops, "keep": keep, "last_bias_bop": bias_bops[-1] if bias_bops else -1, "wgrad_ws_bytes": max_ws,
+        bp = {"bops": bops, "keep": keep, "last_bias_bop": bias_bops[-1] if bias_bops else -1,
               "keep_fwd": keep_fwd, "grad_of": grad_of_map, "grad_src": [fwd[t_] for t_ in grad_of_map],
               "d_reg": d_reg, "d_cls": d_cls, "dyp_cls": dyp_cls, "loss_ws": loss_ws, "plan": plan, "rowinfo": {}}
         self.bplans[key] = bp
         return bp
 
-    # ------------------------------------------------------------------ step
     # ------------------------------------------------------------------ backward lanes
     @staticmethod
     def _bop_io(b):
         """(pointers read, pointers written) of a backward op (accumulating outputs are both)."""
-        kind = b[0]
-        if kind == "padcast":
-            return [b[1].data_ptr()], [b[2].data_ptr()]
-        if kind == "zins":
-            return [b[1].data_ptr()], [b[2].data_ptr()]
-        if kind == "upbwd":
-            return [b[1].data_ptr()] + ([b[2].data_ptr()] if b[4] else []), [b[2].data_ptr()]
-        if kind == "poolbwd":
-            return [b[1].data_ptr(), b[2].data_ptr(), b[5].data_ptr(), b[6].data_ptr()], [b[3].data_ptr()]
-        d = b[1]
-        if kind == "wgrad":
-            reads = [p_ for i in range(d.ngroups) for p_ in (d.g[i].in_, d.g[i].out)]
-            return reads, [b[2].data_ptr()] + ([b[4].data_ptr()] if b[4] is not None else [])
-        if kind == "dgrad":
-            reads, writes = [], []
-            for i in range(d.ngroups):
-                g = d.g[i]
-                reads.append(g.in_)
-                if d.flags & L.CONV_RELU_MASK:
-                    reads.append(g.mask)
-                if d.flags & (L.CONV_RES_SAME | L.CONV_RES_UPSAMPLE):
-                    reads.append(g.res)
-                writes.append(g.out)
-            return reads, writes
-        raise RuntimeError(kind)
+        return b.io()
 
     def _bschedule(self, bops, nwg, dyp_cls):
         """Lane of every backward op and the cross-lane events it must wait for.  Lane 0: the data-gradient chain; lanes
         1..nwg: weight / bias gradients (independent of each other: round-robin); lane nwg+1: the data gradients of the
-        classification tower, which only meet the rest of the graph where the pyramid gradients are summed.  Events come from
-        schedule_lanes; write-after-read hazards arise here (gradient buffers are accumulated in place by several ops)."""
-        lanes, turn = [], 0
-        extra = os.environ.get("RTN_BWD_EXTRA_LANE", "0") != "0"
-        for b in bops:
-            if b[0] in ("wgrad", "bgrad"):
-                lanes.append(1 + turn % nwg)
-                turn += 1
-            elif (b[0] == "dgrad" and str(b[2]).startswith("pyramid_classification")) or (b[0] == "padcast" and b[2] is dyp_cls):
-                lanes.append(nwg + 1)
-            elif extra and b[0] == "dgrad" and (str(b[2]).endswith("_branch1") or str(b[2]) in ("P6", "P7", "P5", "P4")):
-                lanes.append(nwg + 2)
-            else:
-                lanes.append(0)
-        return schedule_lanes(lanes, [Trainer._bop_io(b) for b in bops])
+        classification tower, which only meet the rest of the graph where the pyramid gradients are summed; lane nwg+2
+        (RTN_BWD_EXTRA_LANE): the data gradients beside the forward graph's forks.  Events come from schedule_lanes;
+        write-after-read hazards arise here (gradient buffers are accumulated in place by several ops)."""
+        fixed = {O.MAIN: 0, O.CLS: nwg + 1, O.EXTRA: nwg + 2 if os.environ.get("RTN_BWD_EXTRA_LANE", "0") != "0" else 0}
+        weight = itertools.cycle(range(1, nwg + 1))
+        lanes = [next(weight) if cls == O.WEIGHT else fixed[cls] for cls in (b.lane(dyp_cls) for b in bops)]
+        return schedule_lanes(lanes, [b.io() for b in bops])
 
     def forward_backward(self, images, regression_batch, labels_batch):
         """Forward, loss and backward; leaves dL/dparams in self.grad (flat f32) and returns the device tensor
@@ -568,90 +528,23 @@ class Trainer:
         self.grad.zero_()
         # Lanes (see _bschedule): data-gradient chain on the launch stream; weight / bias gradients round-robin over side streams;
         # the classification tower's data gradients on one more.  Events follow the per-buffer hazards.
+        bops = bp["bops"]
+        if not self.wgrad_lane:
+            for bi, b in enumerate(bops):
+                b.launch(self, bp, bi)
+            return self.loss_sums
         main = torch.cuda.current_stream(eng.device)
-        lane_on = self.wgrad_lane
         nwg = self.wgrad_lanes        # also under DP: the bucketer records one event per (bucket, lane) and waits for all of them
-        if lane_on:
-            key = ("bsched", nwg)
-            if key not in bp:
-                sch = self._bschedule(bp["bops"], nwg, bp["dyp_cls"])
-                sch["ev"] = {i: torch.cuda.Event() for i in sch["events"]}
-                bp[key] = sch
-            sch = bp[key]
-            if self._wg_stream is None or len(self._wg_stream) < sch["nlanes"] - 1:
-                # lanes on hardware queues of their own as far as the runtime has them (Engine._concurrent_streams)
-                self._wg_stream = eng._concurrent_streams(self.WG_LANES + 2, beside=(main,))
-                self._wg_ev = torch.cuda.Event()
-            streams = [main] + self._wg_stream[:sch["nlanes"] - 1]
-            self._wg_ev.record(main)                      # side lanes start behind the loss backward and the gradient reset
-            for st in streams[1:]:
-                st.wait_event(self._wg_ev)
-        for bi, b in enumerate(bp["bops"]):
-            kind = b[0]
-            on_side = False
-            if lane_on:
-                ln = sch["lanes"][bi]
-                st = streams[ln]
-                for j in sch["waits"][bi]:
-                    st.wait_event(sch["ev"][j])
-                on_side = ln != 0
-                if on_side:
-                    side = st
-                    h.set_stream(st.cuda_stream)
-            if kind == "wgrad":
-                tab = bp["rowinfo"].get(bi)
-                if tab is None:                       # the row-info table depends on the descriptor only: built once per layer
-                    tab = torch.empty(L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(b[1])), dtype=torch.uint8, device=eng.device)
-                    h.check(lib.rtn_conv2d_wgrad_rowinfo(h.raw, C.byref(b[1]), tab.data_ptr(), tab.numel()))
-                    bp["rowinfo"][bi] = tab
-                h.check(lib.rtn_conv2d_wgrad_prepared(h.raw, C.byref(b[1]), b[2].data_ptr(), b[4].data_ptr() if b[4] is not None else None,
-                                                      b[5] if b[4] is not None else 0, tab.data_ptr(), tab.numel()))
-                if self.record_impls:
-                    self.impls[("wgrad", b[3])] = lib.rtn_debug_last_wgrad_impl(h.raw)
-                if self.bucketer is not None:         # this layer's weight gradient is enqueued: its bucket may go out
-                    last_bias = bi == bp["last_bias_bop"]
-                    done_names = [b[3]] + (self.bias_names if last_bias else [])   # last fused bias gradient
-                    if last_bias and lane_on:         # the bias gradients came from every weight-gradient lane: mark them all
-                        for ln_ in range(1, nwg + 1):
-                            with torch.cuda.stream(streams[ln_]):
-                                for bn_ in self.bias_names:
-                                    self.bucketer.mark(bn_)
-                    for dn in done_names:
-                        if on_side:
-                            with torch.cuda.stream(side):     # the bucket's event must follow the kernels on THEIR stream
-                                self.bucketer.layer_done(dn)
-                        else:
-                            self.bucketer.layer_done(dn)
-            elif kind == "dgrad":
-                h.check(lib.rtn_conv2d_dgrad(h.raw, C.byref(b[1])))
-                if self.record_impls:
-                    self.impls[("dgrad", b[2])] = lib.rtn_debug_last_conv_impl(h.raw)
-            elif kind == "bgrad":
-                h.check(lib.rtn_bias_grad(h.raw, b[1].data_ptr(), eng.rdt, b[2], b[3], b[4], b[5].data_ptr()))
-            elif kind == "padcast":
-                h.check(lib.rtn_pad_cast_rows(h.raw, b[1].data_ptr(), b[2].data_ptr(), eng.rdt, b[3], b[4], b[5]))
-            elif kind == "zins":
-                Bn, Ho, Wo, Cc, Hs, Ws = b[3]
-                h.check(lib.rtn_zero_insert2(h.raw, b[1].data_ptr(), b[2].data_ptr(), eng.rdt, Bn, Ho, Wo, Cc, Hs, Ws))
-            elif kind == "upbwd":
-                Bn, Hd, Wd, Hs, Ws, Cc = b[3]
-                h.check(lib.rtn_upsample_add_bwd(h.raw, b[1].data_ptr(), b[2].data_ptr(), eng.rdt, Bn, Hd, Wd, Hs, Ws, Cc, b[4]))
-            elif kind == "poolbwd":
-                Bn, Hi, Wi, Cc = b[4]
-                # the fused stem (bf16 training forward) never writes conv1's output: the ReLU mask comes from the pooled tensor
-                fused = self.fwd_key[0] != 0
-                h.check(lib.rtn_maxpool3x3s2_tfsame_bwd_idx(h.raw, b[2].data_ptr(), b[5].data_ptr(), (b[6] if fused else b[1]).data_ptr(),
-                                                            b[3].data_ptr(), eng.rdt, Bn, Hi, Wi, Cc, 2 if fused else 1))
-            else:
-                raise RuntimeError(kind)
-            if lane_on:
-                if bi in sch["ev"]:
-                    sch["ev"][bi].record(st)
-                if on_side:
-                    h.set_stream(main.cuda_stream)
-        if lane_on:
-            for j in sch["joins"]:
-                main.wait_event(sch["ev"][j])
+        sch = bp.get(("bsched", nwg))
+        if sch is None:
+            sch = bp[("bsched", nwg)] = self._bschedule(bops, nwg, bp["dyp_cls"])
+            sch["ev"] = {i: torch.cuda.Event() for i in sch["events"]}
+        if self._wg_stream is None:
+            # lanes on hardware queues of their own as far as the runtime has them (Engine._concurrent_streams)
+            self._wg_stream = eng._concurrent_streams(self.WG_LANES + 2, beside=(main,))
+            self._wg_ev = torch.cuda.Event()
+        # the fork (_wg_ev): side lanes start behind the loss backward and the gradient reset
+        run_lanes(h, [main] + self._wg_stream, sch, sch["ev"], self._wg_ev, lambda bi, st: bops[bi].launch(self, bp, bi, st))
         return self.loss_sums
 
     def optimizer_step(self, lr=None):

@@ -1,0 +1,212 @@
+"""Pin of the engine's and trainer's plans: op lists, lane schedules, descriptor wiring and result bits of seven small rows.
+
+  python tools/record_plan_schedule.py            # writes tests/golden/plan_schedule.json (run at the commit to pin against)
+  python tools/record_plan_schedule.py --full F   # also every op's full serialisation, for reading a mismatch
+
+tests/test_gpu_plan_schedule.py rebuilds the rows with the code under test (build_rows below) and compares them with the fixture.
+A row holds the fusion key, per op [kind, name-or-null, hash of the op's serialisation], the schedule (lanes, waits, events, joins,
+nlanes) and SHA-256 of the outputs; training rows hold the same for the backward op list and the hash of Trainer.grad.  An op is
+serialised element by element: a descriptor as its scalar fields (per group for the first `ngroups` groups), a tensor as shape and
+dtype, a meta dict by key; every device address - a tensor's or a descriptor's pointer field - becomes the ordinal at which it first
+appears in the row, which pins the wiring of the buffers without pinning addresses.  The recorder builds every row twice: a
+result hash that differs between the two runs is written as null, with the tensor's norms (per layer for the gradient) under "stats",
+which the test then compares within the tolerance of tests/test_gpu_train.py; op lists, schedules and descriptors must agree, and
+so must the outputs of the three bf16 inference rows, or the recorder stops."""
+import argparse
+import ctypes as C
+import hashlib
+import importlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "retinanet-for-table-detection_amd"
+FIXTURE = os.path.join(ROOT, "tests", "golden", "plan_schedule.json")
+BF16_CANVAS, F32_CANVAS = (320, 448), (146, 210)
+
+
+class _Ser:
+    """Serialiser of one row: the address -> ordinal map is shared by the row's forward and backward lists."""
+
+    def __init__(self):
+        self.ordinal = {}
+
+    def ptr(self, p):
+        if not p:
+            return None
+        return ["p", self.ordinal.setdefault(int(p), len(self.ordinal))]
+
+    def ser(self, v):
+        if isinstance(v, torch.Tensor):
+            return ["t", self.ptr(v.data_ptr()), list(v.shape), str(v.dtype)]
+        if isinstance(v, C.Structure):
+            out = {}
+            for fname, ftype in v._fields_:
+                if fname.startswith("reserved"):
+                    continue
+                val = getattr(v, fname)
+                if ftype is C.c_void_p:
+                    out[fname] = self.ptr(val)
+                elif isinstance(val, C.Array):
+                    n = v.ngroups if fname == "g" else len(val)
+                    out[fname] = [self.ser(val[i]) for i in range(n)]
+                else:
+                    out[fname] = val
+            return out
+        if isinstance(v, dict):
+            return {str(k): self.ser(v[k]) for k in sorted(v, key=str)}
+        if isinstance(v, (list, tuple)):
+            return [self.ser(e) for e in v]
+        if v is None or isinstance(v, (bool, int, float, str)):
+            return v
+        raise TypeError("cannot serialise %r" % (type(v),))
+
+    def ops(self, ops):
+        """(pins, full): per op [kind, name or None, hash], and the serialisations the hashes were taken of."""
+        pins, full = [], []
+        for op in ops:
+            s = self.ser(list(op[1:]))
+            name = next((e for e in op[1:] if isinstance(e, str)), None)
+            pins.append([op[0], name, hashlib.sha256(json.dumps(s, sort_keys=True).encode()).hexdigest()[:16]])
+            full.append(s)
+        return pins, full
+
+
+def _sched(s):
+    return {"lanes": list(s["lanes"]), "waits": [list(w) for w in s["waits"]], "events": sorted(s["events"]),
+            "joins": list(s["joins"]), "nlanes": s["nlanes"]}
+
+
+def _sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def page(canvas, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, 256, (2,) + canvas + (3,), generator=g, dtype=torch.uint8).cuda()
+
+
+def targets(B, N, K, seed=1):
+    """Seeded training targets in the generator's layout: regression (B,N,5) and labels (B,N,K+1), anchor state in the last column
+    (2 % positive, 5 % ignored)."""
+    g = torch.Generator().manual_seed(seed)
+    u = torch.rand(B, N, generator=g)
+    state = (u < 0.02).float() - ((u >= 0.02) & (u < 0.07)).float()
+    reg = torch.cat([0.5 * torch.randn(B, N, 4, generator=g), state[..., None]], dim=2)
+    lab = torch.zeros(B, N, K + 1)
+    lab[..., 0] = (state == 1).float()
+    lab[..., -1] = state
+    return reg.cuda(), lab.cuda()
+
+
+def norms(t):
+    """[|t|, max |t|]: what stands in for a hash the recording commit cannot reproduce."""
+    return [float(t.double().norm()), float(t.abs().max())]
+
+
+def _outputs(plan):
+    return ({"regression": _sha(plan["regression"]), "classification": _sha(plan["classification"])},
+            {"regression": norms(plan["regression"]), "classification": norms(plan["classification"])})
+
+
+def _forward_row(eng, x, detect):
+    if detect:
+        eng.detect(x)
+    else:
+        eng.forward(x)
+    torch.cuda.synchronize()
+    plan = eng._plan(*x.shape[:3])
+    key = eng._fused(private=detect)
+    var = eng._variant(plan, key)
+    pins, full = _Ser().ops(var["ops"])
+    hashes, stats = _outputs(plan)
+    return dict(hashes, key=[int(k) for k in key], ops=pins, sched=_sched(var["sched"]), stats=stats), {"ops": full}
+
+
+def _train_row(eng, T, x, trainable):
+    tr = T.Trainer(eng, lr=1e-4, clipnorm=0.001, trainable=trainable)
+    B, H, W = x.shape[:3]
+    reg_t, lab_t = targets(B, eng._plan(B, H, W)["N"], eng.K)
+    tr.forward_backward(x, reg_t, lab_t)
+    torch.cuda.synchronize()
+    bp = tr.bplans[(B, H, W)]
+    plan = bp["plan"]
+    var = eng._variant(plan, tr.fwd_key)
+    ser = _Ser()
+    pins, full = ser.ops(var["ops"])
+    bpins, bfull = ser.ops(bp["bops"])
+    hashes, stats = _outputs(plan)
+    stats["grad"] = {name: norms(tr.grad_views(name)[0]) + norms(tr.grad_views(name)[1]) for name in eng.layout}
+    row = dict(hashes, key=[int(k) for k in tr.fwd_key], ops=pins, sched=_sched(var["sched"]), bops=bpins,
+               bsched=_sched(bp[("bsched", tr.wgrad_lanes)]), grad=_sha(tr.grad), stats=stats)
+    return row, {"ops": full, "bops": bfull}
+
+
+def build_rows(pkg_name=PKG):
+    """{row name: (pins, full serialisations)} of the seven rows, built with the installed code on the current device."""
+    E, Wt, T = [importlib.import_module(pkg_name + "." + m) for m in ("engine", "weights", "trainer")]
+    state = Wt.init_state(seed=0, randomize_bn=True)
+    rows = {}
+    eng = E.Engine("resnet50", 1, 9, dtype="bf16")
+    eng.load_state(state)
+    x = page(BF16_CANVAS)
+    rows["bf16_forward"] = _forward_row(eng, x, detect=False)
+    rows["bf16_detect"] = _forward_row(eng, x, detect=True)
+    rows["bf16_train"] = _train_row(eng, T, x, None)
+    heads = frozenset(n for n in eng.layout if not (n == "conv1" or n.startswith("res")))
+    rows["bf16_train_frozen_backbone"] = _train_row(eng, T, x, heads)
+    eng.calibrate_fp8(x, backbone=True)
+    rows["bf16_fp8_backbone_forward"] = _forward_row(eng, x, detect=False)
+    eng.calibrate_fp8(None)
+    eng32 = E.Engine("resnet50", 1, 9, dtype="f32")
+    eng32.load_state(state)
+    x32 = page(F32_CANVAS)
+    rows["f32_forward"] = _forward_row(eng32, x32, detect=False)
+    rows["f32_train"] = _train_row(eng32, T, x32, None)
+    return rows
+
+
+HASHES = ("regression", "classification", "grad")
+MUST_REPRODUCE = ("bf16_forward", "bf16_detect", "bf16_fp8_backbone_forward")
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", default=FIXTURE)
+    ap.add_argument("--full", default=None, help="also write every op's full serialisation to this file")
+    args = ap.parse_args()
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    first, second = build_rows(), build_rows()
+    fixture, unstable = {}, []
+    for name, (row, _) in first.items():
+        again = second[name][0]
+        for k in row:
+            if k in HASHES or k == "stats":
+                continue
+            if row[k] != again[k]:
+                raise SystemExit("%s: %s differs between two builds of the same commit" % (name, k))
+        for k in HASHES:
+            if k in row and row[k] != again[k]:
+                if name in MUST_REPRODUCE:
+                    raise SystemExit("%s: the %s output is not reproducible at this commit" % (name, k))
+                row[k] = None
+                unstable.append("%s.%s" % (name, k))
+        row["stats"] = {k: v for k, v in row["stats"].items() if row[k] is None}     # only a tensor without a stable hash needs them
+        if not row["stats"]:
+            del row["stats"]
+        fixture[name] = row
+    with open(args.out, "w") as f:
+        json.dump(fixture, f, separators=(",", ":"), sort_keys=True)
+        f.write("\n")
+    if args.full:
+        with open(args.full, "w") as f:
+            json.dump({name: full for name, (_, full) in first.items()}, f, sort_keys=True)
+    print("wrote %s (%d bytes); hashes written as null: %s" % (args.out, os.path.getsize(args.out), unstable or "none"))
+
+
+if __name__ == "__main__":
+    main()
