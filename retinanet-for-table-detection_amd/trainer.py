@@ -13,7 +13,7 @@ Mirrors what the reference gets from Keras (RetinaNet.py:125-131, 280-291):
   * the optimizer runs over element ranges of the flat parameter vector, one per trainable weight tensor and bias vector
     (rtn_sumsq_ranges + rtn_adam_clipnorm_step_ranges[_pertensor]): the same kernels whether every layer trains or a few.
 
-The backward graph is derived from the forward op list of engine.Engine._plan: every conv gets a wgrad (+ bias grad) and a
+The backward graph is derived from the forward op list of engine.Engine._plan (bplan.py): every conv gets a wgrad (+ bias grad) and a
 dgrad per input; ReLU, residual adds, UpsampleLike+Add, C6_relu, max-pool and the stride-2 convs are handled by epilogue
 flags of the dgrad launch or by the small kernels of rtn_backward.hip.  All arithmetic is in the HIP library; PyTorch
 provides memory, the stream and (optionally) torch.distributed for the gradient all-reduce.
@@ -24,7 +24,6 @@ and a data gradient (with its zero-insert / upsample / pool backward / head pad-
 range tables hold the trainable layers only, the all-reduce runs over their segments, and the training forward runs the
 stem and the 64-channel blocks in their inference form when the backward never reads their extra outputs (Engine.train_keep).
 """
-import ctypes as C
 import itertools
 
 import numpy as np
@@ -34,10 +33,11 @@ import weakref
 import torch
 
 from . import _lib as L
+from . import bplan as BP
 from . import ops as O
 from . import weights as Wt
 from . import parallel as Par
-from .engine import run_lanes, schedule_lanes
+from .engine import Engine, run_lanes, schedule_lanes
 
 
 def _ceil128(v):
@@ -206,7 +206,7 @@ class Trainer:
     def _dy_channels(self, name):
         """Channels of the dY tensor a layer's backward reads: Cout, or the padded width for the skinny head outputs."""
         cout = self.eng.layout[name]["cout"]
-        if name in ("pyramid_regression", "pyramid_classification"):
+        if name in Engine.TOWERS:
             cp = 64
             while cp < cout:
                 cp *= 2
@@ -241,239 +241,13 @@ class Trainer:
 
     # ------------------------------------------------------------------ backward plan
     def _bplan(self, B, H, W):
+        """The backward plan of a canvas, cached: the op list (bplan.Emit), the gradient buffers and the loss-side tensors."""
         key = (B, H, W)
-        eng = self.eng
         if key in self.bplans:
-            eng._plan(B, H, W)                             # marks the canvas as recently used in the engine's cache
+            self.eng._plan(B, H, W)                        # marks the canvas as recently used in the engine's cache
             return self.bplans[key]
-        plan = eng._plan(B, H, W)                          # may evict the least recently used canvas: _drop_bplan() follows
-        dev, tdt, rdt = eng.device, eng.tdt, eng.rdt
-        ops = plan["ops"]
-        keep, bops = [], []
-        tid = id
-
-        # producers / consumers
-        prod, ncons, relu_src = {}, {}, {}
-        for op in ops:
-            if op.kind == "conv":
-                me = op.meta
-                for y in me["ys"]:
-                    prod[tid(y)] = me
-                for x in me["xs"]:
-                    ncons[tid(x)] = ncons.get(tid(x), 0) + 1
-                for r in me["res"]:
-                    if r is not None:
-                        ncons[tid(r)] = ncons.get(tid(r), 0) + 1
-            elif op.kind == "pool":
-                ncons[tid(op.src)] = ncons.get(tid(op.src), 0) + 1
-                prod[tid(op.dst)] = {"relu": False, "name": "pool1"}
-            elif op.kind == "relu":
-                relu_src[tid(op.dst)] = op.src                     # P6r -> P6
-        for t_, src in relu_src.items():                            # a consumer of relu(S) counts as a consumer of S
-            ncons[tid(src)] = ncons.get(tid(src), 0) + ncons.pop(t_, 0)
-        # needs-grad: a tensor needs a gradient iff its producer is a trainable layer or any input of its producer needs one.  Every
-        # consumer of a tensor is pruned alike, so the first-writer / accumulate order below is the full backward's, minus whole tensors.
-        need = set()
-        for op in ops:
-            if op.kind == "conv":
-                me = op.meta
-                if self._is_trainable(op.name) or any(tid(x) in need for x in me["xs"]) or \
-                        any(r is not None and tid(r) in need for r in me["res"]):
-                    need.update(tid(y) for y in me["ys"])
-            elif op.kind in ("pool", "relu") and tid(op.src) in need:
-                need.add(tid(op.dst))
-
-        grads, gstate, done = {}, {}, {}
-
-        def gbuf(t):
-            if tid(t) not in grads:
-                grads[tid(t)] = torch.zeros_like(t)                 # zeros: scatter targets and never-touched pixels stay 0
-                keep.append(grads[tid(t)])
-            return grads[tid(t)]
-
-        cells_total = sum(plan["cfg"].H[i] * plan["cfg"].W[i] for i in range(plan["cfg"].nlevels))
-        N = plan["N"]
-        d_reg = torch.zeros(B, N, 4, dtype=torch.float32, device=dev)
-        d_cls = torch.zeros(B, N, eng.K, dtype=torch.float32, device=dev)
-        cp_reg, cp_cls = self._dy_channels("pyramid_regression"), self._dy_channels("pyramid_classification")
-        dyp_reg = torch.zeros(B, cells_total, cp_reg, dtype=tdt, device=dev)
-        dyp_cls = torch.zeros(B, cells_total, cp_cls, dtype=tdt, device=dev)
-        keep += [d_reg, d_cls, dyp_reg, dyp_cls]
-        grads[tid(plan["regression"])] = dyp_reg
-        grads[tid(plan["classification"])] = dyp_cls
-        if tid(plan["regression"]) in need:
-            bops.append(O.PadCast("padcast", d_reg, dyp_reg, B * cells_total, eng.A * 4, cp_reg))
-        if tid(plan["classification"]) in need:
-            bops.append(O.PadCast("padcast", d_cls, dyp_cls, B * cells_total, eng.A * eng.K, cp_cls))
-
-        for op in reversed(ops):
-            if op.kind == "conv":
-                d_f, name, me = op.desc, op.name, op.meta
-                if tid(me["ys"][0]) not in need:             # frozen, and nothing below it trains
-                    continue
-                lo = eng.layout[name]
-                head_out = name in ("pyramid_regression", "pyramid_classification")
-                ng = d_f.ngroups
-                crun = self._dy_channels(name)
-                def grad_of(t):                      # a tensor whose only consumer is a residual add: its gradient IS that sum's
-                    if tid(t) in grads:
-                        return grads[tid(t)]
-                    st_ = gstate.get(tid(t))
-                    return st_[1] if isinstance(st_, tuple) else None
-                dys = [grad_of(y) for y in me["ys"]]
-                if any(dy is None for dy in dys):
-                    raise RuntimeError("no gradient reached the output of %s" % name)
-                dW, db = self.grad_views(name)
-                # ---------- wgrad: forward geometry, `out` re-pointed at dY
-                dw = L.ConvDesc()
-                C.memmove(C.byref(dw), C.byref(d_f), C.sizeof(L.ConvDesc))
-                dw.flags, dw.w, dw.bias = 0, None, None
-                dw.N = crun
-                dw.out_ld = crun
-                cell_off = 0
-                for gi in range(ng):
-                    g = dw.g[gi]
-                    dy = dys[gi]
-                    g.out, g.out_elems = dy.data_ptr(), dy.numel()
-                    g.res, g.res_elems = None, 0
-                    cells = g.Hout * g.Wout
-                    if head_out:
-                        g.out_img_stride, g.out_off = cells_total * crun, cell_off * crun
-                        cell_off += cells
-                    else:
-                        g.out_img_stride, g.out_off = cells * crun, 0
-                if self._is_trainable(name):
-                    bops.append(O.Wgrad("wgrad", dw, dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
-                # ---------- residual inputs of the forward epilogue
-                for gi in range(ng):
-                    r = me["res"][gi]
-                    if r is None or tid(r) not in need:
-                        continue
-                    done[tid(r)] = done.get(tid(r), 0) + 1
-                    if me["flags"] & L.CONV_RES_SAME:
-                        if gstate.get(tid(r)) is not None:
-                            raise RuntimeError("identity gradient must be the first contribution (%s)" % name)
-                        gstate[tid(r)] = ("alias", dys[gi])
-                    else:                                            # UpsampleLike + Add
-                        acc = 1 if gstate.get(tid(r)) == "buf" else 0
-                        bops.append(O.UpBwd("upbwd", dys[gi], gbuf(r), (B, dys[gi].shape[1], dys[gi].shape[2], r.shape[1], r.shape[2], r.shape[3]), acc))
-                        gstate[tid(r)] = "buf"
-                # ---------- dgrad into every input
-                if me.get("stem"):
-                    continue
-                dd = L.ConvDesc()
-                dd.ngroups, dd.batch, dd.dtype = ng, B, rdt
-                wd = self.wd[name]
-                dd.w, dd.bias, dd.w_rows, dd.N = wd.data_ptr(), None, wd.shape[0], lo["cin"]
-                dd.KH, dd.KW, dd.Crun, dd.pix_stride = lo["kh"], lo["kw"], crun, crun
-                dd.sy = dd.sx = 1
-                dd.out_ld = lo["cin"]
-                stride, (pt, pl) = me["stride"], me["pad"]
-                flags_all = None
-                cell_off = 0
-                ngd = 0                                              # groups whose input needs a gradient
-                for gi in range(ng):
-                    x = me["xs"][gi]
-                    target, pre_mask = x, False
-                    if tid(x) in relu_src:                           # x = relu(S): differentiate straight into S
-                        target, pre_mask = relu_src[tid(x)], True
-                    if tid(target) not in need:
-                        if head_out:
-                            cell_off += d_f.g[gi].Hout * d_f.g[gi].Wout
-                        continue
-                    done[tid(target)] = done.get(tid(target), 0) + 1
-                    state = gstate.get(tid(target))
-                    dy = dys[gi]
-                    g = L.ConvGroup()
-                    Hx, Wx = x.shape[1], x.shape[2]
-                    Ho, Wo = d_f.g[gi].Hout, d_f.g[gi].Wout
-                    flags = 0
-                    if stride == 1:
-                        src, Hs, Ws = dy, Ho, Wo
-                        dd.pad_t, dd.pad_l = lo["kh"] - 1 - pt, lo["kw"] - 1 - pl
-                        g.Hout, g.Wout = Hx, Wx
-                        if head_out:
-                            g.in_img_stride, in_off = cells_total * crun, cell_off * crun
-                            cell_off += Ho * Wo
-                        else:
-                            g.in_img_stride, in_off = Ho * Wo * crun, 0
-                        g.in_, g.in_elems = src.data_ptr() + in_off * src.element_size(), src.numel() - in_off
-                        g.in_row_stride = Wo * crun
-                    elif lo["kh"] == 1:                              # stride-2 1x1 'valid': scatter onto the stride grid
-                        src, Hs, Ws = dy, Ho, Wo
-                        dd.pad_t = dd.pad_l = 0
-                        g.Hout, g.Wout = Ho, Wo
-                        g.out_step, g.out_pix_w = stride, Wx
-                        g.in_, g.in_elems = src.data_ptr(), src.numel()
-                        g.in_img_stride, g.in_row_stride = Ho * Wo * crun, Wo * crun
-                    else:                                            # stride-2 3x3: stride-1 conv over the zero-inserted dY
-                        Hs, Ws = 2 * Ho - 1, 2 * Wo - 1
-                        up = torch.zeros(B, Hs, Ws, crun, dtype=tdt, device=dev)
-                        keep.append(up)
-                        bops.append(O.Zins("zins", dy, up, (B, Ho, Wo, crun, Hs, Ws)))
-                        src = up
-                        dd.pad_t, dd.pad_l = lo["kh"] - 1 - pt, lo["kw"] - 1 - pl
-                        g.Hout, g.Wout = Hx, Wx
-                        g.in_, g.in_elems = src.data_ptr(), src.numel()
-                        g.in_img_stride, g.in_row_stride = Hs * Ws * crun, Ws * crun
-                    g.Hin, g.Win = Hs, Ws
-                    out = gbuf(target)
-                    g.out, g.out_elems = out.data_ptr(), out.numel()
-                    g.out_img_stride = out.numel() // B
-                    if state is not None:
-                        rs = out if state == "buf" else state[1]
-                        flags |= L.CONV_RES_SAME
-                        g.res, g.res_elems, g.res_img_stride, g.res_ld = rs.data_ptr(), rs.numel(), rs.numel() // B, rs.shape[-1]
-                    needs_relu = pre_mask or prod.get(tid(target), {}).get("relu", False)
-                    if needs_relu:
-                        flags |= L.CONV_RELU_MASK
-                        # an aliased identity gradient is not yet masked by this tensor's ReLU: mask the sum; otherwise
-                        # mask this contribution alone (the accumulated part was masked when it was written)
-                        if not (state is not None and state != "buf"):
-                            flags |= L.CONV_MASK_PRE
-                        g.mask, g.mask_elems, g.mask_img_stride, g.mask_ld = target.data_ptr(), target.numel(), target.numel() // B, target.shape[-1]
-                    gstate[tid(target)] = "buf"
-                    if flags_all is None:
-                        flags_all = flags
-                    elif flags_all != flags:
-                        raise RuntimeError("grouped dgrad of %s needs uniform epilogue flags" % name)
-                    dd.g[ngd] = g
-                    ngd += 1
-                if ngd == 0:
-                    continue
-                dd.ngroups = ngd
-                dd.flags = flags_all
-                L.attach_conv_workspace(eng.h, dd)                   # caller-owned K-split slabs, one buffer per launch
-                bops.append(O.Dgrad("dgrad", dd, name))
-            elif op.kind == "pool":
-                x, y = op.src, op.dst
-                if tid(x) not in need:
-                    continue
-                dy = grads.get(tid(y))
-                done[tid(x)] = done.get(tid(x), 0) + 1
-                bops.append(O.PoolBwd("poolbwd", x, dy, gbuf(x), op.bhwc, op.idx, y))      # y: the pooled tensor (the fused stem's ReLU mask)
-                gstate[tid(x)] = "buf"
-        loss_ws = torch.empty(L.lib.rtn_retina_loss_workspace_bytes(B * N), dtype=torch.uint8, device=dev)
-        bias_bops = [i for i, b in enumerate(bops) if b.kind == "wgrad" and b.db is not None]
-        # every weight-gradient op owns its workspace (row-info table + the slabs of its ordered split reduction: 130 MB for a head
-        # layer at batch 16 x 800 x 1333, 3.4 GB over the 107 layers), allocated at its first launch (ops.Wgrad.launch): ops on
-        # different lanes never share scratch, and the table is built once per layer
-        # what the pruned backward reads of the training forward's extra outputs: branch2b of the fused 64-channel blocks, the pool taps
-        reads = set(p_ for b in bops for p_ in b.io()[0])
-        keep_fwd = (any(blk.b2.data_ptr() in reads for blk in plan["fusion"]["blocks"] if blk.f == 64), any(b.kind == "poolbwd" for b in bops))
-        # id(forward tensor) -> the tensor that holds its gradient after the backward pass: its own buffer, or the aliased sum's for a
-        # tensor whose only consumer is a residual add.  grad_src keeps those forward tensors alive, so the ids stay valid.
-        grad_of_map = dict(grads)
-        grad_of_map.update({t_: st_[1] for t_, st_ in gstate.items() if isinstance(st_, tuple)})
-        fwd = {}
-        for op in ops:
-            ts = (list(op.meta["xs"]) + list(op.meta["ys"]) + [r for r in op.meta["res"] if r is not None]) if op.kind == "conv" else \
-                [op.src, op.dst] if op.kind in ("pool", "relu") else []
-            fwd.update((tid(t), t) for t in ts)
-        bp = {"bops": bops, "keep": keep, "last_bias_bop": bias_bops[-1] if bias_bops else -1,
-              "keep_fwd": keep_fwd, "grad_of": grad_of_map, "grad_src": [fwd[t_] for t_ in grad_of_map],
-              "d_reg": d_reg, "d_cls": d_cls, "dyp_cls": dyp_cls, "loss_ws": loss_ws, "plan": plan, "rowinfo": {}}
-        self.bplans[key] = bp
+        plan = self.eng._plan(B, H, W)                     # may evict the least recently used canvas: _drop_bplan() follows
+        bp = self.bplans[key] = BP.Emit(self, plan, B).build()
         return bp
 
     # ------------------------------------------------------------------ backward lanes

@@ -1,0 +1,181 @@
+"""Host logic of the backward plan (bplan.py, behind trainer.Trainer._bplan): the graph pass with the pruning rule of frozen-layer
+training, the gradient slots, the dY layout and the descriptor builders.  Pure host code: CPU tensors stand in for device buffers."""
+import importlib
+
+import pytest
+import torch
+
+
+def _mods():
+    return [importlib.import_module("retinanet-for-table-detection_amd." + m) for m in ("bplan", "ops", "_lib")]
+
+
+def _graph():
+    """conv1 -> pool -> a (1x1, ReLU) -> r (+ pool output, identity) -> P6 (stride 2) -> relu -> P7; the head reads P6 and P7."""
+    BP, O, L = _mods()
+    t = {n: torch.zeros(1) for n in ("img", "c1", "p", "a", "r", "P6", "P6r", "P7", "h")}
+
+    def conv(name, xs, ys, res=None, flags=0, relu=False, **more):
+        meta = dict({"xs": [t[x] for x in xs], "ys": [t[y] for y in ys], "res": [t[r] if r else None for r in res or [None] * len(xs)],
+                     "flags": flags, "relu": relu}, **more)
+        return O.Conv("conv", None, name, meta)
+    ops = [
+        conv("conv1", ["img"], ["c1"], relu=True, stem=True),
+        O.Pool("pool", t["c1"], t["p"], (1, 1, 1, 1), None),
+        conv("a", ["p"], ["a"], relu=True),
+        conv("r", ["a"], ["r"], res=["p"], flags=L.CONV_RES_SAME | L.CONV_RELU, relu=True),
+        conv("P6", ["r"], ["P6"]),
+        O.Relu("relu", t["P6"], t["P6r"]),
+        conv("P7", ["P6r"], ["P7"]),
+        conv("head", ["P6", "P7"], ["h", "h"]),
+    ]
+    return BP, ops, t
+
+
+@pytest.mark.parametrize("trainable,want", [
+    (None, "c1 p a r P6 P6r P7 h"),              # every layer: all produced tensors, not the image
+    ({"head"}, "h"),
+    ({"P6"}, "P6 P6r P7 h"),                     # nothing below the lowest trainable layer
+    ({"r"}, "r P6 P6r P7 h"),                    # the residual's source (the pool output) needs none
+    (set(), ""),
+])
+def test_need_set_follows_the_pruning_rule(trainable, want):
+    BP, ops, t = _graph()
+    g = BP.analyse(ops, lambda name: trainable is None or name in trainable)
+    assert g.need == {id(t[n]) for n in want.split()}
+
+
+def test_relu_map_relu_producers_and_tensors():
+    BP, ops, t = _graph()
+    g = BP.analyse(ops, lambda name: True)
+    assert g.relu_src == {id(t["P6r"]): t["P6"]}
+    assert g.relu_out == {id(t["c1"]), id(t["a"]), id(t["r"])}            # the pool output is not ReLU-producing
+    assert g.tensors == {id(v): v for v in t.values()}
+
+
+def test_gradient_slots():
+    BP, _, _ = _mods()
+    keep = []
+    s = BP.GradSlots(keep)
+    a, b, dy = torch.ones(2, 3), torch.ones(2, 3), torch.ones(2, 3)
+    assert s.of(a) is None and s.state(a) is None
+    out, res = s.contribute(a)                   # first writer: a fresh zero buffer, nothing to add to
+    assert res is None and out.shape == a.shape and not out.any() and keep == [out] and s.state(a) == BP.BUF and s.of(a) is out
+    out2, res2 = s.contribute(a)                 # second writer: accumulates onto the buffer
+    assert out2 is out and res2 is out and len(keep) == 1
+    with pytest.raises(RuntimeError, match="identity gradient must be the first contribution \\(layer\\)"):
+        s.alias(a, dy, "layer")
+    s.alias(b, dy, "layer")
+    assert s.state(b) == BP.ALIAS and s.of(b) is dy and len(keep) == 1
+    assert s.grad_of() == {id(a): out, id(b): dy}                  # buffers and aliases alike
+    outb, resb = s.contribute(b)                 # a contribution after the alias: own buffer, the alias as the residual source
+    assert resb is dy and outb is not dy and not outb.any() and s.state(b) == BP.BUF and s.of(b) is outb
+    with pytest.raises(RuntimeError):
+        s.alias(b, dy, "layer")
+    head, dyp = torch.ones(2, 3), torch.zeros(2, 4)
+    s.adopt(head, dyp)                           # written by the loss backward, not by an op
+    assert s.of(head) is dyp and s.state(head) is None and keep[-1] is dyp
+    assert s.grad_of() == {id(a): out, id(b): outb, id(head): dyp}
+
+
+def test_dgrad_group_stride1_3x3_same():
+    BP, O, L = _mods()
+    x, dy = torch.zeros(2, 5, 7, 32), torch.zeros(2, 5, 7, 64)
+    g, pads, zins = BP.dgrad_group(x, dy, 5, 7, 3, 3, 1, (1, 1), 64, (5 * 7 * 64, 0))
+    assert pads == (1, 1) and zins is None
+    assert (g.Hin, g.Win, g.Hout, g.Wout) == (5, 7, 5, 7)
+    assert (g.in_, g.in_elems, g.in_img_stride, g.in_row_stride) == (dy.data_ptr(), 2 * 5 * 7 * 64, 5 * 7 * 64, 7 * 64)
+    assert (g.out_step, g.out_pix_w) == (0, 0)
+
+
+def test_dgrad_group_stride2_1x1_scatters_onto_the_stride_grid():
+    BP, O, L = _mods()
+    x, dy = torch.zeros(2, 5, 7, 8), torch.zeros(2, 3, 4, 16)
+    g, pads, zins = BP.dgrad_group(x, dy, 3, 4, 1, 1, 2, (0, 0), 16, (3 * 4 * 16, 0))
+    assert pads == (0, 0) and zins is None
+    assert (g.Hin, g.Win, g.Hout, g.Wout) == (3, 4, 3, 4)
+    assert (g.out_step, g.out_pix_w) == (2, 7)
+    assert (g.in_, g.in_elems, g.in_img_stride, g.in_row_stride) == (dy.data_ptr(), 2 * 3 * 4 * 16, 3 * 4 * 16, 4 * 16)
+
+
+def test_dgrad_group_stride2_3x3_reads_the_zero_inserted_dy():
+    BP, O, L = _mods()
+    x, dy = torch.zeros(2, 5, 7, 8), torch.ones(2, 3, 4, 16)
+    # the builder takes the forward pads as given: unequal here, so that a swap shows
+    g, pads, zins = BP.dgrad_group(x, dy, 3, 4, 3, 3, 2, (0, 1), 16, (3 * 4 * 16, 0))
+    assert pads == (2, 1)
+    assert isinstance(zins, O.Zins) and zins.src is dy and zins.dims == (2, 3, 4, 16, 5, 7)
+    up = zins.dst
+    assert up.shape == (2, 5, 7, 16) and up.dtype == dy.dtype and not up.any()
+    assert (g.Hin, g.Win, g.Hout, g.Wout) == (5, 7, 5, 7)
+    assert (g.in_, g.in_elems, g.in_img_stride, g.in_row_stride) == (up.data_ptr(), 2 * 5 * 7 * 16, 5 * 7 * 16, 7 * 16)
+    assert (g.out_step, g.out_pix_w) == (0, 0)
+
+
+def _two_level_head(L):
+    """Forward descriptor of a head output conv over two pyramid levels, 5 x 7 and 3 x 4 cells: 47 cells per image."""
+    d = L.ConvDesc()
+    d.ngroups, d.KH, d.KW, d.N, d.out_ld, d.flags = 2, 3, 3, 36, 36, L.CONV_RELU
+    (d.g[0].Hout, d.g[0].Wout), (d.g[1].Hout, d.g[1].Wout) = (5, 7), (3, 4)
+    return d
+
+
+def test_head_outputs_share_one_dy_over_the_levels():
+    BP, O, L = _mods()
+    d_f = _two_level_head(L)
+    assert BP.dy_layout(d_f, 64) == [(35 * 64, 0), (12 * 64, 0)]              # any other layer: a dY per group
+    layout = BP.dy_layout(d_f, 64, cells_total=47)
+    assert layout == [(47 * 64, 0), (47 * 64, 35 * 64)]
+    dyp = torch.zeros(2, 47, 64, dtype=torch.bfloat16)
+    xs = [torch.zeros(2, 5, 7, 256), torch.zeros(2, 3, 4, 256)]
+    g0, g1 = [BP.dgrad_group(x, dyp, d_f.g[i].Hout, d_f.g[i].Wout, 3, 3, 1, (1, 1), 64, layout[i])[0] for i, x in enumerate(xs)]
+    assert (g0.in_, g0.in_elems) == (dyp.data_ptr(), 2 * 47 * 64)
+    assert (g1.in_, g1.in_elems) == (dyp.data_ptr() + 35 * 64 * 2, 2 * 47 * 64 - 35 * 64)       # 2 bytes per element
+    assert g0.in_img_stride == g1.in_img_stride == 47 * 64
+    assert (g1.Hin, g1.Win, g1.Hout, g1.Wout, g1.in_row_stride) == (3, 4, 3, 4, 4 * 64)
+
+
+def test_wgrad_desc_is_the_forward_descriptor_pointed_at_dy():
+    BP, O, L = _mods()
+    d_f = _two_level_head(L)
+    x0 = torch.zeros(4)
+    d_f.g[0].in_, d_f.g[0].res, d_f.g[0].res_elems, d_f.w = x0.data_ptr(), x0.data_ptr(), 4, x0.data_ptr()
+    dyp = torch.zeros(2, 47, 64, dtype=torch.bfloat16)
+    dw = BP.wgrad_desc(d_f, [dyp, dyp], 64, BP.dy_layout(d_f, 64, cells_total=47))
+    assert (dw.ngroups, dw.KH, dw.KW, dw.g[0].in_, dw.g[1].Hout, dw.g[1].Wout) == (2, 3, 3, x0.data_ptr(), 3, 4)      # forward geometry
+    assert (dw.flags, dw.w, dw.bias, dw.N, dw.out_ld) == (0, None, None, 64, 64)
+    for g, off in ((dw.g[0], 0), (dw.g[1], 35 * 64)):
+        assert (g.out, g.out_elems, g.out_img_stride, g.out_off) == (dyp.data_ptr(), 2 * 47 * 64, 47 * 64, off)
+        assert (g.res, g.res_elems) == (None, 0)
+    assert (d_f.flags, d_f.N, d_f.g[0].res) == (L.CONV_RELU, 36, x0.data_ptr())          # the forward descriptor is a copy's source only
+
+
+@pytest.mark.parametrize("pre_mask,prod_relu", [(False, False), (True, False), (False, True)])
+@pytest.mark.parametrize("state", [None, "buf", "alias"])
+def test_dgrad_epilogue_flags(state, pre_mask, prod_relu):
+    """MASK_PRE (mask this contribution alone) goes with every ReLU mask except when accumulating onto an alias, whose sum is not masked yet."""
+    BP, O, L = _mods()
+    s = BP.GradSlots([])
+    target, dy = torch.zeros(2, 5, 7, 8), torch.zeros(2, 5, 7, 8)
+    if state == "buf":
+        s.contribute(target)
+    elif state == "alias":
+        s.alias(target, dy, "layer")
+    before = s.state(target)
+    assert before == {None: None, "buf": BP.BUF, "alias": BP.ALIAS}[state]
+    out, res = s.contribute(target)
+    g = L.ConvGroup()
+    flags = BP.dgrad_epilogue(g, target, before, res, pre_mask, prod_relu)
+    want_res = {None: None, "buf": out, "alias": dy}[state]
+    assert res is want_res
+    want = L.CONV_RES_SAME if state else 0
+    if pre_mask or prod_relu:
+        want |= L.CONV_RELU_MASK | (0 if state == "alias" else L.CONV_MASK_PRE)
+        assert (g.mask, g.mask_elems, g.mask_img_stride, g.mask_ld) == (target.data_ptr(), 2 * 5 * 7 * 8, 5 * 7 * 8, 8)
+    else:
+        assert g.mask is None
+    assert flags == want
+    if state:
+        assert (g.res, g.res_elems, g.res_img_stride, g.res_ld) == (want_res.data_ptr(), 2 * 5 * 7 * 8, 5 * 7 * 8, 8)
+    else:
+        assert g.res is None

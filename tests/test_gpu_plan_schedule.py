@@ -15,7 +15,8 @@ REC = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(REC)
 with open(REC.FIXTURE) as f:
     FIXTURE = json.load(f)
-ROWS = ("bf16_forward", "bf16_detect", "bf16_train", "bf16_train_frozen_backbone", "bf16_fp8_backbone_forward", "f32_forward", "f32_train")
+ROWS = ("bf16_forward", "bf16_detect", "bf16_train", "bf16_train_frozen_backbone", "bf16_train_C4_reduced_and_P6",
+        "bf16_fp8_backbone_forward", "f32_forward", "f32_train")
 
 
 @pytest.fixture(scope="module")

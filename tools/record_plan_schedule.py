@@ -1,4 +1,4 @@
-"""Pin of the engine's and trainer's plans: op lists, lane schedules, descriptor wiring and result bits of seven small rows.
+"""Pin of the engine's and trainer's plans: op lists, lane schedules, descriptor wiring and result bits of eight small rows.
 
   python tools/record_plan_schedule.py            # writes tests/golden/plan_schedule.json (run at the commit to pin against)
   python tools/record_plan_schedule.py --full F   # also every op's full serialisation, for reading a mismatch
@@ -146,7 +146,7 @@ def _train_row(eng, T, x, trainable):
 
 
 def build_rows(pkg_name=PKG):
-    """{row name: (pins, full serialisations)} of the seven rows, built with the installed code on the current device."""
+    """{row name: (pins, full serialisations)} of the eight rows, built with the installed code on the current device."""
     E, Wt, T = [importlib.import_module(pkg_name + "." + m) for m in ("engine", "weights", "trainer")]
     state = Wt.init_state(seed=0, randomize_bn=True)
     rows = {}
@@ -158,6 +158,9 @@ def build_rows(pkg_name=PKG):
     rows["bf16_train"] = _train_row(eng, T, x, None)
     heads = frozenset(n for n in eng.layout if not (n == "conv1" or n.startswith("res")))
     rows["bf16_train_frozen_backbone"] = _train_row(eng, T, x, heads)
+    # a cut through the middle of the graph: grouped dgrads that keep some of their groups, an upsample backward into a tensor whose
+    # own layer is frozen, the zero-insert path of P7 through the ReLU into P6
+    rows["bf16_train_C4_reduced_and_P6"] = _train_row(eng, T, x, frozenset(("C4_reduced", "P6")))
     eng.calibrate_fp8(x, backbone=True)
     rows["bf16_fp8_backbone_forward"] = _forward_row(eng, x, detect=False)
     eng.calibrate_fp8(None)
