@@ -733,6 +733,31 @@ int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blobs, const v
                           uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_png_stream_inflate_host(const void* blob, size_t segment_bytes, void* out, size_t want_bytes, int32_t* status);
 
+/* ---- every other pixel layout of PNG ("Pixel layouts") ---------------------------------------------------------------------------------------
+ * The files rtn_png_stream_inspect refuses for their pixels: gray of 1, 2 or 4 bits, palette pages of 1, 2, 4 or 8 bits, gray + alpha
+ * and R,G,B,A of 8 or 16 bits, R,G,B of 16 bits, each with or without Adam7 interlace, with the pixels Image.open(f).convert("RGB")
+ * gives (gray scaled to 0 .. 255, the PLTE entry or (0,0,0) past the last one, the high byte of a 16-bit sample, alpha and tRNS
+ * ignored).  Stages 1 - 7 are those of rtn_png_stream_decode over the same blob and workspace layout; the last stage reconstructs
+ * every pass in place and gathers the pixels into the page.  All conventions are those of the rtn_png_stream_* functions.
+ *
+ * rtn_png_layout_inspect (host only; h may be NULL): accepts what rtn_png_stream_inspect accepts, and: colour type 0 at depth 1, 2, 4;
+ *   type 2 at depth 16; type 3 at depth 1, 2, 4, 8 with exactly one PLTE before the first IDAT, its length a multiple of 3 and
+ *   1 .. 2^depth entries; types 4 and 6 at depth 8, 16; interlace 0 or 1; tRNS anywhere, and PLTE in types 2 and 6, passed over after
+ *   a CRC check.  16-bit gray (Pillow clips it), bKGD, unknown chunks and illegal (type, depth) pairs are RTN_EINVAL with a reason.
+ *   info->components is the file's samples per pixel; the stream length behind info->workspace_bytes is the sum over the passes
+ *   that have rows and columns of rows * (1 + ceil(columns * bits per pixel / 8)), < 2^31.  The blob also holds depth, colour type,
+ *   interlace flag and the palette entries present.
+ * rtn_png_layout_decode: status as rtn_png_stream_decode's, the filter types being those of every pass's rows.
+ * rtn_png_layout_pixels_host (host only, no handle): the last stage on the CPU: the filtered stream of a layout blob's page (`bytes`
+ *   must be its length; rtn_png_stream_inflate_host gives it, for blobs of either inspector) -> height * width * 3 bytes B,G,R in
+ *   out_bgr and *status = 0, or *status != 0 (a filter type above 4) and out_bgr not written. */
+size_t rtn_png_layout_blob_bound(size_t file_bytes);
+int rtn_png_layout_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob, size_t blob_capacity);
+size_t rtn_png_layout_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
+int rtn_png_layout_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                          uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+int rtn_png_layout_pixels_host(const void* blob, const void* filtered_stream, size_t bytes, void* out_bgr, int32_t* status);
+
 /* ---- detection rendering (render_detections' outlines, captions and crops, on the device) ----------------------------------
  * Every output image of a batch (crops and annotated pages alike) is a rectangle of one source page with some of that page's
  * operations painted over it.  Page p owns the operations op_begin[p] .. op_begin[p + 1] - 1 (at most RTN_RENDER_MAX_OPS), in drawing

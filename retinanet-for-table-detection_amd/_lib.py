@@ -227,6 +227,11 @@ SIGNATURES = {
     "rtn_png_stream_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_png_stream_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_png_stream_inflate_host": (_I, [_P, _SZ, _P, _SZ, C.POINTER(C.c_int32)]),
+    "rtn_png_layout_blob_bound": (_SZ, [_SZ]),
+    "rtn_png_layout_inspect": (_I, [_P, _P, _SZ, C.POINTER(PngInfo), _P, _SZ]),
+    "rtn_png_layout_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_png_layout_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_png_layout_pixels_host": (_I, [_P, _P, _SZ, _P, C.POINTER(C.c_int32)]),
     "rtn_render_workspace_bytes": (_SZ, [_I, _I, _I]),
     "rtn_render_pages": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _SZ]),
     "rtn_render_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ]),

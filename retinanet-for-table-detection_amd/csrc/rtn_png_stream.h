@@ -1,5 +1,5 @@
 // rtn_png_stream.h — the host side of the stream PNG decoder: the blob and workspace layouts, the file inspector and
-// the CPU twin of the device's inflate.  Plain C++ (no HIP), so that csrc/rtn_png_stream.hip and a stand-alone sanitizer build
+// the CPU twin of the device's inflate, for both of its entry points (rtn_png_stream_* and rtn_png_layout_*).  Plain C++ (no HIP), so that csrc/rtn_png_stream.hip and a stand-alone sanitizer build
 // (tools/png_stream_fuzz.cpp) compile the same text.  Everything that reads file bytes checks each position against the length
 // it was given before it uses it.
 #pragma once
@@ -11,6 +11,7 @@
 #include "rtn.h"
 #include "rtn_png_inflate.h"
 #include "rtn_png_crc.h"
+#include "rtn_png_layout.h"
 
 constexpr uint32_t PS_MAGIC = 0x534e5052u;     // "RPNS"
 constexpr int PS_CHUNK = 32768;                // bytes of the filtered stream per Adler pair (and per resolve workgroup)
@@ -25,7 +26,7 @@ struct PSHdr {                                 // start of a blob; 64 bytes
     uint32_t adler;                            // the stream's last four bytes
     uint32_t off_table;                        // PSIdat[nidat], from the blob's start
     uint32_t off_data;                         // the deflate bytes, from the blob's start (a multiple of 4; the zlib header sits 2 before)
-    uint32_t pad_;
+    uint32_t fmt;                              // PS_MAGIC: 0; PL_MAGIC: the page's format word (pl_fmt), its palette behind the table
     int64_t blob_bytes, ws_bytes;
 };
 static_assert(sizeof(PSHdr) == 64, "blob header");
@@ -102,9 +103,10 @@ inline uint32_t ps_crc(uint32_t c, const uint8_t* p, size_t n) {
     return c;
 }
 
-// rtn_png_stream_inspect without the handle: RTN_OK, or RTN_EINVAL and a reason in why[whylen].  S: the segment size.
-inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* info, void* blob_out, size_t blob_capacity, char* why,
-                      size_t whylen) {
+// rtn_png_stream_inspect (layout false) and rtn_png_layout_inspect (layout true: every pixel layout of pl_accepts, Adam7, PLTE and
+// tRNS) without the handle: RTN_OK, or RTN_EINVAL and a reason in why[whylen].  S: the segment size.
+inline int ps_inspect_any(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* info, void* blob_out, size_t blob_capacity, char* why,
+                          size_t whylen, bool layout) {
 #define PS_FAIL(...) do { snprintf(why, whylen, __VA_ARGS__); return RTN_EINVAL; } while (0)
     memset(info, 0, sizeof(*info));
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', '\r', '\n', 0x1a, '\n'};
@@ -115,22 +117,32 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
     if (~ps_crc(0xffffffffu, f + 12, 17) != ps_be32(f + 29)) PS_FAIL("CRC of IHDR");
     const uint32_t W = ps_be32(f + 16), H = ps_be32(f + 20);
     const int depth = f[24], ctype = f[25];
-    if (depth != 8) PS_FAIL("bit depth %d (only 8-bit PNG is decoded on the device)", depth);
-    if (ctype != 0 && ctype != 2) PS_FAIL("colour type %d (only gray and R,G,B are decoded on the device)", ctype);
+    if (!layout) {
+        if (depth != 8) PS_FAIL("bit depth %d (only 8-bit PNG is decoded on the device)", depth);
+        if (ctype != 0 && ctype != 2) PS_FAIL("colour type %d (only gray and R,G,B are decoded on the device)", ctype);
+    } else if (!pl_accepts(ctype, depth)) {
+        if (ctype == 0 && depth == 16) PS_FAIL("16-bit gray PNG (left to the host decoder)");
+        PS_FAIL("colour type %d at bit depth %d", ctype, depth);
+    }
     if (f[26] != 0 || f[27] != 0) PS_FAIL("compression method %d, filter method %d", f[26], f[27]);
-    if (f[28] != 0) PS_FAIL("interlaced PNG");
-    const int nc = ctype == 2 ? 3 : 1;
+    if (f[28] != 0 && !layout) PS_FAIL("interlaced PNG");
+    if (f[28] > 1) PS_FAIL("interlace method %d", f[28]);
+    const int nc = pl_samples(ctype);
     if (W < 1 || H < 1 || W > 0x7fffffffu || H > 0x7fffffffu) PS_FAIL("PNG sides %u x %u", W, H);
-    const unsigned long long rb1 = 1ull + (unsigned long long)W * nc;
-    if (rb1 >= (1ull << 31) || (unsigned long long)H * rb1 >= (1ull << 31))
-        PS_FAIL("%u x %u page: height * (1 + width * components) must be < 2^31", W, H);
-    const long long stream = (long long)((unsigned long long)H * rb1);
+    PLGeom geom;
+    pl_geometry((int)W, (int)H, pl_fmt(depth, ctype, f[28], 0), &geom);
+    if (geom.stream >= (1ll << 31)) {
+        if (!layout) PS_FAIL("%u x %u page: height * (1 + width * components) must be < 2^31", W, H);
+        PS_FAIL("%u x %u page: the filtered rows of all passes must take < 2^31 bytes", W, H);
+    }
+    const long long stream = geom.stream;
 
     // ancillary chunks that cannot change what Image.open(f).convert("RGB") returns
     static const char* const harmless[] = {"pHYs", "tEXt", "zTXt", "iTXt", "tIME", "gAMA", "cHRM", "sRGB", "iCCP", "eXIf"};
     struct Part { size_t at; uint32_t len, crc; };
     std::vector<Part> parts;
-    size_t pos = 8 + 25, zbytes = 0;
+    size_t pos = 8 + 25, zbytes = 0, pal_at = 0;
+    int npal = 0;
     int state = 0;                                                     // 0 before the IDATs, 1 among them, 2 behind them
     for (;;) {                                                         // every chunk takes at least 12 bytes
         if (n - pos < 12) PS_FAIL("truncated PNG (chunk header at byte %zu)", pos);
@@ -139,6 +151,7 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
         if ((size_t)len > n - pos - 12) PS_FAIL("truncated PNG (the chunk at byte %zu runs past the file)", pos);
         if (memcmp(type, "IEND", 4) == 0) {
             if (state == 0) PS_FAIL("no IDAT");
+            if (ctype == 3 && !npal) PS_FAIL("palette PNG without a PLTE chunk before the first IDAT");
             if (len != 0 || ps_be32(f + pos + 8) != 0xae426082u) PS_FAIL("IEND is not empty or its CRC is wrong");
             if (pos + 12 != n) PS_FAIL("%zu bytes after IEND", n - pos - 12);
             break;
@@ -151,6 +164,16 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
         } else {
             bool ok = false;
             for (const char* t : harmless) ok = ok || memcmp(type, t, 4) == 0;
+            if (layout && memcmp(type, "tRNS", 4) == 0) ok = true;     // the conversion to R,G,B ignores it
+            if (layout && memcmp(type, "PLTE", 4) == 0 && (ctype == 2 || ctype == 6)) ok = true;     // a suggested palette: unused
+            if (layout && memcmp(type, "PLTE", 4) == 0 && ctype == 3) {
+                if (state != 0) PS_FAIL("PLTE after the first IDAT");
+                if (npal) PS_FAIL("a second PLTE chunk");
+                if (len % 3u != 0 || len < 3u || len / 3u > (1u << depth)) PS_FAIL("PLTE of %u bytes at bit depth %d", len, depth);
+                npal = (int)(len / 3u);
+                pal_at = pos + 8;
+                ok = true;
+            }
             if (!ok) PS_FAIL("chunk %02x %02x %02x %02x (not one the device decoder passes over)", type[0], type[1], type[2], type[3]);
             if (~ps_crc(0xffffffffu, type, 4 + (size_t)len) != ps_be32(f + pos + 8 + len)) PS_FAIL("CRC of the chunk at byte %zu", pos);
             if (state == 1) state = 2;
@@ -175,7 +198,8 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
     const size_t nsegs = (in_bytes + S - 1) / S;
     const size_t nidat = parts.size();
     const size_t off_table = sizeof(PSHdr);
-    const size_t off_data = ((off_table + nidat * sizeof(PSIdat) + 15) & ~(size_t)15) + 4;
+    const size_t off_pal = off_table + nidat * sizeof(PSIdat);         // 3 npal bytes; none in a stream blob
+    const size_t off_data = ((off_pal + 3 * (size_t)npal + 15) & ~(size_t)15) + 4;
     const size_t total = (off_data - 2 + zbytes + 4 + 15) & ~(size_t)15;      // at least one zero word behind the stream
     info->width = (int32_t)W; info->height = (int32_t)H; info->components = nc; info->chunks = (int32_t)nsegs;
     info->blob_bytes = (int64_t)total;
@@ -183,12 +207,13 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
     info->payload_bytes = (int64_t)zbytes;
     if (!blob_out) return RTN_OK;
     if (total > 128 + 2 * n) PS_FAIL("internal: blob bound");
-    if (blob_capacity < total) PS_FAIL("rtn_png_stream_inspect: blob capacity %zu < %zu bytes", blob_capacity, total);
+    if (blob_capacity < total) PS_FAIL("rtn_png_%s_inspect: blob capacity %zu < %zu bytes", layout ? "layout" : "stream", blob_capacity, total);
     uint8_t* bl = static_cast<uint8_t*>(blob_out);
     memset(bl, 0, total);
     PSHdr hd;
     memset(&hd, 0, sizeof(hd));
-    hd.magic = PS_MAGIC;
+    hd.magic = layout ? PL_MAGIC : PS_MAGIC;
+    hd.fmt = layout ? pl_fmt(depth, ctype, f[28], npal) : 0u;
     hd.W = (int32_t)W; hd.H = (int32_t)H; hd.nc = nc;
     hd.nsegs = (uint32_t)nsegs; hd.nidat = (uint32_t)nidat; hd.seg_bytes = S; hd.in_bytes = (uint32_t)in_bytes;
     hd.adler = ps_be32(z.data() + zbytes - 4);
@@ -201,23 +226,53 @@ inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* in
         memcpy(bl + off_table + k * sizeof(PSIdat), &e, sizeof(e));
         at += parts[k].len;
     }
+    if (npal) memcpy(bl + off_pal, f + pal_at, 3 * (size_t)npal);
     memcpy(bl + off_data - 2, z.data(), zbytes);
     return RTN_OK;
 #undef PS_FAIL
 }
 
-// A blob's header if [blob, blob + avail) can hold what it describes, else null.
-inline const PSHdr* ps_blob(const void* blob, size_t avail) {
+inline int ps_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* info, void* blob_out, size_t blob_capacity, char* why,
+                      size_t whylen) {
+    return ps_inspect_any(f, n, S, info, blob_out, blob_capacity, why, whylen, false);
+}
+inline int pl_inspect(const uint8_t* f, size_t n, uint32_t S, rtn_png_info_t* info, void* blob_out, size_t blob_capacity, char* why,
+                      size_t whylen) {
+    return ps_inspect_any(f, n, S, info, blob_out, blob_capacity, why, whylen, true);
+}
+
+// The format word of a blob's page: a layout blob carries it, a stream blob is 8-bit gray or R,G,B without interlace.
+inline uint32_t ps_fmt(const PSHdr* hd) { return hd->magic == PL_MAGIC ? hd->fmt : pl_fmt(8, hd->nc == 3 ? 2 : 0, 0, 0); }
+// The length of a blob's filtered stream (< 2^31 for a blob ps_blob_any passed).
+inline long long ps_want(const PSHdr* hd) {
+    PLGeom g;
+    pl_geometry(hd->W, hd->H, ps_fmt(hd), &g);
+    return g.stream;
+}
+
+// A blob's header (of either inspector) if [blob, blob + avail) can hold what it describes, else null.
+inline const PSHdr* ps_blob_any(const void* blob, size_t avail) {
     if (avail < sizeof(PSHdr)) return nullptr;
     const PSHdr* hd = static_cast<const PSHdr*>(blob);
-    if (hd->magic != PS_MAGIC || hd->W < 1 || hd->H < 1 || (hd->nc != 1 && hd->nc != 3) || hd->nsegs < 1 || hd->nidat < 1) return nullptr;
+    if ((hd->magic != PS_MAGIC && hd->magic != PL_MAGIC) || hd->W < 1 || hd->H < 1 || hd->nsegs < 1 || hd->nidat < 1) return nullptr;
+    if (hd->magic == PS_MAGIC ? (hd->nc != 1 && hd->nc != 3) || hd->fmt != 0 : !pl_fmt_ok(hd->fmt) || hd->nc != pl_samples(pl_ctype(hd->fmt)))
+        return nullptr;
     if (hd->seg_bytes < PS_SEGMENT_MIN || hd->seg_bytes > PS_SEGMENT_MAX || hd->in_bytes < 1 || hd->in_bytes >= (1u << 30)) return nullptr;
-    if ((unsigned long long)hd->H * (1ull + (unsigned long long)hd->W * hd->nc) >= (1ull << 31)) return nullptr;
+    if (ps_want(hd) >= (1ll << 31)) return nullptr;
     if (hd->nsegs != (hd->in_bytes + hd->seg_bytes - 1) / hd->seg_bytes) return nullptr;
     if (hd->blob_bytes < 0 || (size_t)hd->blob_bytes > avail || hd->off_table != sizeof(PSHdr) || (hd->off_data & 3)) return nullptr;
-    if ((size_t)hd->off_data < hd->off_table + (size_t)hd->nidat * sizeof(PSIdat) + 2) return nullptr;
+    if ((size_t)hd->off_data < hd->off_table + (size_t)hd->nidat * sizeof(PSIdat) + 3 * (size_t)pl_npal(ps_fmt(hd)) + 2) return nullptr;
     if ((size_t)hd->off_data + hd->in_bytes + 8 > (size_t)hd->blob_bytes) return nullptr;
     return hd;
+}
+// The same for one inspector's blobs alone.
+inline const PSHdr* ps_blob(const void* blob, size_t avail, uint32_t magic = PS_MAGIC) {
+    const PSHdr* hd = ps_blob_any(blob, avail);
+    return hd && hd->magic == magic ? hd : nullptr;
+}
+// The palette of a layout blob: 3 pl_npal(fmt) bytes behind the IDAT table.
+inline const uint8_t* pl_palette(const PSHdr* hd) {
+    return reinterpret_cast<const uint8_t*>(hd) + hd->off_table + (size_t)hd->nidat * sizeof(PSIdat);
 }
 
 struct PSHostCtx {                             // the CPU twin: one caller does everything
@@ -276,10 +331,10 @@ struct PSHostCtx {                             // the CPU twin: one caller does 
 // after the other on the CPU.  segment_bytes 0: the blob's own.  Returns RTN_OK with *status set, or RTN_EINVAL (*why: the reason).
 inline int ps_inflate_host(const void* blob, size_t blob_bytes, uint32_t segment_bytes, uint8_t* out, size_t want_bytes, int32_t* status,
                            const char** why, uint32_t* links_out = nullptr) {
-    const PSHdr* hd = ps_blob(blob, blob_bytes);
-    if (!hd) { *why = "not an rtn_png_stream_inspect blob"; return RTN_EINVAL; }
-    const uint32_t want = (uint32_t)((unsigned long long)hd->H * (1ull + (unsigned long long)hd->W * hd->nc));
-    if (want_bytes != want) { *why = "want_bytes is not height * (1 + width * components)"; return RTN_EINVAL; }
+    const PSHdr* hd = ps_blob_any(blob, blob_bytes);
+    if (!hd) { *why = "not an rtn_png_stream_inspect or rtn_png_layout_inspect blob"; return RTN_EINVAL; }
+    const uint32_t want = (uint32_t)ps_want(hd);
+    if (want_bytes != want) { *why = "want_bytes is not the length of the page's filtered stream"; return RTN_EINVAL; }
     uint32_t S = segment_bytes ? segment_bytes : hd->seg_bytes;
     if (S < PS_SEGMENT_MIN || S > PS_SEGMENT_MAX) { *why = "segment_bytes outside 256 .. 2^24"; return RTN_EINVAL; }
     const uint8_t* bl = static_cast<const uint8_t*>(blob);
@@ -351,5 +406,19 @@ inline int ps_inflate_host(const void* blob, size_t blob_bytes, uint32_t segment
     }
     *status = (int32_t)st;
     if (st == 0) memcpy(out, bytes.data(), want);
+    return RTN_OK;
+}
+
+// rtn_png_layout_pixels_host without the error text: the device's last stage (reconstruct every pass, expand every pixel) on the CPU
+// over the filtered stream of a layout blob's page.  Returns RTN_OK with *status set (out written only if it is 0), or RTN_EINVAL.
+inline int pl_pixels_host(const void* blob, size_t blob_bytes, const uint8_t* stream, size_t bytes, uint8_t* out, int32_t* status,
+                          const char** why) {
+    const PSHdr* hd = ps_blob(blob, blob_bytes, PL_MAGIC);
+    if (!hd) { *why = "not an rtn_png_layout_inspect blob"; return RTN_EINVAL; }
+    PLGeom g;
+    pl_geometry(hd->W, hd->H, hd->fmt, &g);
+    if ((long long)bytes != g.stream) { *why = "bytes is not the length of the page's filtered stream"; return RTN_EINVAL; }
+    std::vector<uint8_t> rec(stream, stream + bytes);
+    *status = (int32_t)pl_pixels(g, hd->fmt, hd->W, hd->H, rec.data(), pl_palette(hd), out);
     return RTN_OK;
 }

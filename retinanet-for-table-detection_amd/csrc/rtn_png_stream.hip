@@ -18,6 +18,10 @@
 //   7. psd_page_kernel     one lane per page: joins the Adler pairs, ORs the status words.
 //   8. psd_unfilter_kernel one workgroup per page: thread t of a band of 1024 rows computes pixel s - t of its row at step s, so
 //                          the row above is always one pixel ahead (what Average and Paeth need); writes the B,G,R page.
+// rtn_png_layout_decode (pages of the other pixel layouts: sub-byte gray, palette, alpha, 16-bit samples, Adam7; csrc/rtn_png_layout.h)
+// runs stages 1 - 7 unchanged (the page record carries the stream's length and the format word) and then, instead of 8:
+//   8a. pld_unfilter_kernel one workgroup per page and pass: the same schedule over filter units of 1 .. 8 bytes, in place.
+//   8b. pld_expand_kernel   one thread per four pixels of the page: sample -> B,G,R, every pass gathered into the page.
 // No workgroup waits on another, no loop's end depends on file bytes alone, and every position derived from them is checked before
 // use.  Any non-zero status word sends the page to the host decoder.
 #include "rtn_internal.h"
@@ -36,6 +40,7 @@ struct PSPage {
     uint8_t* out;
     int32_t W, H, nc;
     uint32_t nsegs, nidat, S, in_bytes, adler, off_table, off_data;
+    uint32_t stream, fmt;                      // the filtered stream's length (ps_want) and the page's format word (ps_fmt)
 };
 struct PSBatch {
     int n, pad_;
@@ -43,7 +48,7 @@ struct PSBatch {
 };
 static_assert(sizeof(PSBatch) <= 3072, "kernel arguments");
 
-__device__ inline long long ps_stream(const PSPage& pg) { return (long long)pg.H * (1 + (long long)pg.W * pg.nc); }
+__device__ inline long long ps_stream(const PSPage& pg) { return (long long)pg.stream; }
 
 template <bool WRITE>
 struct PSDevCtx {                              // one wave; the tables (and the ring) are in LDS
@@ -286,6 +291,7 @@ __global__ __launch_bounds__(PS_BAND) void psd_window_kernel(uint8_t* ws, PSBatc
 // ---- kernel 6: bytes ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PS_THREADS) void psd_resolve_kernel(uint8_t* ws, PSBatch bt) {
     __shared__ uint32_t red[2][PS_THREADS / 64];
+    __shared__ PLGeom geom;
     const int page = blockIdx.y;
     if (page >= bt.n) return;
     const PSPage& pg = bt.p[page];
@@ -308,6 +314,7 @@ __global__ __launch_bounds__(PS_THREADS) void psd_resolve_kernel(uint8_t* ws, PS
     const uint32_t c0 = (uint32_t)(j * PS_CHUNK);
     const uint32_t want = (uint32_t)(stream - c0 < PS_CHUNK ? stream - c0 : PS_CHUNK);
     const int tid = threadIdx.x;
+    if (tid == 0) pl_geometry(pg.W, pg.H, pg.fmt, &geom);
     uint32_t sa = 0, l = 0, loff = 0, lend = 0;
     unsigned long long sb = 0;
     int bad = 0;
@@ -326,11 +333,14 @@ __global__ __launch_bounds__(PS_THREADS) void psd_resolve_kernel(uint8_t* ws, PS
         sa += d;
         sb += (unsigned long long)(want - i) * d;
     }
-    __syncthreads();                                                   // this chunk's bytes are written
-    const long long rb1 = 1 + (long long)pg.W * pg.nc;
+    __syncthreads();                                                   // this chunk's bytes are written, the geometry is known
     int badf = 0;
-    for (long long r = (c0 + rb1 - 1) / rb1 + tid; r * rb1 < (long long)c0 + want; r += PS_THREADS)
-        if (dst[r * rb1 - c0] > 4) badf = 1;
+    for (int q = 0; q < geom.npass; ++q) {                             // the filter bytes of every pass's rows that start in this chunk
+        const long long rb1 = 1 + (long long)geom.p[q].rb, lo = geom.p[q].off, hi = lo + geom.p[q].rows * rb1;
+        const long long a = lo > (long long)c0 ? lo : (long long)c0, b = hi < (long long)c0 + want ? hi : (long long)c0 + want;
+        for (long long r = (a - lo + rb1 - 1) / rb1 + tid; lo + r * rb1 < b; r += PS_THREADS)
+            if (dst[lo + r * rb1 - c0] > 4) badf = 1;
+    }
     const uint32_t wa = ps_wave_sum(sa), wb = ps_wave_sum((uint32_t)(sb % PE_ADLER));
     if ((tid & 63) == 0) { red[0][tid >> 6] = wa; red[1][tid >> 6] = wb; }
     const int anybad = __syncthreads_or(bad), anyf = __syncthreads_or(badf);
@@ -423,11 +433,106 @@ __global__ __launch_bounds__(PS_BAND) void psd_unfilter_kernel(const uint8_t* ws
     }
 }
 
-const PSHdr* psd_blob(const void* host_blobs, int64_t off) {
+// ---- kernel 8a (layout pages): the five filters undone in place, one workgroup per page and pass ------------------------------------------------
+// The schedule of psd_unfilter_kernel over filter units of bpp bytes: thread t of a band computes unit s - t of its row at step s.
+// Every pass has a zero row above its first, so the passes do not wait for each other.
+__global__ __launch_bounds__(PS_BAND) void pld_unfilter_kernel(uint8_t* ws, PSBatch bt) {
+    __shared__ unsigned long long pub[2][PS_BAND];                     // the unit every thread computed in the last two steps, bytes packed
+    __shared__ PLGeom geom;
+    const int page = blockIdx.y, q = blockIdx.x, tid = threadIdx.x;
+    if (page >= bt.n) return;
+    const PSPage& pg = bt.p[page];
+    if (tid == 0) pl_geometry(pg.W, pg.H, pg.fmt, &geom);
+    __syncthreads();
+    if (q >= geom.npass || geom.p[q].rows == 0) return;                // the whole workgroup leaves
+    const PLPass ps = geom.p[q];
+    const int bpp = geom.bpp, rows = ps.rows;
+    const long long rb1 = 1 + (long long)ps.rb, units = ((long long)ps.rb + bpp - 1) / bpp;     // rb is a multiple of bpp when bpp > 1
+    uint8_t* base = ws + pg.ws_off + ps.off;                           // [off, off + rows * rb1) lies inside the stream: pl_geometry
+    for (int y0 = 0; y0 < rows; y0 += PS_BAND) {
+        const int y = y0 + tid;
+        const bool live = y < rows;
+        uint8_t* row = base + (long long)(live ? y : 0) * rb1;
+        uint32_t type = live ? row[0] : 0u;
+        if (type > 4u) type = 0u;                                      // the page is flagged (PI_FILTER)
+        const int band = rows - y0 < PS_BAND ? rows - y0 : PS_BAND;
+        const long long steps = units + band - 1;
+        unsigned long long a = 0, c = 0;                               // the unit to the left, the unit above it
+        for (long long s = 0; s < steps; ++s) {
+            const long long x = s - tid;
+            unsigned long long cur = 0;
+            if (live && x >= 0 && x < units) {
+                unsigned long long b = 0;                              // the unit above
+                if (tid > 0) b = pub[(s - 1) & 1][tid - 1];
+                else if (y > 0)
+                    for (int ch = 0; ch < bpp; ++ch) b |= (unsigned long long)row[1 - rb1 + x * bpp + ch] << (8 * ch);
+                for (int ch = 0; ch < bpp; ++ch) {
+                    uint8_t* at = row + 1 + x * bpp + ch;
+                    const uint32_t v = pl_unfilter_byte(type, *at, (uint32_t)(a >> (8 * ch)) & 255u, (uint32_t)(b >> (8 * ch)) & 255u,
+                                                        (uint32_t)(c >> (8 * ch)) & 255u);
+                    *at = (uint8_t)v;
+                    cur |= (unsigned long long)v << (8 * ch);
+                }
+                c = b;
+                a = cur;
+            }
+            pub[s & 1][tid] = cur;
+            __syncthreads();
+        }
+        __syncthreads();                                               // the band's last row is reconstructed before the next band reads it
+    }
+}
+
+// ---- kernel 8b (layout pages): samples -> B,G,R, every pass gathered into the page -----------------------------------------------------------
+// One thread per four consecutive pixels of the page (12 bytes, three aligned words when the page starts on a word), so the stores of a
+// workgroup are contiguous whatever the interlace; the palette is read from LDS.
+constexpr int PL_THREADS = 256, PL_MAX_GRID = 8192;
+__global__ __launch_bounds__(PL_THREADS) void pld_expand_kernel(const uint8_t* blobs, const uint8_t* ws, PSBatch bt) {
+    __shared__ uint8_t pal[768];
+    __shared__ PLGeom geom;
+    const int page = blockIdx.y, tid = threadIdx.x;
+    if (page >= bt.n) return;
+    const PSPage& pg = bt.p[page];
+    const uint32_t fmt = pg.fmt;
+    const int npal = pl_npal(fmt) <= 256 ? pl_npal(fmt) : 256;
+    const uint8_t* src = blobs + pg.blob_off + pg.off_table + (size_t)pg.nidat * sizeof(PSIdat);
+    for (int i = tid; i < 3 * npal; i += PL_THREADS) pal[i] = src[i];
+    if (tid == 0) pl_geometry(pg.W, pg.H, fmt, &geom);
+    __syncthreads();
+    const int W = pg.W;
+    const long long npix = (long long)W * pg.H, groups = (npix + 3) >> 2;
+    const uint8_t* rec = ws + pg.ws_off;
+    uint8_t* out = pg.out;
+    const bool words = ((uintptr_t)out & 3) == 0;
+    for (long long u = (long long)blockIdx.x * PL_THREADS + tid; u < groups; u += (long long)gridDim.x * PL_THREADS) {
+        const long long i0 = u << 2;
+        int y = (int)(i0 / W), x = (int)(i0 - (long long)y * W);
+        const int n = npix - i0 < 4 ? (int)(npix - i0) : 4;
+        uint32_t w[3] = {0u, 0u, 0u};
+        for (int k = 0; k < n; ++k) {
+            uint32_t b, g, r;
+            pl_pixel(geom, fmt, rec, pal, y, x, &b, &g, &r);
+            const uint32_t v[3] = {b, g, r};
+            for (int ch = 0; ch < 3; ++ch) {
+                const int at = 3 * k + ch;
+                w[at >> 2] |= v[ch] << (8 * (at & 3));
+            }
+            if (++x == W) { x = 0; ++y; }
+        }
+        if (n == 4 && words) {
+            uint32_t* o = reinterpret_cast<uint32_t*>(out + 3 * i0);
+            o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+        } else {
+            for (int at = 0; at < 3 * n; ++at) out[3 * i0 + at] = (uint8_t)(w[at >> 2] >> (8 * (at & 3)));
+        }
+    }
+}
+
+const PSHdr* psd_blob(const void* host_blobs, int64_t off, uint32_t magic = PS_MAGIC) {
     if (off < 0) return nullptr;
     const PSHdr* hd = reinterpret_cast<const PSHdr*>(static_cast<const uint8_t*>(host_blobs) + off);
-    if (hd->magic != PS_MAGIC || hd->blob_bytes < (int64_t)sizeof(PSHdr)) return nullptr;
-    return ps_blob(hd, (size_t)hd->blob_bytes);
+    if (hd->magic != magic || hd->blob_bytes < (int64_t)sizeof(PSHdr)) return nullptr;
+    return ps_blob(hd, (size_t)hd->blob_bytes, magic);
 }
 
 uint32_t psd_segment_bytes() {
@@ -436,19 +541,15 @@ uint32_t psd_segment_bytes() {
     return v < (int)PS_SEGMENT_MIN ? PS_SEGMENT_MIN : v > (int)PS_SEGMENT_MAX ? PS_SEGMENT_MAX : (uint32_t)v;
 }
 
-}  // namespace
-
-// rtn_png_stream_*: see include/rtn.h
-extern "C" size_t rtn_png_stream_blob_bound(size_t file_bytes) { return RTN_PNG_BLOB_BOUND(file_bytes); }
-
-extern "C" int rtn_png_stream_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob_out,
-                                      size_t blob_capacity) {
-    if (!info) return rtn_fail_host(h, RTN_EINVAL, "rtn_png_stream_inspect: info is NULL");
+int psd_inspect(const char* name, bool layout, rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob_out,
+                size_t blob_capacity) {
+    if (!info) return rtn_fail_host(h, RTN_EINVAL, "%s: info is NULL", name);
     memset(info, 0, sizeof(*info));
-    if (!file) return rtn_fail_host(h, RTN_EINVAL, "rtn_png_stream_inspect: file is NULL");
+    if (!file) return rtn_fail_host(h, RTN_EINVAL, "%s: file is NULL", name);
     char why[200];
     why[0] = 0;
-    const int rc = ps_inspect(static_cast<const uint8_t*>(file), file_bytes, psd_segment_bytes(), info, blob_out, blob_capacity, why, sizeof(why));
+    const int rc = ps_inspect_any(static_cast<const uint8_t*>(file), file_bytes, psd_segment_bytes(), info, blob_out, blob_capacity, why,
+                                  sizeof(why), layout);
     if (rc != RTN_OK) {
         memset(info, 0, sizeof(*info));
         return rtn_fail_host(h, rc, "%s", why);
@@ -456,51 +557,39 @@ extern "C" int rtn_png_stream_inspect(rtn_handle_t h, const void* file, size_t f
     return RTN_OK;
 }
 
-extern "C" int rtn_png_stream_inflate_host(const void* blob, size_t segment_bytes, void* out, size_t want_bytes, int32_t* status) {
-    if (!blob || !out || !status) { rtn_set_host_error("rtn_png_stream_inflate_host: NULL argument"); return RTN_EINVAL; }
-    const PSHdr* hd = static_cast<const PSHdr*>(blob);
-    if (hd->magic != PS_MAGIC || hd->blob_bytes < (int64_t)sizeof(PSHdr)) {
-        rtn_set_host_error("rtn_png_stream_inflate_host: not an rtn_png_stream_inspect blob");
-        return RTN_EINVAL;
-    }
-    if (segment_bytes > PS_SEGMENT_MAX) { rtn_set_host_error("rtn_png_stream_inflate_host: segment_bytes outside 256 .. 2^24"); return RTN_EINVAL; }
-    const char* why = "";
-    const int rc = ps_inflate_host(blob, (size_t)hd->blob_bytes, (uint32_t)segment_bytes, static_cast<uint8_t*>(out), want_bytes, status, &why);
-    if (rc != RTN_OK) rtn_set_host_error(why);
-    return rc;
-}
-
-extern "C" size_t rtn_png_stream_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
+size_t psd_workspace_bytes(uint32_t magic, int n, const void* host_blobs, const int64_t* offsets) {
     if (n <= 0 || !host_blobs || !offsets) return 0;
     size_t tot = 0;
     for (int i = 0; i < n; ++i) {
-        const PSHdr* hd = psd_blob(host_blobs, offsets[i]);
+        const PSHdr* hd = psd_blob(host_blobs, offsets[i], magic);
         if (!hd) return 0;
         tot += (size_t)hd->ws_bytes;
     }
     return tot;
 }
 
-extern "C" int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
-                                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
+// rtn_png_stream_decode (magic PS_MAGIC) and rtn_png_layout_decode (PL_MAGIC): stages 1 - 7 are the same launches, the last stage is
+// psd_unfilter_kernel for the one and pld_unfilter_kernel + pld_expand_kernel for the other.
+int psd_decode(const char* name, uint32_t magic, rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+               uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: n < 0");
+    if (n < 0) return rtn_fail(h, RTN_EINVAL, "%s: n < 0", name);
     if (n == 0) return RTN_OK;
-    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace)
-        return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: NULL argument");
+    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace) return rtn_fail(h, RTN_EINVAL, "%s: NULL argument", name);
     if (((uintptr_t)dev_blobs & 15) || ((uintptr_t)workspace & 255))
-        return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: blobs must be 16-byte aligned, the workspace 256-byte aligned");
+        return rtn_fail(h, RTN_EINVAL, "%s: blobs must be 16-byte aligned, the workspace 256-byte aligned", name);
+    const char* inspector = magic == PL_MAGIC ? "rtn_png_layout_inspect" : "rtn_png_stream_inspect";
     size_t need = 0;
     for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: blob %d offset not 16-byte aligned", i);
-        const PSHdr* hd = psd_blob(host_blobs, offsets[i]);
-        if (!hd) return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: blob %d is not an rtn_png_stream_inspect blob", i);
-        if (hd->ws_bytes != ps_layout((long long)hd->H * (1 + (long long)hd->W * hd->nc), hd->nsegs).total)
-            return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: blob %d: workspace size does not match its header", i);
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "rtn_png_stream_decode: page %d is NULL", i);
+        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "%s: blob %d offset not 16-byte aligned", name, i);
+        const PSHdr* hd = psd_blob(host_blobs, offsets[i], magic);
+        if (!hd) return rtn_fail(h, RTN_EINVAL, "%s: blob %d is not an %s blob", name, i, inspector);
+        if (hd->ws_bytes != ps_layout(ps_want(hd), hd->nsegs).total)
+            return rtn_fail(h, RTN_EINVAL, "%s: blob %d: workspace size does not match its header", name, i);
+        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "%s: page %d is NULL", name, i);
         need += (size_t)hd->ws_bytes;
     }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_png_stream_decode: workspace %zu < %zu bytes", workspace_bytes, need);
+    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
     const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
     long long ws = 0;
@@ -508,10 +597,10 @@ extern "C" int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blo
         PSBatch bt;
         memset(&bt, 0, sizeof(bt));
         bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        unsigned maxsegs = 1, maxidat = 1;
-        long long maxchunks = 1;
+        unsigned maxsegs = 1, maxidat = 1, maxpass = 1;
+        long long maxchunks = 1, maxgroups = 1;
         for (int j = 0; j < bt.n; ++j) {
-            const PSHdr* hd = psd_blob(host_blobs, offsets[i0 + j]);
+            const PSHdr* hd = psd_blob(host_blobs, offsets[i0 + j], magic);
             PSPage& p = bt.p[j];
             p.blob_off = offsets[i0 + j];
             p.ws_off = ws;
@@ -519,11 +608,14 @@ extern "C" int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blo
             p.W = hd->W; p.H = hd->H; p.nc = hd->nc;
             p.nsegs = hd->nsegs; p.nidat = hd->nidat; p.S = hd->seg_bytes; p.in_bytes = hd->in_bytes; p.adler = hd->adler;
             p.off_table = hd->off_table; p.off_data = hd->off_data;
+            p.stream = (uint32_t)ps_want(hd); p.fmt = ps_fmt(hd);
             ws += hd->ws_bytes;
-            const long long nchunks = ps_layout((long long)hd->H * (1 + (long long)hd->W * hd->nc), hd->nsegs).nchunks;
+            const long long nchunks = ps_layout(ps_want(hd), hd->nsegs).nchunks, groups = ((long long)hd->W * hd->H + 3) / 4;
             maxsegs = p.nsegs > maxsegs ? p.nsegs : maxsegs;
             maxidat = p.nidat > maxidat ? p.nidat : maxidat;
             maxchunks = nchunks > maxchunks ? nchunks : maxchunks;
+            maxgroups = groups > maxgroups ? groups : maxgroups;
+            if (pl_interlace(p.fmt)) maxpass = 7;
         }
         const dim3 per_seg(maxsegs, bt.n);
         psd_find_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
@@ -542,8 +634,79 @@ extern "C" int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blo
         RTN_CHECK_LAUNCH(h, "psd_resolve_kernel");
         psd_page_kernel<<<bt.n, PS_WAVE, 0, h->stream>>>(wsp, status + i0, bt);
         RTN_CHECK_LAUNCH(h, "psd_page_kernel");
-        psd_unfilter_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_unfilter_kernel");
+        if (magic == PS_MAGIC) {
+            psd_unfilter_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_unfilter_kernel");
+        } else {
+            pld_unfilter_kernel<<<dim3(maxpass, bt.n), PS_BAND, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "pld_unfilter_kernel");
+            const long long blocks = (maxgroups + PL_THREADS - 1) / PL_THREADS;
+            pld_expand_kernel<<<dim3((unsigned)(blocks < PL_MAX_GRID ? blocks : PL_MAX_GRID), bt.n), PL_THREADS, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "pld_expand_kernel");
+        }
     }
     return RTN_OK;
+}
+
+}  // namespace
+
+// rtn_png_stream_*, rtn_png_layout_*: see include/rtn.h
+extern "C" size_t rtn_png_stream_blob_bound(size_t file_bytes) { return RTN_PNG_BLOB_BOUND(file_bytes); }
+// the table, the palette and the stream are disjoint parts of the file, so the bound of the stream blob holds
+extern "C" size_t rtn_png_layout_blob_bound(size_t file_bytes) { return RTN_PNG_BLOB_BOUND(file_bytes); }
+
+extern "C" int rtn_png_stream_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob_out,
+                                      size_t blob_capacity) {
+    return psd_inspect("rtn_png_stream_inspect", false, h, file, file_bytes, info, blob_out, blob_capacity);
+}
+
+extern "C" int rtn_png_layout_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob_out,
+                                      size_t blob_capacity) {
+    return psd_inspect("rtn_png_layout_inspect", true, h, file, file_bytes, info, blob_out, blob_capacity);
+}
+
+extern "C" int rtn_png_stream_inflate_host(const void* blob, size_t segment_bytes, void* out, size_t want_bytes, int32_t* status) {
+    if (!blob || !out || !status) { rtn_set_host_error("rtn_png_stream_inflate_host: NULL argument"); return RTN_EINVAL; }
+    const PSHdr* hd = static_cast<const PSHdr*>(blob);
+    if ((hd->magic != PS_MAGIC && hd->magic != PL_MAGIC) || hd->blob_bytes < (int64_t)sizeof(PSHdr)) {
+        rtn_set_host_error("rtn_png_stream_inflate_host: not an rtn_png_stream_inspect or rtn_png_layout_inspect blob");
+        return RTN_EINVAL;
+    }
+    if (segment_bytes > PS_SEGMENT_MAX) { rtn_set_host_error("rtn_png_stream_inflate_host: segment_bytes outside 256 .. 2^24"); return RTN_EINVAL; }
+    const char* why = "";
+    const int rc = ps_inflate_host(blob, (size_t)hd->blob_bytes, (uint32_t)segment_bytes, static_cast<uint8_t*>(out), want_bytes, status, &why);
+    if (rc != RTN_OK) rtn_set_host_error(why);
+    return rc;
+}
+
+extern "C" int rtn_png_layout_pixels_host(const void* blob, const void* filtered_stream, size_t bytes, void* out_bgr, int32_t* status) {
+    if (!blob || !filtered_stream || !out_bgr || !status) { rtn_set_host_error("rtn_png_layout_pixels_host: NULL argument"); return RTN_EINVAL; }
+    const PSHdr* hd = static_cast<const PSHdr*>(blob);
+    if (hd->magic != PL_MAGIC || hd->blob_bytes < (int64_t)sizeof(PSHdr)) {
+        rtn_set_host_error("rtn_png_layout_pixels_host: not an rtn_png_layout_inspect blob");
+        return RTN_EINVAL;
+    }
+    const char* why = "";
+    const int rc = pl_pixels_host(blob, (size_t)hd->blob_bytes, static_cast<const uint8_t*>(filtered_stream), bytes, static_cast<uint8_t*>(out_bgr),
+                                  status, &why);
+    if (rc != RTN_OK) rtn_set_host_error(why);
+    return rc;
+}
+
+extern "C" size_t rtn_png_stream_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
+    return psd_workspace_bytes(PS_MAGIC, n, host_blobs, offsets);
+}
+
+extern "C" size_t rtn_png_layout_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
+    return psd_workspace_bytes(PL_MAGIC, n, host_blobs, offsets);
+}
+
+extern "C" int rtn_png_stream_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
+    return psd_decode("rtn_png_stream_decode", PS_MAGIC, h, n, host_blobs, dev_blobs, offsets, pages, status, workspace, workspace_bytes);
+}
+
+extern "C" int rtn_png_layout_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
+    return psd_decode("rtn_png_layout_decode", PL_MAGIC, h, n, host_blobs, dev_blobs, offsets, pages, status, workspace, workspace_bytes);
 }

@@ -1,6 +1,8 @@
 """Page files, read and written as cv2.imread / cv2.imwrite do, with the five device codecs behind them: baseline
 JPEG and chunked-layout PNG pages are decoded and encoded on the device, ordinary 8-bit gray and R,G,B PNG pages (one zlib stream,
-all five row filters) are decoded there in calls of at least RTN_PNG_STREAM_MIN files (default 4), every other file is left to Pillow.  csv_generator.py,
+all five row filters) are decoded there in calls of at least RTN_PNG_STREAM_MIN files (default 4), PNG pages of the other pixel
+layouts (1-, 2- and 4-bit gray, palette, alpha, 16-bit R,G,B, Adam7 interlace, tRNS) by the same decoder with another last stage in
+calls of at least RTN_PNG_LAYOUT_MIN files (default 2), every other file (16-bit gray PNG, BMP, ...) is left to Pillow.  csv_generator.py,
 model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
 import contextlib
 import ctypes as C
@@ -44,6 +46,20 @@ def png_stream_min():
         return PNG_STREAM_MIN_DEFAULT
 
 
+PNG_LAYOUT_MIN_DEFAULT = 2
+
+
+def png_layout_min():
+    """RTN_PNG_LAYOUT_MIN: the fewest files in one call for which its PNGs of the other pixel layouts (sub-byte gray, palette, alpha,
+    16-bit R,G,B, Adam7; DESIGN §3.4f, "Pixel layouts") are decoded on the device; 0 leaves them all to Pillow.  Same semantics as
+    RTN_PNG_STREAM_MIN.  The default, 2, is the smallest batch at which the device beat Pillow on one thread on all four kinds of
+    sample-sized page measured (1-bit gray, 16-colour palette, R,G,B,A, Adam7 R,G,B: profiles/png_layout_decode_bench.txt)."""
+    try:
+        return max(0, int(os.environ.get("RTN_PNG_LAYOUT_MIN", "") or PNG_LAYOUT_MIN_DEFAULT))
+    except ValueError:
+        return PNG_LAYOUT_MIN_DEFAULT
+
+
 # One record per format the device decodes, in the order _decode_datas tries them: JPEG first, then PNG of the chunked layout,
 # then any other PNG.  min_files(): the fewest files in one call for which the format is tried at all (0: never).
 _Format = namedtuple("_Format", "name Info inspect blob_bound workspace_bytes decode min_files")
@@ -56,6 +72,21 @@ _FORMATS = (
             L.lib.rtn_png_stream_decode_workspace_bytes, L.lib.rtn_png_stream_decode, png_stream_min),
 )
 _JPEG, _PNG, _PNG_STREAM = _FORMATS
+# The formats tried after those of _FORMATS (the dispatch loops run over _FORMATS + _MORE_FORMATS): the PNGs whose pixels are not
+# whole 8-bit gray or R,G,B samples, or that are interlaced.
+def _layout_only_inspect(h, data, n, info, blob, capacity):
+    """rtn_png_layout_inspect for the files rtn_png_stream_inspect refuses.  The layout inspector takes ordinary PNGs too, but where
+    those are decoded is RTN_PNG_STREAM_MIN's to say: in a call too small for it they stay on Pillow, as before."""
+    if L.lib.rtn_png_stream_inspect(h, data, n, C.byref(L.PngInfo()), None, 0) == 0:
+        return -1                                                     # *info is read only after a 0
+    return L.lib.rtn_png_layout_inspect(h, data, n, info, blob, capacity)
+
+
+_MORE_FORMATS = (
+    _Format("png_layout", L.PngInfo, _layout_only_inspect, L.lib.rtn_png_layout_blob_bound,
+            L.lib.rtn_png_layout_decode_workspace_bytes, L.lib.rtn_png_layout_decode, png_layout_min),
+)
+_PNG_LAYOUT, = _MORE_FORMATS
 
 
 def _inspect(fmt, data):
@@ -86,9 +117,17 @@ def png_stream_inspect(data):
     return _inspect(_PNG_STREAM, data)
 
 
+def png_layout_inspect(data):
+    """Parse one file's bytes with rtn_png_layout_inspect (host only) -> (PngInfo, blob bytes) for a PNG of any pixel layout the
+    device decodes (what png_stream_inspect accepts, and 1-, 2- and 4-bit gray, palette, gray + alpha, R,G,B,A, 16-bit R,G,B, each
+    with or without Adam7 interlace, with tRNS; DESIGN §3.4f, "Pixel layouts"), or (None, reason) for anything else (16-bit gray,
+    bKGD, unknown chunks, ...).  PngInfo.components is the file's samples per pixel."""
+    return _inspect(_PNG_LAYOUT._replace(inspect=L.lib.rtn_png_layout_inspect), data)
+
+
 def _decode_datas(datas, host_decode, device, handle, stream):
     """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that the inspector of one
-    of _FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
+    of _FORMATS + _MORE_FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
     words of all are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
     from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
     (None where no device decoder took the file)."""
@@ -96,13 +135,16 @@ def _decode_datas(datas, host_decode, device, handle, stream):
     on_host = [i for i, d in enumerate(datas) if d is None]        # host_decode raises the file's exception below, in page order
     limit = Image.MAX_IMAGE_PIXELS
     # a file with the PNG signature fails rtn_jpeg_inspect at its first two bytes, before anything is written
-    cap = sum((_PNG if d[:8] == PNG_SIGNATURE else _JPEG).blob_bound(len(d)) for d in datas if d is not None)
+    # (a PNG blob is bounded by the larger of its inspectors' bounds)
+    cap = sum(max(_PNG.blob_bound(len(d)), _PNG_LAYOUT.blob_bound(len(d))) if d[:8] == PNG_SIGNATURE else _JPEG.blob_bound(len(d))
+              for d in datas if d is not None)
+    every = _FORMATS + _MORE_FORMATS
     with torch.cuda.stream(stream):
         host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
         hp = host.data_ptr()
         pos = 0
-        kinds = {fmt.name: ([], [], []) for fmt in _FORMATS}         # blob offsets, pages, file indices
-        formats = [fmt for fmt in _FORMATS if 1 <= fmt.min_files() <= len(datas)]
+        kinds = {fmt.name: ([], [], []) for fmt in every}            # blob offsets, pages, file indices
+        formats = [fmt for fmt in every if 1 <= fmt.min_files() <= len(datas)]
         for i, data in enumerate(datas):
             if data is None:
                 continue
@@ -127,7 +169,7 @@ def _decode_datas(datas, host_decode, device, handle, stream):
             handle.set_stream(stream.cuda_stream)
             keep = []                                                  # the workspaces live until the stream is synchronised
             first = 0
-            for fmt in _FORMATS:
+            for fmt in every:
                 offsets, pages, which = kinds[fmt.name]
                 m = len(which)
                 if not m:
@@ -192,8 +234,11 @@ def read_images_bgr(paths, device=None):
     csrc/rtn_png_dec.hip) on the current stream after one copy of the files' entropy-coded bytes.  Ordinary PNGs (what Pillow,
     libpng and cv2.imwrite write: 8-bit gray or R,G,B, one zlib stream, any of the five row filters, harmless ancillary chunks)
     take the same road through csrc/rtn_png_stream.hip when the call holds at least RTN_PNG_STREAM_MIN files
-    (default 4; 0: never).  Every other file (16-bit, palette, alpha and interlaced PNGs, PNGs with tRNS or unknown chunks, BMP, ...),
-    and any file whose stream a device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset can
+    (default 4; 0: never).  PNGs of the other pixel layouts (1-, 2- and 4-bit gray, palette, gray + alpha, R,G,B,A, 16-bit R,G,B,
+    each with or without Adam7 interlace or a tRNS chunk: what ImageMagick, pdftoppm -mono, optipng, pngquant, screenshot tools
+    and cv2.imwrite of four channels write) go through the same decoder with its pixel-layout stage (rtn_png_layout_decode, DESIGN
+    §3.4f "Pixel layouts") when the call holds at least RTN_PNG_LAYOUT_MIN files (default 2; 0: never).  Every other file (16-bit
+    gray PNGs, PNGs with bKGD or unknown chunks, BMP, ...), and any file whose stream a device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset can
     also be converted once with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises
     what read_image_bgr raises."""
     with _reader(device) as (dev, h):
@@ -205,7 +250,9 @@ def decode_png_bgr(files, device=None, return_status=False):
     the counterpart of encode_png_bgr, on read_images_bgr's path.  Files of the chunked layout are decoded in one
     batched rtn_png_decode on the current stream (csrc/rtn_png_dec.hip), ordinary 8-bit gray and R,G,B PNGs in one batched
     rtn_png_stream_decode (csrc/rtn_png_stream.hip, DESIGN §3.4f) when the call holds at least RTN_PNG_STREAM_MIN files (default 4;
-    0: never); any other file, or one that the device flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
+    0: never), PNGs of the other pixel layouts (sub-byte gray, palette, alpha, 16-bit R,G,B, Adam7, tRNS) in one batched
+    rtn_png_layout_decode when the call holds at least RTN_PNG_LAYOUT_MIN files (default 2; 0: never); any other file (16-bit gray,
+    ...), or one that the device flags, is decoded by Pillow from the bytes.  return_status=True returns (pages, status) instead, status[i] being the
     device's status word for file i (0 = the device's page was kept) or None where the device did not take the file."""
     files = [bytes(f) for f in files]
     with _reader(device) as (dev, h):

@@ -19,6 +19,12 @@ measures the stream PNG decoder (csrc/rtn_png_stream.hip) instead
 default settings: read_images_bgr with RTN_PNG_STREAM_MIN=1 at batch sizes 1, 2, 4, 8 and 16 for every RTN_PNG_SEGMENT value asked
 for, the decode kernels alone at batch 16, and the yardsticks on the same files: read_image_bgr (Pillow) on one thread, which is
 what read_images_bgr does with these files without the device path, and the same decode spread over 16 host threads.
+
+  python tools/bench_decode_png.py --layout [--iters 10] [--kinds gray1,palette16,rgba,interlaced_rgb]
+
+measures the pixel-layout decoder (DESIGN §3.4f "Pixel layouts") on 16 copies of the sample page as 1-bit gray, 16-colour palette,
+R,G,B,A and Adam7 R,G,B files: see bench_layout.  For the per-kernel split: rocprofv3 --kernel-trace --stats --output-format csv
+-d rocprof_out -o png_layout -- python tools/bench_decode_png.py --layout --iters 3
 """
 import argparse
 import ctypes as C
@@ -263,6 +269,116 @@ def bench_stream(content, a):
     shutil.rmtree(tmp, ignore_errors=True)
 
 
+def interlaced_rgb_png(rgb):
+    """An Adam7 R,G,B file of the page (Pillow writes none): filter Sub on every row of every pass, zlib level 6."""
+    import struct
+    import zlib
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xffffffff)
+    h, w = rgb.shape[:2]
+    raw = []
+    for x0, y0, dx, dy in ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2)):
+        sub = rgb[y0::dy, x0::dx].astype(np.int16)
+        if sub.size == 0:
+            continue
+        left = np.zeros_like(sub)
+        left[:, 1:] = sub[:, :-1]
+        rows = np.empty((sub.shape[0], 1 + 3 * sub.shape[1]), np.uint8)
+        rows[:, 0] = 1
+        rows[:, 1:] = ((sub - left) & 255).reshape(sub.shape[0], -1)
+        raw.append(rows.tobytes())
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 1)) +
+            chunk(b"IDAT", zlib.compress(b"".join(raw), 6)) + chunk(b"IEND", b""))
+
+
+def bench_layout(a):
+    """--layout: the pixel layouts of DESIGN §3.4f "Pixel layouts" on 16 copies of the sample page in four forms: 1-bit gray,
+    16-colour palette, R,G,B,A (all written by Pillow) and Adam7 R,G,B.  decode_png_bgr with RTN_PNG_LAYOUT_MIN=1 at batch sizes 1, 2,
+    4, 8 and 16 against Pillow on one thread and on 16 threads in the same run, and the decode kernels alone at batch 16."""
+    import io
+    from concurrent.futures import ThreadPoolExecutor
+    dev = torch.device("cuda", 0)
+    o = Image.open(os.path.join(GOLDEN, "sample_0717_023_orig.jpg"))
+
+    def png(img):
+        b = io.BytesIO()
+        img.save(b, "PNG")
+        return b.getvalue()
+    kinds = {"gray1": lambda: png(o.convert("L").convert("1")), "palette16": lambda: png(o.convert("RGB").quantize(16)),
+             "rgba": lambda: png(o.convert("RGBA")), "interlaced_rgb": lambda: interlaced_rgb_png(np.asarray(o.convert("RGB")))}
+    res = {}
+    wins = {}
+    for kind in a.kinds:
+        data = kinds[kind]()
+        files = [data] * 16
+        want = PIO._pillow_bgr(io.BytesIO(data))
+
+        def line(key, label, v, per):
+            m, lo, hi = stat(v)
+            print("%-58s %9.3f ms per %2d page(s) (min %.3f, max %.3f, %d runs): %.1f pages/s" % (label, m, per, lo, hi, len(v), per / m * 1e3))
+            res[kind + "_" + key] = round(m, 3)
+            return m
+        info, blob = PIO.png_layout_inspect(data)
+        assert info is not None, blob
+        print("== %s: %dx%d, depth %d, colour type %d, interlace %d, file %d B, %d segments, blob %d B, workspace %.1f MB per page" %
+              (kind, info.width, info.height, data[24], data[25], data[28], len(data), info.chunks, info.blob_bytes, info.workspace_bytes / 1e6))
+
+        def pillow(d):
+            return PIO._pillow_bgr(io.BytesIO(d))
+        one = line("pillow_ms_per_page", "Pillow from memory, one thread", times_ms(lambda: pillow(data), a.iters), 1)
+        with ThreadPoolExecutor(16) as pool:
+            list(pool.map(pillow, files))
+            line("pillow_16_threads_ms", "Pillow from memory, 16 threads", times_ms(lambda: list(pool.map(pillow, files)), a.iters), 16)
+        os.environ["RTN_PNG_LAYOUT_MIN"] = "0"
+
+        def read_n(n):
+            PIO.decode_png_bgr(files[:n])
+            torch.cuda.synchronize()
+        read_n(16)
+        line("host_path_ms", "decode_png_bgr, device path off (Pillow, then upload)", times_ms(lambda: read_n(16), max(2, a.iters // 3)), 16)
+        os.environ["RTN_PNG_LAYOUT_MIN"] = "1"
+        got, words = PIO.decode_png_bgr([data], return_status=True)
+        assert words == [0] and np.array_equal(got[0].cpu().numpy(), want)
+        for n in (1, 2, 4, 8, 16):
+            read_n(n)
+            m = line("decode_png_bgr_ms_B%d" % n, "decode_png_bgr, device path, batch %d" % n, times_ms(lambda: read_n(n), a.iters), n)
+            print("    %.2fx the one-thread Pillow decode of the same files" % (one * n / m))
+            if one * n / m > 1.0:
+                wins.setdefault(kind, n)
+        n = 16
+        host = np.concatenate([blob] * n)
+        offs = np.arange(n, dtype=np.int64) * blob.size
+        dblobs = torch.from_numpy(host).to(dev)
+        wsb = int(L.lib.rtn_png_layout_decode_workspace_bytes(n, host.ctypes.data, offs.ctypes.data))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        pages = [torch.empty(info.height, info.width, 3, dtype=torch.uint8, device=dev) for _ in range(n)]
+        ptrs = (C.c_void_p * n)(*[p.data_ptr() for p in pages])
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+        h = L.Handle(0)
+        h.set_stream(torch.cuda.current_stream(dev).cuda_stream)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        k_ms = []
+        for it in range(a.iters + 2):
+            ev[0].record()
+            h.check(L.lib.rtn_png_layout_decode(h.raw, n, host.ctypes.data, dblobs.data_ptr(), offs.ctypes.data, ptrs, status.data_ptr(),
+                                                ws.data_ptr(), wsb))
+            ev[1].record()
+            torch.cuda.synchronize()
+            if it >= 2:
+                k_ms.append(ev[0].elapsed_time(ev[1]))
+        assert int(status.abs().sum()) == 0 and np.array_equal(pages[n - 1].cpu().numpy(), want)
+        line("kernels_ms", "decode kernels alone, batch 16", k_ms, n)
+        pinfo = L.PngInfo()
+        out = np.empty(int(L.lib.rtn_png_layout_blob_bound(len(data))), np.uint8)
+        line("inspect_ms_per_page", "rtn_png_layout_inspect on the host",
+             times_ms(lambda: L.lib.rtn_png_layout_inspect(None, data, len(data), C.byref(pinfo), out.ctypes.data, out.size), max(a.iters, 5)), 1)
+        h.close()
+    res["smallest_winning_batch"] = {k: wins.get(k) for k in a.kinds}
+    print("smallest batch at which the device beats Pillow on one thread, per kind: %s" % res["smallest_winning_batch"])
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -271,7 +387,11 @@ def main():
     ap.add_argument("--content", choices=("map", "page", "gray", "all"), default="all")
     ap.add_argument("--stream", action="store_true", help="measure the stream PNG decoder on Pillow-written files")
     ap.add_argument("--segments", type=lambda v: [int(x) for x in v.split(",")], default=[16384], help="RTN_PNG_SEGMENT values (--stream)")
+    ap.add_argument("--layout", action="store_true", help="measure the pixel-layout decoder on the sample page in four forms")
+    ap.add_argument("--kinds", type=lambda v: v.split(","), default=["gray1", "palette16", "rgba", "interlaced_rgb"], help="forms (--layout)")
     a = ap.parse_args()
+    if a.layout:
+        return bench_layout(a)
     for content in (("map", "page", "gray") if a.content == "all" else (a.content,)):
         (bench_stream if a.stream else bench)(content, a)
 
