@@ -931,6 +931,37 @@ int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const* pages, con
 int rtn_visual_effect_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const double* params,
                            const uint32_t* flags, uint8_t* const* outs);
 
+/* ---- 8-bit bicubic resize (cv2.resize(INTER_CUBIC) of a uint8 page: interpolateImages, DetectTablesUtils.py:296-316, which enlarges
+ * 72- and 100-dpi scans by 4.17 and 3; Shapes.Image.data, FasterRCNN/Shapes.py:27-28) --------------------------------------
+ * A batch is n pages (at most 65535), uint8 (heights[i], widths[i], channels[i]) with 1 or 3 channels and sides 1 .. 65500, resized to
+ * (out_heights[i], out_widths[i], channels[i]), sides 1 .. 65500, rows without padding.  All arrays are host arrays; the pages, the
+ * outputs and the workspace (256-byte aligned, >= rtn_resize_u8_workspace_bytes(n)) are device memory of any alignment.  No output
+ * may overlap its page.  inv_x[i], inv_y[i] are the inverse scales (positive, finite, at most 2^31): 1 / fx and 1 / fy for cv2's
+ * factor form, where the caller computes out_width = rint(width * fx) and out_height = rint(height * fy) (half to even), and
+ * width / out_width, height / out_height for its size form.
+ *   Per axis and destination index d: f = (d + 0.5) * inv - 0.5 in float64, s = floor(f), x = (float)(f - s); the four float32
+ *   coefficients of x with A = -0.75, one rounding per operation, c3 = 1 - c0 - c1 - c2, each turned into
+ *   saturate_cast<short>(c * 2048) (half to even); taps at clip(s - 1 + k, 0, n - 1).  Horizontal sums, then vertical sums, in int32;
+ *   the sample is clip((v + 2^21) >> 22, 0, 255).  This is OpenCV's portable C form as recalled (not verifiable offline); its
+ *   vectorised builds run the vertical pass in float32 and can differ by 1 at rare samples.  A factor of 1 copies the page.
+ * rtn_resize_u8 copies its page table into the workspace (for which the call waits on the stream) and queues one launch for the
+ *   whole batch on the handle's stream.  A page outside the limits, or a batch of more than 2^24 - 1 tiles (128 GiB of output),
+ *   fails the call before anything is launched.
+ * rtn_resize_u8_path: the path a page of that vertical inverse scale takes, 1 = tiled (the horizontal sums of a tile's source rows
+ *   pass through LDS; inv_y <= 1), 2 = direct (every sample from its 16 taps); both give the same bits.  RTN_RESIZE_U8_PATH=2 sends
+ *   every page the direct way, =1 and 0 choose by inv_y.  rtn_resize_u8_tile: the destination rows and bytes of a tile.
+ * rtn_resize_u8_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers and no workspace, through the functions of csrc/rtn_resize_u8.h with the kernel's tile walk; the device's bits. */
+size_t rtn_resize_u8_workspace_bytes(int n);
+int rtn_resize_u8(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                  const int32_t* channels, const int32_t* out_heights, const int32_t* out_widths, const double* inv_x,
+                  const double* inv_y, uint8_t* const* outs, void* workspace, size_t workspace_bytes);
+int rtn_resize_u8_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                       const int32_t* out_heights, const int32_t* out_widths, const double* inv_x, const double* inv_y,
+                       uint8_t* const* outs);
+int rtn_resize_u8_path(double inv_y);
+int rtn_resize_u8_tile(int32_t* rows, int32_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

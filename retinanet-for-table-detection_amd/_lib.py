@@ -257,6 +257,11 @@ SIGNATURES = {
     "rtn_visual_effect_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_visual_effect_u8": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_visual_effect_host": (_I, [_I, _P, _P, _P, _P, _P, _P]),
+    "rtn_resize_u8_workspace_bytes": (_SZ, [_I]),
+    "rtn_resize_u8": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_resize_u8_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "rtn_resize_u8_path": (_I, [_D]),
+    "rtn_resize_u8_tile": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
 }
 
 

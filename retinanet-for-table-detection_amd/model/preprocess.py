@@ -48,7 +48,15 @@ def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
         raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
     if not src_paths:
         return
-    pages = read_images_bgr(src_paths)
+    write_images_bgr(dst_paths, preprocess_device_pages(read_images_bgr(src_paths)), quality=quality, png=png)
+
+
+def preprocess_device_pages(pages):
+    """The distance maps of a list of CUDA uint8 (H,W,3) B,G,R pages of any sizes, as CUDA uint8 (H,W,3) tensors in the same order:
+    rtn_preprocess_dt3 on the current stream, one call per page size.  No pixel comes to the host."""
+    pages = list(pages)
+    if not pages:
+        return []
     h = _rt.handle()
     groups = {}
     for i, p in enumerate(pages):
@@ -65,7 +73,125 @@ def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
             h.check(L.lib.rtn_preprocess_dt3(h.raw, src.data_ptr(), 3, B, H, W, dst.data_ptr(), None, ws.data_ptr(), wsb))
             for k, i in enumerate(part):
                 out[i] = dst[k]
-    write_images_bgr(dst_paths, out, quality=quality, png=png)
+    return out
+
+
+# ---- DetectTablesUtils.interpolateImages (DetectTablesUtils.py:296-316) on the device: csrc/rtn_resize_u8.hip, DESIGN §3.4k --------------
+RESIZE_MAX_SIDE = 65500
+
+
+def interpolation_factor(name):
+    """The factor interpolateImages enlarges a low-resolution scan by, from its file name: 4.17 for names ending "-72.jpg", 3 for
+    "-100.jpg" (72- and 100-dpi pages), 1.0 for every other name.  The reference keeps the last factor for the following files that
+    have neither suffix, in os.listdir order; that is not reproduced: a name without a suffix always gives 1.0."""
+    name = str(name)
+    if name.endswith("-72.jpg"):
+        return 4.17
+    if name.endswith("-100.jpg"):
+        return 3.0
+    return 1.0
+
+
+def interpolated_size(height, width, fx, fy=None):
+    """(Ho, Wo) of cv2.resize(..., fx=fx, fy=fy): saturate_cast<int> of the products, half to even.  ValueError where a side
+    leaves 1 .. 65500."""
+    fy = fx if fy is None else fy
+    ho, wo = int(np.rint(height * float(fy))), int(np.rint(width * float(fx)))
+    if not (1 <= ho <= RESIZE_MAX_SIDE and 1 <= wo <= RESIZE_MAX_SIDE):
+        raise ValueError("%dx%d by (%g, %g) gives %dx%d: sides must be 1..%d" % (height, width, fx, fy, ho, wo, RESIZE_MAX_SIDE))
+    return ho, wo
+
+
+def _per_page(v, n, name):
+    if isinstance(v, (list, tuple, np.ndarray)) and not (name == "dsize" and len(v) == 2 and np.ndim(v[0]) == 0):
+        v = list(v)
+        if len(v) != n:
+            raise ValueError("%d %s values for %d pages" % (len(v), name, n))
+        return v
+    return [v] * n
+
+
+def interpolate_images(pages, fx=None, fy=None, dsize=None):
+    """cv2.resize(page, None, fx=fx, fy=fy, interpolation=cv2.INTER_CUBIC) of a list of uint8 (H,W,3) or (H,W) pages (NumPy arrays or
+    CUDA tensors, sizes may differ), as interpolateImages applies it to low-resolution scans; with dsize, cv2.resize(page, dsize,
+    interpolation=cv2.INTER_CUBIC) instead.  fx, fy: scalars or one value per page, fy defaults to fx.  dsize: (width, height) for
+    all pages or one pair per page; fx and fy are then not taken.  One rtn_resize_u8 launch on the current stream resizes the whole
+    batch; pages already on the device are not copied to the host.  Returns a list of CUDA uint8 tensors.  The arithmetic is
+    OpenCV's 8-bit fixed-point form as recalled (csrc/rtn_resize_u8.h)."""
+    import ctypes as C
+    pages = list(pages)
+    n = len(pages)
+    if dsize is not None:
+        if fx is not None or fy is not None:
+            raise ValueError("either factors or dsize, not both")
+    elif fx is None:
+        raise ValueError("fx or dsize is required")
+    src = []
+    for i, p in enumerate(pages):
+        if isinstance(p, torch.Tensor):
+            if p.dtype != torch.uint8:
+                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, p.dtype))
+            p = p.cuda().contiguous()
+        else:
+            a = np.asarray(p)
+            if a.dtype != np.uint8:
+                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, a.dtype))
+            p = torch.as_tensor(np.ascontiguousarray(a)).cuda()
+        if not (p.dim() == 2 or (p.dim() == 3 and p.shape[2] == 3)) or not (1 <= p.shape[0] <= RESIZE_MAX_SIDE and 1 <= p.shape[1] <= RESIZE_MAX_SIDE):
+            raise ValueError("page %d: shape (H,W,3) or (H,W) with sides 1..%d expected, got %s" % (i, RESIZE_MAX_SIDE, tuple(p.shape)))
+        src.append(p)
+    if n == 0:
+        return []
+    sizes, inv_x, inv_y = [], [], []
+    if dsize is not None:
+        for p, d in zip(src, _per_page(dsize, n, "dsize")):
+            wo, ho = int(d[0]), int(d[1])
+            if not (1 <= ho <= RESIZE_MAX_SIDE and 1 <= wo <= RESIZE_MAX_SIDE):
+                raise ValueError("dsize %s: sides must be 1..%d" % ((wo, ho), RESIZE_MAX_SIDE))
+            sizes.append((ho, wo))
+            inv_x.append(p.shape[1] / float(wo))
+            inv_y.append(p.shape[0] / float(ho))
+    else:
+        fxs = _per_page(fx, n, "fx")
+        fys = fxs if fy is None else _per_page(fy, n, "fy")
+        for p, a, b in zip(src, fxs, fys):
+            a, b = float(a), float(b)
+            if not (np.isfinite(a) and np.isfinite(b) and a > 0 and b > 0):
+                raise ValueError("factors must be positive and finite, got (%r, %r)" % (a, b))
+            sizes.append(interpolated_size(p.shape[0], p.shape[1], a, b))
+            inv_x.append(1.0 / a)
+            inv_y.append(1.0 / b)
+    h = _rt.handle()
+    outs = [torch.empty((ho, wo) + tuple(p.shape[2:]), dtype=torch.uint8, device=p.device) for p, (ho, wo) in zip(src, sizes)]
+    i32 = lambda v: np.ascontiguousarray(v, np.int32)
+    arrays = (i32([p.shape[0] for p in src]), i32([p.shape[1] for p in src]), i32([3 if p.dim() == 3 else 1 for p in src]),
+              i32([s[0] for s in sizes]), i32([s[1] for s in sizes]), np.ascontiguousarray(inv_x, np.float64),
+              np.ascontiguousarray(inv_y, np.float64))
+    wsb = int(L.lib.rtn_resize_u8_workspace_bytes(n))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=src[0].device)
+    h.check(L.lib.rtn_resize_u8(h.raw, n, (C.c_void_p * n)(*[p.data_ptr() for p in src]), *[a.ctypes.data for a in arrays],
+                                (C.c_void_p * n)(*[o.data_ptr() for o in outs]), ws.data_ptr(), wsb))
+    return outs                                                 # queued on the current stream, like the sources' uploads
+
+
+def interpolate_files(src_paths, dst_paths, factors=None, quality=95, png="host"):
+    """DetectTablesUtils.interpolateImages as a batch: read every page (page_io.read_images_bgr), enlarge all of them in one
+    rtn_resize_u8 launch (interpolate_images) and write them (page_io.write_images_bgr: .jpg names encoded on the device at
+    `quality`, 4:2:0, cv2.imwrite's defaults; png="device" encodes the .png names on the device too).  factors: one per file, by
+    default interpolation_factor of the source's base name (4.17 / 3 / 1.0; a factor of 1 copies the page).  On the JPEG -> JPEG
+    path no pixel comes to the host."""
+    import os
+    src_paths, dst_paths = list(src_paths), list(dst_paths)
+    if png not in ("host", "device"):
+        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
+    if len(src_paths) != len(dst_paths):
+        raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
+    if factors is None:
+        factors = [interpolation_factor(os.path.basename(str(p))) for p in src_paths]
+    factors = _per_page(factors, len(src_paths), "factors")
+    if not src_paths:
+        return
+    write_images_bgr(dst_paths, interpolate_images(read_images_bgr(src_paths), factors), quality=quality, png=png)
 
 
 def resize_cubic(img, scale):

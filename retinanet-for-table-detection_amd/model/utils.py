@@ -429,6 +429,34 @@ def render_detections_device(draw_pages, boxes, scores, labels, image_scales, re
     return kept, per_page
 
 
+def _render_batch(draw_pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers):
+    """The output step of one batch that detect_files and detect_raw_files share: render_detections_device, and with headers=True
+    HeaderDetect.py's step on the crops while they are on the device.  Returns the kept list of every page."""
+    import os
+    got = render_detections_device(draw_pages, boxes, scores, labels, scales, result_dir, names, labels_to_names=labels_to_names,
+                                   score_threshold=score_threshold, png=png, return_pages=headers)
+    if not headers:
+        return got
+    from . import header
+    got, per_page = got
+    crops, crop_names = [], []
+    for name, (page_crops, _page) in zip(names, per_page):
+        crop_name = _render_names(result_dir, name)[0]
+        for k, crop in enumerate(page_crops):
+            if crop is not None:
+                crops.append(crop)
+                crop_names.append(crop_name(k))
+    out_dir = os.path.join(result_dir, "headerResults")
+    fits = [header.sampled_points(c.shape[0], c.shape[1]) <= header.MAX_POINTS for c in crops]
+    for c, name, ok in zip(crops, crop_names, fits):
+        if not ok:                          # a sliver of a box: 500 x dh points past the limit; its OrigImage.png alone is written
+            warnings.warn("header detection skipped for %s: %d x %d is too tall for a width of 500" % (name, c.shape[0], c.shape[1]))
+    found = iter(header.detect_headers([c for c, ok in zip(crops, fits) if ok]))
+    paths, images = header._header_outputs(crops, crop_names, [next(found) if ok else None for ok in fits], out_dir)
+    write_images_bgr(paths, images, png=png)
+    return got
+
+
 def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
                  min_side=800, max_side=1333, headers=False):
     """The loop of RetinaNet.py's test() over files, in batches of batch_size, with every pixel on the device: read_images_bgr of
@@ -456,26 +484,47 @@ def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_t
         canvas, scales = preprocess.compute_inputs_device(read_images_bgr(src), min_side=min_side, max_side=max_side, dtype=dtype)
         boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
         names = [os.path.basename(p) for p in src]
-        got = render_detections_device(read_images_bgr(orig), boxes, scores, labels, scales, result_dir, names,
-                                       labels_to_names=labels_to_names, score_threshold=score_threshold, png=png,
-                                       return_pages=headers)
-        if headers:
-            from . import header
-            got, per_page = got
-            crops, crop_names = [], []
-            for name, (page_crops, _page) in zip(names, per_page):
-                crop_name = _render_names(result_dir, name)[0]
-                for k, crop in enumerate(page_crops):
-                    if crop is not None:
-                        crops.append(crop)
-                        crop_names.append(crop_name(k))
-            out_dir = os.path.join(result_dir, "headerResults")
-            fits = [header.sampled_points(c.shape[0], c.shape[1]) <= header.MAX_POINTS for c in crops]
-            for c, name, ok in zip(crops, crop_names, fits):
-                if not ok:                          # a sliver of a box: 500 x dh points past the limit; its OrigImage.png alone is written
-                    warnings.warn("header detection skipped for %s: %d x %d is too tall for a width of 500" % (name, c.shape[0], c.shape[1]))
-            found = iter(header.detect_headers([c for c, ok in zip(crops, fits) if ok]))
-            paths, images = header._header_outputs(crops, crop_names, [next(found) if ok else None for ok in fits], out_dir)
-            write_images_bgr(paths, images, png=png)
-        kept += got
+        kept += _render_batch(read_images_bgr(orig), boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold,
+                              png, headers)
+    return kept
+
+
+def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
+                     min_side=800, max_side=1333, headers=False):
+    """Raw scans to detections in one call, in batches of batch_size, with every pixel on the device: read_images_bgr of the scans,
+    interpolate_images where a page's factor is not 1 (factors: one per file, by default preprocess.interpolation_factor of its
+    base name: 4.17 for "-72.jpg", 3 for "-100.jpg"), preprocess_device_pages (the distance maps), compute_inputs_device, the
+    inference model's engine().detect, and detect_files' output step on the (enlarged) pages with image_names =
+    basename(orig_paths); headers=True as in detect_files.  `model`: a retinanet_bbox model (ValueError otherwise).
+    Unlike the reference's flow (interpolateImages, preProcessSampleImages, then test() on the written files), the enlarged and the
+    processed page never pass through a JPEG file: the results are those of that flow with lossless (PNG) intermediate files.
+    Returns the kept list of every file."""
+    import os
+    from . import preprocess
+    from .page_io import read_images_bgr
+    if not getattr(model, "bbox", False):
+        raise ValueError("detect_raw_files: the inference model (retinanet_bbox) is required")
+    orig_paths = list(orig_paths)
+    if factors is None:
+        factors = [preprocess.interpolation_factor(os.path.basename(str(p))) for p in orig_paths]
+    factors = [float(f) for f in factors]
+    if len(factors) != len(orig_paths):
+        raise ValueError("%d factors for %d pages" % (len(factors), len(orig_paths)))
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    dtype = torch.float32 if model._root().dtype == "f32" else torch.bfloat16
+    eng = model.engine()
+    kept = []
+    for i in range(0, len(orig_paths), int(batch_size)):
+        orig, fs = orig_paths[i:i + int(batch_size)], factors[i:i + int(batch_size)]
+        pages = read_images_bgr(orig)
+        grow = [k for k, f in enumerate(fs) if f != 1.0]
+        if grow:
+            for k, big in zip(grow, preprocess.interpolate_images([pages[k] for k in grow], [fs[k] for k in grow])):
+                pages[k] = big
+        processed = preprocess.preprocess_device_pages(pages)
+        canvas, scales = preprocess.compute_inputs_device(processed, min_side=min_side, max_side=max_side, dtype=dtype)
+        boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
+        names = [os.path.basename(str(p)) for p in orig]
+        kept += _render_batch(pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers)
     return kept
