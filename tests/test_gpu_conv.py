@@ -506,42 +506,9 @@ def test_gemm8_narrow_instance_for_128_columns(pkg, handle, monkeypatch, levels,
 
 
 
-EPI_MODES = ["none", "res", "mask", "mask_pre", "res+mask", "res+mask_pre"]
-EPI_FORMS = {
-    # name: (impl, k, cin, cout, levels, form)
-    "h8": (4, 3, 64, 136, [(12, 11), (2, 3)], None),       # generation 4 full width: 264 + 12 rows = two tiles at both tile heights, a group
-                                                           # boundary inside the second; columns 136..255 of the tile are never stored
-    "h8-128": (4, 3, 64, 72, [(12, 11), (2, 3)], None),    # ... its 128-column instance (8-byte accesses)
-    "g8": (5, 1, 128, 256, [(11, 13)], None),              # generation 5 full width: 286 rows = 3 / 2 tiles, the last one part full
-    "g8-128": (5, 1, 128, 128, [(11, 13)], None),          # ... its narrow instance
-    "h8-kslice": (4, 3, 64, 136, [(12, 11)], "kslice"),    # generation 4, three K slices (one kernel row each) through the f32 slabs
-    "g8-scatter": (5, 1, 128, 256, [(5, 4)], "scatter"),   # generation 5: rows land on every second pixel of a 9 x 7 grid (out_step 2)
-    "g8-up": (5, 1, 128, 256, [(7, 9)], "up"),             # ... residual = the coarser level (4 x 5: ratios 0.571 / 0.556)
-    "g8-sk": (5, 1, 128, 256, [(11, 13)], "sk"),           # ... stream-K: two K steps per tile, tiles cut between workgroups
-}
-_EPI_REF = {}
-
-
-def epi_exact_operands(form):
-    """Small-integer operands of one EPI_FORMS entry and the float64 convolution + bias of every level, computed once per form:
-    inputs and `other` in [-3, 3], filters in [-2, 2], bias in [-8, 8] - every partial sum is an integer below 2^24, exact in f32
-    in any order, so the only rounding on the device is the final one to bf16."""
-    if form not in _EPI_REF:
-        impl, k, cin, cout, levels, kind = EPI_FORMS[form]
-        g = torch.Generator().manual_seed(4000 + sorted(EPI_FORMS).index(form))
-        w = torch.randint(-2, 3, (k, k, cin, cout), generator=g).double()
-        bias = torch.randint(-8, 9, (cout,), generator=g).double()
-        B, lv = 2, []
-        for H, W in levels:
-            x = torch.randint(-3, 4, (B, H, W, cin), generator=g).double()
-            Hg, Wg = (2 * H - 1, 2 * W - 1) if kind == "scatter" else (H, W)         # the grid `out`, `other` and `act` live on
-            other = torch.randint(-3, 4, (B, (H + 1) // 2, (W + 1) // 2, cout) if kind == "up" else (B, Hg, Wg, cout), generator=g).double()
-            act = torch.randint(-3, 4, (B, Hg, Wg, cout), generator=g).double()
-            act[0, 0, 0, :8] = torch.tensor([0.0, -0.0, 1e-30, -1e-30, 1.0, -1.0, 0.5, 0.0])     # zeros of either sign do not pass
-            act = q(act, "bf16")
-            lv.append((x, other, act, ref_conv(x, w, bias, 1, (k - 1) // 2, (k - 1) // 2, H, W)))
-        _EPI_REF[form] = (w, bias, lv)
-    return _EPI_REF[form]
+# The forms, modes and small-integer operands of the register-epilogue tests live in tests/conv_exact.py (their bias is drawn from
+# [-600, 600] so that the final rounding to bf16 matters; tests/test_conv_exact_cases.py checks that without a GPU).
+from conv_exact import EPI_FORMS, EPI_MODES, epi_exact_operands, epi_stages
 
 
 def run_epi_exact(pkg, handle, form, mode, relu):
@@ -565,7 +532,8 @@ def run_epi_exact(pkg, handle, form, mode, relu):
     d.flags = (L.CONV_RELU if relu else 0) | (L.CONV_RELU_MASK if "mask" in mode else 0) | (L.CONV_MASK_PRE if "pre" in mode else 0) | \
         ((L.CONV_RES_UPSAMPLE if kind == "up" else L.CONV_RES_SAME) if "res" in mode else 0)
     keep, outs, res = [], [], []
-    for gi, ((H, W), (x, other, act, y)) in enumerate(zip(levels, lv)):
+    stages = epi_stages(form, mode, relu)
+    for gi, ((H, W), (x, other, act, y, _)) in enumerate(zip(levels, lv)):
         step = 2 if kind == "scatter" else 1
         Hg, Wg = act.shape[1], act.shape[2]
         xd = x.to(torch.bfloat16).to(dev).contiguous()
@@ -587,17 +555,7 @@ def run_epi_exact(pkg, handle, form, mode, relu):
         d.g[gi] = grp
         keep += [xd, rd, ad]
         outs.append(od)
-        # the float64 reference on the written pixels: [mask] [+ other] [mask], ReLU, one rounding to bf16
-        keepm = (act[:, ::step, ::step] > 0) if "mask" in mode else torch.ones_like(y, dtype=torch.bool)
-        o = upsample_nearest_legacy(other, H, W) if kind == "up" else other[:, ::step, ::step]
-        want = y
-        if "pre" in mode:
-            want = want * keepm
-        if "res" in mode:
-            want = want + o
-        if "mask" in mode and "pre" not in mode:
-            want = want * keepm
-        res.append((step, torch.relu(want) if relu else want))
+        res.append((step, stages[gi][1].pre))              # the float64 reference on the written pixels, before its one rounding
     L.attach_conv_workspace(handle, d)
     handle.check(L.lib.rtn_conv2d_fwd(handle.raw, C.byref(d)))
     torch.cuda.synchronize()
