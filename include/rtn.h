@@ -759,6 +759,38 @@ int rtn_png_layout_decode(rtn_handle_t h, int n, const void* host_blobs, const v
                           uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_png_layout_pixels_host(const void* blob, const void* filtered_stream, size_t bytes, void* out_bgr, int32_t* status);
 
+/* ---- TIFF decode (scanner and archive pages, on the device) ------------------------------------------------------------------
+ * Decodes the first page of a classic strip TIFF to the pixels Image.open(f).convert("RGB") gives, as B,G,R.  Blob / offsets / pages /
+ * status / workspace conventions are those of rtn_png_decode.
+ *
+ * rtn_tiff_inspect (host only; h may be NULL): RTN_OK only for: II or MM, version 42, a first IFD inside the file whose tags are BYTE,
+ *   SHORT or LONG, values inline or by offset; sides 1 .. 65535; strips (no tile tags), PlanarConfiguration 1; Compression 1, 32773
+ *   (PackBits), 5 (LZW; not the old-style form), 8 or 32946 (Deflate), or 4 (Group 4, T6Options 0); 1-bit bilevel (photometric 0 or 1,
+ *   FillOrder 1 or 2), 8-bit gray (photometric 0 or 1), 8-bit palette with a ColorMap of 768 SHORTs, or 8-bit R,G,B of 3 samples, no
+ *   ExtraSamples, SampleFormat 1; Predictor 1, or 2 on 8-bit samples under LZW or Deflate; Orientation 1; any RowsPerStrip; every strip
+ *   inside the file, an uncompressed strip holding all its rows, and no more strip bytes in all than the file has.  A Group 4 page of
+ *   more than 64 rows in ONE strip is refused unless RTN_TIFF_G4_ONE_STRIP=1 (one serial decoder per page loses to the host: DESIGN
+ *   §3.4l).  Anything else: RTN_EINVAL and a reason.  It decodes nothing.  The blob (at most rtn_tiff_blob_bound(file_bytes) bytes,
+ *   exactly info->blob_bytes, a multiple of 16) holds a header, a table of offset / byte count / first row / rows per strip, the palette
+ *   as B,G,R bytes and the strips' bytes (bit-reversed for FillOrder 2).
+ * rtn_tiff_decode: status (device, n int32) is the OR of the strips' words: 0 only if every strip decoded to exactly its rows (TF_* bits
+ *   of csrc/rtn_tiff_decode.h, PI_* bits of csrc/rtn_png_inflate.h for a Deflate strip, otherwise): no invalid code, no run past a
+ *   row's end, no output short of or past the strip, no LZW code before the first Clear, no Group 4 extension, a whole zlib stream
+ *   with the right Adler-32.  A page with any other status holds unspecified bytes and the caller decodes that file on the host.
+ * rtn_tiff_decode_host (host only, no handle): the same decode functions run on the CPU over one blob, every position checked (a
+ *   position outside its buffer aborts): *status as the device's; out_bgr (height * width * 3 bytes = out_bytes) is written only if 0. */
+typedef struct {
+    int32_t width, height, components, strips;
+    int32_t compression, bits, photometric, predictor;   /* compression: 32946 is reported as 8 */
+    int64_t blob_bytes, workspace_bytes, payload_bytes;  /* payload_bytes: the strips' bytes */
+} rtn_tiff_info_t;
+size_t rtn_tiff_blob_bound(size_t file_bytes);
+int rtn_tiff_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_tiff_info_t* info, void* blob, size_t blob_capacity);
+size_t rtn_tiff_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets);
+int rtn_tiff_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
+                    uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
+int rtn_tiff_decode_host(const void* blob, uint8_t* out_bgr, size_t out_bytes, int32_t* status);
+
 /* ---- detection rendering (render_detections' outlines, captions and crops, on the device) ----------------------------------
  * Every output image of a batch (crops and annotated pages alike) is a rectangle of one source page with some of that page's
  * operations painted over it.  Page p owns the operations op_begin[p] .. op_begin[p + 1] - 1 (at most RTN_RENDER_MAX_OPS), in drawing

@@ -112,6 +112,14 @@ class PngInfo(C.Structure):
     ]
 
 
+class TiffInfo(C.Structure):
+    _fields_ = [
+        ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("strips", C.c_int32),
+        ("compression", C.c_int32), ("bits", C.c_int32), ("photometric", C.c_int32), ("predictor", C.c_int32),
+        ("blob_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("payload_bytes", C.c_int64),
+    ]
+
+
 def png_blob_bound(file_bytes):
     """RTN_PNG_BLOB_BOUND of include/rtn.h: the most bytes rtn_png_inspect writes for a file of that size."""
     return 128 + 2 * int(file_bytes)
@@ -232,6 +240,11 @@ SIGNATURES = {
     "rtn_png_layout_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_png_layout_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_png_layout_pixels_host": (_I, [_P, _P, _SZ, _P, C.POINTER(C.c_int32)]),
+    "rtn_tiff_blob_bound": (_SZ, [_SZ]),
+    "rtn_tiff_inspect": (_I, [_P, _P, _SZ, C.POINTER(TiffInfo), _P, _SZ]),
+    "rtn_tiff_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
+    "rtn_tiff_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_tiff_decode_host": (_I, [_P, _P, _SZ, C.POINTER(C.c_int32)]),
     "rtn_render_workspace_bytes": (_SZ, [_I, _I, _I]),
     "rtn_render_pages": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _SZ]),
     "rtn_render_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ]),

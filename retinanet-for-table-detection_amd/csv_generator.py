@@ -4,9 +4,10 @@ Same class names, constructor arguments and method names as the reference's Gene
 (:234-247) constructs it unchanged; what differs is where the work runs:
 
   host   CSV rows, grouping / shuffling, annotation filtering, the 3x3 augmentation matrices and box corners (a few flops),
-         parsing the page files (rtn_jpeg_inspect, rtn_png_inspect)
-  device per batch: rtn_jpeg_decode of the baseline-JPEG pages and rtn_png_decode of the chunked-layout PNG pages
-         (read_images_bgr, re-exported here from model/page_io.py; other files are decoded by Pillow and uploaded)
+         parsing the page files (rtn_jpeg_inspect, rtn_png_inspect, rtn_tiff_inspect)
+  device per batch: rtn_jpeg_decode of the baseline-JPEG pages, rtn_png_decode of the chunked-layout PNG pages and rtn_tiff_decode
+         of the strip TIFF pages (read_images_bgr, re-exported here from model/page_io.py; other files are decoded by Pillow and
+         uploaded)
          per batch, with apply_visual_effect=True: rtn_visual_effect_u8, the colour effects of the whole group in one call
          per page: [rtn_warp_affine_u8, when a transform generator is given] -> rtn_resize_cubic, which fuses the
          x/127.5-1 normalisation (preprocess_image 'custom_tf'), the INTER_CUBIC resize and the write into the zero-padded batch
@@ -34,13 +35,13 @@ try:                                    # as a module of the package ...
     from .model import anchors as _anchors
     from .model.transform import adjust_transform_for_image, invert_affine, transform_aabb, visual_effect_batch, warp_codes
     from .model.utils import compute_resize_scale
-    from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
+    from .model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, tiff_inspect, _decode_batch  # noqa: F401
 except ImportError:                     # ... or top-level, with the package directory on sys.path like the reference's layout
     from model import Parameters, _rt
     from model import anchors as _anchors
     from model.transform import adjust_transform_for_image, invert_affine, transform_aabb, visual_effect_batch, warp_codes
     from model.utils import compute_resize_scale
-    from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, _decode_batch  # noqa: F401
+    from model.page_io import read_image_bgr, read_images_bgr, jpeg_inspect, png_inspect, png_stream_inspect, tiff_inspect, _decode_batch  # noqa: F401
 
 L = _rt.L
 

@@ -1,8 +1,10 @@
-"""Page files, read and written as cv2.imread / cv2.imwrite do, with the five device codecs behind them: baseline
+"""Page files, read and written as cv2.imread / cv2.imwrite do, with the six device codecs behind them: baseline
 JPEG and chunked-layout PNG pages are decoded and encoded on the device, ordinary 8-bit gray and R,G,B PNG pages (one zlib stream,
 all five row filters) are decoded there in calls of at least RTN_PNG_STREAM_MIN files (default 4), PNG pages of the other pixel
 layouts (1-, 2- and 4-bit gray, palette, alpha, 16-bit R,G,B, Adam7 interlace, tRNS) by the same decoder with another last stage in
-calls of at least RTN_PNG_LAYOUT_MIN files (default 2), every other file (16-bit gray PNG, BMP, ...) is left to Pillow.  csv_generator.py,
+calls of at least RTN_PNG_LAYOUT_MIN files (default 2), strip TIFF pages (uncompressed, PackBits, LZW, Deflate or CCITT Group 4;
+bilevel, 8-bit gray, palette or R,G,B) in calls of at least RTN_TIFF_MIN files (default 2), every other
+file (16-bit gray PNG, tiled, JPEG-in-TIFF or 16-bit TIFF, BMP, ...) is left to Pillow.  csv_generator.py,
 model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
 import contextlib
 import ctypes as C
@@ -60,6 +62,20 @@ def png_layout_min():
         return PNG_LAYOUT_MIN_DEFAULT
 
 
+TIFF_MIN_DEFAULT = 2
+
+
+def tiff_min():
+    """RTN_TIFF_MIN: the fewest files in one call for which its TIFFs are decoded on the device; 0 leaves them all
+    to Pillow.  Same semantics as RTN_PNG_STREAM_MIN.  The default, 2, is the smallest batch at which the device beat Pillow on one
+    thread on every kind of sample-sized page it takes by default (Group 4 needs 2 files, every other kind 1; a Group 4 page written
+    as one strip wins only at 16 and is refused by the inspector unless RTN_TIFF_G4_ONE_STRIP=1: profiles/tiff_decode_bench.txt)."""
+    try:
+        return max(0, int(os.environ.get("RTN_TIFF_MIN", "") or TIFF_MIN_DEFAULT))
+    except ValueError:
+        return TIFF_MIN_DEFAULT
+
+
 # One record per format the device decodes, in the order _decode_datas tries them: JPEG first, then PNG of the chunked layout,
 # then any other PNG.  min_files(): the fewest files in one call for which the format is tried at all (0: never).
 _Format = namedtuple("_Format", "name Info inspect blob_bound workspace_bytes decode min_files")
@@ -72,7 +88,7 @@ _FORMATS = (
             L.lib.rtn_png_stream_decode_workspace_bytes, L.lib.rtn_png_stream_decode, png_stream_min),
 )
 _JPEG, _PNG, _PNG_STREAM = _FORMATS
-# The formats tried after those of _FORMATS (the dispatch loops run over _FORMATS + _MORE_FORMATS): the PNGs whose pixels are not
+# The formats tried after those of _FORMATS (the dispatch loops run over _ALL_FORMATS, below): the PNGs whose pixels are not
 # whole 8-bit gray or R,G,B samples, or that are interlaced.
 def _layout_only_inspect(h, data, n, info, blob, capacity):
     """rtn_png_layout_inspect for the files rtn_png_stream_inspect refuses.  The layout inspector takes ordinary PNGs too, but where
@@ -87,6 +103,14 @@ _MORE_FORMATS = (
             L.lib.rtn_png_layout_decode_workspace_bytes, L.lib.rtn_png_layout_decode, png_layout_min),
 )
 _PNG_LAYOUT, = _MORE_FORMATS
+# Tried after every PNG format: strip TIFFs.  _ALL_FORMATS is what the dispatch loops run over.
+_TIFF_FORMATS = (
+    _Format("tiff", L.TiffInfo, L.lib.rtn_tiff_inspect, L.lib.rtn_tiff_blob_bound, L.lib.rtn_tiff_decode_workspace_bytes,
+            L.lib.rtn_tiff_decode, tiff_min),
+)
+_TIFF, = _TIFF_FORMATS
+_ALL_FORMATS = _FORMATS + _MORE_FORMATS + _TIFF_FORMATS
+TIFF_SIGNATURES = (b"II*\0", b"MM\0*")
 
 
 def _inspect(fmt, data):
@@ -125,20 +149,36 @@ def png_layout_inspect(data):
     return _inspect(_PNG_LAYOUT._replace(inspect=L.lib.rtn_png_layout_inspect), data)
 
 
+def tiff_inspect(data):
+    """Parse one file's bytes with rtn_tiff_inspect (host only) -> (TiffInfo, blob bytes) for a strip TIFF the device decodes
+    (first IFD; Compression 1, 32773, 5, 8 / 32946 or 4; bilevel, 8-bit gray, palette or R,G,B), or (None, reason)
+    for anything else (tiles, BigTIFF, Group 3, JPEG-in-TIFF, old-style LZW, 2-, 4- or 16-bit samples, CMYK / YCbCr / Lab, extra
+    samples, planar 2, Orientation other than 1, offsets outside the file, ...)."""
+    return _inspect(_TIFF, data)
+
+
+def _blob_bound(d):
+    """The most blob bytes any inspector of _ALL_FORMATS writes for the file d: formats are told apart by signature."""
+    if d[:8] == PNG_SIGNATURE:
+        return max(_PNG.blob_bound(len(d)), _PNG_LAYOUT.blob_bound(len(d)))
+    if d[:4] in TIFF_SIGNATURES:
+        return _TIFF.blob_bound(len(d))
+    return _JPEG.blob_bound(len(d))
+
+
 def _decode_datas(datas, host_decode, device, handle, stream):
     """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that the inspector of one
-    of _FORMATS + _MORE_FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
+    of _ALL_FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
     words of all are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
     from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
     (None where no device decoder took the file)."""
     out, words = [None] * len(datas), [None] * len(datas)
     on_host = [i for i, d in enumerate(datas) if d is None]        # host_decode raises the file's exception below, in page order
     limit = Image.MAX_IMAGE_PIXELS
-    # a file with the PNG signature fails rtn_jpeg_inspect at its first two bytes, before anything is written
-    # (a PNG blob is bounded by the larger of its inspectors' bounds)
-    cap = sum(max(_PNG.blob_bound(len(d)), _PNG_LAYOUT.blob_bound(len(d))) if d[:8] == PNG_SIGNATURE else _JPEG.blob_bound(len(d))
-              for d in datas if d is not None)
-    every = _FORMATS + _MORE_FORMATS
+    # a file with the PNG or a TIFF signature fails rtn_jpeg_inspect at its first two bytes, before anything is written, and the
+    # other inspectors refuse at the signature likewise (a PNG blob is bounded by the larger of its inspectors' bounds)
+    cap = sum(_blob_bound(d) for d in datas if d is not None)
+    every = _ALL_FORMATS
     with torch.cuda.stream(stream):
         host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
         hp = host.data_ptr()
@@ -237,7 +277,13 @@ def read_images_bgr(paths, device=None):
     (default 4; 0: never).  PNGs of the other pixel layouts (1-, 2- and 4-bit gray, palette, gray + alpha, R,G,B,A, 16-bit R,G,B,
     each with or without Adam7 interlace or a tRNS chunk: what ImageMagick, pdftoppm -mono, optipng, pngquant, screenshot tools
     and cv2.imwrite of four channels write) go through the same decoder with its pixel-layout stage (rtn_png_layout_decode, DESIGN
-    §3.4f "Pixel layouts") when the call holds at least RTN_PNG_LAYOUT_MIN files (default 2; 0: never).  Every other file (16-bit
+    §3.4f "Pixel layouts") when the call holds at least RTN_PNG_LAYOUT_MIN files (default 2; 0: never).  Strip TIFFs (what scanners
+    and scan archives write: first IFD, uncompressed, PackBits, LZW, Deflate or CCITT Group 4; bilevel with either photometric and
+    fill order, 8-bit gray, palette or R,G,B; predictor 2; any RowsPerStrip, byte order and field type) go through
+    csrc/rtn_tiff.hip, one wave per strip, when the call holds at least RTN_TIFF_MIN files (default 2; 0: never); the inspector
+    refuses tiles, BigTIFF, Group 3, JPEG-in-TIFF, old-style LZW, 2-, 4- and 16-bit samples, CMYK / YCbCr / Lab, extra samples,
+    planar 2, Orientation other than 1, offsets outside the file and, unless RTN_TIFF_G4_ONE_STRIP=1, Group 4 pages written as one
+    strip (one serial decoder per page).  Every other file (16-bit
     gray PNGs, PNGs with bKGD or unknown chunks, BMP, ...), and any file whose stream a device decode flags, is decoded by read_image_bgr on one thread and uploaded; a PNG dataset can
     also be converted once with write_images_bgr(paths, read_images_bgr(paths), png="device").  A file Pillow cannot open raises
     what read_image_bgr raises."""
@@ -258,6 +304,16 @@ def decode_png_bgr(files, device=None, return_status=False):
     with _reader(device) as (dev, h):
         pages, words = _decode_datas(files, lambda i: _pillow_bgr(io.BytesIO(files[i])), dev, h, torch.cuda.current_stream(dev))
     return (pages, words) if return_status else pages
+
+
+def decode_tiff_bgr(files, device=None, return_status=False):
+    """The pages of TIFF files held in memory (list of bytes) as CUDA uint8 (H,W,3) B,G,R tensors with the bits Pillow gives: the
+    counterpart of decode_png_bgr, on read_images_bgr's path.  The files tiff_inspect accepts are decoded in one batched
+    rtn_tiff_decode on the current stream (csrc/rtn_tiff.hip) when the call holds at least RTN_TIFF_MIN files (0:
+    never); any other file, or one that the device flags, is decoded by Pillow from the bytes.  return_status=True returns (pages,
+    status) instead, status[i] being the device's status word for file i (0 = the device's page was kept) or None where the device
+    did not take the file."""
+    return decode_png_bgr(files, device=device, return_status=return_status)
 
 
 def write_image(path, image):
