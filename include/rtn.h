@@ -454,6 +454,24 @@ int rtn_retina_loss_fwd(rtn_handle_t h, int64_t rows /* B*N */, int num_classes,
                         float alpha, float gamma, float sigma, double* sums,
                         void* workspace, size_t workspace_bytes);
 size_t rtn_retina_loss_workspace_bytes(int64_t rows);
+
+/* The same four sums per IMAGE, straight from the ground-truth boxes (rtn_anchor_targets' gt_boxes / gt_labels / gt_count /
+ * img_hw layout and thresholds): every anchor is rebuilt from its index, assigned (float64 IoU, float32 compare, first
+ * maximum, box deltas rounded to float32, outside-the-image rule) and fed to the float32 loss terms in registers.  The
+ * (B,N,5) / (B,N,K+1) target tensors are neither written nor read.  N is the anchor count of `cfg`.
+ * image_sums[b][0..3] is bit-identical to rtn_anchor_targets on the batch followed by rtn_retina_loss_fwd on image b's
+ * rows alone (rows = N): same row-to-thread mapping, same reduction trees, one final workgroup per image, no atomics.
+ * classification [B][N][K], regression [B][N][4] (16-byte aligned), image_sums device f64 [B][4] (the caller may pass
+ * a row offset into a larger [num_images][4] array).  gt_count is clamped to [0, RTN_MAX_GT].  B in [1, 65535].
+ * RTN_EINVAL on bad arguments, RTN_ENOMEM when workspace_bytes < rtn_retina_loss_boxes_workspace_bytes(B, N). */
+size_t rtn_retina_loss_boxes_workspace_bytes(int B, int64_t N);
+int rtn_retina_loss_boxes_fwd(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes,
+                              const double* gt_boxes, const int32_t* gt_labels, const int32_t* gt_count, const int32_t* img_hw,
+                              double negative_overlap, double positive_overlap,
+                              const float* classification, const float* regression,
+                              float alpha, float gamma, float sigma,
+                              double* image_sums, void* workspace, size_t workspace_bytes);
+
 int rtn_retina_loss_bwd(rtn_handle_t h, int64_t rows, int num_classes,
                         const float* labels_batch, const float* regression_batch,
                         const float* classification, const float* regression,

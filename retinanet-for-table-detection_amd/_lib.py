@@ -203,6 +203,8 @@ SIGNATURES = {
     "rtn_warp_affine_u8": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, _P, _P]),
     "rtn_retina_loss_fwd": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _F, _F, _P, _P, _SZ]),
     "rtn_retina_loss_workspace_bytes": (_SZ, [_I64]),
+    "rtn_retina_loss_boxes_workspace_bytes": (_SZ, [_I, _I64]),
+    "rtn_retina_loss_boxes_fwd": (_I, [_P, C.POINTER(AnchorCfg), _I, _I, _P, _P, _P, _P, _D, _D, _P, _P, _F, _F, _F, _P, _P, _SZ]),
     "rtn_retina_loss_bwd": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _P, _P]),
     "rtn_retina_loss_bwd_dev": (_I, [_P, _I64, _I, _P, _P, _P, _P, _F, _F, _F, _P, _I, _P, _P]),
     "rtn_detect_workspace_bytes": (_SZ, [_I, _I64, _I]),

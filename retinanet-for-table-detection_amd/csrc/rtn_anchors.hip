@@ -17,6 +17,8 @@
 
 #pragma clang fp contract(off)
 
+#include "rtn_assign_dev.h"
+
 extern "C" int rtn_generate_anchors(double base_size, const double* ratios, int nratios, const double* scales, int nscales,
                                     double* out) {
     if (!ratios || !scales || !out || nratios < 1 || nscales < 1 || nratios * nscales > 16) return RTN_EINVAL;
@@ -46,15 +48,6 @@ extern "C" int rtn_generate_anchors(double base_size, const double* ratios, int 
 
 namespace {
 
-// anchors_for_shape, f64: base + ((i + 0.5) * stride)
-__device__ __forceinline__ void anchor_f64(const DevAnchorCfg& c, int n, double a[4]) {
-    const AnchorIdx ai = locate(c, n);
-    const double sx = ((double)ai.x + 0.5) * (double)c.stride[ai.level];
-    const double sy = ((double)ai.y + 0.5) * (double)c.stride[ai.level];
-    const double* b = c.base[ai.level][ai.a];
-    a[0] = b[0] + sx; a[1] = b[1] + sy; a[2] = b[2] + sx; a[3] = b[3] + sy;
-}
-
 __global__ __launch_bounds__(256) void anchors_f64_kernel(const DevAnchorCfg c, double* __restrict__ out) {
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < c.total; n += gridDim.x * blockDim.x) {
         double a[4];
@@ -80,19 +73,9 @@ __global__ __launch_bounds__(256) void anchor_targets_kernel(const DevAnchorCfg 
                                                              const int* __restrict__ img_hw, float neg_ov, float pos_ov,
                                                              float* __restrict__ reg_out, float* __restrict__ lab_out,
                                                              const double* __restrict__ anchors_explicit, int n_explicit) {
-    __shared__ double s_gt[RTN_MAX_GT][4];
-    __shared__ double s_area[RTN_MAX_GT];
-    __shared__ int s_lab[RTN_MAX_GT];
+    __shared__ GtShared s_gt;
     const int b = blockIdx.y;
-    int G = gt_count[b];
-    G = G < 0 ? 0 : (G > RTN_MAX_GT ? RTN_MAX_GT : G);
-    for (int i = threadIdx.x; i < G; i += blockDim.x) {
-        const double* g = gt_boxes + ((long long)b * RTN_MAX_GT + i) * 4;
-        s_gt[i][0] = g[0]; s_gt[i][1] = g[1]; s_gt[i][2] = g[2]; s_gt[i][3] = g[3];
-        s_area[i] = (g[2] - g[0]) * (g[3] - g[1]);
-        s_lab[i] = gt_labels[(long long)b * RTN_MAX_GT + i];
-    }
-    __syncthreads();
+    const int G = stage_gt(s_gt, b, gt_boxes, gt_labels, gt_count);
     const int img_h = img_hw[2 * b], img_w = img_hw[2 * b + 1];
     const int N = anchors_explicit ? n_explicit : c.total;
     for (int n = blockIdx.x * blockDim.x + threadIdx.x; n < N; n += gridDim.x * blockDim.x) {
@@ -103,44 +86,12 @@ __global__ __launch_bounds__(256) void anchor_targets_kernel(const DevAnchorCfg 
         } else {
             anchor_f64(c, n, a);
         }
-        float state = 0.f;
-        float t[4] = {0.f, 0.f, 0.f, 0.f};
-        int label = -1;
-        if (G > 0) {
-            const double area1 = (a[2] - a[0]) * (a[3] - a[1]);
-            float best = 0.f;
-            int arg = 0;
-            for (int i = 0; i < G; ++i) {
-                const double x1 = fmax(a[0], s_gt[i][0]);
-                const double y1 = fmax(a[1], s_gt[i][1]);
-                const double x2 = fmin(a[2], s_gt[i][2]);
-                const double y2 = fmin(a[3], s_gt[i][3]);
-                const double w = fmax(0.0, x2 - x1);
-                const double hh = fmax(0.0, y2 - y1);
-                const double inter = w * hh;
-                const double uni = area1 + s_area[i] - inter;
-                const float iou = (float)(inter / uni);          // result array is float32
-                if (i == 0 || iou > best) { best = iou; arg = i; }  // np.argmax: first maximum
-            }
-            const bool positive = best >= pos_ov;
-            const bool ignore = (best > neg_ov) && !positive;
-            state = positive ? 1.f : (ignore ? -1.f : 0.f);
-            if (positive) label = s_lab[arg];
-            // bbox_transform over ALL anchors with their argmax box
-            const double aw = a[2] - a[0], ah = a[3] - a[1];
-            t[0] = (float)(((s_gt[arg][0] - a[0]) / aw) / 0.2);
-            t[1] = (float)(((s_gt[arg][1] - a[1]) / ah) / 0.2);
-            t[2] = (float)(((s_gt[arg][2] - a[2]) / aw) / 0.2);
-            t[3] = (float)(((s_gt[arg][3] - a[3]) / ah) / 0.2);
-        }
-        // anchors whose centre lies outside this image's own extent are ignored
-        const double cx = (a[0] + a[2]) / 2, cy = (a[1] + a[3]) / 2;
-        if (cx >= (double)img_w || cy >= (double)img_h) state = -1.f;
+        const AnchorTarget at = assign_anchor(a, s_gt, G, neg_ov, pos_ov, img_h, img_w);   // rtn_assign_dev.h
         float* r = reg_out + ((long long)b * N + n) * 5;
-        r[0] = t[0]; r[1] = t[1]; r[2] = t[2]; r[3] = t[3]; r[4] = state;
+        r[0] = at.t[0]; r[1] = at.t[1]; r[2] = at.t[2]; r[3] = at.t[3]; r[4] = at.state;
         float* l = lab_out + ((long long)b * N + n) * (K + 1);
-        for (int k = 0; k < K; ++k) l[k] = (k == label) ? 1.f : 0.f;
-        l[K] = state;
+        for (int k = 0; k < K; ++k) l[k] = (k == at.label) ? 1.f : 0.f;
+        l[K] = at.state;
     }
 }
 

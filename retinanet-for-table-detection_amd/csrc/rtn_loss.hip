@@ -10,9 +10,14 @@
 // HBM-bound: one pass over (K+1) + 5 + K + 4 floats per anchor; per-thread f64 partials,
 // wave shuffle reduction, fixed-order second stage => bitwise reproducible run to run.
 // The division by the normaliser is the caller's (it is all-reduced under data parallelism).
+// rtn_retina_loss_boxes_fwd gives the same four sums per image without the dense targets: each anchor is assigned against the
+// image's ground-truth boxes (rtn_assign_dev.h, the text anchor_targets_kernel runs) and its terms are taken in registers;
+// 4 + K floats read per anchor, bits identical to the two-kernel path on that image's rows (validation: model/eval.py).
 #include "rtn_internal.h"
 
 #pragma clang fp contract(off)
+
+#include "rtn_assign_dev.h"
 
 namespace {
 
@@ -26,6 +31,37 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The float32 terms of one row and the reduction trees, shared by loss_fwd_kernel (dense targets) and loss_boxes_kernel (targets
+// derived per anchor from the ground-truth boxes): one text, so the two give the same bits.
+__device__ __forceinline__ float focal_term(float y, float p, float alpha, float gamma) {
+    const bool one = (y == 1.f);
+    const float af = one ? alpha : 1.f - alpha;
+    const float fw0 = one ? 1.f - p : p;
+    const float fw = af * (gamma == 2.f ? fw0 * fw0 : powf(fw0, gamma));
+    const float pc = fminf(fmaxf(p, BCE_EPS), 1.f - BCE_EPS);
+    const float bce = -(y * logf(pc) + (1.f - y) * logf(1.f - pc));
+    return fw * bce;
+}
+
+__device__ __forceinline__ float smooth_l1_term(float pred, float target, float sigma2) {
+    const float d = fabsf(pred - target);
+    return d < 1.0f / sigma2 ? 0.5f * sigma2 * (d * d) : d - 0.5f / sigma2;
+}
+
+// wave shuffle, then the block's waves in order: partial[0..3] = {focal, smooth-L1, positives (labels), positives (regression)}
+__device__ __forceinline__ void block_sums(double s_cls, double s_reg, double n_pos, double n_pos_reg, double* __restrict__ partial) {
+    __shared__ double sh[4][LOSS_BLOCK / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    s_cls = wave_sum(s_cls); s_reg = wave_sum(s_reg); n_pos = wave_sum(n_pos); n_pos_reg = wave_sum(n_pos_reg);
+    if (lane == 0) { sh[0][wave] = s_cls; sh[1][wave] = s_reg; sh[2][wave] = n_pos; sh[3][wave] = n_pos_reg; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double v = 0.0;
+        for (int w = 0; w < LOSS_BLOCK / 64; ++w) v += sh[threadIdx.x][w];
+        partial[threadIdx.x] = v;
+    }
+}
+
 __global__ __launch_bounds__(LOSS_BLOCK) void loss_fwd_kernel(long long rows, int K, const float* __restrict__ lab,
                                                                const float* __restrict__ regt, const float* __restrict__ cls,
                                                                const float* __restrict__ reg, float alpha, float gamma,
@@ -35,17 +71,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void loss_fwd_kernel(long long rows, in
         const float* l = lab + r * (K + 1);
         const float state = l[K];
         if (state != -1.f) {
-            for (int k = 0; k < K; ++k) {
-                const float y = l[k];
-                const float p = cls[r * K + k];
-                const bool one = (y == 1.f);
-                const float af = one ? alpha : 1.f - alpha;
-                const float fw0 = one ? 1.f - p : p;
-                const float fw = af * (gamma == 2.f ? fw0 * fw0 : powf(fw0, gamma));
-                const float pc = fminf(fmaxf(p, BCE_EPS), 1.f - BCE_EPS);
-                const float bce = -(y * logf(pc) + (1.f - y) * logf(1.f - pc));
-                s_cls += (double)(fw * bce);
-            }
+            for (int k = 0; k < K; ++k) s_cls += (double)focal_term(l[k], cls[r * K + k], alpha, gamma);
         }
         if (state == 1.f) n_pos += 1.0;
         const float4 t4 = *reinterpret_cast<const float4*>(reg + r * 4);   // prediction
@@ -54,28 +80,53 @@ __global__ __launch_bounds__(LOSS_BLOCK) void loss_fwd_kernel(long long rows, in
             n_pos_reg += 1.0;
             const float pr[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float d = fabsf(pr[j] - tg[j]);
-                const float v = d < 1.0f / sigma2 ? 0.5f * sigma2 * (d * d) : d - 0.5f / sigma2;
-                s_reg += (double)v;
-            }
+            for (int j = 0; j < 4; ++j) s_reg += (double)smooth_l1_term(pr[j], tg[j], sigma2);
         }
     }
-    __shared__ double sh[4][LOSS_BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    s_cls = wave_sum(s_cls); s_reg = wave_sum(s_reg); n_pos = wave_sum(n_pos); n_pos_reg = wave_sum(n_pos_reg);
-    if (lane == 0) { sh[0][wave] = s_cls; sh[1][wave] = s_reg; sh[2][wave] = n_pos; sh[3][wave] = n_pos_reg; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        double v = 0.0;
-        for (int w = 0; w < LOSS_BLOCK / 64; ++w) v += sh[threadIdx.x][w];
-        partial[(long long)blockIdx.x * 4 + threadIdx.x] = v;
-    }
+    block_sums(s_cls, s_reg, n_pos, n_pos_reg, partial + (long long)blockIdx.x * 4);
 }
 
+// One image per blockIdx.y; within an image the rows map to threads exactly as loss_fwd_kernel maps `rows = N` rows onto
+// loss_blocks(N) blocks, so every per-thread partial, wave sum and block sum has that launch's bits.  The targets of a row are
+// computed from the image's boxes (rtn_assign_dev.h) and used in registers: nothing of the (B,N,5) / (B,N,K+1) tensors exists.
+__global__ __launch_bounds__(LOSS_BLOCK) void loss_boxes_kernel(const DevAnchorCfg c, int K, const double* __restrict__ gt_boxes,
+                                                                 const int* __restrict__ gt_labels, const int* __restrict__ gt_count,
+                                                                 const int* __restrict__ img_hw, float neg_ov, float pos_ov,
+                                                                 const float* __restrict__ cls, const float* __restrict__ reg,
+                                                                 float alpha, float gamma, float sigma2, double* __restrict__ partial) {
+    __shared__ GtShared s_gt;
+    const int b = blockIdx.y;
+    const int G = stage_gt(s_gt, b, gt_boxes, gt_labels, gt_count);
+    const int img_h = img_hw[2 * b], img_w = img_hw[2 * b + 1];
+    const int N = c.total;
+    const float* cls_b = cls + (long long)b * N * K;
+    const float* reg_b = reg + (long long)b * N * 4;
+    double s_cls = 0.0, s_reg = 0.0, n_pos = 0.0, n_pos_reg = 0.0;
+    for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < N; r += (long long)gridDim.x * blockDim.x) {
+        double a[4];
+        anchor_f64(c, (int)r, a);
+        const AnchorTarget at = assign_anchor(a, s_gt, G, neg_ov, pos_ov, img_h, img_w);
+        if (at.state != -1.f) {
+            for (int k = 0; k < K; ++k) s_cls += (double)focal_term((k == at.label) ? 1.f : 0.f, cls_b[r * K + k], alpha, gamma);
+        }
+        if (at.state == 1.f) {
+            n_pos += 1.0;
+            const float4 t4 = *reinterpret_cast<const float4*>(reg_b + r * 4);   // prediction
+            n_pos_reg += 1.0;
+            const float pr[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s_reg += (double)smooth_l1_term(pr[j], at.t[j], sigma2);
+        }
+    }
+    block_sums(s_cls, s_reg, n_pos, n_pos_reg, partial + ((long long)b * gridDim.x + blockIdx.x) * 4);
+}
+
+// one workgroup per set of block partials (blockIdx.x: the image of loss_boxes_kernel; 0 for loss_fwd_kernel)
 __global__ __launch_bounds__(256) void loss_final_kernel(const double* __restrict__ partial, int nblocks, double* __restrict__ sums) {
     // fixed-order tree over the block partials: thread j owns partials j, j+256, ...
     __shared__ double sh[4][256];
+    partial += (long long)blockIdx.x * nblocks * 4;
+    sums += (long long)blockIdx.x * 4;
     double v[4] = {0, 0, 0, 0};
     for (int i = threadIdx.x; i < nblocks; i += 256)
         for (int q = 0; q < 4; ++q) v[q] += partial[(long long)i * 4 + q];
@@ -174,6 +225,38 @@ extern "C" int rtn_retina_loss_fwd(rtn_handle_t h, int64_t rows, int num_classes
                        regression_batch, classification, regression, alpha, gamma, sigma * sigma, (double*)workspace);
     RTN_CHECK_LAUNCH(h, "loss_fwd_kernel");
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, h->stream, (const double*)workspace, nb, sums);
+    RTN_CHECK_LAUNCH(h, "loss_final_kernel");
+    return RTN_OK;
+}
+
+extern "C" size_t rtn_retina_loss_boxes_workspace_bytes(int B, int64_t N) {
+    if (B < 1) B = 1;
+    return (size_t)B * loss_blocks(N) * 4 * sizeof(double);
+}
+
+extern "C" int rtn_retina_loss_boxes_fwd(rtn_handle_t h, const rtn_anchor_cfg_t* cfg, int B, int num_classes, const double* gt_boxes,
+                                         const int32_t* gt_labels, const int32_t* gt_count, const int32_t* img_hw,
+                                         double negative_overlap, double positive_overlap, const float* classification,
+                                         const float* regression, float alpha, float gamma, float sigma, double* image_sums,
+                                         void* workspace, size_t workspace_bytes) {
+    if (!h) return RTN_EINVAL;
+    if (B < 1 || B > 65535 || num_classes < 1) return rtn_fail(h, RTN_EINVAL, "loss_boxes_fwd: B %d / classes %d", B, num_classes);
+    if (!gt_boxes || !gt_labels || !gt_count || !img_hw || !classification || !regression || !image_sums || !workspace)
+        return rtn_fail(h, RTN_EINVAL, "loss_boxes_fwd: null pointer");
+    if ((uintptr_t)regression & 15) return rtn_fail(h, RTN_EINVAL, "loss_boxes_fwd: regression not 16-byte aligned");
+    if (((uintptr_t)image_sums & 7) || ((uintptr_t)workspace & 7)) return rtn_fail(h, RTN_EINVAL, "loss_boxes_fwd: image_sums / workspace not 8-byte aligned");
+    DevAnchorCfg d;
+    const int rc = make_dev_cfg(h, cfg, &d);
+    if (rc) return rc;
+    const size_t need = rtn_retina_loss_boxes_workspace_bytes(B, d.total);
+    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "loss_boxes_fwd: workspace %zu < %zu", workspace_bytes, need);
+    const int nb = loss_blocks(d.total);
+    // thresholds compare against a float32 array: NumPy casts the Python float to float32 (as rtn_anchor_targets)
+    hipLaunchKernelGGL(loss_boxes_kernel, dim3(nb, B), dim3(LOSS_BLOCK), 0, h->stream, d, num_classes, gt_boxes, gt_labels, gt_count,
+                       img_hw, (float)negative_overlap, (float)positive_overlap, classification, regression, alpha, gamma,
+                       sigma * sigma, (double*)workspace);
+    RTN_CHECK_LAUNCH(h, "loss_boxes_kernel");
+    hipLaunchKernelGGL(loss_final_kernel, dim3(B), dim3(256), 0, h->stream, (const double*)workspace, nb, image_sums);
     RTN_CHECK_LAUNCH(h, "loss_final_kernel");
     return RTN_OK;
 }

@@ -61,6 +61,30 @@ def detect_flags(nms=True, class_specific_filter=True):
     return (0 if nms else L.RTN_DET_NO_NMS) | (0 if class_specific_filter else L.RTN_DET_CLASS_AGNOSTIC)
 
 
+class BoxLoss:
+    """What Engine.detect(loss=...) needs to run the focal + smooth-L1 sums of one batch from its ground-truth boxes:
+    device tensors in rtn_anchor_targets' layout - gt_boxes f64 (B, RTN_MAX_GT, 4) at network scale, gt_labels i32 (B, RTN_MAX_GT),
+    gt_count i32 (B,), img_hw i32 (B, 2): each page's own resized (h, w) - uploaded in the caller's stream order before the call;
+    `out`: the caller's f64 (num_images, 4) device array and `row`: the first of the B rows this batch writes."""
+
+    def __init__(self, gt_boxes, gt_labels, gt_count, img_hw, out, row, alpha=0.25, gamma=2.0, sigma=3.0,
+                 negative_overlap=0.4, positive_overlap=0.5):
+        for t, dt, shape in ((gt_boxes, torch.float64, (L.RTN_MAX_GT, 4)), (gt_labels, torch.int32, (L.RTN_MAX_GT,)),
+                             (gt_count, torch.int32, ()), (img_hw, torch.int32, (2,))):
+            if t.device.type != "cuda" or t.dtype != dt or tuple(t.shape[1:]) != shape or t.shape[0] != gt_boxes.shape[0] \
+                    or not t.is_contiguous():
+                raise ValueError("BoxLoss: contiguous device tensors f64 (B,%d,4), i32 (B,%d), i32 (B,), i32 (B,2) expected"
+                                 % (L.RTN_MAX_GT, L.RTN_MAX_GT))
+        if out.device.type != "cuda" or out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 4 or not out.is_contiguous():
+            raise ValueError("BoxLoss: out must be a contiguous f64 (num_images, 4) device tensor")
+        self.gt_boxes, self.gt_labels, self.gt_count, self.img_hw, self.out, self.row = gt_boxes, gt_labels, gt_count, img_hw, out, int(row)
+        self.alpha, self.gamma, self.sigma = float(alpha), float(gamma), float(sigma)
+        self.negative_overlap, self.positive_overlap = float(negative_overlap), float(positive_overlap)
+
+    def tensors(self):
+        return (self.gt_boxes, self.gt_labels, self.gt_count, self.img_hw, self.out)
+
+
 def make_anchor_cfg(image_hw, params=None, levels=(3, 4, 5, 6, 7)):
     """rtn_anchor_cfg_t for a canvas: guess_shapes (model/anchors.py:155-165) + base anchors."""
     params = params or AnchorParams()
@@ -789,7 +813,8 @@ class Engine:
                 totals[i] += evs[i].elapsed_time(evs[i + 1])
         return [(op.kind, totals[i]) for i, op in enumerate(ops)] + [("detect", totals[-1])]
 
-    def detect(self, images, score_threshold=0.05, nms_threshold=0.5, max_detections=300, nms=True, class_specific_filter=True):
+    def detect(self, images, score_threshold=0.05, nms_threshold=0.5, max_detections=300, nms=True, class_specific_filter=True,
+               loss=None):
         """Inference model outputs [boxes (B,300,4), scores (B,300), labels (B,300)] (model/defineModel.py:310-315).
         Views of the plan's output buffers: overwritten by the next call with the same (B,H,W) - clone to keep them.
         nms / class_specific_filter: FilterDetections' two switches (model/layers.py:200-264); the defaults are the reference's.
@@ -799,13 +824,17 @@ class Engine:
         use 44-175 of 256 CUs and every kernel has a tail - the neighbouring batch's kernels run there; measured 4.07 -> 3.57 ms per
         batch of 8 at 800x1333, profiles/r4_in_flight.txt).  The page tensor is consumed in the caller's stream order (the stem packer
         runs on the caller's stream), so it may be overwritten as soon as the call returns.  The returned views belong to the buffer
-        set: valid after join() (or any device synchronisation) and until the in_flight-th call after this one."""
+        set: valid after join() (or any device synchronisation) and until the in_flight-th call after this one.
+
+        loss (a BoxLoss): the same forward also feeds the validation loss - rtn_retina_loss_boxes_fwd runs on this batch's
+        regression / classification outputs, on the stream that ran the forward, beside postprocess, and writes its (B,4) rows at
+        loss.row of loss.out.  Nothing is read back."""
         md = int(max_detections)
         if not 1 <= md <= L.RTN_MAX_DET:
             raise ValueError("max_detections must be in [1, %d]" % L.RTN_MAX_DET)
         flags = detect_flags(nms, class_specific_filter)
         if self.in_flight > 1 and not self.training:
-            return self._detect_in_flight(images, score_threshold, nms_threshold, md, flags)
+            return self._detect_in_flight(images, score_threshold, nms_threshold, md, flags, loss)
         reg, cls = self.forward(images, private=True)
         B, H, W, _ = images.shape
         plan = self._plan(B, H, W)
@@ -814,9 +843,34 @@ class Engine:
         scores = plan["scores"].view(-1)[:B * md].view(B, md)
         labels = plan["labels"].view(-1)[:B * md].view(B, md)
         self.postprocess(plan["cfg"], reg, cls, H, W, boxes, scores, labels, plan["det_ws"], score_threshold, nms_threshold, md, flags)
+        if loss is not None:
+            self.loss_from_boxes(plan, loss)
         return boxes, scores, labels
 
-    def _detect_in_flight(self, images, score_threshold, nms_threshold, md, flags=0):
+    def loss_from_boxes(self, plan, loss):
+        """rtn_retina_loss_boxes_fwd on the outputs `plan` holds, on the current stream: per image {focal sum, smooth-L1 sum,
+        positives, positives} into rows loss.row .. loss.row + B of loss.out (csrc/rtn_loss.hip).  The workspace belongs to the
+        plan (one per buffer set), so batches in flight on different sets do not share it."""
+        self._bind_stream()
+        reg, cls = plan["regression"], plan["classification"]
+        B, N, K = cls.shape
+        if loss.gt_boxes.shape[0] != B or loss.row < 0 or loss.row + B > loss.out.shape[0]:
+            raise ValueError("BoxLoss: %d images of ground truth at row %d of %d for a batch of %d"
+                             % (loss.gt_boxes.shape[0], loss.row, loss.out.shape[0], B))
+        need = int(L.lib.rtn_retina_loss_boxes_workspace_bytes(B, N))
+        ws = plan.get("loss_ws")
+        if ws is None or ws.numel() < need:
+            ws = plan["loss_ws"] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        cur = torch.cuda.current_stream(self.device)
+        for t in loss.tensors():
+            t.record_stream(cur)
+        self.h.check(L.lib.rtn_retina_loss_boxes_fwd(self.h.raw, C.byref(plan["cfg"]), B, K, loss.gt_boxes.data_ptr(),
+                                                     loss.gt_labels.data_ptr(), loss.gt_count.data_ptr(), loss.img_hw.data_ptr(),
+                                                     loss.negative_overlap, loss.positive_overlap, cls.data_ptr(), reg.data_ptr(),
+                                                     loss.alpha, loss.gamma, loss.sigma, loss.out[loss.row:].data_ptr(),
+                                                     ws.data_ptr(), ws.numel()))
+
+    def _detect_in_flight(self, images, score_threshold, nms_threshold, md, flags=0, loss=None):
         if images.device.type != "cuda" or images.dim() != 4 or images.shape[3] != 3:
             raise ValueError("images must be a (B,H,W,3) tensor on the GPU")
         if images.dtype not in _SRC_DT:
@@ -876,6 +930,8 @@ class Engine:
             labels = plan["labels"].view(-1)[:B * md].view(B, md)
             self.postprocess(plan["cfg"], plan["regression"], plan["classification"], H, W, boxes, scores, labels, plan["det_ws"],
                              score_threshold, nms_threshold, md, flags)
+            if loss is not None:
+                self.loss_from_boxes(plan, loss)             # its inputs were uploaded in the caller's order, before `fed`
             slot["done"] = torch.cuda.Event()
             slot["done"].record(st)
             if self.trace_in_flight is not None:

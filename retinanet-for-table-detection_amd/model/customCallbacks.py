@@ -1,8 +1,10 @@
 """model/customCallbacks.py of the reference (RedirectModel) and the evaluation callback its training script leaves a slot for
 (RetinaNet.py:149, "Callback : Evaluation"): Evaluate computes AP / P / R / F1 on a validation generator at the end of every epoch,
 on the device (model/eval.py evaluate_generator), and writes them into the epoch's logs, so callbacks that come after it in the
-list (ModelCheckpoint(monitor='mAP')-style) can select by them.  Model.fit_generator calls set_model / on_epoch_begin /
-on_epoch_end in list order."""
+list (ModelCheckpoint(monitor='mAP')-style) can select by them.  Validate does the same in one pass that also yields the validation
+loss (model/eval.py validate_generator): `val_loss` - what the reference's ModelCheckpoint monitors, RetinaNet.py:153-161 - and mAP
+from one forward per group.  Model.fit_generator calls set_model / on_train_begin / on_epoch_begin / on_epoch_end / on_train_end in
+list order; the Keras callbacks of RetinaNet.py's create_callbacks are in model/callbacks.py."""
 from . import eval as _eval
 
 
@@ -92,4 +94,40 @@ class Evaluate:
             if 'weighted_f1' in logs:
                 line += " - weighted_f1: %.4f" % logs['weighted_f1']
             print("Epoch %d evaluation - %s" % (epoch + 1, line))
+        return logs
+
+
+class Validate(Evaluate):
+    """Evaluate plus the validation loss, from ONE pass over the generator at the end of every epoch (validate_generator): besides
+    logs['mAP'] (and logs['weighted_f1'] with more than one threshold) it writes logs['val_loss'], logs['val_regression_loss'] and
+    logs['val_classification_loss'] - Keras' evaluate_generator numbers on the generator's pages without augmentation - so
+    ModelCheckpoint(monitor='val_loss'), EarlyStopping and ReduceLROnPlateau placed after it in the list select by them.
+    Takes Evaluate's arguments and is wrapped by RedirectModel the same way; alpha / gamma / sigma are the losses' parameters
+    (model/losses.py).  `result['image_losses']` lists each page's share of the loss."""
+
+    def __init__(self, generator, iou_thresholds=(0.5,), score_threshold=0.05, max_detections=300, f1_score_threshold=0.5,
+                 weighted_average=False, in_flight=2, verbose=1, evaluate=None, alpha=0.25, gamma=2.0, sigma=3.0):
+        super(Validate, self).__init__(generator, iou_thresholds, score_threshold, max_detections, f1_score_threshold,
+                                       weighted_average, in_flight, verbose, evaluate or self._validate)
+        self.alpha, self.gamma, self.sigma = alpha, gamma, sigma
+
+    def _validate(self, model, generator, **kw):
+        return _eval.validate_generator(model, generator, alpha=self.alpha, gamma=self.gamma, sigma=self.sigma, **kw)
+
+    def on_epoch_end(self, epoch, logs=None):
+        logs = logs if logs is not None else {}
+        verbose, self.verbose = self.verbose, 0
+        try:
+            super(Validate, self).on_epoch_end(epoch, logs)
+        finally:
+            self.verbose = verbose
+        r = self.result
+        logs['val_loss'] = float(r["loss"])
+        logs['val_regression_loss'] = float(r["regression_loss"])
+        logs['val_classification_loss'] = float(r["classification_loss"])
+        if self.verbose:
+            line = "val_loss: %.4f - mAP: %.4f" % (logs['val_loss'], logs['mAP'])
+            if 'weighted_f1' in logs:
+                line += " - weighted_f1: %.4f" % logs['weighted_f1']
+            print("Epoch %d validation - %s" % (epoch + 1, line))
         return logs

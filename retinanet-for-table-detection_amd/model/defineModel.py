@@ -199,22 +199,97 @@ class Model:
                                             lr=getattr(self._compiled, "lr", None))
         return [total, reg, cls]
 
+    @property
+    def optimizer(self):
+        """The compiled optimizer (keras.Model.optimizer): callbacks read and set its `lr`, which every training step picks up."""
+        if self._compiled is None:
+            self._compiled = Adam(lr=1e-4, clipnorm=0.001)
+        return self._compiled
+
+    def _loss_sums(self, x, y):
+        """One forward of the training model and ONE rtn_retina_loss_fwd on its outputs against the dense targets
+        y = [regression_batch (B,N,5), labels_batch (B,N,K+1)]: the device f64 {focal sum, smooth-L1 sum, positives, positives}.
+        The outputs never leave the device."""
+        if self.bbox:
+            raise ValueError("test_on_batch: the training model's outputs are needed (this is the inference model)")
+        x = _rt.dev(x, torch.float32) if not (isinstance(x, np.ndarray) and x.dtype == np.uint8) else _rt.dev(x, torch.uint8)
+        reg, cls = self.engine().forward(x)
+        regt, lab = _rt.dev(y[0], torch.float32), _rt.dev(y[1], torch.float32)
+        B, N, K = cls.shape
+        if tuple(regt.shape) != (B, N, 5) or tuple(lab.shape) != (B, N, K + 1):
+            raise ValueError("targets (%d,%d,5) and (%d,%d,%d) expected, got %s and %s"
+                             % (B, N, B, N, K + 1, tuple(regt.shape), tuple(lab.shape)))
+        h = _rt.handle()
+        wsb = _rt.L.lib.rtn_retina_loss_workspace_bytes(B * N)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=cls.device)
+        sums = torch.zeros(4, dtype=torch.float64, device=cls.device)
+        h.check(_rt.L.lib.rtn_retina_loss_fwd(h.raw, B * N, K, lab.data_ptr(), regt.data_ptr(), cls.data_ptr(), reg.data_ptr(),
+                                              0.25, 2.0, 3.0, sums.data_ptr(), ws.data_ptr(), wsb))     # the functors' defaults
+        return sums
+
+    @staticmethod
+    def _losses_of(s):
+        """[regression_loss, classification_loss] of four sums, as the functors of model/losses.py round them (float32)."""
+        return [float(np.float32(s[1] / max(1.0, s[3]))), float(np.float32(s[0] / max(1.0, s[2])))]
+
+    def test_on_batch(self, x, y):
+        """keras.Model.test_on_batch for the compiled pair of losses: [loss, regression_loss, classification_loss].  Each part has
+        the bits of losses.smooth_l1()(y[0], regression) / losses.focal()(y[1], classification) on the same outputs (one launch
+        computes both halves; the halves do not mix); loss is their sum."""
+        reg, cls = self._losses_of(_rt.host(self._loss_sums(x, y)))
+        return [reg + cls, reg, cls]
+
+    def _test_batches(self, batches):
+        """test_on_batch over an iterable of (x, y) with one read-back for all of them: [(batch size, regression_loss,
+        classification_loss)]."""
+        sizes, sums = [], []
+        for x, y in batches:
+            sums.append(self._loss_sums(x, y))
+            sizes.append(int(y[0].shape[0]))
+        if not sums:
+            return []
+        s = _rt.host(torch.stack(sums))
+        return [(n,) + tuple(self._losses_of(row)) for n, row in zip(sizes, s)]
+
+    def evaluate_generator(self, generator, steps=None, **kwargs):
+        """keras.Model.evaluate_generator: [loss, regression_loss, classification_loss] over `steps` batches of a Sequence
+        (default: all of it), each batch through test_on_batch's path, averaged with the batch sizes as weights (Keras:
+        np.average(outs, weights=batch_sizes))."""
+        n = len(generator) if steps is None else int(steps)
+        per = self._test_batches(generator[j % len(generator)] for j in range(n))
+        if not per:
+            raise ValueError("evaluate_generator: no batches")
+        w = np.asarray([p[0] for p in per], np.float64)
+        reg = float(np.average([p[1] for p in per], weights=w))
+        cls = float(np.average([p[2] for p in per], weights=w))
+        return [reg + cls, reg, cls]
+
     def fit_generator(self, generator, steps_per_epoch=None, epochs=1, verbose=1, callbacks=None, validation_data=None,
                       workers=1, use_multiprocessing=False, max_queue_size=10, shuffle=True, initial_epoch=0, **kwargs):
-        """ RetinaNet.py:280-291: Sequence-style generator (generator[i] -> (inputs, [regression_batch, labels_batch]))."""
+        """ RetinaNet.py:280-291: Sequence-style generator (generator[i] -> (inputs, [regression_batch, labels_batch])).
+        Callbacks (model/callbacks.py, model/customCallbacks.py, or any object with some of the hooks) are called in list order:
+        set_model, on_train_begin, per epoch on_epoch_begin / on_epoch_end(epoch, logs), on_train_end; training stops after the
+        epoch in which one of them sets `stop_training`."""
+        from .callbacks import LearningRateScheduler
         hist = History()
         callbacks = callbacks or []
         steps = steps_per_epoch or len(generator)
         if self._compiled is None:                                # fit without compile(): the defaults _get_trainer would take
             self._compiled = Adam(lr=1e-4, clipnorm=0.001)
+        self.stop_training = False
         for cb in callbacks:
             if hasattr(cb, "set_model"):
                 cb.set_model(self)
+        for cb in callbacks:
+            if hasattr(cb, "on_train_begin"):
+                cb.on_train_begin({})
         for epoch in range(initial_epoch, epochs):
             for cb in callbacks:
                 if hasattr(cb, "on_epoch_begin"):
                     cb.on_epoch_begin(epoch, {})
-                if hasattr(cb, "schedule"):                       # LearningRateScheduler(lr_schedule), RetinaNet.py:47-66
+                # LearningRateScheduler(lr_schedule), RetinaNet.py:47-66: a foreign object with a `.schedule`; the package's own
+                # class has set the rate in its on_epoch_begin already
+                if hasattr(cb, "schedule") and not isinstance(cb, LearningRateScheduler):
                     self._compiled.lr = cb.schedule(epoch)
             sums = np.zeros(3)
             for i in range(steps):
@@ -223,10 +298,8 @@ class Model:
             logs = dict(zip(("loss", "regression_loss", "classification_loss"), (sums / steps).tolist()))
             if validation_data is not None:
                 v = np.zeros(3)
-                for j in range(len(validation_data)):
-                    x, y = validation_data[j]
-                    r, c = self.predict_on_batch(x) if not self.bbox else (None, None)
-                    v += np.array([0.0, float(losses.smooth_l1()(y[0], r)), float(losses.focal()(y[1], c))])
+                for _, reg, cls in self._test_batches(validation_data[j] for j in range(len(validation_data))):
+                    v += np.array([0.0, reg, cls])
                 v /= max(1, len(validation_data))
                 v[0] = v[1] + v[2]
                 logs.update(dict(zip(("val_loss", "val_regression_loss", "val_classification_loss"), v.tolist())))
@@ -239,6 +312,9 @@ class Model:
                     cb.on_epoch_end(epoch, logs)
             if self.stop_training:
                 break
+        for cb in callbacks:
+            if hasattr(cb, "on_train_end"):
+                cb.on_train_end({})
         return hist
 
     # ---- weights

@@ -12,14 +12,19 @@ IoU comes from the device (`rtn_compute_overlap`, the float32 IoU of model/utils
 
 DeviceEvaluator / evaluate_generator run the same evaluation on the device (csrc/rtn_eval.hip) at up to 16 IoU thresholds at once,
 with P/R/F1 at a score threshold, without a host sync per batch: callbacks.Evaluate uses them as a training metric.
+
+validate_generator adds the validation loss to that pass: the forward that produces a batch's detections also feeds
+rtn_retina_loss_boxes_fwd (focal + smooth-L1 per image, straight from the ground-truth boxes), so `val_loss` and mAP come from one
+forward per group and one small copy at the end (customCallbacks.Validate).
 """
+import copy
 import csv
 import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _rt
+from . import Parameters, _rt
 from .utils import compute_overlap, compute_resize_scale
 
 
@@ -260,8 +265,11 @@ class DeviceEvaluator:
                 self._events.append(ev)
         self.num_images += B
 
-    def result(self):
+    def result(self, extra=None):
+        """extra: a float64 device tensor that rides in the same device-to-host copy (validate_generator's per-image loss sums);
+        with it the return value is (result, extra on the host as a NumPy array of extra's shape)."""
         K, T = self.K, self.T
+        extra_host = None
         ap = {t: {c: (0.0, 0) for c in range(K)} for t in self.iou_thresholds}
         f1 = {t: {c: (0, 0, 0, 0.0, 0.0, 0.0) for c in range(K)} for t in self.iou_thresholds}
         if self.num_images:
@@ -276,12 +284,18 @@ class DeviceEvaluator:
             self._h.check(_rt.L.lib.rtn_eval_finalize(self._h.raw, self.num_images, self.S, self.slots.data_ptr(), self.counts.data_ptr(),
                                                       K, T, self.f1_score_threshold, out.data_ptr(), self._ws.data_ptr(),
                                                       self._ws.numel()))
-            r = out.cpu().numpy().reshape(K, T, 8)
+            if extra is not None:
+                both = torch.cat([out, extra.reshape(-1)]).cpu().numpy()
+                r, extra_host = both[:K * T * 8].reshape(K, T, 8), both[K * T * 8:].reshape(tuple(extra.shape))
+            else:
+                r = out.cpu().numpy().reshape(K, T, 8)
             for ti, t in enumerate(self.iou_thresholds):
                 for c in range(K):
                     v = r[c, ti]
                     ap[t][c] = (float(v[0]), int(v[1]))
                     f1[t][c] = (int(v[2]), int(v[3]), int(v[4]), float(v[5]), float(v[6]), float(v[7]))
+        if extra is not None:
+            return summarize(self.iou_thresholds, ap, f1), (extra_host if extra_host is not None else extra.cpu().numpy())
         return summarize(self.iou_thresholds, ap, f1)
 
     def slot_view(self):
@@ -295,10 +309,9 @@ class DeviceEvaluator:
         return raw[..., 0].view(np.float32), mask, cls
 
 
-def _generator_batch(generator, group):
-    """The inputs half of Generator.compute_input_output (csv_generator.py:373-398) without augmentation: the pages of `group`
-    resized into one canvas by the generator's own compute_inputs on its stream, their resize scales, and their annotations in
-    original coordinates (load_annotations_group).  Returns (canvas on the current stream's order, scales, annotations)."""
+def _load_batch(generator, group):
+    """The pages of `group` (device, uint8) and their canvas, built by the generator's own compute_inputs on its stream without
+    augmentation; the canvas is handed over to the current stream.  Returns (canvas, scales, annotations as loaded, pages)."""
     images = generator.load_image_group(group)
     annotations = generator.load_annotations_group(group)
     with generator._lock, torch.cuda.stream(generator._stream):
@@ -311,7 +324,14 @@ def _generator_batch(generator, group):
     cur = torch.cuda.current_stream(generator.device)
     cur.wait_event(done)
     canvas.record_stream(cur)
-    return canvas, scales, annotations
+    return canvas, scales, annotations, pages
+
+
+def _generator_batch(generator, group):
+    """The inputs half of Generator.compute_input_output (csv_generator.py:373-398) without augmentation: the pages of `group`
+    resized into one canvas by the generator's own compute_inputs on its stream, their resize scales, and their annotations in
+    original coordinates (load_annotations_group).  Returns (canvas on the current stream's order, scales, annotations)."""
+    return _load_batch(generator, group)[:3]
 
 
 def evaluate_generator(model, generator, iou_thresholds=(0.5,), score_threshold=0.05, max_detections=300, f1_score_threshold=0.5,
@@ -343,3 +363,89 @@ def evaluate_generator(model, generator, iou_thresholds=(0.5,), score_threshold=
         eng.join()
         eng.in_flight = prev
     return ev.result()
+
+
+def _loss_annotations(generator, group, annotations, pages, scales):
+    """What compute_input_output (csv_generator.py:373-398) hands compute_targets for `group`, without augmentation: the
+    generator's filter_annotations on (a copy of) the loaded annotations, boxes times the resize scale in float64, and each
+    page's own resized (h, w) - in rtn_anchor_targets' layout, on the host."""
+    _, annotations = generator.filter_annotations(pages, [copy.deepcopy(a) for a in annotations], group)
+    B = len(group)
+    gb = np.zeros((B, _rt.L.RTN_MAX_GT, 4), np.float64)
+    gl = np.zeros((B, _rt.L.RTN_MAX_GT), np.int32)
+    gc = np.zeros((B,), np.int32)
+    hw = np.zeros((B, 2), np.int32)
+    for i, (ann, p, s) in enumerate(zip(annotations, pages, scales)):
+        boxes = np.asarray(ann['bboxes'], np.float64).reshape(-1, 4) * s
+        n = boxes.shape[0]
+        if n > _rt.L.RTN_MAX_GT:
+            raise ValueError("at most %d ground-truth boxes per image are supported, got %d" % (_rt.L.RTN_MAX_GT, n))
+        gb[i, :n], gl[i, :n], gc[i] = boxes, np.asarray(ann['labels']).astype(np.int32), n
+        hw[i] = (int(np.rint(p.shape[0] * s)), int(np.rint(p.shape[1] * s)))
+    return gb, gl, gc, hw
+
+
+def combine_losses(image_sums, group_sizes):
+    """Keras' rule for evaluate_generator on per-image sums (n, 4) = {focal, smooth-L1, positives, positives}: per group the
+    loss is sum of the image sums / max(1, sum of positives) (model/losses.py:42,88 on the group's batch), a float32 as the loss
+    tensor and the functors of model/losses.py yield it; across groups the mean weighted by group size
+    (keras/engine/training_generator.py evaluate_generator: np.average(outs, weights=batch_sizes)), float64 on the host.
+    Returns (classification_loss, regression_loss, loss)."""
+    s = np.asarray(image_sums, np.float64).reshape(-1, 4)
+    cls = reg = 0.0
+    lo = 0
+    for n in group_sizes:
+        g = s[lo:lo + n].sum(axis=0)
+        cls += n * float(np.float32(g[0] / max(1.0, g[2])))
+        reg += n * float(np.float32(g[1] / max(1.0, g[3])))
+        lo += n
+    total = float(max(1, sum(group_sizes)))
+    cls, reg = float(cls / total), float(reg / total)
+    return cls, reg, cls + reg
+
+
+def validate_generator(model, generator, iou_thresholds=(0.5,), score_threshold=0.05, max_detections=300, f1_score_threshold=0.5,
+                       in_flight=2, steps=None, alpha=0.25, gamma=2.0, sigma=3.0):
+    """evaluate_generator and the validation loss in ONE pass over the generator's groups: every group runs one forward
+    (Engine.detect with `in_flight` batches at a time); on the stream that ran it the detections are matched (DeviceEvaluator.add,
+    with what evaluate_generator gives it) and rtn_retina_loss_boxes_fwd computes each page's focal and smooth-L1 sums from the
+    page's filtered annotations times its resize scale and its own resized (h, w) - what compute_input_output hands
+    compute_targets - against the anchors of the model's plan.  No dense target tensor exists and nothing is read back per batch.
+    Returns DeviceEvaluator.result() plus
+      classification_loss, regression_loss, loss : combine_losses (the `val_*` numbers Keras' evaluate_generator reports)
+      image_losses : (n, 4) float64 rows (image index, focal sum, smooth-L1 sum, positives), one per page in group order."""
+    if not getattr(model, "bbox", False):
+        raise ValueError("validate_generator: the inference model (retinanet_bbox / convert_model) is needed")
+    eng = model.engine()
+    modes = {"nms": model.nms, "class_specific_filter": model.class_specific_filter}
+    groups = generator.groups if steps is None else generator.groups[:int(steps)]
+    total = sum(len(g) for g in groups)
+    ev = DeviceEvaluator(model.num_classes, iou_thresholds, score_threshold, max_detections, f1_score_threshold,
+                         device=eng.device.index)
+    ev.reserve(total)
+    sums = torch.zeros(max(1, total), 4, dtype=torch.float64, device=eng.device)
+    prev = eng.in_flight
+    eng.join()
+    eng.in_flight = max(1, int(in_flight))
+    row = 0
+    try:
+        for group in groups:
+            canvas, scales, annotations, pages = _load_batch(generator, group)
+            host = _loss_annotations(generator, group, annotations, pages, scales)
+            x = _rt.dev(canvas, torch.float32)
+            gt = [torch.from_numpy(a).pin_memory().to(eng.device, non_blocking=True) for a in host]
+            job = _rt.engine.BoxLoss(gt[0], gt[1], gt[2], gt[3], sums, row, alpha=alpha, gamma=gamma, sigma=sigma,
+                                     negative_overlap=Parameters.negative_overlap, positive_overlap=Parameters.positive_overlap)
+            boxes, scores, labels = eng.detect(x, loss=job, **modes)
+            st = eng.slot_stream(eng.last_slot) if eng.in_flight > 1 and not eng.training else None
+            ev.add(boxes, scores, labels, scales, annotations, stream=st)
+            row += len(group)
+    finally:
+        eng.join()
+        eng.in_flight = prev
+    result, s = ev.result(extra=sums[:total])                 # the pass's one small copy: the evaluator's numbers and the sums
+    cls, reg, loss = combine_losses(s, [len(g) for g in groups])
+    index = np.asarray([i for g in groups for i in g], np.float64).reshape(-1, 1)
+    result.update({"classification_loss": cls, "regression_loss": reg, "loss": loss,
+                   "image_losses": np.concatenate([index, s[:, :3]], axis=1) if total else np.zeros((0, 4))})
+    return result
