@@ -97,12 +97,15 @@ def dy_layout(d_f, crun, cells_total=None):
     return out
 
 
-def wgrad_desc(d_f, dys, crun, layout):
-    """Weight-gradient descriptor: the forward geometry with `out` re-pointed at dY."""
+def wgrad_desc(d_f, dys, crun, layout, rows=None):
+    """Weight-gradient descriptor: the forward geometry with `out` re-pointed at dY.  rows: the rows of the layer's dW."""
     dw = L.ConvDesc()
     C.memmove(C.byref(dw), C.byref(d_f), C.sizeof(L.ConvDesc))
     dw.flags, dw.w, dw.bias = 0, None, None
-    dw.N = dw.out_ld = crun
+    # dY is `crun` columns wide; the head outputs pad it to a power of two that can exceed dW's ceil128(cout) rows (270 -> 512 of 384):
+    # the columns behind the last row of dW are padding, so the launch leaves them out
+    dw.out_ld = crun
+    dw.N = crun if rows is None else min(crun, rows)
     for gi, (dy, (img_stride, off)) in enumerate(zip(dys, layout)):
         g = dw.g[gi]
         g.out, g.out_elems = dy.data_ptr(), dy.numel()
@@ -214,7 +217,7 @@ class Emit:
         layout = dy_layout(d_f, crun, self.cells_total if name in Engine.TOWERS else None)
         if tr._is_trainable(name):
             dW, db = tr.grad_views(name)
-            bops.append(O.Wgrad("wgrad", wgrad_desc(d_f, dys, crun, layout), dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
+            bops.append(O.Wgrad("wgrad", wgrad_desc(d_f, dys, crun, layout, dW.shape[0]), dW, name, db if lo["has_bias"] else None, lo["cout"]))     # bias gradient fused
         for r, dy in zip(me["res"], dys):                # residual inputs of the forward epilogue
             if r is None or id(r) not in need:
                 continue

@@ -282,6 +282,35 @@ class DgradCase(Case):
         self.masks = [self.act] if "mask" in mode else []
 
 
+class HeadDgradCase(Case):
+    """rtn_pack_dgrad_weights + ONE grouped rtn_conv2d_dgrad of a head-output layer (3x3 'same', cin -> cout) over the pyramid levels:
+    the integer dY of every level lies in the concatenated [B][cells of all levels][cp] tensor, cout columns of it and zeros up to
+    cp (what rtn_pad_cast_rows leaves there), and the launch runs at Crun = cp.  Modes, bias and `other` as in DgradCase; the levels'
+    dX are compared as one tensor [B][cells][cin] (the 1 x 1 level alone is too small for the rounding shares)."""
+
+    def __init__(self, levels, cin, cout, cp, mode, B=2, seed=0):
+        self.levels_hw, self.cin, self.cout, self.cp, self.mode, self.B, self.k = levels, cin, cout, cp, mode, B, 3
+        g = torch.Generator().manual_seed(seed)
+        self.w = ints(g, -2, 2, 3, 3, cin, cout)
+        self.bias = None if "res" in mode else ints(g, -BIAS, BIAS, cin)
+        self.dy, self.other, self.act, pres, bounds = [], [], [], [], []
+        for H, W in levels:
+            dy = ints(g, -3, 3, B, H, W, cout)
+            other = bf16(ints(g, -BIAS, BIAS, B, H, W, cin))
+            act = mask_tensor(g, B, H, W, cin)
+            dx = ref_conv_transpose(dy, self.w, 1, 1, 1, H, W)
+            bound = ref_conv_transpose(dy.abs(), self.w.abs(), 1, 1, 1, H, W)
+            if self.bias is not None:
+                dx, bound = dx + self.bias, bound + self.bias.abs()
+            pre = epilogue(dx, other, act > 0, "res" in mode, "pre" if "pre" in mode else ("post" if "mask" in mode else None), False)
+            if "res" in mode:
+                bound = bound + other.abs()
+            self.dy.append(dy); self.other.append(other); self.act.append(act)
+            pres.append(pre.reshape(B, H * W, cin)); bounds.append(bound.reshape(B, H * W, cin))
+        self.stages = [Stage("dx", torch.cat(pres, 1), torch.cat(bounds, 1), False, "bf16")]
+        self.masks = list(self.act) if "mask" in mode else []
+
+
 class BottleneckCase(Case):
     """rtn_bottleneck64_fwd, identity (proj = False) or projection-shortcut form: ReLU-like inputs in [0, 3], 3x3 filters in [-2, 2],
     ternary 1x1 filters; h1, x_out and a_out are rounded to bf16 exactly where the header says (h1 and x_out before they are
@@ -498,6 +527,12 @@ for _relu in (0, 1):
     _add("fp8out/3x3/relu%d" % _relu, _fwd(levels=LEVELS2, cin=256, cout=136, k=3, out="e4m3", relu=bool(_relu), seed=114, out_scale=0.25))
 for _out in ("f32", "bf16"):
     _add("head/%s" % _out, _fwd(levels=HEAD_LEVELS, cin=256, cout=36, k=3, out=_out, concat=True, seed=61))
+HEAD_COUTS = (27, 54, 72, 180, 270)       # K * 9 anchors for K = 3, 6, 8, 20, 30: up to 48 (generation 6), one 64 / 128 / 256 tile, two N tiles
+for _cout in HEAD_COUTS:
+    for _out in ("f32", "bf16"):
+        _add("head%d/%s" % (_cout, _out), _fwd(levels=HEAD_LEVELS, cin=256, cout=_cout, k=3, out=_out, concat=True, seed=62))
+# the head outputs' data gradient: the forward layer is 3x3 256 -> cout, dY lies in the concatenated tensor padded to cp columns
+HEAD_DGRAD = ((54, 64), (72, 128), (180, 256), (270, 512))
 for _mode in ("res", "mask", "res+mask_pre"):
     _add("dgrad/3x3-64-256/%s" % _mode, functools.partial(DgradCase, 9, 13, 64, 256, 3, 1, "same", _mode, seed=71))
     _add("dgrad/3x3-256-64/%s" % _mode, functools.partial(DgradCase, 9, 13, 256, 64, 3, 1, "same", _mode, seed=72))
@@ -505,6 +540,8 @@ for _mode in ("res", "mask", "res+mask_pre"):
     _add("dgrad/1x1s2-even/%s" % _mode, functools.partial(DgradCase, 10, 14, 256, 128, 1, 2, 0, _mode, seed=74))
     _add("dgrad/3x3s2/%s" % _mode, functools.partial(DgradCase, 9, 13, 256, 128, 3, 2, "same", _mode, seed=75))        # 2 Ho - 1 = H: every generation
     _add("dgrad/3x3s2-even/%s" % _mode, functools.partial(DgradCase, 10, 12, 256, 128, 3, 2, "same", _mode, seed=76))  # asymmetric pad
+    for _cout, _cp in HEAD_DGRAD:
+        _add("dgrad/head%d-%d/%s" % (_cout, _cp, _mode), functools.partial(HeadDgradCase, HEAD_LEVELS, 256, _cout, _cp, _mode, seed=77))
 for _proj in (False, True):
     for _shape in ((2, 9, 13), (1, 1, 1), (3, 5, 4), (2, 41, 67)):
         _add("bneck/%s/%dx%dx%d" % ("proj" if _proj else "id", *_shape), functools.partial(BottleneckCase, *_shape, proj=_proj, seed=81))

@@ -112,10 +112,11 @@ def test_dgrad_group_stride2_3x3_reads_the_zero_inserted_dy():
     assert (g.out_step, g.out_pix_w) == (0, 0)
 
 
-def _two_level_head(L):
+def _two_level_head(L, cout=36, rows=0):
     """Forward descriptor of a head output conv over two pyramid levels, 5 x 7 and 3 x 4 cells: 47 cells per image."""
     d = L.ConvDesc()
-    d.ngroups, d.KH, d.KW, d.N, d.out_ld, d.flags = 2, 3, 3, 36, 36, L.CONV_RELU
+    d.ngroups, d.KH, d.KW, d.N, d.out_ld, d.flags = 2, 3, 3, cout, cout, L.CONV_RELU
+    d.w_rows = rows
     (d.g[0].Hout, d.g[0].Wout), (d.g[1].Hout, d.g[1].Wout) = (5, 7), (3, 4)
     return d
 
@@ -148,6 +149,20 @@ def test_wgrad_desc_is_the_forward_descriptor_pointed_at_dy():
         assert (g.out, g.out_elems, g.out_img_stride, g.out_off) == (dyp.data_ptr(), 2 * 47 * 64, 47 * 64, off)
         assert (g.res, g.res_elems) == (None, 0)
     assert (d_f.flags, d_f.N, d_f.g[0].res) == (L.CONV_RELU, 36, x0.data_ptr())          # the forward descriptor is a copy's source only
+
+
+@pytest.mark.parametrize("cout,crun,n", [(36, 64, 64), (72, 128, 128), (180, 256, 256), (270, 512, 384), (522, 1024, 640)])
+def test_wgrad_desc_never_runs_past_the_rows_of_dw(cout, crun, n):
+    """dY of a head output is padded to a power of two (Trainer._dy_channels), dW has ceil128(cout) rows: from 29 classes on (261
+    channels: 512 columns, 384 rows) the padded width exceeds the rows, and the launch covers the columns that have a row - the rest
+    are padding of dY.  rtn_conv2d_wgrad refuses N > w_rows."""
+    BP, O, L = _mods()
+    rows = -(-cout // 128) * 128                           # the engine's filters and dW: rows padded to a multiple of 128
+    d_f = _two_level_head(L, cout, rows)
+    dyp = torch.zeros(2, 47, crun, dtype=torch.bfloat16)
+    dw = BP.wgrad_desc(d_f, [dyp, dyp], crun, BP.dy_layout(d_f, crun, cells_total=47), rows)
+    assert (dw.N, dw.out_ld, dw.w_rows) == (n, crun, rows) and cout <= dw.N <= dw.w_rows
+    assert (dw.g[1].out_img_stride, dw.g[1].out_off) == (47 * crun, 35 * crun)
 
 
 @pytest.mark.parametrize("pre_mask,prod_relu", [(False, False), (True, False), (False, True)])

@@ -336,6 +336,11 @@ def test_wgrad_window_kernel(pkg, handle, monkeypatch, levels, cin, cout, B, bia
     ([(7, 250)], 64, 128, 1, False),
     ([(40, 334)], 64, 64, 2, False),
     ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, 64, 4, True),
+    # head outputs of 8, 20 and 30 classes, (cout, cp): dY has cout columns and zeros up to cp, the width Trainer._dy_channels pads to;
+    # dW has ceil128(cout) rows, so the launch runs on N = min(cp, ceil128(cout)) of the cp columns (270: 384 of 512)
+    ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, (72, 128), 4, True),
+    ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, (180, 256), 4, True),
+    ([(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)], 256, (270, 512), 4, True),
 ])
 def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypatch, levels, cin, cout, B, concat):
     """x and dY are integers in [-2, 2] stored as bf16: every product and every partial sum is an integer below 2^24, so dW and db
@@ -345,12 +350,15 @@ def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypat
     L = pkg._lib
     tdt, code = DT["bf16"]
     total = sum(H * W for H, W in levels)
+    real, cout = cout if isinstance(cout, tuple) else (cout, cout)         # real columns of dY, its padded width
+    rows = -(-real // 128) * 128 if real != cout else cout                 # rows of dW: the forward weights' ceil128(cout)
+    nrun = min(cout, rows)
     dyfull = torch.zeros(B, total, cout, dtype=tdt, device=DEV) if concat else None
     g = torch.Generator().manual_seed(1300 + cin + cout)
-    w = torch.zeros(3, 3, cin, cout, dtype=torch.float64, requires_grad=True)
+    w = torch.zeros(3, 3, cin, nrun, dtype=torch.float64, requires_grad=True)
     d = L.ConvDesc()
     d.ngroups, d.batch, d.dtype = len(levels), B, code
-    d.w_rows, d.N, d.KH, d.KW = cout, cout, 3, 3
+    d.w_rows, d.N, d.KH, d.KW = rows, nrun, 3, 3
     d.Crun = d.pix_stride = cin
     d.sy = d.sx = 1
     d.pad_t = d.pad_l = 1
@@ -359,8 +367,9 @@ def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypat
     for gi, (H, W) in enumerate(levels):
         x = torch.randint(-2, 3, (B, H, W, cin), generator=g).double()
         dy = torch.randint(-2, 3, (B, H, W, cout), generator=g).double()
-        want = want + torch.autograd.grad(fwd_ref(x, w, 1, 1, 1, H, W), w, dy)[0]
-        wantb = wantb + dy.sum(dim=(0, 1, 2))
+        dy[..., real:] = 0
+        want = want + torch.autograd.grad(fwd_ref(x, w, 1, 1, 1, H, W), w, dy[..., :nrun])[0]
+        wantb = wantb + dy[..., :nrun].sum(dim=(0, 1, 2))
         xd, dyd = x.to(tdt).to(DEV).contiguous(), dy.to(tdt).to(DEV).contiguous()
         keep += [xd, dyd]
         grp = L.ConvGroup()
@@ -375,10 +384,12 @@ def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypat
             grp.out, grp.out_elems, grp.out_img_stride = dyd.data_ptr(), dyd.numel(), H * W * cout
         d.g[gi] = grp
         tiles += -(-B * H * W // 64)
-    wantm = want.permute(3, 0, 1, 2).reshape(cout, -1)
+    wantm = torch.zeros(rows, 9 * cin, dtype=torch.float64)
+    wantm[:nrun] = want.permute(3, 0, 1, 2).reshape(nrun, -1)
     assert float(wantm.abs().max()) < 2 ** 24 and float(wantm.abs().max()) > 64
-    wantm, wantb = wantm.float(), wantb.float()
-    big = cout > 128                                       # the 256 x 256 LDS-DMA kernel needs more than 128 filters (K = 9 cin >= 256 here)
+    assert not bool(wantm[real:].any()) and bool(wantm[:real].any(dim=1).all())      # exact zeros in rows cout .. ceil128(cout), none above
+    wantm, wantb = wantm.float(), wantb[:real].float()
+    big = nrun > 128                                       # the 256 x 256 LDS-DMA kernel needs more than 128 filters (K = 9 cin >= 256 here)
     runs = [({"RTN_WGRAD_WIN": "1"}, 4)]
     for dma, impl in ((None, 2 if (big and tiles >= 2048) else 3), ("2", 2 if big else 3), ("0", 0)):
         for blocks in (None, "64", "1024"):
@@ -396,12 +407,13 @@ def test_wgrad_of_small_integers_is_exact_on_every_kernel(pkg, handle, monkeypat
                 monkeypatch.delenv(k, raising=False)
         wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(d))
         ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-        dW = torch.full((cout, 9 * cin), 3.0, dtype=torch.float32, device=DEV)
-        db = torch.full((cout,), 5.0, dtype=torch.float32, device=DEV)
-        handle.check(L.lib.rtn_conv2d_wgrad_bias(handle.raw, C.byref(d), dW.data_ptr(), db.data_ptr(), cout, ws.data_ptr(), wsb))
+        dW = torch.full((rows + 1, 9 * cin), 3.0, dtype=torch.float32, device=DEV)        # one row more than dW has: it keeps its 3.0
+        db = torch.full((rows,), 5.0, dtype=torch.float32, device=DEV)
+        handle.check(L.lib.rtn_conv2d_wgrad_bias(handle.raw, C.byref(d), dW.data_ptr(), db.data_ptr(), real, ws.data_ptr(), wsb))
         torch.cuda.synchronize()
         assert L.lib.rtn_debug_last_wgrad_impl(handle.raw) == impl, (env, L.lib.rtn_debug_last_wgrad_impl(handle.raw), impl)
-        gw, gb = dW.cpu() - 3.0, db.cpu() - 5.0
+        assert torch.all(dW[rows] == 3.0) and torch.all(db[real:] == 5.0)
+        gw, gb = dW.cpu()[:rows] - 3.0, db.cpu()[:real] - 5.0
         assert torch.equal(gw, wantm), "%s: dW differs at %d entries, by up to %g" % (env, int((gw != wantm).sum()), float((gw - wantm).abs().max()))
         assert torch.equal(gb, wantb), "%s: db differs by up to %g" % (env, float((gb - wantb).abs().max()))
 
@@ -510,9 +522,23 @@ def test_wgrad_rowinfo_then_prepared_equals_the_one_call_form(pkg, handle, monke
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
 def test_wgrad_grouped_levels_and_padded_head_output(pkg, handle, dtype):
     """Shared head weights: one wgrad launch over five pyramid levels; dY of the 36-channel output padded to 64."""
+    padded_head_wgrad(pkg, handle, dtype, 36, 64)
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+@pytest.mark.parametrize("cout,cp", [(72, 128), (180, 256), (270, 512)])
+def test_wgrad_padded_head_output_at_many_classes(pkg, handle, dtype, cout, cp):
+    """... and of the 72-, 180- and 270-channel outputs (8, 20, 30 classes) padded to 128, 256 and 512: dW has ceil128(cout) rows, the
+    launch runs on min(cp, ceil128(cout)) columns of dY, and rows cout .. ceil128(cout) stay exact zeros."""
+    padded_head_wgrad(pkg, handle, dtype, cout, cp)
+
+
+def padded_head_wgrad(pkg, handle, dtype, cout, cp):
     L = pkg._lib
     tdt, code = DT[dtype]
-    B, cin, cout, cp = 2, 256, 36, 64
+    B, cin = 2, 256
+    rows = -(-cout // 128) * 128
+    nrun = min(cp, rows)
     levels = [(16, 24), (8, 12), (4, 6), (2, 3), (1, 2)]
     g = torch.Generator().manual_seed(7)
     w = q(torch.randn(3, 3, cin, cout, generator=g, dtype=torch.float64) / 48, dtype).requires_grad_(True)
@@ -523,7 +549,7 @@ def test_wgrad_grouped_levels_and_padded_head_output(pkg, handle, dtype):
     handle.check(L.lib.rtn_pad_cast_rows(handle.raw, dy32d.data_ptr(), dyp.data_ptr(), code, B * total_cells, cout, cp))
     d = L.ConvDesc()
     d.ngroups, d.batch, d.dtype = len(levels), B, code
-    d.w_rows, d.N, d.KH, d.KW = 128, cp, 3, 3
+    d.w_rows, d.N, d.KH, d.KW = rows, nrun, 3, 3
     d.Crun = d.pix_stride = cin
     d.sy = d.sx = 1
     d.pad_t = d.pad_l = 1
@@ -546,13 +572,16 @@ def test_wgrad_grouped_levels_and_padded_head_output(pkg, handle, dtype):
         off += H * W
     wsb = L.lib.rtn_conv2d_wgrad_workspace_bytes(C.byref(d))
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
-    dW = torch.zeros(128, 9 * cin, dtype=torch.float32, device=DEV)
+    dW = torch.zeros(rows + 1, 9 * cin, dtype=torch.float32, device=DEV)
+    dW[rows] = 3.0                                                              # behind dW's last row
     handle.check(L.lib.rtn_conv2d_wgrad(handle.raw, C.byref(d), dW.data_ptr(), ws.data_ptr(), wsb))
     torch.cuda.synchronize()
     wantm = want.permute(3, 0, 1, 2).reshape(cout, -1)
     got = dW.cpu().double()
+    print("padded head wgrad %s cout %d cp %d N %d: kernel %d, err %.3e of %.3e" % (dtype, cout, cp, nrun, L.lib.rtn_debug_last_wgrad_impl(handle.raw),
+          float((got[:cout] - wantm).abs().max()), tol(dtype) * max(1.0, float(wantm.abs().max()))))
     assert float((got[:cout] - wantm).abs().max()) <= tol(dtype) * max(1.0, float(wantm.abs().max()))
-    assert torch.all(got[cout:] == 0)
+    assert torch.all(got[cout:rows] == 0) and torch.all(got[rows] == 3.0)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])

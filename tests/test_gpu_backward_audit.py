@@ -20,7 +20,12 @@ checks the stem's recorded pool taps against it and routes pool1's gradient by t
 
 Rows (ResNet-50, K = 1, tame weights, cls_bias -2; every page 1-3 boxes, the last one none):
     bf16 2x320x448 default | RTN_CONV_IMPL=4 RTN_WGRAD_WIN=1 | RTN_CONV_IMPL=5 RTN_WGRAD_DMA=2 ; bf16 3x146x210 ; f32 3x146x210.
-Over the five rows together the data-gradient kernels {1, 2, 4, 5} and the weight-gradient kernels {0, 2, 3, 4} must each have run.
+Rows at other head widths and another backbone (2x146x210, ten boxes on the first page with labels in [0, K), every class below 8 and
+class K - 1 with a positive anchor - asserted on the CPU before the step):
+    bf16 K = 8 (72 classification channels, dY padded to 128) | bf16 K = 30 (270 channels, 384 weight rows, dY padded to 512: the weight
+    gradient runs on 384 of the 512 columns) | f32 K = 20 (180, 256 rows, 256 columns) | bf16 ResNet-101, K = 1 (122 layers).
+Each row asserts the classification output's weight rows, the padded width of its dY and the kernels its two gradients ran on.
+Over the first five rows together the data-gradient kernels {1, 2, 4, 5} and the weight-gradient kernels {0, 2, 3, 4} must each have run.
 No launch returned an error under the forced knobs in the training forward (a launch that did would be dropped from the row and
 reported here).  Run with -s for the per-tensor table.
 
@@ -31,9 +36,14 @@ MEASURED on the MI355X (worst err / bound per check kind, seconds per row):
     bf16_2x320x448_gen5_dma2   0.003   0.215   0.017   0.996   0.9
     bf16_3x146x210             0.003   0.173   0.011   0.996   0.9
     f32_3x146x210              0.003   0.309   0.073   0.125   0.9
+    bf16_2x146x210_K8          0.003   0.230   0.018   0.996   1.0
+    bf16_2x146x210_K30         0.003   0.235   0.015   0.996   1.0
+    f32_2x146x210_K20          0.003   0.305   0.066   0.130   0.9
+    bf16_2x146x210_r101        0.004   0.218   0.013   0.996   1.2
 (act 0.99 in bf16 is the output rounding itself: half an ulp of a value just above a power of two is 2^-8 of it.)  Kernels that ran:
-data gradients {1, 2, 4} | {2, 3, 4} | {2, 5} | {1, 2} | {1, 2}, weight gradients {3} | {3, 4} | {2, 3} | {3} | {0}; in the fused-stem rows
-71-72 % of the live pool windows have a single possible winner.  The module takes 8 s.  With the plan's MASK_PRE choice forced on
+data gradients {1, 2, 4} | {2, 3, 4} | {2, 5} | {1, 2} | {1, 2}, weight gradients {3} | {3, 4} | {2, 3} | {3} | {0}; in the four new rows
+data gradients {1, 2}, weight gradients {3} (f32: {0}), the classification output's own on generation 2 and kernel 3 (f32: 0).  In the
+fused-stem rows 71-72 % of the live pool windows have a single possible winner.  The module takes 12 s.  With the plan's MASK_PRE choice forced on
 (the identity gradient left unmasked) the audit fails at res2a_branch2c with 445110 elements out of bound."""
 import importlib
 import os
@@ -55,8 +65,16 @@ ROWS = {
     "bf16_2x320x448_gen5_dma2": ("bf16", 2, (320, 448), {"RTN_CONV_IMPL": "5", "RTN_WGRAD_DMA": "2"}),
     "bf16_3x146x210": ("bf16", 3, (146, 210), {}),
     "f32_3x146x210": ("f32", 3, (146, 210), {}),
+    # (..., backbone, classes): 72, 270 and 180 classification channels, dY padded to 128, 512 and 256; ResNet-101
+    "bf16_2x146x210_K8": ("bf16", 2, (146, 210), {}, "resnet50", 8),
+    "bf16_2x146x210_K30": ("bf16", 2, (146, 210), {}, "resnet50", 30),
+    "f32_2x146x210_K20": ("f32", 2, (146, 210), {}, "resnet50", 20),
+    "bf16_2x146x210_r101": ("bf16", 2, (146, 210), {}, "resnet101", 1),
 }
-STAGE_BLOCKS = (3, 4, 6, 3)                     # ResNet-50: res2a-c, res3a-d, res4a-f, res5a-c
+FIRST_ROWS = list(ROWS)[:5]
+# keras_resnet: blocks per stage, and the stages whose blocks are named a, b1, b2, ... instead of a, b, c, ...
+STAGE_BLOCKS = {"resnet50": (3, 4, 6, 3), "resnet101": (3, 4, 23, 3), "resnet152": (3, 8, 36, 3)}
+NUMERICAL = {"resnet50": (), "resnet101": (1, 2), "resnet152": (1, 2)}
 TOWERS = ("pyramid_regression", "pyramid_classification")
 
 
@@ -64,8 +82,17 @@ def mods(pkg):
     return [importlib.import_module(pkg.__name__ + "." + m) for m in ("engine", "weights", "trainer")]
 
 
-def make_batch(B, canvas, seed):
-    """Pages and NumPy-oracle targets as in test_gpu_train.py: 1-3 boxes per page, none on the last page."""
+def row_config(row):
+    """(dtype, B, canvas, env, backbone, K) of a row."""
+    r = ROWS[row]
+    return r + ("resnet50", 1) if len(r) == 4 else r
+
+
+def make_batch(B, canvas, seed, K=1):
+    """Pages and NumPy-oracle targets as in test_gpu_train.py: 1-3 boxes per page, none on the last page.
+    K > 1: min(K, 8) + 2 boxes on every other page with random labels in [0, K), the first min(K, 8) of them a permutation of the
+    first classes and one more of class K - 1; checked here, on the CPU: every class in [0, min(K, 8)) and the last class have a
+    positive anchor, the last page has none."""
     g = torch.Generator().manual_seed(seed)
     raw = torch.clamp(torch.empty(B, canvas[0], canvas[1], 3).exponential_(1 / 12.0, generator=g) *
                       torch.rand(B, canvas[0], canvas[1], 3, generator=g), 0, 255).round().to(torch.uint8)
@@ -74,13 +101,26 @@ def make_batch(B, canvas, seed):
     rng = np.random.RandomState(seed)
     gts, shapes = [], []
     for b in range(B):
-        n = 0 if b == B - 1 else rng.randint(1, 4)
-        w, h = rng.uniform(30, 120, n), rng.uniform(25, 90, n)
+        n = 0 if b == B - 1 else (rng.randint(1, 4) if K == 1 else min(K, 8) + 2)
+        w, h = (rng.uniform(30, 120, n), rng.uniform(25, 90, n)) if K == 1 else (rng.uniform(24, 70, n), rng.uniform(20, 60, n))
         x1, y1 = rng.uniform(0, canvas[1] - w), rng.uniform(0, canvas[0] - h)
         gts.append(np.stack([x1, y1, x1 + w, y1 + h], axis=1).reshape(-1, 4))
         shapes.append((canvas[0], int(rng.randint(150, canvas[1] + 1))))
-    reg, lab = R.anchor_targets(anchors, shapes, gts, [np.zeros(len(g_)) for g_ in gts], 1)
-    assert (lab[..., 1] == 1).sum() > 10 and (lab[-1, :, 1] == 1).sum() == 0
+    if K == 1:
+        classes = [np.zeros(len(g_)) for g_ in gts]
+    else:
+        classes = []
+        for g_ in gts:
+            c = rng.randint(0, K, len(g_))
+            if len(g_):
+                c[:min(K, 8)] = rng.permutation(min(K, 8))
+                c[min(K, 8)] = K - 1
+            classes.append(c.astype(np.float64))
+    reg, lab = R.anchor_targets(anchors, shapes, gts, classes, K)
+    assert lab.shape[-1] == K + 1
+    assert (lab[..., K] == 1).sum() > 10 and (lab[-1, :, K] == 1).sum() == 0
+    per_class = ((lab[..., :K] == 1) & (lab[..., K:] == 1)).sum(axis=(0, 1))
+    assert np.all(per_class[:min(K, 8)] > 0) and per_class[K - 1] > 0, per_class
     return x, reg, lab
 
 
@@ -109,7 +149,7 @@ def geo(name):
     raise KeyError(name)
 
 
-def graph():
+def graph(backbone="resnet50"):
     """inputs: layer -> the activation key of every group's input; cons: activation key -> its consumers.  Keys: (layer, group) for a
     conv output, "pool1", "image".  Consumers: ("conv", layer, group, premask) - premask: the conv reads relu(T), not T;
     ("add", key): T is added into `key` as is; ("up", key): UpsampleLike(T) is added into `key`; ("pool", key)."""
@@ -125,9 +165,9 @@ def graph():
     cons.setdefault(c1, []).append(("pool", "pool1"))
     x = "pool1"
     feats = []
-    for stage, nblocks in enumerate(STAGE_BLOCKS):
+    for stage, nblocks in enumerate(STAGE_BLOCKS[backbone]):
         for block in range(nblocks):
-            blk = "res%d%s" % (stage + 2, "abcdef"[block])
+            blk = "res%d%s" % (stage + 2, "b%d" % block if (block and stage in NUMERICAL[backbone]) else "abcdef"[block])
             a, = conv(blk + "_branch2a", [x])
             b2, = conv(blk + "_branch2b", [a])
             y, = conv(blk + "_branch2c", [b2])
@@ -161,7 +201,7 @@ class BackwardAudit:
         self.tr, self.eng, self.bp, self.plan, self.tag, self.dtype = tr, eng, bp, bp["plan"], tag, eng.dtype
         self.state = state
         self.layers = {l[0]: l for l in Wt.conv_layers(eng.backbone, eng.K, eng.A)}
-        self.inputs, self.cons = graph()
+        self.inputs, self.cons = graph(eng.backbone)
         assert set(self.inputs) == set(self.layers), set(self.inputs) ^ set(self.layers)
         plan = self.plan
         self.convs = {op[2]: op[3] for op in plan["ops"] if op[0] == "conv"}
@@ -365,15 +405,17 @@ class BackwardAudit:
 
 
 def run_row(pkg, row):
-    dtype, B, canvas, env = ROWS[row]
+    dtype, B, canvas, env, backbone, K = row_config(row)
     E, Wt, T = mods(pkg)
     old = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     t0 = time.time()
     try:
-        state = Wt.init_state("resnet50", 1, 9, seed=0, randomize_bn=True, cls_bias=-2.0, tame=True)
-        x, reg_t, lab_t = make_batch(B, canvas, seed=11)
-        eng = E.Engine("resnet50", 1, 9, dtype=dtype)
+        # with its CPU checks, before anything runs on the device.  K > 1, seed 13: the first seed from 11 on at which every one of the
+        # ten overlapping boxes of the 146 x 210 page keeps a positive anchor of its own
+        x, reg_t, lab_t = make_batch(B, canvas, seed=11 if K == 1 else 13, K=K)
+        state = Wt.init_state(backbone, K, 9, seed=0, randomize_bn=True, cls_bias=-2.0, tame=True)
+        eng = E.Engine(backbone, K, 9, dtype=dtype)
         eng.load_state(state)
         tr = T.Trainer(eng, lr=1e-4, clipnorm=0.001)
         assert tr.wgrad_lane, "the audit is of the real lane schedule"
@@ -407,7 +449,11 @@ def run_row(pkg, row):
     dt = time.time() - t0
     print("%s: %d layers, %d gradients audited; worst err/bound %s; dgrad kernels %s, wgrad kernels %s; %.1f s" % (
         row, len(names), len(ids), ", ".join("%s %.3f" % kv for kv in sorted(worst.items())), impls["dgrad"], impls["wgrad"], dt))
-    return {"impls": impls, "worst": worst, "seconds": dt,
+    cls = TOWERS[1]
+    head = {"cout": eng.layout[cls]["cout"], "rows": eng.layout[cls]["rows"], "crun": tr._dy_channels(cls), "dy_shape": tuple(bp["dyp_cls"].shape),
+            "dgrad": tr.impls.get(("dgrad", cls)), "wgrad": tr.impls.get(("wgrad", cls))}
+    print("%s: %s %s" % (row, cls, head))
+    return {"impls": impls, "worst": worst, "seconds": dt, "head": head,
             "per_layer": {k: Counter(v for (kk, _), v in tr.impls.items() if kk == k) for k in ("dgrad", "wgrad")}}
 
 
@@ -428,6 +474,13 @@ def test_backward_audit(pkg, handle, rows_done, row):
     if "RTN_CONV_IMPL" in ROWS[row][3]:
         want = int(ROWS[row][3]["RTN_CONV_IMPL"])
         assert want in res["impls"]["dgrad"], "generation %d ran no data gradient: %s" % (want, res["per_layer"]["dgrad"])
+    dtype, K, head = row_config(row)[0], row_config(row)[5], res["head"]
+    cout = 9 * K                                            # the classification output: weight rows, the padded width of its dY, its kernels
+    assert head["cout"] == cout and head["rows"] == -(-cout // 128) * 128
+    assert head["crun"] == max(64, 1 << (cout - 1).bit_length()) and head["dy_shape"][2] == head["crun"]
+    # its data gradient is a grouped 3x3 launch with N = 256: the per-tap kernel, or generation 4 where the grid fills the chip (or is forced);
+    # its weight gradient: the register-staged kernel in f32, an LDS-DMA or the window kernel in bf16
+    assert head["dgrad"] in (2, 4) and head["wgrad"] in ((0,) if dtype == "f32" else (2, 3, 4)), head
 
 
 def test_every_backward_kernel_family_ran(pkg, handle, rows_done):
@@ -435,11 +488,11 @@ def test_every_backward_kernel_family_ran(pkg, handle, rows_done):
     LDS-DMA), 3 (128 x 128 LDS-DMA) and 4 (window) each on at least one layer."""
     t0 = time.time()
     d, w = set(), set()
-    for row in ROWS:
+    for row in FIRST_ROWS:
         res = row_result(pkg, rows_done, row)
         d |= set(res["impls"]["dgrad"])
         w |= set(res["impls"]["wgrad"])
     assert {1, 2, 4, 5} <= d, d
     assert {0, 2, 3, 4} <= w, w
     print("backward audit: %.1f s over the five rows (%.1f s spent in this test)" % (
-        sum(r["seconds"] for r in rows_done.values()), time.time() - t0))
+        sum(rows_done[r]["seconds"] for r in FIRST_ROWS), time.time() - t0))

@@ -10,6 +10,10 @@ case used here has sums below 2^24, exercises the final rounding (>= 5 % of each
 What stays on a tolerance elsewhere: the sigmoid head (exp is not exact; tests/test_gpu_conv.py) and every random-operand test, the
 check on realistic magnitudes.
 
+The head outputs at 27, 54, 72, 180 and 270 channels (3 to 30 classes) run under the default dispatch and every forced generation and
+tile width, in the engine's dense layout and with pad columns and gap rows that must keep their fill; their data gradient reads the
+padded concatenated dY at Crun = 64 ... 512, and rtn_pad_cast_rows is compared alone.
+
 The module runs in a few seconds, so no knob combination of the matrix is cut.  K slices (RTN_CONV_H8_KSPLIT=3) exist only for the
 full-width single-level layer without residual or mask, so they have a test of their own at (12, 11); every other generation-4 case
 pins RTN_CONV_H8_KSPLIT=1."""
@@ -44,9 +48,11 @@ def assert_equal(got, want, what):
                                                        float(want[tuple(bad[0])]), sorted(set(bad[:, -1].tolist()))[:24]))
 
 
-def launch_conv(pkg, handle, c, entry="fwd"):
+def launch_conv(pkg, handle, c, entry="fwd", pad_cols=0, gap_rows=0):
     """One launch of a ConvCase through `entry` ("fwd", "dual", "fp8", "fp8out"); compares every level with the reference and checks
-    the never-written columns / pixels.  Returns the descriptor (its workspace fields tell whether a K split was planned)."""
+    the never-written columns / pixels.  Returns the descriptor (its workspace fields tell whether a K split was planned).
+    Concatenated cases: out_ld = cout + pad_cols, and gap_rows rows of out_ld elements in front of the first level, between two levels
+    and behind the last one of every image; the pad columns and the gap rows must keep the buffer's fill."""
     L = pkg._lib
     tdt = {"bf16": torch.bfloat16, "f32": torch.float32, "fp8": torch.uint8}[c.dtype]
     odt = {"bf16": torch.bfloat16, "f32": torch.float32, "e4m3": torch.uint8}[c.fmt]
@@ -66,16 +72,16 @@ def launch_conv(pkg, handle, c, entry="fwd"):
     d.w, d.bias, d.w_rows, d.N, d.KH, d.KW = wd.data_ptr(), bd.data_ptr(), rows, cout, k, k
     d.Crun = d.pix_stride = cin
     d.sy = d.sx = c.stride
-    d.out_ld = cout
+    d.out_ld = ld = cout + pad_cols
     d.flags = (L.CONV_RELU if c.relu else 0) | {None: 0, "same": L.CONV_RES_SAME, "up": L.CONV_RES_UPSAMPLE}[c.res] | \
         {None: 0, "post": L.CONV_RELU_MASK, "pre": L.CONV_RELU_MASK | L.CONV_MASK_PRE}[c.mask] | \
         (L.CONV_OUT_F32 if (c.fmt == "f32" and c.dtype == "bf16") else 0)
     fill = 7 if c.fmt == "e4m3" else SENTINEL
     keep, outs, s2 = [wd, bd], [], None
     if c.concat:                                           # head-output style: all levels into one (B, total, cout) tensor
-        total = sum(lv.Ho * lv.Wo for lv in c.levels)
-        big = torch.full((B, total * cout + 8), fill, dtype=odt, device=DEV)
-        off = 0
+        total = sum(lv.Ho * lv.Wo + gap_rows for lv in c.levels) + gap_rows
+        big = torch.full((B, total * ld + 8), fill, dtype=odt, device=DEV)
+        off = gap_rows * ld
     for gi, lv in enumerate(c.levels):
         xd = _to_dev(lv.x, c.dtype, c.s_x)
         grp = L.ConvGroup()
@@ -84,9 +90,9 @@ def launch_conv(pkg, handle, c, entry="fwd"):
         d.pad_t, d.pad_l = lv.pt, lv.pl                    # the same for every level of the grouped cases (stride 1)
         Hg, Wg = lv.act.shape[1], lv.act.shape[2]
         if c.concat:
-            grp.out, grp.out_elems, grp.out_img_stride, grp.out_off = big.data_ptr(), big.numel(), total * cout + 8, off
-            outs.append((off, lv.Ho * lv.Wo))
-            off += lv.Ho * lv.Wo * cout
+            grp.out, grp.out_elems, grp.out_img_stride, grp.out_off = big.data_ptr(), big.numel(), total * ld + 8, off
+            outs.append((off // ld, lv.Ho * lv.Wo))
+            off += (lv.Ho * lv.Wo + gap_rows) * ld
         else:
             od = torch.full((B, Hg, Wg, cout), fill, dtype=odt, device=DEV)
             grp.out, grp.out_elems, grp.out_img_stride = od.data_ptr(), od.numel(), Hg * Wg * cout
@@ -128,8 +134,14 @@ def launch_conv(pkg, handle, c, entry="fwd"):
     torch.cuda.synchronize()
     if c.concat:
         flat = _from_dev(big, c.fmt)
-        assert torch.all(flat[:, total * cout:] == fill)
-        assert_equal(flat[:, :total * cout].reshape(B, total, cout), c.stages[0].want, c.name)
+        assert torch.all(flat[:, total * ld:] == fill), c.name + ": wrote behind the image's last row"
+        rows = flat[:, :total * ld].reshape(B, total, ld)
+        written = torch.zeros(total, ld, dtype=torch.bool)
+        for row0, cells in outs:
+            written[row0:row0 + cells, :cout] = True
+        stray = (rows != fill) & ~written
+        assert not bool(stray.any()), "%s: %d elements outside the levels' slices were written, first at %s" % (c.name, int(stray.sum()), stray.nonzero()[0].tolist())
+        assert_equal(torch.cat([rows[:, row0:row0 + cells, :cout] for row0, cells in outs], 1), c.stages[0].want, c.name)
     else:
         s = c.out_step
         for lv, od in zip(c.levels, outs):
@@ -324,6 +336,45 @@ def test_head_output_concat(pkg, handle, monkeypatch, out, impl):
         assert last_impl(pkg, handle) == impl
 
 
+def head_output_runs(cout, out):
+    """[(RTN_CONV_IMPL or 0, RTN_CONV_BN2 or 0, generation that must run, tile width that must run or None)] of a head-output launch:
+    what csrc/rtn_conv.hip documents.  Generation 6 takes up to 48 channels with f32 output; generation 4 wants dense outputs and
+    generation 5 a 1x1 layer, so a forced 4 goes to the shared-halo kernel and a forced 5 / 6 that does not apply to the per-tap
+    kernel.  RTN_CONV_BN2 is honoured up to N rounded up to 64 columns; the cost model picks 64 on grids this small."""
+    gen6 = cout <= 48 and out == "f32"
+    runs = [(0, 0, (2, 6) if gen6 else (2,), 64),(1, 0, (1,), 64 if cout <= 64 else 128), (4, 0, (3,), 64), (5, 0, (2,), 64),
+            (6, 0, (6,) if gen6 else (2,), None if gen6 else 64)]
+    for impl in (2, 3):
+        runs += [(impl, bn, (impl,), bn or 64) for bn in (0, 64, 128, 256) if bn <= -(-cout // 64) * 64]
+    return runs
+
+
+@pytest.mark.parametrize("out", ["f32", "bf16"])
+@pytest.mark.parametrize("cout", X.HEAD_COUTS)
+def test_head_output_concat_at_many_classes(pkg, handle, monkeypatch, cout, out):
+    """cout = 9 K for K = 3, 6, 8, 20, 30 into the concatenation of the five levels: above 48 channels generation 6 never runs, not
+    even when asked for; 72 fills a 128-wide tile, 180 a 256-wide one and 270 needs a second N tile in every generation.  Every run in
+    the dense layout the engine uses (out_ld = cout) and with 16 pad columns and 3 gap rows around every level, all of which must
+    keep the fill: an N tile that stores past column cout - 1, or a row tile past its level's last cell, lands there."""
+    c = X.case("head%d/%s" % (cout, out))
+    ran = []
+    for impl, bn, gens, width in head_output_runs(cout, out):
+        for k, v in (("RTN_CONV_IMPL", impl), ("RTN_CONV_BN2", bn)):
+            if v:
+                monkeypatch.setenv(k, str(v))
+            else:
+                monkeypatch.delenv(k, raising=False)
+        for pad_cols, gap_rows in ((0, 0), (16, 3)):
+            launch_conv(pkg, handle, c, pad_cols=pad_cols, gap_rows=gap_rows)
+            got, tile = last_impl(pkg, handle), pkg._lib.lib.rtn_debug_last_conv_tile(handle.raw) & 0xFFFF
+            ran.append((impl, bn, got, tile))
+            assert got in gens, "RTN_CONV_IMPL=%d RTN_CONV_BN2=%d ran generation %d, expected %s" % (impl, bn, got, gens)
+            assert cout <= 48 or got != 6
+            if width is not None and got != 6:
+                assert tile == width, "RTN_CONV_IMPL=%d RTN_CONV_BN2=%d ran on %d-wide tiles, expected %d" % (impl, bn, tile, width)
+    print("head%d/%s (forced, BN2, generation, tile width): %s" % (cout, out, ran))
+
+
 # ------------------------------------------------------------------------------------------------ 7. data gradient
 def launch_dgrad(pkg, handle, c, impl):
     L = pkg._lib
@@ -401,6 +452,102 @@ def test_data_gradient(pkg, handle, monkeypatch, layer, impl, mode):
     monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
     launch_dgrad(pkg, handle, X.case("dgrad/%s/%s" % (layer, mode)), impl)
     assert last_impl(pkg, handle) == impl
+
+
+def launch_head_dgrad(pkg, handle, c, impl):
+    """The grouped launch the trainer builds for a head-output layer: dY of the five levels inside one [B][cells][cp] tensor whose
+    columns cout .. cp - 1 are zero, Crun = cp, the forward weights packed for Cout_run = cp, one dX tensor per level."""
+    L = pkg._lib
+    B, cin, cout, cp, k = c.B, c.cin, c.cout, c.cp, 3
+    wf = torch.zeros(-(-cout // 128) * 128, k * k * cin, dtype=torch.float64)
+    wf[:cout] = c.w.permute(3, 0, 1, 2).reshape(cout, -1)
+    wf = wf.to(torch.bfloat16).to(DEV).contiguous()
+    rows_d = 256 if impl == 4 else -(-cin // 128) * 128
+    wd = torch.full((rows_d, k * k * cp), 9.0, dtype=torch.bfloat16, device=DEV)     # the pack must write the zeros of channels cout .. cp - 1 itself
+    handle.check(L.lib.rtn_pack_dgrad_weights(handle.raw, wf.data_ptr(), wd.data_ptr(), L.RTN_BF16, cout, wf.shape[0], k, k, cin, cp, rows_d))
+    total = sum(H * W for H, W in c.levels_hw)
+    dyp = torch.zeros(B, total, cp, dtype=torch.float64)
+    off = 0
+    for (H, W), dy in zip(c.levels_hw, c.dy):
+        dyp[:, off:off + H * W, :cout] = dy.reshape(B, H * W, cout)
+        off += H * W
+    dyd = dyp.to(torch.bfloat16).to(DEV).contiguous()
+    d = L.ConvDesc()
+    d.ngroups, d.batch, d.dtype = len(c.levels_hw), B, L.RTN_BF16
+    d.w, d.w_rows, d.N, d.KH, d.KW = wd.data_ptr(), rows_d, cin, k, k
+    d.Crun = d.pix_stride = cp
+    d.sy = d.sx = 1
+    d.pad_t = d.pad_l = 1
+    d.out_ld = cin
+    d.flags = (L.CONV_RES_SAME if "res" in c.mode else 0) | (L.CONV_RELU_MASK if "mask" in c.mode else 0) | (L.CONV_MASK_PRE if "pre" in c.mode else 0)
+    keep = [wd, dyd]
+    if c.bias is not None:
+        bd = torch.zeros(rows_d, dtype=torch.float32)
+        bd[:cin] = c.bias.float()
+        bd = bd.to(DEV)
+        d.bias = bd.data_ptr()
+        keep.append(bd)
+    outs, off = [], 0
+    for gi, (H, W) in enumerate(c.levels_hw):
+        grp = L.ConvGroup()
+        grp.in_, grp.in_elems = dyd.data_ptr() + off * cp * 2, dyd.numel() - off * cp      # as bplan.dgrad_group points a level into the tensor
+        grp.in_img_stride, grp.in_row_stride = total * cp, W * cp
+        grp.Hin, grp.Win, grp.Hout, grp.Wout = H, W, H, W
+        prefill = c.other[gi] if "res" in c.mode else torch.full((B, H, W, cin), SENTINEL, dtype=torch.float64)
+        dxd = prefill.to(torch.bfloat16).to(DEV).contiguous()
+        grp.out, grp.out_elems, grp.out_img_stride = dxd.data_ptr(), dxd.numel(), H * W * cin
+        if "res" in c.mode:
+            grp.res, grp.res_elems, grp.res_img_stride, grp.res_ld = dxd.data_ptr(), dxd.numel(), H * W * cin, cin
+        if "mask" in c.mode:
+            actd = c.act[gi].to(torch.bfloat16).to(DEV).contiguous()
+            grp.mask, grp.mask_elems, grp.mask_img_stride, grp.mask_ld = actd.data_ptr(), actd.numel(), H * W * cin, cin
+            keep.append(actd)
+        d.g[gi] = grp
+        outs.append(dxd)
+        off += H * W
+    L.attach_conv_workspace(handle, d)
+    handle.check(L.lib.rtn_conv2d_dgrad(handle.raw, C.byref(d)))
+    torch.cuda.synchronize()
+    assert_equal(torch.cat([o.cpu().double().reshape(B, -1, cin) for o in outs], 1), c.stages[0].want, c.name)
+
+
+@pytest.mark.parametrize("mode", ["res", "mask", "res+mask_pre"])
+@pytest.mark.parametrize("impl", [0, 1, 2, 4])
+@pytest.mark.parametrize("cout,cp", X.HEAD_DGRAD)
+def test_data_gradient_of_the_head_outputs(pkg, handle, monkeypatch, cout, cp, impl, mode):
+    """dX of the 3x3 256 -> cout head-output layer from the padded concatenated dY: Crun = 64, 128, 256 and 512 (6, 8, 20 and 30 classes).
+    The default dispatch must take one of the 256-row generations; generations 1, 2 and 4 where forced."""
+    if impl:
+        monkeypatch.setenv("RTN_CONV_IMPL", str(impl))
+    monkeypatch.setenv("RTN_CONV_H8_GRID", "2")
+    launch_head_dgrad(pkg, handle, X.case("dgrad/head%d-%d/%s" % (cout, cp, mode)), impl)
+    got = last_impl(pkg, handle)
+    print("head dgrad cout %d Crun %d %s: forced %d ran generation %d" % (cout, cp, mode, impl, got))
+    assert got == impl if impl else got in (2, 3, 4)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f32"])
+@pytest.mark.parametrize("cin,cp", [(9, 64), (36, 64), (54, 64), (72, 128), (180, 256), (270, 512)])
+def test_pad_cast_rows_alone(pkg, handle, dtype, cin, cp):
+    """rtn_pad_cast_rows on 2 x 129 + 1 = 259 rows (no multiple of 256): the kept columns are torch's round-to-nearest-even cast of the
+    f32 input bit for bit (ties, values that overflow bf16's mantissa, both zeros, a subnormal), the pad columns are exact +0, and
+    nothing behind the last row is written."""
+    L = pkg._lib
+    tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    rows = 259
+    g = torch.Generator().manual_seed(cin)
+    src = torch.randn(rows, cin, generator=g) * 3.0
+    src[0, :8] = torch.tensor([257.0, 259.0, 1.00390625, -1.01171875, 0.0, -0.0, 1e-40, 3.3895313892515355e38])     # ties both ways, zeros, a subnormal, rounds to bf16 max
+    raw = torch.full((rows * cp + 64,), SENTINEL, dtype=tdt, device=DEV)
+    srcd = src.to(DEV).contiguous()
+    handle.check(L.lib.rtn_pad_cast_rows(handle.raw, srcd.data_ptr(), raw.data_ptr(), L.RTN_BF16 if dtype == "bf16" else L.RTN_F32, rows, cin, cp))
+    torch.cuda.synchronize()
+    got = raw.cpu()
+    assert torch.all(got[rows * cp:] == SENTINEL)
+    got = got[:rows * cp].view(rows, cp)
+    bits = (lambda t: t.contiguous().view(torch.int16)) if dtype == "bf16" else (lambda t: t.contiguous().view(torch.int32))
+    assert torch.equal(bits(got[:, :cin]), bits(src.to(tdt)))
+    assert torch.all(bits(got[:, cin:]) == 0)
 
 
 # ------------------------------------------------------------------------------------------------ 8. rtn_bottleneck64_fwd

@@ -21,8 +21,9 @@ AGN, NO_NMS = 1, 2
 MODES = [0, AGN, NO_NMS, AGN | NO_NMS]
 
 
-def run_ex(pkg, handle, canvas, reg, cls, flags, thr=0.05, iou=0.5, max_det=300, old=False):
-    """One rtn_decode_filter_nms_ex (old=True: rtn_decode_filter_nms) call -> boxes, scores, labels, indices (None for old)."""
+def run_ex(pkg, handle, canvas, reg, cls, flags, thr=0.05, iou=0.5, max_det=300, old=False, refused=False):
+    """One rtn_decode_filter_nms_ex (old=True: rtn_decode_filter_nms) call -> boxes, scores, labels, indices (None for old).
+    refused=True: the call must fail; -> (the RtnError, the four output arrays as the call left them)."""
     E = importlib.import_module(pkg.__name__ + ".engine")
     cfg, N = E.make_anchor_cfg(canvas)
     B, _, K = cls.shape
@@ -30,6 +31,8 @@ def run_ex(pkg, handle, canvas, reg, cls, flags, thr=0.05, iou=0.5, max_det=300,
     r = torch.as_tensor(reg).to(DEV)
     c = torch.as_tensor(cls).to(DEV)
     wsb = pkg.lib.rtn_detect_workspace_bytes(B, N, K) if old else pkg.lib.rtn_detect_workspace_bytes_ex(B, N, K, flags)
+    if refused:
+        wsb = max(wsb, pkg.lib.rtn_detect_workspace_bytes_ex(B, N, K, flags | AGN))     # a workspace some mode accepts: not what is refused
     assert wsb > 0
     ws = torch.empty(wsb, dtype=torch.uint8, device=DEV)
     boxes = torch.full((B, max_det, 4), 7.0, dtype=torch.float32, device=DEV)
@@ -41,9 +44,15 @@ def run_ex(pkg, handle, canvas, reg, cls, flags, thr=0.05, iou=0.5, max_det=300,
                                                    iou, max_det, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), ws.data_ptr(),
                                                    wsb))
     else:
-        handle.check(pkg.lib.rtn_decode_filter_nms_ex(handle.raw, C.byref(cfg), B, K, r.data_ptr(), c.data_ptr(), canvas[0], canvas[1],
-                                                      thr, iou, max_det, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                                      ws.data_ptr(), wsb, flags, idx.data_ptr()))
+        rc = pkg.lib.rtn_decode_filter_nms_ex(handle.raw, C.byref(cfg), B, K, r.data_ptr(), c.data_ptr(), canvas[0], canvas[1],
+                                              thr, iou, max_det, boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
+                                              ws.data_ptr(), wsb, flags, idx.data_ptr())
+        if refused:
+            with pytest.raises(pkg.RtnError) as err:
+                handle.check(rc)
+            torch.cuda.synchronize()
+            return err.value, [boxes.cpu().numpy(), scores.cpu().numpy(), labels.cpu().numpy(), idx.cpu().numpy()]
+        handle.check(rc)
     torch.cuda.synchronize()
     out = [boxes.cpu().numpy(), scores.cpu().numpy(), labels.cpu().numpy()]
     return out + [None if old else idx.cpu().numpy()]
@@ -115,6 +124,34 @@ def test_no_candidates_and_max_detections(pkg, handle, flags):
     reg, cls = synth(canvas, 2, 3, 31, 0.05, quantise=16)
     for md in (1, 300):
         compare(run_ex(pkg, handle, canvas, reg, cls, flags, max_det=md), restate(canvas, reg, cls, flags, max_det=md))
+
+
+@pytest.mark.parametrize("K", [20, 27])
+@pytest.mark.parametrize("flags", MODES)
+def test_modes_bit_exact_at_many_classes(pkg, handle, K, flags):
+    """Twenty and twenty-seven lists per image at 256 x 384 (27 x 300 = 8100: the most the class-specific merge holds), ~1,000
+    candidates per image, quantised scores and cross-class ties of the max; every class keeps detections."""
+    canvas = (256, 384)
+    reg, cls = synth(canvas, 2, K, 50 + K, 0.03 / K, quantise=64, class_ties=0.02)
+    got = run_ex(pkg, handle, canvas, reg, cls, flags)
+    if not flags & NO_NMS:
+        assert set(got[2][got[2] >= 0].tolist()) == set(range(K))
+    compare(got, restate(canvas, reg, cls, flags))
+
+
+def test_class_specific_limit_at_28_classes(pkg, handle):
+    """include/rtn.h: class-specific filtering handles classes * max_detections <= 8192, class-agnostic mode has no such limit.
+    28 x 300 = 8400: the class-specific modes are refused with RTN_EINVAL and a message that names the limit, before anything is
+    written; both class-agnostic modes run and equal the restatement; 28 x 292 = 8176 is accepted again."""
+    canvas, K = (256, 384), 28
+    reg, cls = synth(canvas, 2, K, 78, 0.03 / K, quantise=64, class_ties=0.02)
+    for flags in (0, NO_NMS):
+        err, outs = run_ex(pkg, handle, canvas, reg, cls, flags, refused=True)
+        assert err.code == -1 and "classes*max_detections > 8192" in str(err), str(err)
+        assert all(np.all(o == 7) for o in outs), "a refused call wrote its outputs"
+    for flags in (AGN, AGN | NO_NMS):
+        compare(run_ex(pkg, handle, canvas, reg, cls, flags), restate(canvas, reg, cls, flags))
+    compare(run_ex(pkg, handle, canvas, reg, cls, 0, max_det=292), restate(canvas, reg, cls, 0, max_det=292))
 
 
 def test_invariants(pkg, handle):

@@ -116,10 +116,10 @@ def test_device_evaluator_edge_cases(E):
     assert list(mask[2][:4] & 1) == [1, 0, 0, 1]
 
 
-@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("K", [1, 3, 20])
 def test_device_evaluator_random_sets(E, K):
     rng = np.random.default_rng(40 + K)
-    n = 2000 if K == 3 else 600
+    n = {1: 600, 3: 2000, 20: 300}[K]                     # twenty classes: 300 pages, every class's lists far shorter
     images, anns, scales = random_detect_set(rng, n, K, n_max=120)
     thresholds = M.COCO
     want, want_slots = M.evaluate(images, anns, scales, K, thresholds)

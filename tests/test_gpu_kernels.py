@@ -171,7 +171,7 @@ def make_loss_inputs(B, N, K, seed):
     return lab, regt, p, pred
 
 
-@pytest.mark.parametrize("B,N,K", [(2, 5000, 1), (8, 200700, 1), (2, 3001, 3)])
+@pytest.mark.parametrize("B,N,K", [(2, 5000, 1), (8, 200700, 1), (2, 3001, 3), (2, 3001, 8), (1, 1501, 30)])
 def test_retina_loss_fwd_bwd(pkg, handle, B, N, K):
     lab, regt, p, pred = make_loss_inputs(B, N, K, seed=N % 97)
     d = [torch.as_tensor(a).to(DEV) for a in (lab, regt, p, pred)]

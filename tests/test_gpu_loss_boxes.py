@@ -168,7 +168,7 @@ def run_case(pkg, handle, kinds, K, canvas, gamma, seed):
 
 
 @pytest.mark.parametrize("gamma", [2.0, 1.5])
-@pytest.mark.parametrize("K", [1, 3])
+@pytest.mark.parametrize("K", [1, 3, 8])
 @pytest.mark.parametrize("batch", sorted(BATCHES))
 def test_loss_boxes_bits_of_two_kernel_path(pkg, handle, batch, K, gamma):
     run_case(pkg, handle, BATCHES[batch], K, CANVAS, gamma, seed=7 + K)

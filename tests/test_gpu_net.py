@@ -390,6 +390,7 @@ def test_map_of_the_device_paths_against_the_float64_oracle(pkg, state):
     (3, 1, (97, 131), "f32", 0.05, 0.5, 300),     # odd canvas, three classes, one image
     (1, 3, (224, 160), "u8", 0.30, 0.3, 17),      # portrait canvas, uint8 pages, tight thresholds, 17 detections
     (2, 2, (64, 64), "bf16", 0.60, 0.7, 100),     # tiny canvas: P6/P7 are 1x1 and 1x1
+    (20, 2, (97, 131), "bf16", 0.05, 0.5, 300),   # twenty classes: 180 classification channels, per-class NMS over 20 lists
 ])
 def test_detect_parameters_and_shapes(pkg, K, B, hw, src, thr, nms, md):
     """End to end on unusual shapes and detection parameters: the post-processing must equal the oracle's filter_detections on
