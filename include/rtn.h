@@ -1013,6 +1013,37 @@ int rtn_resize_u8_host(int n, const uint8_t* const* pages, const int32_t* height
 int rtn_resize_u8_path(double inv_y);
 int rtn_resize_u8_tile(int32_t* rows, int32_t* bytes);
 
+/* ---- skew angle of scanned pages (a Postl / Bloomberg profile sweep in integers) -----------------------------------------
+ * A batch is n pages (at most 65535), uint8 (heights[i], widths[i], channels[i]) with 1 (gray) or 3 (B,G,R) channels and sides
+ * 1 .. 32767 (rtn_warp_affine_u8's limit, which rotates the page afterwards), rows without padding.  heights, widths, channels and
+ * shear_q16 are host arrays; the pages, the four result arrays and the workspace (256-byte aligned, >= rtn_skew_workspace_bytes)
+ * are device memory.
+ *   gray: (1868 B + 9617 G + 4899 R + 8192) >> 14.  threshold 1 .. 255 is taken as given; 0 means Otsu's threshold of the page's
+ *   256-bin histogram: for t = 1 .. 255, w0 = sum_{g<t} h[g], m0 = sum_{g<t} g h[g], w1 = N - w0, m1 = M - m0 in int64, candidates with
+ *   an empty class skipped, d = m0/w0 - m1/w1 and v = w0 * w1 * d * d in double, left to right, one rounding per operation; the
+ *   smallest t of the largest v.  A constant page has no candidate: threshold 0, ink 0, all scores 0, best = K / 2.
+ *   A pixel is ink when gray < t.  band is 8, 16, 32 or 64; C[y][b] counts the ink of row y in columns [b band, min(W, (b+1) band)).
+ *   shear_q16[k], k = 0 .. K-1 with K = 2 n_steps + 1 <= 401, is rint(tan(angle_k) * 65536), at most 17561 (15 degrees) in magnitude;
+ *   the library does no trigonometry.  The shift of band b at angle k is floor(((b band + band/2 - W/2) shear + 32768) / 65536),
+ *   P_k[r] = sum_b C[r + shift][b] over the bands whose r + shift lies in [0, H), scores[i * K + k] = sum_r (P_k[r+1] - P_k[r])^2.
+ *   best[i] is the k of the largest score; ties go to the smallest |k - n_steps|, then to the smaller k.  Ink of a text line lies
+ *   along y = y0 + (x - W/2) tan(angle_best), y down.
+ * rtn_skew_estimate copies its page table and the shear factors into the workspace (for which the call waits on the stream) and
+ *   queues every stage for the whole batch on the handle's stream; no stage waits for the host.  A bad argument fails the call before
+ *   anything is launched.  thresholds: int32[n], ink: int64[n], best: int32[n], scores: uint64[n * K].
+ * rtn_skew_counts_layout: offsets[i] is the byte offset in the workspace of page i's band counts after a call, one byte each,
+ *   band-major: count (y, b) at b * heights[i] + y (a view for tests).
+ * rtn_skew_estimate_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers and no workspace, through the functions of csrc/rtn_skew.h; the device's bits. */
+size_t rtn_skew_workspace_bytes(int n, const int32_t* heights, const int32_t* widths, int band, int K);
+int rtn_skew_counts_layout(int n, const int32_t* heights, const int32_t* widths, int band, int K, int64_t* offsets);
+int rtn_skew_estimate(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                      const int32_t* channels, int threshold, int band, int K, const int32_t* shear_q16, int32_t* thresholds, int64_t* ink,
+                      int32_t* best, uint64_t* scores, void* workspace, size_t workspace_bytes);
+int rtn_skew_estimate_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                           int threshold, int band, int K, const int32_t* shear_q16, int32_t* thresholds, int64_t* ink, int32_t* best,
+                           uint64_t* scores);
+
 #ifdef __cplusplus
 }
 #endif

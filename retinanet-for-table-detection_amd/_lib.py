@@ -277,6 +277,10 @@ SIGNATURES = {
     "rtn_resize_u8_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "rtn_resize_u8_path": (_I, [_D]),
     "rtn_resize_u8_tile": (_I, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "rtn_skew_workspace_bytes": (_SZ, [_I, _P, _P, _I, _I]),
+    "rtn_skew_counts_layout": (_I, [_I, _P, _P, _I, _I, _P]),
+    "rtn_skew_estimate": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_skew_estimate_host": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 

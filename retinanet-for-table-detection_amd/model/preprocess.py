@@ -194,6 +194,155 @@ def interpolate_files(src_paths, dst_paths, factors=None, quality=95, png="host"
     write_images_bgr(dst_paths, interpolate_images(read_images_bgr(src_paths), factors), quality=quality, png=png)
 
 
+# ---- skew of a scanned page: csrc/rtn_skew.hip, DESIGN §3.4m ------------------------------------------------------------------------------
+SKEW_MAX_SIDE, SKEW_MAX_ANGLE, SKEW_MAX_ANGLES, SKEW_MAX_SHEAR = 32767, 15.0, 401, 17561
+
+
+def skew_shears(max_angle=5.0, step=0.1):
+    """(shear_q16, n_steps) of rtn_skew_estimate: entry k is rint(tan(radians((k - n_steps) * step)) * 65536) in float64, with
+    n_steps = floor(max_angle / step + 1e-9).  ValueError for max_angle > 15, a step that is not positive, or more than 401 angles."""
+    max_angle, step = float(max_angle), float(step)
+    if not (np.isfinite(max_angle) and np.isfinite(step) and step > 0 and 0 <= max_angle <= SKEW_MAX_ANGLE):
+        raise ValueError("max_angle must be 0..%g degrees and step positive, got (%r, %r)" % (SKEW_MAX_ANGLE, max_angle, step))
+    n_steps = int(np.floor(max_angle / step + 1e-9))
+    if 2 * n_steps + 1 > SKEW_MAX_ANGLES:
+        raise ValueError("%d angles: at most %d" % (2 * n_steps + 1, SKEW_MAX_ANGLES))
+    k = np.arange(-n_steps, n_steps + 1, dtype=np.float64)
+    shear = np.rint(np.tan(np.radians(k * step)) * 65536.0).astype(np.int32)
+    if np.abs(shear).max() > SKEW_MAX_SHEAR:
+        raise ValueError("a shear factor beyond 15 degrees")
+    return np.ascontiguousarray(shear), n_steps
+
+
+def _skew_pages(pages):
+    """The pages as contiguous CUDA uint8 tensors, (H,W) or (H,W,3) with sides 1..32767."""
+    out = []
+    for i, p in enumerate(pages):
+        if isinstance(p, torch.Tensor):
+            if p.dtype != torch.uint8:
+                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, p.dtype))
+            q = p if (p.is_cuda and p.is_contiguous()) else p.cuda().contiguous()
+        else:
+            a = np.asarray(p)
+            if a.dtype != np.uint8:
+                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, a.dtype))
+            q = torch.as_tensor(np.ascontiguousarray(a)).cuda()
+        if not (q.dim() == 2 or (q.dim() == 3 and q.shape[2] == 3)) or not (1 <= q.shape[0] <= SKEW_MAX_SIDE and 1 <= q.shape[1] <= SKEW_MAX_SIDE):
+            raise ValueError("page %d: shape (H,W,3) or (H,W) with sides 1..%d expected, got %s" % (i, SKEW_MAX_SIDE, tuple(q.shape)))
+        out.append(q)
+    return out
+
+
+def _estimate_skew(src, max_angle, step, threshold, band, return_scores):
+    import ctypes as C
+    if band not in (8, 16, 32, 64):
+        raise ValueError("band must be 8, 16, 32 or 64, got %r" % (band,))
+    threshold = 0 if threshold is None else int(threshold)
+    if not 0 <= threshold <= 255:
+        raise ValueError("threshold must be None (Otsu) or 1..255, got %r" % (threshold,))
+    shear, n_steps = skew_shears(max_angle, step)
+    n, K = len(src), len(shear)
+    if n > 65535:
+        raise ValueError("at most 65535 pages a call")
+    if n == 0:
+        return ([], []) if return_scores else []
+    hs = np.ascontiguousarray([p.shape[0] for p in src], np.int32)
+    wd = np.ascontiguousarray([p.shape[1] for p in src], np.int32)
+    ch = np.ascontiguousarray([3 if p.dim() == 3 else 1 for p in src], np.int32)
+    h = _rt.handle()
+    dev = src[0].device
+    # one result block: scores (uint64 [n][K]), ink (int64 [n]), thresholds and best (int32 [n] each), read back in one copy
+    res = torch.empty(n * K + n + n, dtype=torch.int64, device=dev)
+    scores_ptr = res.data_ptr()
+    ink_ptr = scores_ptr + 8 * n * K
+    thr_ptr = ink_ptr + 8 * n
+    best_ptr = thr_ptr + 4 * n
+    wsb = int(L.lib.rtn_skew_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, band, K))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    h.check(L.lib.rtn_skew_estimate(h.raw, n, (C.c_void_p * n)(*[p.data_ptr() for p in src]), hs.ctypes.data, wd.ctypes.data, ch.ctypes.data,
+                                    threshold, band, K, shear.ctypes.data, thr_ptr, ink_ptr, best_ptr, scores_ptr, ws.data_ptr(), wsb))
+    host = res.cpu().numpy()                                      # the single read-back
+    scores = host[:n * K].view(np.uint64).reshape(n, K)
+    ink = host[n * K:n * K + n]
+    small = host[n * K + n:].view(np.int32)
+    thr, best = small[:n], small[n:2 * n]
+    angles = [float((int(b) - n_steps) * float(step)) for b in best]
+    if return_scores:
+        return angles, [dict(threshold=int(t), ink=int(i), best=int(b), scores=s.copy()) for t, i, b, s in zip(thr, ink, best, scores)]
+    return angles
+
+
+def estimate_skew(pages, max_angle=5.0, step=0.1, threshold=None, band=32, return_scores=False):
+    """The skew angle of every page in degrees: a list of uint8 (H,W,3) B,G,R or (H,W) gray pages (NumPy arrays or CUDA tensors, sizes
+    may differ, sides 1..32767), swept over the angles (k - n_steps) * step, k = 0 .. 2 n_steps, n_steps = floor(max_angle / step +
+    1e-9), by rtn_skew_estimate on the current stream: one call for the batch, one read-back of the small result block.  Ink is
+    gray < threshold; threshold=None takes Otsu's of each page.  band: the width of a column band, 8, 16, 32 or 64.  Ink of a text
+    line of a page of angle a lies along y = y0 + (x - W/2) tan(a), y down.  With return_scores, (angles, details): per page a dict of
+    threshold, ink, best and the uint64 scores of all angles.  ValueError for max_angle > 15, more than 401 angles, a bad band or
+    bad pages."""
+    return _estimate_skew(_skew_pages(list(pages)), max_angle, step, threshold, band, return_scores)
+
+
+def deskew_map(angle, height, width):
+    """The destination->source map of deskew_images, 2 x 3 float64: the rotation by `angle` degrees about ((W-1)/2, (H-1)/2)."""
+    t = np.radians(float(angle))
+    c, s = np.cos(t), np.sin(t)
+    cx, cy = (width - 1) / 2.0, (height - 1) / 2.0
+    return np.array([[c, -s, cx - c * cx + s * cy], [s, c, cy - s * cx - c * cy]], np.float64)
+
+
+def deskew_images(pages, max_angle=5.0, step=0.1, threshold=None, band=32, fill=255, min_angle=None):
+    """estimate_skew, then every page whose angle is at least min_angle (default: step) in magnitude rotated upright into a canvas of its
+    own size by rtn_warp_affine_u8 (INTER_LINEAR, constant border `fill` in every channel) with deskew_map as the destination->source
+    map.  Returns (pages, angles): CUDA uint8 tensors and degrees.  A page below min_angle is returned as the tensor it came in as (a
+    NumPy page: as its upload).  No pixel comes to the host."""
+    import ctypes as C
+    src = _skew_pages(list(pages))
+    angles = _estimate_skew(src, max_angle, step, threshold, band, False)
+    min_angle = float(step) if min_angle is None else float(min_angle)
+    fill = int(fill)
+    if not 0 <= fill <= 255:
+        raise ValueError("fill must be 0..255, got %r" % (fill,))
+    cval = np.full(4, fill, np.uint8)
+    h = _rt.handle()
+    out = []
+    for p, a in zip(src, angles):
+        if abs(a) < min_angle:
+            out.append(p)
+            continue
+        H, W = int(p.shape[0]), int(p.shape[1])
+        inv = np.ascontiguousarray(deskew_map(a, H, W))
+        dst = torch.empty_like(p)
+        h.check(L.lib.rtn_warp_affine_u8(h.raw, p.data_ptr(), H, W, 3 if p.dim() == 3 else 1, inv.ctypes.data_as(C.c_void_p), 1, 0,
+                                         cval.ctypes.data_as(C.c_void_p), dst.data_ptr()))
+        out.append(dst)
+    return out, angles
+
+
+def deskew_files(src_paths, dst_paths, max_angle=5.0, step=0.1, threshold=None, band=32, fill=255, min_angle=None, quality=95, png="host"):
+    """Read every page (page_io.read_images_bgr), deskew all of them (deskew_images) and write them (page_io.write_images_bgr: .jpg
+    names encoded on the device at `quality`, 4:2:0; png="device" encodes the .png names on the device too).  Returns the angles."""
+    src_paths, dst_paths = list(src_paths), list(dst_paths)
+    if png not in ("host", "device"):
+        raise ValueError("png must be 'host' or 'device', got %r" % (png,))
+    if len(src_paths) != len(dst_paths):
+        raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
+    if not src_paths:
+        return []
+    out, angles = deskew_images(read_images_bgr(src_paths), max_angle, step, threshold, band, fill, min_angle)
+    write_images_bgr(dst_paths, out, quality=quality, png=png)
+    return angles
+
+
+def boxes_to_scan(boxes, angle, height, width):
+    """Boxes (x1, y1, x2, y2) found on a page that deskew_images rotated by `angle` degrees, mapped back to the scan of height x width:
+    the axis-aligned hull of the four corners under deskew_map (transform.transform_aabb).  Host arithmetic; returns float64 (n, 4)."""
+    from .transform import transform_aabb
+    m = np.vstack([deskew_map(angle, height, width), [0.0, 0.0, 1.0]])
+    b = np.asarray(boxes, np.float64).reshape(-1, 4)
+    return np.array([transform_aabb(m, row) for row in b], np.float64).reshape(-1, 4)
+
+
 def resize_cubic(img, scale):
     """cv2.resize(img, None, fx=scale, fy=scale, interpolation=cv2.INTER_CUBIC) of a float32 (H,W,C) image."""
     img = np.asarray(img, np.float32)

@@ -490,12 +490,14 @@ def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_t
 
 
 def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
-                     min_side=800, max_side=1333, headers=False):
+                     min_side=800, max_side=1333, headers=False, deskew=False):
     """Raw scans to detections in one call, in batches of batch_size, with every pixel on the device: read_images_bgr of the scans,
     interpolate_images where a page's factor is not 1 (factors: one per file, by default preprocess.interpolation_factor of its
     base name: 4.17 for "-72.jpg", 3 for "-100.jpg"), preprocess_device_pages (the distance maps), compute_inputs_device, the
     inference model's engine().detect, and detect_files' output step on the (enlarged) pages with image_names =
     basename(orig_paths); headers=True as in detect_files.  `model`: a retinanet_bbox model (ValueError otherwise).
+    deskew=True rotates every page upright right after it is read (preprocess.deskew_images with its defaults); everything after,
+    the rendered pages included, is the deskewed page, and the boxes are in its coordinates (preprocess.boxes_to_scan maps them back).
     Unlike the reference's flow (interpolateImages, preProcessSampleImages, then test() on the written files), the enlarged and the
     processed page never pass through a JPEG file: the results are those of that flow with lossless (PNG) intermediate files.
     Returns the kept list of every file."""
@@ -518,6 +520,8 @@ def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, 
     for i in range(0, len(orig_paths), int(batch_size)):
         orig, fs = orig_paths[i:i + int(batch_size)], factors[i:i + int(batch_size)]
         pages = read_images_bgr(orig)
+        if deskew:
+            pages = preprocess.deskew_images(pages)[0]
         grow = [k for k, f in enumerate(fs) if f != 1.0]
         if grow:
             for k, big in zip(grow, preprocess.interpolate_images([pages[k] for k in grow], [fs[k] for k in grow])):
