@@ -321,17 +321,8 @@ class Model:
     def get_state(self):
         root = self._root()
         if root._trainer is not None:                               # pull the trained master weights back into Keras layout
-            tr, eng = root._trainer, root._engine
-            for name, lo in eng.layout.items():
-                wm = tr.master[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]].view(lo["rows"], lo["K"]).cpu()
-                cout = lo["cout"]
-                if name == "conv1":
-                    k = wm[:cout].reshape(cout, 8, 8, 4)[:, :7, :7, :3].permute(1, 2, 3, 0)
-                else:
-                    k = wm[:cout].reshape(cout, lo["kh"], lo["kw"], lo["cin"]).permute(1, 2, 3, 0)
-                root._state[name + "/kernel"] = k.contiguous().numpy()
-                if lo["has_bias"]:
-                    root._state[name + "/bias"] = tr.master[tr.NW + lo["boff"]:tr.NW + lo["boff"] + cout].cpu().numpy()
+            trained = root._trainer.get_state()
+            root._state.update((k, v) for k, v in trained.items() if k.endswith(("/kernel", "/bias")))
         return root._state
 
     def save_weights(self, path):

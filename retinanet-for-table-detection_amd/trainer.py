@@ -233,6 +233,21 @@ class Trainer:
             return
         eng.h.check(L.lib.rtn_pack_dgrad_weights_multi(eng.h.raw, table.data_ptr(), n, total, eng.rdt))
 
+    def get_state(self):
+        """The Keras-named state of the trained model: the engine's loaded state with every kernel (HWIO) and every Keras bias taken
+        from the f32 master copy; the frozen BatchNorm arrays are the loaded ones.  A new dict of new arrays: what a checkpoint holds,
+        and what Engine.load_state() turns back into these forward weights."""
+        self._check_engine_state()
+        eng, master = self.eng, self.master.cpu()
+        state = dict(eng.state)
+        for name, lo in eng.layout.items():
+            wm = master[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]].view(lo["rows"], lo["K"])
+            state[name + "/kernel"] = Wt.unpack_conv(name, lo, wm).contiguous().numpy()
+            if lo["has_bias"]:
+                bo = self.NW + lo["boff"]
+                state[name + "/bias"] = master[bo:bo + lo["cout"]].clone().numpy()
+        return state
+
     def grad_views(self, name):
         """(dW [rows][K] f32, db [rows] f32) views of the flat gradient buffer for one layer."""
         lo = self.eng.layout[name]

@@ -139,3 +139,13 @@ def pack_stem(kernel_hwio, bias, bn, torch_dtype, device):
     bk = torch.zeros(rows, dtype=torch.float32)
     bk[:cout] = b
     return wk.reshape(rows, 256).to(torch_dtype).contiguous().to(device), bk.to(device)
+
+
+def unpack_conv(name, lo, w2d):
+    """The inverse of pack_conv / pack_stem ("conv1") on the filter layout: [rows][K] -> HWIO (a view of w2d, any dtype).  lo: the
+    layer's kh / kw / cin / cout (an Engine.layout entry).  Drops the padding rows and, for the stem, the structural zeros of the
+    [8][8][4] run layout."""
+    cout = lo["cout"]
+    if name == "conv1":
+        return w2d[:cout].reshape(cout, 8, 8, 4)[:, :7, :7, :3].permute(1, 2, 3, 0)
+    return w2d[:cout].reshape(cout, lo["kh"], lo["kw"], lo["cin"]).permute(1, 2, 3, 0)

@@ -66,12 +66,7 @@ def unpack_grad(tr, Wt, name):
     dW, db = tr.grad_views(name)
     gs = tr.gscale[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]].view(lo["rows"], lo["K"])
     g = (dW * gs).cpu().double()
-    cout = lo["cout"]
-    if name == "conv1":
-        k = g[:cout].reshape(cout, 8, 8, 4)[:, :7, :7, :3].permute(1, 2, 3, 0)
-    else:
-        k = g[:cout].reshape(cout, lo["kh"], lo["kw"], lo["cin"]).permute(1, 2, 3, 0)
-    return k, db[:cout].cpu().double()
+    return Wt.unpack_conv(name, lo, g), db[:lo["cout"]].cpu().double()
 
 
 @pytest.mark.parametrize("dtype,K", [pytest.param("f32", 1, id="f32"), pytest.param("bf16", 1, id="bf16"),
@@ -126,11 +121,7 @@ def test_training_step(pkg, dtype, K):
     for name in LAYERS:
         lo = eng.layout[name]
         wm = tr.master[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]].view(lo["rows"], lo["K"]).cpu().double()
-        cout = lo["cout"]
-        if name == "conv1":
-            k = wm[:cout].reshape(cout, 8, 8, 4)[:, :7, :7, :3].permute(1, 2, 3, 0)
-        else:
-            k = wm[:cout].reshape(cout, lo["kh"], lo["kw"], lo["cin"]).permute(1, 2, 3, 0)
+        k = Wt.unpack_conv(name, lo, wm)
         want = new[name + "/kernel"]
         # Adam's first step moves every weight by ~lr: compare the MOVE, it is what the optimizer computes
         move_got, move_want = k - params[name + "/kernel"].double(), want - params[name + "/kernel"].double()
@@ -245,10 +236,7 @@ def test_per_tensor_clipnorm_switch(pkg):
             lo = eng.layout[name]
             wm = tr.master[lo["woff"]:lo["woff"] + lo["rows"] * lo["K"]].view(lo["rows"], lo["K"]).cpu().double()
             cout = lo["cout"]
-            if name == "conv1":
-                k = wm[:cout].reshape(cout, 8, 8, 4)[:, :7, :7, :3].permute(1, 2, 3, 0)
-            else:
-                k = wm[:cout].reshape(cout, lo["kh"], lo["kw"], lo["cin"]).permute(1, 2, 3, 0)
+            k = Wt.unpack_conv(name, lo, wm)
             move = k - params[name + "/kernel"].double()
             moves[(global_clip, name)] = move
             if not global_clip:                        # per tensor: the oracle on a subset of tensors is the oracle on all of them

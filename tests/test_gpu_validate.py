@@ -208,6 +208,9 @@ def test_reference_callback_list_through_fit_generator(tmp_path):
     if improving[-1] == 1:
         state = m.get_state()
         assert all(np.array_equal(fresh._root()._state[k], state[k]) for k in state)
+    # the file holds the model that was validated: loaded into a new model, the last checkpoint validates to the recorded numbers
+    r = E.validate_generator(DM.retinanet_bbox(model=fresh), val)
+    assert r["loss"] == seen[improving[-1]]["val_loss"] and r["mAP"] == seen[improving[-1]]["mAP"]
     # the CSV: 'epoch' plus the sorted keys of the first epoch's logs, one row per epoch
     with open(log, newline="") as f:
         rows = list(csv.reader(f))
