@@ -809,6 +809,42 @@ int rtn_tiff_decode(rtn_handle_t h, int n, const void* host_blobs, const void* d
                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_tiff_decode_host(const void* blob, uint8_t* out_bgr, size_t out_bytes, int32_t* status);
 
+/* ---- TIFF encode (bilevel pages as CCITT Group 4 strip TIFFs, on the device) -------------------------------------------------
+ * A page (uint8 (H, W) gray or (H, W, 3) B,G,R, rows without padding) is thresholded (gray as rtn_skew's: (1868 B + 9617 G + 4899 R +
+ * 8192) >> 14; ink = gray < threshold, threshold 1 .. 255) and written as a little-endian classic TIFF: the strips from offset 8, each
+ * the T.6 code of its rows (the first against an all-white row) that libtiff writes for the same bits, EOFB and zero bits up to the next
+ * byte; a pad byte to an even offset; an IFD of nine fields (256, 257, 258 = 1, 259 = 4, 262, 273, 278, 279, 284 = 1; SHORT but for the
+ * LONG arrays 273 and 279), the two arrays behind it (inline for one strip), next-IFD 0.  photometric 0 (WhiteIsZero) codes ink as the
+ * set bit, photometric 1 non-ink (Pillow's mode "1" default).  rows_per_strip is 1 .. 65535 and is stored as asked; a value above the
+ * height gives one strip.  Sides are 1 .. 65500.
+ *
+ * rtn_tiff_encode_bound (host only): the largest file a page can give, rounded up to a multiple of 4 (the kernels write 32-bit words);
+ *   0 for an invalid page or a file of 4 GiB or more.  Per row at most 7 width + 24 bits: a coding step that moves a0 forward by p
+ *   pixels takes at most 7 p bits (vertical: 7 bits, p >= 1; pass: 4 bits, p >= 1; horizontal with runs r1, r2 >= 1: 3 bits and the
+ *   two run codes, where a run of 1 takes at most 6 bits (3 if black, and one of the two is black) and a run of r >= 2 at most 7 r - 2:
+ *   12-bit terminating codes, 13-bit make-up codes from 64 pixels on, one 12-bit code per 2560 pixels more), and only two steps of a
+ *   row move by less than their runs pay for: the first where the row starts black (a vertical code that moves 0 pixels, 7 bits, or a
+ *   horizontal one that opens with the zero-length white run, 3 + 8 bits more than its black run pays for), and a horizontal one that
+ *   ends the row with a zero-length run (3 + 10 bits more).  Per strip ceil((row bits + 24) / 8) bytes, then 8 bytes of header, the pad
+ *   byte, 114 bytes of IFD and 8 bytes per strip.
+ * rtn_tiff_encode_workspace_bytes: device scratch for the n pages; 0 for an invalid argument.
+ * rtn_tiff_encode: n pages in one batch on the handle's stream; sizes, component counts, thresholds, strip heights and photometrics
+ *   mixed (host arrays of n).  pages: host array of n device pointers.  out (device): page i's file starts at out + out_offsets[i]
+ *   (4-byte aligned) and its slot [out_offsets[i], out_offsets[i + 1]) holds at least rtn_tiff_encode_bound bytes (host array of n + 1;
+ *   RTN_EINVAL otherwise).  out_bytes (device, n int64): the file length.  status (device, n int32): 0.  Everything is validated before
+ *   any launch; the call zeroes what it needs zeroed itself.  workspace: 256-byte aligned.
+ * rtn_tiff_encode_host (host only, no handle): the CPU twin: the same functions (csrc/rtn_tiff_encode.h) over one page in host memory,
+ *   the device's bytes.  RTN_ENOMEM if capacity is below the file's length (rtn_tiff_encode_bound always suffices). */
+size_t rtn_tiff_encode_bound(int width, int height, int rows_per_strip);
+size_t rtn_tiff_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components,
+                                       const int32_t* rows_per_strip);
+int rtn_tiff_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* widths, const int32_t* heights,
+                    const int32_t* components, const int32_t* thresholds, const int32_t* rows_per_strip, const int32_t* photometric,
+                    uint8_t* out, const int64_t* out_offsets, int64_t* out_bytes, int32_t* status, void* workspace,
+                    size_t workspace_bytes);
+int rtn_tiff_encode_host(int width, int height, int components, const uint8_t* page, int threshold, int rows_per_strip,
+                         int photometric, uint8_t* out, size_t capacity, size_t* out_bytes);
+
 /* ---- detection rendering (render_detections' outlines, captions and crops, on the device) ----------------------------------
  * Every output image of a batch (crops and annotated pages alike) is a rectangle of one source page with some of that page's
  * operations painted over it.  Page p owns the operations op_begin[p] .. op_begin[p + 1] - 1 (at most RTN_RENDER_MAX_OPS), in drawing

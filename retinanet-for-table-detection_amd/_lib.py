@@ -247,6 +247,10 @@ SIGNATURES = {
     "rtn_tiff_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_tiff_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_tiff_decode_host": (_I, [_P, _P, _SZ, C.POINTER(C.c_int32)]),
+    "rtn_tiff_encode_bound": (_SZ, [_I, _I, _I]),
+    "rtn_tiff_encode_workspace_bytes": (_SZ, [_I, _P, _P, _P, _P]),
+    "rtn_tiff_encode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_tiff_encode_host": (_I, [_I, _I, _I, _P, _I, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
     "rtn_render_workspace_bytes": (_SZ, [_I, _I, _I]),
     "rtn_render_pages": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ, _P, _SZ]),
     "rtn_render_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _I, _P, _P, _P, _P, _P, _I, _P, _SZ]),

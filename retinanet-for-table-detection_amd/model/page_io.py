@@ -1,9 +1,10 @@
-"""Page files, read and written as cv2.imread / cv2.imwrite do, with the six device codecs behind them: baseline
+"""Page files, read and written as cv2.imread / cv2.imwrite do, with the seven device codecs behind them: baseline
 JPEG and chunked-layout PNG pages are decoded and encoded on the device, ordinary 8-bit gray and R,G,B PNG pages (one zlib stream,
 all five row filters) are decoded there in calls of at least RTN_PNG_STREAM_MIN files (default 4), PNG pages of the other pixel
 layouts (1-, 2- and 4-bit gray, palette, alpha, 16-bit R,G,B, Adam7 interlace, tRNS) by the same decoder with another last stage in
 calls of at least RTN_PNG_LAYOUT_MIN files (default 2), strip TIFF pages (uncompressed, PackBits, LZW, Deflate or CCITT Group 4;
-bilevel, 8-bit gray, palette or R,G,B) in calls of at least RTN_TIFF_MIN files (default 2), every other
+bilevel, 8-bit gray, palette or R,G,B) in calls of at least RTN_TIFF_MIN files (default 2), bilevel pages are
+written as CCITT Group 4 TIFFs on the device on request (encode_tiff_bgr, write_images_bgr(tiff="g4")), every other
 file (16-bit gray PNG, tiled, JPEG-in-TIFF or 16-bit TIFF, BMP, ...) is left to Pillow.  csv_generator.py,
 model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
 import contextlib
@@ -464,14 +465,69 @@ def encode_png_bgr(pages):
     return _files_to_host(out, offs, nb, list(range(n)), n)
 
 
-def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
+TIFF_EXTENSIONS = ('.tif', '.tiff')
+TIFF_ROWS_PER_STRIP = 64                                # the largest strip tiff_inspect takes for Group 4: the reader's one wave per 64 rows
+
+
+def _check_tiff_settings(threshold, rows_per_strip, photometric, n):
+    """(thresholds, rows per strip, photometrics) as lists of n ints, from ints or per-page sequences; ValueError for anything else."""
+    def per_page(v, name, lo, hi):
+        seq = isinstance(v, (list, tuple, np.ndarray))
+        vs = list(v) if seq else [v] * n
+        if len(vs) != n:
+            raise ValueError("%d %s values for %d pages" % (len(vs), name, n))
+        for x in (vs if seq else [v]):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= x <= hi:
+                raise ValueError("%s must be an integer %d..%d, got %r" % (name, lo, hi, x))
+        return [int(x) for x in vs]
+    return (per_page(threshold, "threshold", 1, 255), per_page(rows_per_strip, "rows_per_strip", 1, 65535),
+            per_page(photometric, "photometric", 0, 1))
+
+
+def encode_tiff_bgr(pages, threshold=128, rows_per_strip=TIFF_ROWS_PER_STRIP, photometric=0):
+    """CCITT Group 4 (T.6) TIFF files of uint8 (H,W,3) B,G,R or (H,W) gray pages (CUDA or host tensors or arrays), thresholded on the
+    device: ink is gray < threshold (gray as estimate_skew's, 1 <= threshold <= 255); photometric 0 (WhiteIsZero) or 1 (what Pillow's
+    mode "1" writes by default); strips of rows_per_strip rows (1..65535; above the height: one strip).  The strips' bytes are those
+    of Image.fromarray(gray >= threshold).save(f, "TIFF", compression="group4", tiffinfo={262: photometric, 278: rows_per_strip}).
+    One batched rtn_tiff_encode on the current stream (csrc/rtn_tiff_enc.hip), one small copy of the n file lengths,
+    then one copy of the used bytes to pinned host memory.  Every setting is an int or a sequence of one value per page.  The
+    default of 64 rows per strip is the largest strip tiff_inspect takes for Group 4, so read_images_bgr decodes the files on the
+    device, one wave per strip.  There is no host path: a valid page always fits its slot (rtn_tiff_encode_bound).  Returns
+    list[bytes]."""
+    pages = list(pages)
+    n = len(pages)
+    ts, rs, ps = _check_tiff_settings(threshold, rows_per_strip, photometric, n)
+    dims = [_check_page(i, p) for i, p in enumerate(pages)]
+    if n == 0:
+        return []
+
+    def bound(i, w, hh, c):
+        b = L.lib.rtn_tiff_encode_bound(w, hh, rs[i])
+        if b == 0:
+            raise ValueError("page %d: %dx%d at %d rows per strip can give a TIFF of 4 GiB or more" % (i, hh, w, rs[i]))
+        return b
+
+    T, R, P = (np.ascontiguousarray(v, np.int32) for v in (ts, rs, ps))
+    out, offs, nb, bounds = _encode_batch(
+        pages, dims, extra=(T, R, P), encode=L.lib.rtn_tiff_encode, bound=bound, slot=lambda b: (b + 255) & ~255,
+        workspace_bytes=lambda m, w, hh, c: L.lib.rtn_tiff_encode_workspace_bytes(m, w, hh, c, R.ctypes.data))
+    if not all(0 < int(nb[i]) <= bounds[i] for i in range(n)):
+        raise RuntimeError("rtn_tiff_encode: file lengths %s outside (0, bound]" % nb.tolist())
+    return _files_to_host(out, offs, nb, list(range(n)), n)
+
+
+def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host", tiff="host"):
     """cv2.imwrite for a list of pages (uint8 (H,W,3) B,G,R or (H,W) gray; CUDA or host tensors or arrays): the .jpg / .jpeg /
     .jpe files through one encode_jpeg_bgr call (the device encoder), every other file through write_image, unchanged.
     png="device" sends the .png files through one encode_png_bgr call instead (lossless, other bytes than write_image's);
-    png="host" (the default) leaves them with write_image."""
+    png="host" (the default) leaves them with write_image.  tiff="g4" sends the .tif / .tiff files through one encode_tiff_bgr
+    call with its defaults (bilevel: ink is gray < 128; Group 4, WhiteIsZero, 64 rows per strip); tiff="host" (the default)
+    leaves them with write_image."""
     paths, pages = list(paths), list(pages)
     if png not in ("host", "device"):
         raise ValueError("png must be 'host' or 'device', got %r" % (png,))
+    if tiff not in ("host", "g4"):
+        raise ValueError("tiff must be 'host' or 'g4', got %r" % (tiff,))
     if len(paths) != len(pages):
         raise ValueError("%d paths for %d pages" % (len(paths), len(pages)))
     qs, ss = _check_settings(quality, subsampling, len(pages))
@@ -486,5 +542,9 @@ def write_images_bgr(paths, pages, quality=95, subsampling=2, png="host"):
     for i, data in zip(dpng, encode_png_bgr([pages[i] for i in dpng])):
         with open(paths[i], 'wb') as f:
             f.write(data)
-    for i in sorted(set(range(len(paths))) - set(jpg) - set(dpng)):
+    g4 = [i for i, e in enumerate(ext) if e in TIFF_EXTENSIONS] if tiff == "g4" else []
+    for i, data in zip(g4, encode_tiff_bgr([pages[i] for i in g4])):
+        with open(paths[i], 'wb') as f:
+            f.write(data)
+    for i in sorted(set(range(len(paths))) - set(jpg) - set(dpng) - set(g4)):
         write_image(paths[i], _host_page(pages[i]))

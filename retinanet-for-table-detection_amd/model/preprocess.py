@@ -51,6 +51,30 @@ def preprocess_files(src_paths, dst_paths, quality=95, png="host"):
     write_images_bgr(dst_paths, preprocess_device_pages(read_images_bgr(src_paths)), quality=quality, png=png)
 
 
+def binarize_files(src_paths, dst_paths, tiff="g4"):
+    """Scan to archive: read every page (page_io.read_images_bgr), take the Gaussian adaptive threshold of each
+    (preprocess_pages(return_binary=True), one call per page size) and write the binary pages (page_io.write_images_bgr).  With
+    tiff="g4" (the default) the .tif / .tiff names become CCITT Group 4 TIFFs of 64 rows per strip, encoded on the device
+    (page_io.encode_tiff_bgr), which read_images_bgr decodes there; tiff="host" leaves them with write_image."""
+    src_paths, dst_paths = list(src_paths), list(dst_paths)
+    if tiff not in ("host", "g4"):
+        raise ValueError("tiff must be 'host' or 'g4', got %r" % (tiff,))
+    if len(src_paths) != len(dst_paths):
+        raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
+    if not src_paths:
+        return
+    pages = read_images_bgr(src_paths)
+    groups = {}
+    for i, p in enumerate(pages):
+        groups.setdefault(tuple(p.shape[:2]), []).append(i)
+    out = [None] * len(pages)
+    for idx in groups.values():
+        binary = preprocess_pages(torch.stack([pages[i] for i in idx]).cpu().numpy(), return_binary=True)[1]
+        for k, i in enumerate(idx):
+            out[i] = binary[k]
+    write_images_bgr(dst_paths, out, tiff=tiff)
+
+
 def preprocess_device_pages(pages):
     """The distance maps of a list of CUDA uint8 (H,W,3) B,G,R pages of any sizes, as CUDA uint8 (H,W,3) tensors in the same order:
     rtn_preprocess_dt3 on the current stream, one call per page size.  No pixel comes to the host."""
@@ -319,18 +343,22 @@ def deskew_images(pages, max_angle=5.0, step=0.1, threshold=None, band=32, fill=
     return out, angles
 
 
-def deskew_files(src_paths, dst_paths, max_angle=5.0, step=0.1, threshold=None, band=32, fill=255, min_angle=None, quality=95, png="host"):
+def deskew_files(src_paths, dst_paths, max_angle=5.0, step=0.1, threshold=None, band=32, fill=255, min_angle=None, quality=95, png="host",
+                 tiff="host"):
     """Read every page (page_io.read_images_bgr), deskew all of them (deskew_images) and write them (page_io.write_images_bgr: .jpg
-    names encoded on the device at `quality`, 4:2:0; png="device" encodes the .png names on the device too).  Returns the angles."""
+    names encoded on the device at `quality`, 4:2:0; png="device" encodes the .png names on the device too; tiff="g4" writes the
+    .tif / .tiff names as bilevel Group 4 TIFFs on the device).  Returns the angles."""
     src_paths, dst_paths = list(src_paths), list(dst_paths)
     if png not in ("host", "device"):
         raise ValueError("png must be 'host' or 'device', got %r" % (png,))
+    if tiff not in ("host", "g4"):
+        raise ValueError("tiff must be 'host' or 'g4', got %r" % (tiff,))
     if len(src_paths) != len(dst_paths):
         raise ValueError("%d source paths for %d destination paths" % (len(src_paths), len(dst_paths)))
     if not src_paths:
         return []
     out, angles = deskew_images(read_images_bgr(src_paths), max_angle, step, threshold, band, fill, min_angle)
-    write_images_bgr(dst_paths, out, quality=quality, png=png)
+    write_images_bgr(dst_paths, out, quality=quality, png=png, tiff=tiff)
     return angles
 
 

@@ -7,7 +7,7 @@ import torch
 
 from . import _rt
 from .Parameters import image_scaling_factor, image_subtraction_factor
-from .page_io import write_image, write_images_bgr, encode_jpeg_bgr, encode_png_bgr, decode_png_bgr, decode_tiff_bgr, JPEG_EXTENSIONS  # noqa: F401
+from .page_io import write_image, write_images_bgr, encode_jpeg_bgr, encode_png_bgr, decode_png_bgr, decode_tiff_bgr, encode_tiff_bgr, JPEG_EXTENSIONS  # noqa: F401
 
 L = _rt.L
 
