@@ -1080,6 +1080,67 @@ int rtn_skew_estimate_host(int n, const uint8_t* const* pages, const int32_t* he
                            int threshold, int band, int K, const int32_t* shear_q16, int32_t* thresholds, int64_t* ink, int32_t* best,
                            uint64_t* scores);
 
+/* ---- table structure (rows, columns and cells of every detected table; model/structure.py) -----------------------------
+ * A batch is n pages as in scan analysis (sides RTN_CCA_MIN_SIDE .. RTN_CCA_MAX_SIDE, 1 or 3 channels) and n_boxes crops, at most
+ * 32767: crops[4 j ..] = x0, y0, w, h of box j inside page box_page[j], w and h within 30 .. 16384 (the caller grows the box by its
+ * margin and cuts it to the page).  Masks are uint8 (h, w), 0 or 255, crop j's at offsets[j] (increasing, not overlapping) of every
+ * packed mask buffer of mask_bytes.  Every array of sizes, offsets, counts and runs is a host array; on the device entries the pages,
+ * masks, profiles, edges, cell tables and the workspace (256-byte aligned, >= rtn_lattice_workspace_bytes(n_boxes, crops, n_items),
+ * n_items the larger of the batch's edges and cells, 0 for the masks and profiles) are device memory.  Every device entry copies its
+ * tables into the workspace, for which the call waits on the stream, and queues one launch (rtn_lattice_masks: four).  All
+ * arithmetic is integer and no launch uses atomics: the same arguments give the same bytes, whatever the buffers held.
+ * rtn_lattice_masks: bw is rtn_cca_lines_mask's thresholded image of the whole page, taken at the crop (the page's borders are
+ *   replicated, never the crop's); hm = bw eroded then dilated along x by the window [x - L / 2, x - L / 2 + L - 1] cut to the crop,
+ *   L = w / line_scale (line_scale within 1 .. 30); vm the same along y with L = h / line_scale; ink = bw & ~hm & ~vm.
+ * rtn_lattice_profiles: box j's four int32 profiles from profiles + prof_offsets[j] (in int32; increasing, not overlapping;
+ *   profiles_count the size of the buffer): rowH[h] (hm per row), rowInk[h] (ink per row), colV[w] (vm per column), colInk[w].
+ * rtn_lattice_separators_host: a profile of n to runs (lo, hi), inclusive.  mode 0: the maximal runs of profile > 0, two runs with at
+ *   most param zeros between them being one.  mode 1: the leading zero run (empty: hi = lo - 1), every inner zero run of at least
+ *   param, the trailing zero run (possibly empty); none where the profile is zero everywhere.  *count receives the true number; with
+ *   count > capacity the call writes the first capacity runs and returns RTN_EINVAL.
+ * Separators of a batch: box j has R[j] row runs then C[j] column runs in crop coordinates from runs + 2 * sep_offsets[j]
+ *   (runs_count pairs in all), in order, apart, inside the crop; an empty run only first or last.
+ * rtn_lattice_edges: box j's R (C - 1) horizontal edges (r, c), row by row, then its (R - 1) C vertical edges, one byte (0 or 1) each
+ *   from edges + edge_offsets[j].  Horizontal edge (r, c): span = the columns strictly between cols[c].hi and cols[c+1].lo, band = the
+ *   rows rows[r].lo - line_tol .. rows[r].hi + line_tol cut to the crop, covered = the span columns with an hm pixel in the band;
+ *   present iff 100 covered >= cover len (an empty span is present).  Vertical edges the same on vm with rows and columns exchanged.
+ * rtn_lattice_cells: box j's (R - 1) (C - 1) cells, row by row, from cell_offsets[j]: cell (r, c) is the rows strictly between
+ *   rows[r].hi and rows[r+1].lo and the columns strictly between cols[c].hi and cols[c+1].lo; cell_ink its count of ink pixels,
+ *   cell_box (4 int32) the bounding box x, y, w, h of that ink in page coordinates, 0,0,0,0 where the count is 0.
+ * An edges or cell buffer smaller than the batch needs (edges_bytes, cells_count) is RTN_EINVAL with the true number in the message.
+ * rtn_lattice_*_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers and no workspace, through the functions of csrc/rtn_lattice.h; the device's bits. */
+size_t rtn_lattice_workspace_bytes(int n_boxes, const int32_t* crops, int64_t n_items);
+int rtn_lattice_masks(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
+                      const int32_t* channels, int n_boxes, const int32_t* box_page, const int32_t* crops, int line_scale,
+                      const int64_t* offsets, uint8_t* bw, uint8_t* hm, uint8_t* vm, uint8_t* ink, size_t mask_bytes, void* workspace,
+                      size_t workspace_bytes);
+int rtn_lattice_profiles(rtn_handle_t h, int n_boxes, const int32_t* crops, const int64_t* offsets, const uint8_t* hm, const uint8_t* vm,
+                         const uint8_t* ink, size_t mask_bytes, const int64_t* prof_offsets, int32_t* profiles, size_t profiles_count,
+                         void* workspace, size_t workspace_bytes);
+int rtn_lattice_edges(rtn_handle_t h, int n_boxes, const int32_t* crops, const int64_t* offsets, const int32_t* R, const int32_t* C,
+                      const int64_t* sep_offsets, const int32_t* runs, size_t runs_count, int line_tol, int cover,
+                      const int64_t* edge_offsets, const uint8_t* hm, const uint8_t* vm, size_t mask_bytes, uint8_t* edges,
+                      size_t edges_bytes, void* workspace, size_t workspace_bytes);
+int rtn_lattice_cells(rtn_handle_t h, int n_boxes, const int32_t* crops, const int64_t* offsets, const int32_t* R, const int32_t* C,
+                      const int64_t* sep_offsets, const int32_t* runs, size_t runs_count, const int64_t* cell_offsets, const uint8_t* ink,
+                      size_t mask_bytes, int32_t* cell_ink, int32_t* cell_box, size_t cells_count, void* workspace,
+                      size_t workspace_bytes);
+int rtn_lattice_separators_host(const int32_t* profile, int n, int mode, int param, int capacity, int32_t* runs, int32_t* count);
+int rtn_lattice_masks_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
+                           int n_boxes, const int32_t* box_page, const int32_t* crops, int line_scale, const int64_t* offsets, uint8_t* bw,
+                           uint8_t* hm, uint8_t* vm, uint8_t* ink, size_t mask_bytes);
+int rtn_lattice_profiles_host(int n_boxes, const int32_t* crops, const int64_t* offsets, const uint8_t* hm, const uint8_t* vm,
+                              const uint8_t* ink, size_t mask_bytes, const int64_t* prof_offsets, int32_t* profiles,
+                              size_t profiles_count);
+int rtn_lattice_edges_host(int n_boxes, const int32_t* crops, const int64_t* offsets, const int32_t* R, const int32_t* C,
+                           const int64_t* sep_offsets, const int32_t* runs, size_t runs_count, int line_tol, int cover,
+                           const int64_t* edge_offsets, const uint8_t* hm, const uint8_t* vm, size_t mask_bytes, uint8_t* edges,
+                           size_t edges_bytes);
+int rtn_lattice_cells_host(int n_boxes, const int32_t* crops, const int64_t* offsets, const int32_t* R, const int32_t* C,
+                           const int64_t* sep_offsets, const int32_t* runs, size_t runs_count, const int64_t* cell_offsets,
+                           const uint8_t* ink, size_t mask_bytes, int32_t* cell_ink, int32_t* cell_box, size_t cells_count);
+
 #ifdef __cplusplus
 }
 #endif

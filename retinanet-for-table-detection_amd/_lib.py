@@ -285,6 +285,16 @@ SIGNATURES = {
     "rtn_skew_counts_layout": (_I, [_I, _P, _P, _I, _I, _P]),
     "rtn_skew_estimate": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_skew_estimate_host": (_I, [_I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "rtn_lattice_workspace_bytes": (_SZ, [_I, _P, C.c_int64]),
+    "rtn_lattice_masks": (_I, [_P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_lattice_profiles": (_I, [_P, _I, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _P, _SZ]),
+    "rtn_lattice_edges": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _P, _P, _P, _SZ, _P, _SZ, _P, _SZ]),
+    "rtn_lattice_cells": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _P, _P, _SZ, _P, _SZ]),
+    "rtn_lattice_separators_host": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "rtn_lattice_masks_host": (_I, [_I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _SZ]),
+    "rtn_lattice_profiles_host": (_I, [_I, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ]),
+    "rtn_lattice_edges_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _P, _P, _P, _SZ, _P, _SZ]),
+    "rtn_lattice_cells_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _P, _P, _SZ]),
 }
 
 

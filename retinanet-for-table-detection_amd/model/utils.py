@@ -457,14 +457,24 @@ def _render_batch(draw_pages, boxes, scores, labels, scales, result_dir, names, 
     return got
 
 
+def _cells_batch(pages, kept, result_dir, names):
+    """cells=True of detect_files and detect_raw_files for one batch: table_cells on the kept boxes, the CSVs under cellResults."""
+    import os
+    from . import structure
+    boxes = [np.array([b for b, _score, _label in k], np.float64).reshape(-1, 4) for k in kept]
+    structure.write_csvs(structure.table_cells(pages, boxes), names, os.path.join(result_dir, "cellResults"))
+
+
 def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
-                 min_side=800, max_side=1333, headers=False):
+                 min_side=800, max_side=1333, headers=False, cells=False):
     """The loop of RetinaNet.py's test() over files, in batches of batch_size, with every pixel on the device: read_images_bgr of
     the preprocessed pages (src_paths) and of the pages to draw on (orig_paths), compute_inputs_device, the inference model's
     engine().detect, render_detections_device with image_names = basename(src_paths).  `model`: a retinanet_bbox model (ValueError
     otherwise).  headers=True also runs HeaderDetect.py's step on the crops of every batch while they are on the device
     (model/header.py detect_headers) and writes its files under result_dir/headerResults/test_<crop file name without extension>/;
-    a crop too tall for detect_headers' point limit is skipped with a warning.
+    a crop too tall for detect_headers' point limit is skipped with a warning.  cells=True also runs model/structure.py's
+    table_cells on every batch's pages (those drawn on) and kept boxes while they are on the device and writes
+    result_dir/cellResults/<name without extension>_table<k>_cells.csv for kept box k; cells=False changes no byte of the outputs.
     Returns the kept list of every file."""
     import os
     from . import preprocess
@@ -484,13 +494,15 @@ def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_t
         canvas, scales = preprocess.compute_inputs_device(read_images_bgr(src), min_side=min_side, max_side=max_side, dtype=dtype)
         boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
         names = [os.path.basename(p) for p in src]
-        kept += _render_batch(read_images_bgr(orig), boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold,
-                              png, headers)
+        pages = read_images_bgr(orig)
+        kept += _render_batch(pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers)
+        if cells:
+            _cells_batch(pages, kept[i:], result_dir, names)
     return kept
 
 
 def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
-                     min_side=800, max_side=1333, headers=False, deskew=False):
+                     min_side=800, max_side=1333, headers=False, deskew=False, cells=False):
     """Raw scans to detections in one call, in batches of batch_size, with every pixel on the device: read_images_bgr of the scans,
     interpolate_images where a page's factor is not 1 (factors: one per file, by default preprocess.interpolation_factor of its
     base name: 4.17 for "-72.jpg", 3 for "-100.jpg"), preprocess_device_pages (the distance maps), compute_inputs_device, the
@@ -498,6 +510,8 @@ def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, 
     basename(orig_paths); headers=True as in detect_files.  `model`: a retinanet_bbox model (ValueError otherwise).
     deskew=True rotates every page upright right after it is read (preprocess.deskew_images with its defaults); everything after,
     the rendered pages included, is the deskewed page, and the boxes are in its coordinates (preprocess.boxes_to_scan maps them back).
+    cells=True as in detect_files, on the (deskewed, enlarged) pages the boxes belong to: with deskew=True the grid is taken on the
+    upright page and the CSV coordinates are those of the upright page.
     Unlike the reference's flow (interpolateImages, preProcessSampleImages, then test() on the written files), the enlarged and the
     processed page never pass through a JPEG file: the results are those of that flow with lossless (PNG) intermediate files.
     Returns the kept list of every file."""
@@ -531,4 +545,6 @@ def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, 
         boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
         names = [os.path.basename(str(p)) for p in orig]
         kept += _render_batch(pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers)
+        if cells:
+            _cells_batch(pages, kept[i:], result_dir, names)
     return kept
