@@ -17,8 +17,7 @@
 // window step, which csrc/rtn_lattice.hip uses too, are in rtn_cca_rows.h.
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_cca.h"
 #include "rtn_cca_rows.h"
 
@@ -339,47 +338,29 @@ Sizes sizes_of(int n, const int32_t* heights, const int32_t* widths) {
     }
     return s;
 }
-size_t a256(int64_t v) { return (size_t)rtn_align256((long long)v); }
 // tables first (the largest any entry uploads: 4 n CRows, n CLab or n pages and 4 n_boxes rectangles), then the per-pixel arrays:
 // labels and ranks (4 bytes each) and flags (1) for labelling; three byte planes for the line masks fit in the same room
-size_t tables_bytes(int n, int n_boxes) { return a256((int64_t)n * 4 * sizeof(CRows)) + a256((int64_t)n * sizeof(CLab)) + a256((int64_t)n_boxes * 4 * sizeof(CRect)); }
-struct Layout { size_t labels, ranks, flags, block_counts, end; };
-Layout layout_of(int n, int n_boxes, const Sizes& s) {
+struct Layout { size_t rows, lab, rects, labels, ranks, flags, block_counts; };
+Layout layout_of(rtn_stage& st, int n, int n_boxes, const Sizes& s) {
     Layout l;
-    l.labels = tables_bytes(n, n_boxes);
-    l.ranks = l.labels + a256(s.pixels * 4);
-    l.flags = l.ranks + a256(s.pixels * 4);
-    l.block_counts = l.flags + a256(s.pixels);
-    l.end = l.block_counts + a256(s.blocks * 4);
+    l.rows = st.reserve((int64_t)n * 4 * sizeof(CRows));
+    l.lab = st.reserve((int64_t)n * sizeof(CLab));
+    l.rects = st.reserve((int64_t)n_boxes * 4 * sizeof(CRect));
+    l.labels = st.reserve(s.pixels * 4);
+    l.ranks = st.reserve(s.pixels * 4);
+    l.flags = st.reserve(s.pixels);
+    l.block_counts = st.reserve(s.blocks * 4);
     return l;
 }
 
-int check_ws(rtn_handle_t h, const char* name, void* workspace, size_t workspace_bytes, size_t need) {
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "%s: the workspace must be 256-byte aligned", name);
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
-    return RTN_OK;
-}
-// a host table to the front of the workspace at `pos`; the call waits for the copy (the host image lives in this call)
-template <class T>
-int upload(rtn_handle_t h, const std::vector<T>& table, uint8_t* ws, size_t pos, const T** out) {
-    if (!table.empty()) {
-        RTN_HIP(h, hipMemcpyAsync(ws + pos, table.data(), table.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-        RTN_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    *out = reinterpret_cast<const T*>(ws + pos);
-    return RTN_OK;
-}
-unsigned blocks_for(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
-
 }  // namespace
-
-#define CCA_PLAN(h, name, expr)                                                           \
-    if (const char* why_ = (expr)) return rtn_fail_host((h), RTN_EINVAL, "%s: %s", name, why_)
 
 // rtn_cca_*: see include/rtn.h
 extern "C" size_t rtn_cca_workspace_bytes(int n, const int32_t* heights, const int32_t* widths, int n_boxes) {
     if (n_boxes < 0 || cca_check_sizes(n, heights, widths)) return 0;
-    return layout_of(n, n_boxes, sizes_of(n, heights, widths)).end;
+    rtn_stage st;
+    layout_of(st, n, n_boxes, sizes_of(n, heights, widths));
+    return st.bytes();
 }
 
 extern "C" int rtn_cca_lines_mask(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
@@ -387,17 +368,17 @@ extern "C" int rtn_cca_lines_mask(rtn_handle_t h, int n, const uint8_t* const* p
                                   size_t mask_bytes, void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     std::vector<CPage> pg;
-    CCA_PLAN(h, "rtn_cca_lines_mask", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
+    RTN_PLAN(h, "rtn_cca_lines_mask", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
     if (n && (!horizontal || !vertical)) return rtn_fail(h, RTN_EINVAL, "rtn_cca_lines_mask: the two mask buffers expected");
     if (n == 0) return RTN_OK;
     const Sizes s = sizes_of(n, heights, widths);
-    const Layout l = layout_of(n, 0, s);
-    if (const int rc = check_ws(h, "rtn_cca_lines_mask", workspace, workspace_bytes, l.end)) return rc;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    rtn_stage st;
+    const Layout l = layout_of(st, n, 0, s);
+    if (const int rc = st.check(h, "rtn_cca_lines_mask", workspace, workspace_bytes)) return rc;
     // three planes of the pages' pixels in the room of the labels: bw, its transpose, the opened transpose
-    uint8_t* bw = ws + l.labels;
-    uint8_t* bwT = bw + a256(s.pixels);
-    uint8_t* vT = bwT + a256(s.pixels);
+    uint8_t* bw = st.at<uint8_t>(l.labels);
+    uint8_t* bwT = bw + rtn_a256(s.pixels);
+    uint8_t* vT = bwT + rtn_a256(s.pixels);
     std::vector<CPage> pbw(pg);
     std::vector<CRows> rows((size_t)4 * n);
     int64_t pos = 0;
@@ -410,18 +391,14 @@ extern "C" int rtn_cca_lines_mask(rtn_handle_t h, int n, const uint8_t* const* p
         rows[3 * n + i] = CRows{vT + pos, vertical + p.off, p.w, p.h, 0, 0};                      // transpose back
         pos += (int64_t)p.h * p.w;
     }
-    const CPage* tp;
-    const CRows* tr;
-    if (const int rc = upload(h, pbw, ws, a256((int64_t)n * 4 * sizeof(CRows)), &tp)) return rc;
-    if (const int rc = upload(h, rows, ws, 0, &tr)) return rc;
-    const unsigned bw_tiles = blocks_for(s.max_w, CCA_BW_TW) * blocks_for(s.max_h, CCA_BW_TH);
-    const unsigned t_tiles = blocks_for(s.max_w, 32) * blocks_for(s.max_h, 32);
-    bw_kernel<<<dim3(bw_tiles, (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(tp, bw);
+    st.put(l.rows, rows);
+    st.put(l.lab, pbw);
+    if (const int rc = st.upload(h)) return rc;
+    const CRows* tr = st.at<const CRows>(l.rows);
+    unsigned t_tiles;
+    bw_kernel<<<dim3(rtn_blocks_for(s.max_w, CCA_BW_TW) * rtn_blocks_for(s.max_h, CCA_BW_TH), (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(st.at<const CPage>(l.lab), bw);
     RTN_CHECK_LAUNCH(h, "bw_kernel");
-    transpose_kernel<<<dim3(t_tiles, (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(tr);
-    RTN_CHECK_LAUNCH(h, "transpose_kernel");
-    open_rows_kernel<<<dim3((unsigned)std::max(s.max_h, s.max_w), (unsigned)(2 * n)), dim3(CCA_ROW_THREADS), row_lds_bytes(std::max(s.max_h, s.max_w)), h->stream>>>(tr + n);
-    RTN_CHECK_LAUNCH(h, "open_rows_kernel");
+    if (const int rc = launch_transpose_open(h, tr, n, s.max_h, s.max_w, &t_tiles)) return rc;
     transpose_kernel<<<dim3(t_tiles, (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(tr + 3 * n);
     RTN_CHECK_LAUNCH(h, "transpose_kernel");
     return RTN_OK;
@@ -432,14 +409,15 @@ extern "C" int rtn_cca_text_mask(rtn_handle_t h, int n, const uint8_t* const* pa
                                  size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     std::vector<CPage> pg;
-    CCA_PLAN(h, "rtn_cca_text_mask", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
+    RTN_PLAN(h, "rtn_cca_text_mask", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
     if (n && !closed) return rtn_fail(h, RTN_EINVAL, "rtn_cca_text_mask: the mask buffer expected");
     if (n == 0) return RTN_OK;
     const Sizes s = sizes_of(n, heights, widths);
-    if (const int rc = check_ws(h, "rtn_cca_text_mask", workspace, workspace_bytes, layout_of(n, 0, s).end)) return rc;
-    const CPage* tp;
-    if (const int rc = upload(h, pg, static_cast<uint8_t*>(workspace), 0, &tp)) return rc;
-    text_rows_kernel<<<dim3((unsigned)s.max_h, (unsigned)n), dim3(CCA_ROW_THREADS), row_lds_bytes(s.max_w), h->stream>>>(tp, closed);
+    rtn_stage st;
+    const Layout l = layout_of(st, n, 0, s);
+    st.put(l.rows, pg);
+    if (const int rc = st.commit(h, "rtn_cca_text_mask", workspace, workspace_bytes)) return rc;
+    text_rows_kernel<<<dim3((unsigned)s.max_h, (unsigned)n), dim3(CCA_ROW_THREADS), row_lds_bytes(s.max_w), h->stream>>>(st.at<const CPage>(l.rows), closed);
     RTN_CHECK_LAUNCH(h, "text_rows_kernel");
     return RTN_OK;
 }
@@ -449,21 +427,21 @@ extern "C" int rtn_cca_label(rtn_handle_t h, int n, const uint8_t* const* images
                              size_t boxes_bytes, void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     std::vector<CLab> im;
-    CCA_PLAN(h, "rtn_cca_label", cca_plan_label(n, images, heights, widths, capacity, box_offsets, counts, boxes, boxes_bytes, &im));
+    RTN_PLAN(h, "rtn_cca_label", cca_plan_label(n, images, heights, widths, capacity, box_offsets, counts, boxes, boxes_bytes, &im));
     if (n == 0) return RTN_OK;
     const Sizes s = sizes_of(n, heights, widths);
-    const Layout l = layout_of(n, 0, s);
-    if (const int rc = check_ws(h, "rtn_cca_label", workspace, workspace_bytes, l.end)) return rc;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    const CLab* t;
-    if (const int rc = upload(h, im, ws, 0, &t)) return rc;
-    int32_t* labels = reinterpret_cast<int32_t*>(ws + l.labels);
-    int32_t* ranks = reinterpret_cast<int32_t*>(ws + l.ranks);
-    uint8_t* flags = ws + l.flags;
-    int32_t* block_counts = reinterpret_cast<int32_t*>(ws + l.block_counts);
-    const dim3 tiles(blocks_for(s.max_w, CCA_TILE_W) * blocks_for(s.max_h, CCA_TILE_H), (unsigned)n);
-    const dim3 pixels(blocks_for(s.max_px, CCA_PIX_THREADS), (unsigned)n);
-    const dim3 groups(blocks_for(s.max_px, CCA_PIX_THREADS * CCA_RANK_PIXELS), (unsigned)n);
+    rtn_stage st;
+    const Layout l = layout_of(st, n, 0, s);
+    st.put(l.rows, im);
+    if (const int rc = st.commit(h, "rtn_cca_label", workspace, workspace_bytes)) return rc;
+    const CLab* t = st.at<const CLab>(l.rows);
+    int32_t* labels = st.at<int32_t>(l.labels);
+    int32_t* ranks = st.at<int32_t>(l.ranks);
+    uint8_t* flags = st.at<uint8_t>(l.flags);
+    int32_t* block_counts = st.at<int32_t>(l.block_counts);
+    const dim3 tiles(rtn_blocks_for(s.max_w, CCA_TILE_W) * rtn_blocks_for(s.max_h, CCA_TILE_H), (unsigned)n);
+    const dim3 pixels(rtn_blocks_for(s.max_px, CCA_PIX_THREADS), (unsigned)n);
+    const dim3 groups(rtn_blocks_for(s.max_px, CCA_PIX_THREADS * CCA_RANK_PIXELS), (unsigned)n);
     int max_cap = 0;
     for (const CLab& m : im) max_cap = std::max(max_cap, m.cap);
     label_tiles_kernel<<<tiles, dim3(CCA_TILE), 0, h->stream>>>(t, labels);
@@ -487,7 +465,7 @@ extern "C" int rtn_cca_label(rtn_handle_t h, int n, const uint8_t* const* images
     if (max_cap > 0) {
         label_boxes_kernel<<<pixels, dim3(CCA_PIX_THREADS), 0, h->stream>>>(t, labels, flags, external_only, ranks, boxes);
         RTN_CHECK_LAUNCH(h, "label_boxes_kernel");
-        label_finish_kernel<<<dim3(blocks_for(max_cap, CCA_PIX_THREADS), (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(t, counts, boxes);
+        label_finish_kernel<<<dim3(rtn_blocks_for(max_cap, CCA_PIX_THREADS), (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(t, counts, boxes);
         RTN_CHECK_LAUNCH(h, "label_finish_kernel");
     }
     // the counts come back: an image with more components than its capacity is an error, never a silent cut
@@ -506,19 +484,17 @@ extern "C" int rtn_cca_paint(rtn_handle_t h, int n, uint8_t* const* pages, const
     if (!h) return RTN_EINVAL;
     std::vector<CPaintPage> pp;
     std::vector<CRect> rects;
-    CCA_PLAN(h, "rtn_cca_paint", cca_plan_paint(n, pages, heights, widths, channels, n_boxes, box_page, boxes, mode, &pp, &rects));
+    RTN_PLAN(h, "rtn_cca_paint", cca_plan_paint(n, pages, heights, widths, channels, n_boxes, box_page, boxes, mode, &pp, &rects));
     if (rects.empty()) return RTN_OK;
-    const size_t need = tables_bytes(n, n_boxes);
-    if (const int rc = check_ws(h, "rtn_cca_paint", workspace, workspace_bytes, need)) return rc;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    const CPaintPage* tp;
-    const CRect* tr;
-    if (const int rc = upload(h, pp, ws, 0, &tp)) return rc;
-    if (const int rc = upload(h, rects, ws, a256((int64_t)n * 4 * sizeof(CRows)) + a256((int64_t)n * sizeof(CLab)), &tr)) return rc;
+    rtn_stage st;
+    const Layout l = layout_of(st, n, n_boxes, Sizes{});                       // the tables alone
+    st.put(l.rows, pp);
+    st.put(l.rects, rects);
+    if (const int rc = st.commit(h, "rtn_cca_paint", workspace, workspace_bytes)) return rc;
     int64_t max_area = 1;
     for (const CRect& r : rects) max_area = std::max(max_area, (int64_t)(r.x1 - r.x0) * (r.y1 - r.y0));
-    const unsigned slices = std::min(blocks_for(max_area, CCA_PIX_THREADS), 1024u);
-    paint_kernel<<<dim3((unsigned)rects.size(), slices), dim3(CCA_PIX_THREADS), 0, h->stream>>>(tp, tr, mode);
+    const unsigned slices = std::min(rtn_blocks_for(max_area, CCA_PIX_THREADS), 1024u);
+    paint_kernel<<<dim3((unsigned)rects.size(), slices), dim3(CCA_PIX_THREADS), 0, h->stream>>>(st.at<const CPaintPage>(l.rows), st.at<const CRect>(l.rects), mode);
     RTN_CHECK_LAUNCH(h, "paint_kernel");
     return RTN_OK;
 }
@@ -528,7 +504,7 @@ extern "C" int rtn_cca_lines_mask_host(int n, const uint8_t* const* pages, const
                                        const int32_t* channels, const int64_t* offsets, uint8_t* horizontal, uint8_t* vertical,
                                        size_t mask_bytes, uint8_t* bw) {
     std::vector<CPage> pg;
-    CCA_PLAN(nullptr, "rtn_cca_lines_mask_host", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
+    RTN_PLAN(nullptr, "rtn_cca_lines_mask_host", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
     if (n && (!horizontal || !vertical)) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_cca_lines_mask_host: the two mask buffers expected");
     for (const CPage& p : pg) cca_lines_mask_page(p, horizontal + p.off, vertical + p.off, bw ? bw + p.off : nullptr);
     return RTN_OK;
@@ -538,7 +514,7 @@ extern "C" int rtn_cca_text_mask_host(int n, const uint8_t* const* pages, const 
                                       const int32_t* channels, const int64_t* offsets, uint8_t* closed, size_t mask_bytes,
                                       uint8_t* stages) {
     std::vector<CPage> pg;
-    CCA_PLAN(nullptr, "rtn_cca_text_mask_host", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
+    RTN_PLAN(nullptr, "rtn_cca_text_mask_host", cca_plan_pages(n, pages, heights, widths, channels, offsets, mask_bytes, &pg));
     if (n && !closed) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_cca_text_mask_host: the mask buffer expected");
     for (const CPage& p : pg) cca_text_mask_page(p, closed + p.off, stages ? stages + 4 * p.off : nullptr);
     return RTN_OK;
@@ -548,7 +524,7 @@ extern "C" int rtn_cca_label_host(int n, const uint8_t* const* images, const int
                                   const int32_t* capacity, const int64_t* box_offsets, int32_t* counts, int32_t* boxes,
                                   size_t boxes_bytes) {
     std::vector<CLab> im;
-    CCA_PLAN(nullptr, "rtn_cca_label_host", cca_plan_label(n, images, heights, widths, capacity, box_offsets, counts, boxes, boxes_bytes, &im));
+    RTN_PLAN(nullptr, "rtn_cca_label_host", cca_plan_label(n, images, heights, widths, capacity, box_offsets, counts, boxes, boxes_bytes, &im));
     int over = -1;
     for (int i = 0; i < n; ++i) {
         counts[i] = (int32_t)cca_label_image(im[i].img, im[i].h, im[i].w, external_only, im[i].cap, boxes + 4 * im[i].box_off);
@@ -564,7 +540,7 @@ extern "C" int rtn_cca_paint_host(int n, uint8_t* const* pages, const int32_t* h
                                   int n_boxes, const int32_t* box_page, const int32_t* boxes, int mode) {
     std::vector<CPaintPage> pp;
     std::vector<CRect> rects;
-    CCA_PLAN(nullptr, "rtn_cca_paint_host", cca_plan_paint(n, pages, heights, widths, channels, n_boxes, box_page, boxes, mode, &pp, &rects));
+    RTN_PLAN(nullptr, "rtn_cca_paint_host", cca_plan_paint(n, pages, heights, widths, channels, n_boxes, box_page, boxes, mode, &pp, &rects));
     for (const CRect& r : rects)
         for (int y = r.y0; y < r.y1; ++y)
             for (int x = r.x0; x < r.x1; ++x) cca_paint_pixel(pp[r.page], mode, y, x);

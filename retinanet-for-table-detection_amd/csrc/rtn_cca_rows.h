@@ -1,6 +1,7 @@
 // rtn_cca_rows.h — the device text that the row kernels of scan analysis (csrc/rtn_cca.hip) and of table structure
 // (csrc/rtn_lattice.hip) share: the tile of the box-mean threshold, the workgroup prefix sum, the binary window step on
-// 64-bit masks, the byte transpose through LDS and the row opening.  Device code only; every file that includes it gets kernels of its own.
+// 64-bit masks, the byte transpose through LDS and the row opening, and the host launch of the last two.  Every file that includes it gets
+// kernels of its own.
 #pragma once
 #include "rtn_cca.h"
 
@@ -111,6 +112,19 @@ __global__ __launch_bounds__(CCA_ROW_THREADS) void open_rows_kernel(const CRows*
     bits = window_step(bits, x0, cnt, n, m.L, m.L / 2, false, P, wave_sums);
     uint8_t* dst = m.dst + (size_t)blockIdx.x * n;
     for (int i = 0; i < cnt; ++i) dst[x0 + i] = (bits >> i) & 1 ? 255 : 0;
+}
+
+// The middle of the two line-mask pipelines on the handle's stream (host; the includer has rtn_internal.h): rows[0 .. n) transposed,
+// then rows[n .. 3 n) opened.  No image is larger than max_h x max_w; *t_tiles receives the 32x32 tiles of that size, for the
+// caller's own last launch.
+inline int launch_transpose_open(rtn_ctx* h, const CRows* rows, int n, int max_h, int max_w, unsigned* t_tiles) {
+    *t_tiles = (unsigned)((max_w + 31) / 32) * (unsigned)((max_h + 31) / 32);
+    const int longest = max_h > max_w ? max_h : max_w;
+    transpose_kernel<<<dim3(*t_tiles, (unsigned)n), dim3(CCA_PIX_THREADS), 0, h->stream>>>(rows);
+    RTN_CHECK_LAUNCH(h, "transpose_kernel");
+    open_rows_kernel<<<dim3((unsigned)longest, (unsigned)(2 * n)), dim3(CCA_ROW_THREADS), row_lds_bytes(longest), h->stream>>>(rows + n);
+    RTN_CHECK_LAUNCH(h, "open_rows_kernel");
+    return RTN_OK;
 }
 
 }  // namespace

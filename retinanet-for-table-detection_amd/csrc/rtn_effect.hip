@@ -14,8 +14,7 @@
 // (rtn_effect.h).
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_effect.h"
 
 namespace {
@@ -146,16 +145,16 @@ __global__ __launch_bounds__(EFX_THREADS) void pixels_kernel(const EfxPage* page
 }
 
 // ---- workspace: the page table, the tables, the column sums -----------------------------------------------------------------------
-struct EfxLayout { size_t tables, sums, sums_bytes, total; };
+struct EfxLayout { size_t pages, tables, sums, sums_bytes; };
 
-EfxLayout ws_layout(int n, const int32_t* widths) {
+EfxLayout ws_layout(rtn_stage& st, int n, const int32_t* widths) {
     EfxLayout l;
-    l.tables = (size_t)rtn_align256((long long)n * (long long)sizeof(EfxPage));
-    l.sums = l.tables + (size_t)rtn_align256((long long)n * EFX_TABLE_BYTES);
-    long long cols = 0;
+    l.pages = st.reserve((int64_t)n * sizeof(EfxPage));
+    l.tables = st.reserve((int64_t)n * EFX_TABLE_BYTES);
+    int64_t cols = 0;
     for (int i = 0; i < n; ++i) cols += 3LL * widths[i];
-    l.sums_bytes = (size_t)rtn_align256(cols * 4);
-    l.total = l.sums + l.sums_bytes;
+    l.sums = st.reserve(cols * 4);
+    l.sums_bytes = st.bytes() - l.sums;
     return l;
 }
 
@@ -164,7 +163,9 @@ EfxLayout ws_layout(int n, const int32_t* widths) {
 // rtn_visual_effect_*: see include/rtn.h
 extern "C" size_t rtn_visual_effect_workspace_bytes(int n, const int32_t* heights, const int32_t* widths) {
     if (efx_check_sizes(n, heights, widths)) return 0;
-    return ws_layout(n, widths).total;
+    rtn_stage st;
+    ws_layout(st, n, widths);
+    return st.bytes();
 }
 
 extern "C" int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
@@ -172,12 +173,12 @@ extern "C" int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const*
                                     size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     std::vector<EfxPage> table((size_t)(n > 0 && n <= EFX_MAX_PAGES ? n : 0));
-    if (const char* why = efx_plan(n, pages, heights, widths, params, flags, outs, true, table.data()))
-        return rtn_fail_host(h, RTN_EINVAL, "rtn_visual_effect_u8: %s", why);
+    RTN_PLAN(h, "rtn_visual_effect_u8", efx_plan(n, pages, heights, widths, params, flags, outs, true, table.data()));
     if (n == 0) return RTN_OK;
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "rtn_visual_effect_u8: the workspace must be 256-byte aligned");
-    const EfxLayout l = ws_layout(n, widths);
-    if (workspace_bytes < l.total) return rtn_fail(h, RTN_ENOMEM, "rtn_visual_effect_u8: workspace %zu < %zu bytes", workspace_bytes, l.total);
+    rtn_stage st;
+    const EfxLayout l = ws_layout(st, n, widths);
+    st.put(l.pages, table);
+    if (const int rc = st.commit(h, "rtn_visual_effect_u8", workspace, workspace_bytes)) return rc;
     // the grids: the largest page decides, smaller pages' spare workgroups return at once
     unsigned sum_x = 0, sum_y = 0, pix_x = 0;
     for (const EfxPage& e : table) {
@@ -189,19 +190,17 @@ extern "C" int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const*
         }
         pix_x = std::max(pix_x, (unsigned)((npix + EFX_BLOCK_PIXELS - 1) / EFX_BLOCK_PIXELS));
     }
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    RTN_HIP(h, hipMemcpyAsync(ws, table.data(), table.size() * sizeof(EfxPage), hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipStreamSynchronize(h->stream));                             // the host image lives in this call
-    const EfxPage* t = reinterpret_cast<const EfxPage*>(ws);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(ws + l.sums);
+    const EfxPage* t = st.at<const EfxPage>(l.pages);
+    uint32_t* sums = st.at<uint32_t>(l.sums);
+    uint8_t* tabs = st.at<uint8_t>(l.tables);
     if (sum_x) {
         RTN_HIP(h, hipMemsetAsync(sums, 0, l.sums_bytes, h->stream));
         colsum_kernel<<<dim3(sum_x, sum_y, (unsigned)n), dim3(EFX_THREADS), 0, h->stream>>>(t, sums);
         RTN_CHECK_LAUNCH(h, "colsum_kernel");
     }
-    tables_kernel<<<dim3((unsigned)n), dim3(EFX_THREADS), 0, h->stream>>>(t, sums, ws + l.tables);
+    tables_kernel<<<dim3((unsigned)n), dim3(EFX_THREADS), 0, h->stream>>>(t, sums, tabs);
     RTN_CHECK_LAUNCH(h, "tables_kernel");
-    pixels_kernel<<<dim3(pix_x, (unsigned)n), dim3(EFX_THREADS), 0, h->stream>>>(t, ws + l.tables);
+    pixels_kernel<<<dim3(pix_x, (unsigned)n), dim3(EFX_THREADS), 0, h->stream>>>(t, tabs);
     RTN_CHECK_LAUNCH(h, "pixels_kernel");
     return RTN_OK;
 }
@@ -210,8 +209,7 @@ extern "C" int rtn_visual_effect_u8(rtn_handle_t h, int n, const uint8_t* const*
 extern "C" int rtn_visual_effect_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
                                       const double* params, const uint32_t* flags, uint8_t* const* outs) {
     std::vector<EfxPage> table((size_t)(n > 0 && n <= EFX_MAX_PAGES ? n : 0));
-    if (const char* why = efx_plan(n, pages, heights, widths, params, flags, outs, false, table.data()))
-        return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_visual_effect_host: %s", why);
+    RTN_PLAN(nullptr, "rtn_visual_effect_host", efx_plan(n, pages, heights, widths, params, flags, outs, false, table.data()));
     int32_t sdiv[256], hdiv[256];
     for (int i = 0; i < 256; ++i) {
         sdiv[i] = hdr_sdiv(i);

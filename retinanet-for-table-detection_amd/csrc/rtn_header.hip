@@ -13,8 +13,7 @@
 // The per-element rules are the text the CPU twins run (rtn_header.h).
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_header.h"
 
 namespace {
@@ -195,12 +194,6 @@ __global__ __launch_bounds__(HDR_PIX_THREADS) void patches_kernel(const HCrop* c
 }
 
 // ---- argument checks and tables -------------------------------------------------------------------------------------------------
-size_t ws_layout(int n_crops, int n_patches, size_t* off_patches) {
-    const size_t pos = (size_t)rtn_align256((long long)n_crops * (long long)sizeof(HCrop));
-    if (off_patches) *off_patches = pos;
-    return pos + (size_t)rtn_align256((long long)n_patches * (long long)sizeof(HPatch));
-}
-
 struct HPlan {
     std::vector<HCrop> crops;
     std::vector<HPatch> patches;
@@ -270,22 +263,14 @@ const char* plan_patches(int n_patches, const int32_t* patch_crop, const uint8_t
     return nullptr;
 }
 
-// the tables into the workspace (one copy, for which the call waits: the host image lives in this call)
-int upload(rtn_handle_t h, const char* name, const HPlan& pl, void* workspace, size_t workspace_bytes, const HCrop** crops,
-           const HPatch** patches) {
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "%s: the workspace must be 256-byte aligned", name);
-    size_t off_patches;
-    const size_t need = ws_layout((int)pl.crops.size(), (int)pl.patches.size(), &off_patches);
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
-    std::vector<uint8_t> image(need, 0);
-    memcpy(image.data(), pl.crops.data(), pl.crops.size() * sizeof(HCrop));
-    if (!pl.patches.empty()) memcpy(image.data() + off_patches, pl.patches.data(), pl.patches.size() * sizeof(HPatch));
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    RTN_HIP(h, hipMemcpyAsync(ws, image.data(), need, hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipStreamSynchronize(h->stream));
-    *crops = reinterpret_cast<const HCrop*>(ws);
-    if (patches) *patches = reinterpret_cast<const HPatch*>(ws + off_patches);
-    return RTN_OK;
+// the workspace: the crop table at 0, then the patch table -> the patch table's offset; with a plan, its two tables are staged
+size_t ws_layout(rtn_stage& st, size_t n_crops, size_t n_patches, const HPlan* pl) {
+    const size_t crops = st.reserve((int64_t)(n_crops * sizeof(HCrop))), patches = st.reserve((int64_t)(n_patches * sizeof(HPatch)));
+    if (pl) {
+        st.put(crops, pl->crops);
+        st.put(patches, pl->patches);
+    }
+    return patches;
 }
 
 unsigned pixel_blocks(const HPlan& pl) { return (unsigned)(((int64_t)pl.max_dh * HDR_W + HDR_PIX_THREADS - 1) / HDR_PIX_THREADS); }
@@ -295,22 +280,23 @@ unsigned pixel_blocks(const HPlan& pl) { return (unsigned)(((int64_t)pl.max_dh *
 // rtn_header_*: see include/rtn.h
 extern "C" size_t rtn_header_workspace_bytes(int n_crops, int n_patches) {
     if (n_crops < 0 || n_patches < 0) return 0;
-    return ws_layout(n_crops, n_patches, nullptr);
+    rtn_stage st;
+    ws_layout(st, (size_t)n_crops, (size_t)n_patches, nullptr);
+    return st.bytes();
 }
-
-#define HDR_PLAN(h, name, expr)                                                           \
-    if (const char* why_ = (expr)) return rtn_fail_host((h), RTN_EINVAL, "%s: %s", name, why_)
 
 extern "C" int rtn_header_sample(rtn_handle_t h, int n, const uint8_t* const* crops, const int32_t* heights, const int32_t* widths,
                                  const int32_t* dst_heights, const int64_t* offsets, uint8_t* hsv, size_t hsv_bytes, void* workspace,
                                  size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     HPlan pl;
-    HDR_PLAN(h, "rtn_header_sample", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
-    HDR_PLAN(h, "rtn_header_sample", plan_sample(n, crops, heights, widths, &pl));
+    RTN_PLAN(h, "rtn_header_sample", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
+    RTN_PLAN(h, "rtn_header_sample", plan_sample(n, crops, heights, widths, &pl));
     if (n == 0) return RTN_OK;
-    const HCrop* t;
-    if (const int rc = upload(h, "rtn_header_sample", pl, workspace, workspace_bytes, &t, nullptr)) return rc;
+    rtn_stage st;
+    ws_layout(st, pl.crops.size(), pl.patches.size(), &pl);
+    if (const int rc = st.commit(h, "rtn_header_sample", workspace, workspace_bytes)) return rc;
+    const HCrop* t = st.at<const HCrop>(0);
     sample_kernel<<<dim3(pixel_blocks(pl), (unsigned)n), dim3(HDR_PIX_THREADS), 0, h->stream>>>(t, hsv);
     RTN_CHECK_LAUNCH(h, "sample_kernel");
     return RTN_OK;
@@ -322,13 +308,15 @@ extern "C" int rtn_header_cluster(rtn_handle_t h, int n, const int32_t* dst_heig
                                   size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     HPlan pl;
-    HDR_PLAN(h, "rtn_header_cluster", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
-    HDR_PLAN(h, "rtn_header_cluster", plan_labels(pl, labels, labels_bytes, 3));
+    RTN_PLAN(h, "rtn_header_cluster", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
+    RTN_PLAN(h, "rtn_header_cluster", plan_labels(pl, labels, labels_bytes, 3));
     if (max_iter < 1 || (n && (!centres || !counts || !passes || !distortion_fx)))
         return rtn_fail(h, RTN_EINVAL, "rtn_header_cluster: max_iter >= 1 and the four per-k outputs expected");
     if (n == 0) return RTN_OK;
-    const HCrop* t;
-    if (const int rc = upload(h, "rtn_header_cluster", pl, workspace, workspace_bytes, &t, nullptr)) return rc;
+    rtn_stage st;
+    ws_layout(st, pl.crops.size(), pl.patches.size(), &pl);
+    if (const int rc = st.commit(h, "rtn_header_cluster", workspace, workspace_bytes)) return rc;
+    const HCrop* t = st.at<const HCrop>(0);
     cluster_kernel<<<dim3((unsigned)n), dim3(HDR_THREADS), 0, h->stream>>>(t, hsv, max_iter, centres, counts, passes, distortion_fx, labels);
     RTN_CHECK_LAUNCH(h, "cluster_kernel");
     return RTN_OK;
@@ -339,13 +327,15 @@ extern "C" int rtn_header_stats(rtn_handle_t h, int n, const int32_t* dst_height
                                 void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     HPlan pl;
-    HDR_PLAN(h, "rtn_header_stats", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
-    HDR_PLAN(h, "rtn_header_stats", plan_labels(pl, labels, labels_bytes, 3));
-    HDR_PLAN(h, "rtn_header_stats", plan_ks(ks, &pl));
+    RTN_PLAN(h, "rtn_header_stats", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
+    RTN_PLAN(h, "rtn_header_stats", plan_labels(pl, labels, labels_bytes, 3));
+    RTN_PLAN(h, "rtn_header_stats", plan_ks(ks, &pl));
     if (n && !hist) return rtn_fail(h, RTN_EINVAL, "rtn_header_stats: the histogram output expected");
     if (n == 0) return RTN_OK;
-    const HCrop* t;
-    if (const int rc = upload(h, "rtn_header_stats", pl, workspace, workspace_bytes, &t, nullptr)) return rc;
+    rtn_stage st;
+    ws_layout(st, pl.crops.size(), pl.patches.size(), &pl);
+    if (const int rc = st.commit(h, "rtn_header_stats", workspace, workspace_bytes)) return rc;
+    const HCrop* t = st.at<const HCrop>(0);
     stats_kernel<<<dim3((unsigned)n), dim3(HDR_THREADS), 0, h->stream>>>(t, hsv, labels, hist);
     RTN_CHECK_LAUNCH(h, "stats_kernel");
     return RTN_OK;
@@ -357,12 +347,14 @@ extern "C" int rtn_header_patches(rtn_handle_t h, int n, const int32_t* dst_heig
                                   size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     HPlan pl;
-    HDR_PLAN(h, "rtn_header_patches", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
-    HDR_PLAN(h, "rtn_header_patches", plan_patches(n_patches, patch_crop, low, high, out_offsets, out, out_bytes, &pl));
+    RTN_PLAN(h, "rtn_header_patches", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 3));
+    RTN_PLAN(h, "rtn_header_patches", plan_patches(n_patches, patch_crop, low, high, out_offsets, out, out_bytes, &pl));
     if (n_patches == 0) return RTN_OK;
-    const HCrop* t;
-    const HPatch* tp;
-    if (const int rc = upload(h, "rtn_header_patches", pl, workspace, workspace_bytes, &t, &tp)) return rc;
+    rtn_stage st;
+    const size_t off_patches = ws_layout(st, pl.crops.size(), pl.patches.size(), &pl);
+    if (const int rc = st.commit(h, "rtn_header_patches", workspace, workspace_bytes)) return rc;
+    const HCrop* t = st.at<const HCrop>(0);
+    const HPatch* tp = st.at<const HPatch>(off_patches);
     patches_kernel<<<dim3(pixel_blocks(pl), (unsigned)n_patches), dim3(HDR_PIX_THREADS), 0, h->stream>>>(t, tp, hsv, out);
     RTN_CHECK_LAUNCH(h, "patches_kernel");
     return RTN_OK;
@@ -372,8 +364,8 @@ extern "C" int rtn_header_patches(rtn_handle_t h, int n, const int32_t* dst_heig
 extern "C" int rtn_header_sample_host(int n, const uint8_t* const* crops, const int32_t* heights, const int32_t* widths,
                                       const int32_t* dst_heights, const int64_t* offsets, uint8_t* hsv, size_t hsv_bytes) {
     HPlan pl;
-    HDR_PLAN(nullptr, "rtn_header_sample_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
-    HDR_PLAN(nullptr, "rtn_header_sample_host", plan_sample(n, crops, heights, widths, &pl));
+    RTN_PLAN(nullptr, "rtn_header_sample_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
+    RTN_PLAN(nullptr, "rtn_header_sample_host", plan_sample(n, crops, heights, widths, &pl));
     for (const HCrop& c : pl.crops)
         for (int64_t i = 0; i < (int64_t)c.dh * HDR_W; ++i) hdr_sample_point(c, i, hsv);
     return RTN_OK;
@@ -383,8 +375,8 @@ extern "C" int rtn_header_cluster_host(int n, const int32_t* dst_heights, const 
                                        int max_iter, float* centres, uint32_t* counts, int32_t* passes, uint64_t* distortion_fx,
                                        uint8_t* labels, size_t labels_bytes) {
     HPlan pl;
-    HDR_PLAN(nullptr, "rtn_header_cluster_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
-    HDR_PLAN(nullptr, "rtn_header_cluster_host", plan_labels(pl, labels, labels_bytes, 0));
+    RTN_PLAN(nullptr, "rtn_header_cluster_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
+    RTN_PLAN(nullptr, "rtn_header_cluster_host", plan_labels(pl, labels, labels_bytes, 0));
     if (max_iter < 1 || (n && (!centres || !counts || !passes || !distortion_fx)))
         return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_header_cluster_host: max_iter >= 1 and the four per-k outputs expected");
     for (int i = 0; i < n; ++i) {
@@ -399,9 +391,9 @@ extern "C" int rtn_header_cluster_host(int n, const int32_t* dst_heights, const 
 extern "C" int rtn_header_stats_host(int n, const int32_t* dst_heights, const int64_t* offsets, const int32_t* ks, const uint8_t* hsv,
                                      size_t hsv_bytes, const uint8_t* labels, size_t labels_bytes, uint32_t* hist) {
     HPlan pl;
-    HDR_PLAN(nullptr, "rtn_header_stats_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
-    HDR_PLAN(nullptr, "rtn_header_stats_host", plan_labels(pl, labels, labels_bytes, 0));
-    HDR_PLAN(nullptr, "rtn_header_stats_host", plan_ks(ks, &pl));
+    RTN_PLAN(nullptr, "rtn_header_stats_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
+    RTN_PLAN(nullptr, "rtn_header_stats_host", plan_labels(pl, labels, labels_bytes, 0));
+    RTN_PLAN(nullptr, "rtn_header_stats_host", plan_ks(ks, &pl));
     if (n && !hist) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_header_stats_host: the histogram output expected");
     for (int i = 0; i < n; ++i) {
         const HCrop& c = pl.crops[i];
@@ -422,8 +414,8 @@ extern "C" int rtn_header_patches_host(int n, const int32_t* dst_heights, const 
                                        int n_patches, const int32_t* patch_crop, const uint8_t* low, const uint8_t* high,
                                        const int64_t* out_offsets, uint8_t* out, size_t out_bytes) {
     HPlan pl;
-    HDR_PLAN(nullptr, "rtn_header_patches_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
-    HDR_PLAN(nullptr, "rtn_header_patches_host", plan_patches(n_patches, patch_crop, low, high, out_offsets, out, out_bytes, &pl));
+    RTN_PLAN(nullptr, "rtn_header_patches_host", plan_crops(n, dst_heights, offsets, hsv_bytes, hsv, &pl, 0));
+    RTN_PLAN(nullptr, "rtn_header_patches_host", plan_patches(n_patches, patch_crop, low, high, out_offsets, out, out_bytes, &pl));
     for (const HPatch& p : pl.patches) {
         const HCrop& c = pl.crops[p.crop];
         for (int64_t i = 0; i < (int64_t)c.dh * HDR_W; ++i)

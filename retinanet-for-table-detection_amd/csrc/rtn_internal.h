@@ -48,18 +48,18 @@ inline int rtn_fail(rtn_ctx* h, int code, const char* fmt, ...) {
                             hipGetErrorString(e_));                                        \
     } while (0)
 
-// Launch `Kernel` with `lds` bytes of dynamic LDS on the handle's stream.  The first launch of a kernel instance on a device raises that
+// Launch `Kernel(args...)` with `lds` bytes of dynamic LDS on the handle's stream.  The first launch of a kernel instance on a device raises that
 // instance's dynamic-LDS limit to `lds_limit` (the 64 KiB default refuses the launch).  The template is keyed on the kernel itself, so
 // every instance owns a flag word, one bit per device.  The caller checks the launch (RTN_CHECK_LAUNCH).
-template <auto Kernel, class Params>
-inline int rtn_launch_lds(rtn_ctx* h, dim3 grid, dim3 block, unsigned lds, int lds_limit, const Params& p) {
+template <auto Kernel, class... Args>
+inline int rtn_launch_lds(rtn_ctx* h, dim3 grid, dim3 block, unsigned lds, int lds_limit, const Args&... args) {
     static std::atomic<unsigned long long> attr_set{0ull};
     const unsigned long long bit = 1ull << (h->device & 63);
     if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
         RTN_HIP(h, hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit));
         attr_set.fetch_or(bit, std::memory_order_relaxed);
     }
-    hipLaunchKernelGGL(Kernel, grid, block, lds, h->stream, p);
+    hipLaunchKernelGGL(Kernel, grid, block, lds, h->stream, args...);
     return RTN_OK;
 }
 

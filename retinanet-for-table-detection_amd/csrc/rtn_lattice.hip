@@ -15,8 +15,7 @@
 // The per-element rules, the argument checks and the CPU twins' bodies are in rtn_lattice.h.
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_lattice.h"
 #include "rtn_cca_rows.h"
 
@@ -151,7 +150,6 @@ __global__ __launch_bounds__(LAT_THREADS) void cell_kernel(const LCell* cells, c
 }
 
 // ---- workspace: the tables first, then (rtn_lattice_masks only) two planes of the crops' pixels ---------------------------------------
-size_t a256(int64_t v) { return (size_t)rtn_align256((long long)v); }
 struct Sizes { int64_t pixels = 0; int max_w = 0, max_h = 0; };
 Sizes sizes_of(int n_boxes, const int32_t* crops) {
     Sizes s;
@@ -162,36 +160,29 @@ Sizes sizes_of(int n_boxes, const int32_t* crops) {
     }
     return s;
 }
-size_t mask_tables_bytes(int n_boxes) { return a256((int64_t)n_boxes * sizeof(LCrop)) + a256((int64_t)n_boxes * 3 * sizeof(CRows)); }
-size_t item_tables_bytes(int n_boxes, int64_t n_items) { return a256(std::max<int64_t>((int64_t)n_boxes * sizeof(LProf), n_items * (int64_t)sizeof(LEdge))); }
-
-int check_ws(rtn_handle_t h, const char* name, void* workspace, size_t workspace_bytes, size_t need) {
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "%s: the workspace must be 256-byte aligned", name);
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
-    return RTN_OK;
+struct MaskLayout { size_t crops, rows, bwT, vT; };
+MaskLayout mask_layout(rtn_stage& st, int n_boxes, int64_t pixels) {
+    MaskLayout l;
+    l.crops = st.reserve((int64_t)n_boxes * sizeof(LCrop));
+    l.rows = st.reserve((int64_t)n_boxes * 3 * sizeof(CRows));
+    l.bwT = st.reserve(pixels);
+    l.vT = st.reserve(pixels);
+    return l;
 }
-// a host table to the workspace at `pos`; the call waits for the copy (the host image lives in this call)
-template <class T>
-int upload(rtn_handle_t h, const std::vector<T>& table, uint8_t* ws, size_t pos, const T** out) {
-    if (!table.empty()) {
-        RTN_HIP(h, hipMemcpyAsync(ws + pos, table.data(), table.size() * sizeof(T), hipMemcpyHostToDevice, h->stream));
-        RTN_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    *out = reinterpret_cast<const T*>(ws + pos);
-    return RTN_OK;
+// the one table of the profile, edge and cell entries lies in room for n_boxes LProf or n_items LEdge (an LCell is as large) -> its offset
+size_t items_room(rtn_stage& st, int n_boxes, int64_t n_items) {
+    return st.reserve(std::max<int64_t>((int64_t)n_boxes * sizeof(LProf), n_items * (int64_t)sizeof(LEdge)));
 }
-unsigned blocks_for(int64_t items, int per) { return (unsigned)((items + per - 1) / per); }
 
 }  // namespace
-
-#define LAT_PLAN(h, name, expr)                                                           \
-    if (const char* why_ = (expr)) return rtn_fail_host((h), RTN_EINVAL, "%s: %s", name, why_)
 
 // rtn_lattice_*: see include/rtn.h
 extern "C" size_t rtn_lattice_workspace_bytes(int n_boxes, const int32_t* crops, int64_t n_items) {
     if (n_boxes < 0 || n_boxes > LAT_MAX_BOXES || n_items < 0 || (n_boxes && !crops)) return 0;
-    const size_t masks = mask_tables_bytes(n_boxes) + 2 * a256(sizes_of(n_boxes, crops).pixels);
-    return std::max(masks, item_tables_bytes(n_boxes, n_items));
+    rtn_stage masks, items;
+    mask_layout(masks, n_boxes, sizes_of(n_boxes, crops).pixels);
+    items_room(items, n_boxes, n_items);
+    return std::max(masks.bytes(), items.bytes());
 }
 
 extern "C" int rtn_lattice_masks(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
@@ -200,17 +191,17 @@ extern "C" int rtn_lattice_masks(rtn_handle_t h, int n, const uint8_t* const* pa
                                  void* workspace, size_t workspace_bytes) {
     if (!h) return RTN_EINVAL;
     std::vector<LCrop> cr;
-    LAT_PLAN(h, "rtn_lattice_masks", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(h, "rtn_lattice_masks", lat_plan_pages(n, pages, heights, widths, channels, n_boxes, box_page, line_scale, &cr));
+    RTN_PLAN(h, "rtn_lattice_masks", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(h, "rtn_lattice_masks", lat_plan_pages(n, pages, heights, widths, channels, n_boxes, box_page, line_scale, &cr));
     if (n_boxes && (!bw || !hm || !vm || !ink)) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_masks: the four mask buffers expected");
     if (n_boxes == 0) return RTN_OK;
     const Sizes s = sizes_of(n_boxes, crops);
-    const size_t tables = mask_tables_bytes(n_boxes);
-    if (const int rc = check_ws(h, "rtn_lattice_masks", workspace, workspace_bytes, tables + 2 * a256(s.pixels))) return rc;
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    rtn_stage st;
+    const MaskLayout l = mask_layout(st, n_boxes, s.pixels);
+    if (const int rc = st.check(h, "rtn_lattice_masks", workspace, workspace_bytes)) return rc;
     // two planes beside the outputs: bw's transpose and its opening; the planes are packed, the crops keep the caller's offsets
-    uint8_t* bwT = ws + tables;
-    uint8_t* vT = bwT + a256(s.pixels);
+    uint8_t* bwT = st.at<uint8_t>(l.bwT);
+    uint8_t* vT = st.at<uint8_t>(l.vT);
     std::vector<CRows> rows((size_t)3 * n_boxes);
     int64_t pos = 0;
     for (int j = 0; j < n_boxes; ++j) {
@@ -221,19 +212,14 @@ extern "C" int rtn_lattice_masks(rtn_handle_t h, int n, const uint8_t* const* pa
         rows[2 * n_boxes + j] = CRows{bwT + pos, vT + pos, c.w, c.h, lat_window(c.h, line_scale), 0};       // open the columns
         pos += (int64_t)c.w * c.h;
     }
-    const LCrop* tc;
-    const CRows* tr;
-    if (const int rc = upload(h, cr, ws, 0, &tc)) return rc;
-    if (const int rc = upload(h, rows, ws, a256((int64_t)n_boxes * sizeof(LCrop)), &tr)) return rc;
-    const unsigned bw_tiles = blocks_for(s.max_w, CCA_BW_TW) * blocks_for(s.max_h, CCA_BW_TH);
-    const unsigned t_tiles = blocks_for(s.max_w, 32) * blocks_for(s.max_h, 32);
-    const int longest = std::max(s.max_h, s.max_w);
-    crop_bw_kernel<<<dim3(bw_tiles, (unsigned)n_boxes), dim3(LAT_THREADS), 0, h->stream>>>(tc, bw);
+    st.put(l.crops, cr);
+    st.put(l.rows, rows);
+    if (const int rc = st.upload(h)) return rc;
+    const LCrop* tc = st.at<const LCrop>(l.crops);
+    unsigned t_tiles;
+    crop_bw_kernel<<<dim3(rtn_blocks_for(s.max_w, CCA_BW_TW) * rtn_blocks_for(s.max_h, CCA_BW_TH), (unsigned)n_boxes), dim3(LAT_THREADS), 0, h->stream>>>(tc, bw);
     RTN_CHECK_LAUNCH(h, "crop_bw_kernel");
-    transpose_kernel<<<dim3(t_tiles, (unsigned)n_boxes), dim3(CCA_PIX_THREADS), 0, h->stream>>>(tr);
-    RTN_CHECK_LAUNCH(h, "transpose_kernel");
-    open_rows_kernel<<<dim3((unsigned)longest, (unsigned)(2 * n_boxes)), dim3(CCA_ROW_THREADS), row_lds_bytes(longest), h->stream>>>(tr + n_boxes);
-    RTN_CHECK_LAUNCH(h, "open_rows_kernel");
+    if (const int rc = launch_transpose_open(h, st.at<const CRows>(l.rows), n_boxes, s.max_h, s.max_w, &t_tiles)) return rc;
     finish_kernel<<<dim3(t_tiles, (unsigned)n_boxes), dim3(LAT_THREADS), 0, h->stream>>>(tc, vT, bw, hm, vm, ink);
     RTN_CHECK_LAUNCH(h, "finish_kernel");
     return RTN_OK;
@@ -245,16 +231,16 @@ extern "C" int rtn_lattice_profiles(rtn_handle_t h, int n_boxes, const int32_t* 
     if (!h) return RTN_EINVAL;
     std::vector<LCrop> cr;
     std::vector<LProf> pr;
-    LAT_PLAN(h, "rtn_lattice_profiles", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(h, "rtn_lattice_profiles", lat_plan_profiles(cr, prof_offsets, profiles_count, &pr));
+    RTN_PLAN(h, "rtn_lattice_profiles", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(h, "rtn_lattice_profiles", lat_plan_profiles(cr, prof_offsets, profiles_count, &pr));
     if (n_boxes && (!hm || !vm || !ink || !profiles)) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_profiles: the three masks and the profiles expected");
     if (n_boxes == 0) return RTN_OK;
-    if (const int rc = check_ws(h, "rtn_lattice_profiles", workspace, workspace_bytes, item_tables_bytes(n_boxes, 0))) return rc;
-    const LProf* tp;
-    if (const int rc = upload(h, pr, static_cast<uint8_t*>(workspace), 0, &tp)) return rc;
+    rtn_stage st;
+    st.put(items_room(st, n_boxes, 0), pr);
+    if (const int rc = st.commit(h, "rtn_lattice_profiles", workspace, workspace_bytes)) return rc;
     unsigned groups = 1;
-    for (const LProf& p : pr) groups = std::max(groups, (unsigned)p.row_groups + blocks_for(p.w, LAT_COLS_PER_GROUP));
-    profile_kernel<<<dim3(groups, (unsigned)n_boxes), dim3(LAT_THREADS), 0, h->stream>>>(tp, hm, vm, ink, profiles);
+    for (const LProf& p : pr) groups = std::max(groups, (unsigned)p.row_groups + rtn_blocks_for(p.w, LAT_COLS_PER_GROUP));
+    profile_kernel<<<dim3(groups, (unsigned)n_boxes), dim3(LAT_THREADS), 0, h->stream>>>(st.at<const LProf>(0), hm, vm, ink, profiles);
     RTN_CHECK_LAUNCH(h, "profile_kernel");
     return RTN_OK;
 }
@@ -268,16 +254,16 @@ extern "C" int rtn_lattice_edges(rtn_handle_t h, int n_boxes, const int32_t* cro
     std::vector<LGrid> gr;
     std::vector<LEdge> ed;
     int64_t need = 0;
-    LAT_PLAN(h, "rtn_lattice_edges", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(h, "rtn_lattice_edges", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
-    LAT_PLAN(h, "rtn_lattice_edges", lat_plan_edges(cr, gr, edge_offsets, line_tol, cover, &need, &ed));
+    RTN_PLAN(h, "rtn_lattice_edges", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(h, "rtn_lattice_edges", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
+    RTN_PLAN(h, "rtn_lattice_edges", lat_plan_edges(cr, gr, edge_offsets, line_tol, cover, &need, &ed));
     if ((uint64_t)need > edges_bytes) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_edges: %lld edges, room for %zu", (long long)need, edges_bytes);
     if (ed.empty()) return RTN_OK;
     if (!hm || !vm || !edges) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_edges: the two masks and the edges expected");
-    if (const int rc = check_ws(h, "rtn_lattice_edges", workspace, workspace_bytes, item_tables_bytes(n_boxes, (int64_t)ed.size()))) return rc;
-    const LEdge* te;
-    if (const int rc = upload(h, ed, static_cast<uint8_t*>(workspace), 0, &te)) return rc;
-    edge_kernel<<<dim3(blocks_for((int64_t)ed.size(), LAT_EDGES_PER_GROUP)), dim3(LAT_THREADS), 0, h->stream>>>(te, (int64_t)ed.size(), hm, vm, cover, edges);
+    rtn_stage st;
+    st.put(items_room(st, n_boxes, (int64_t)ed.size()), ed);
+    if (const int rc = st.commit(h, "rtn_lattice_edges", workspace, workspace_bytes)) return rc;
+    edge_kernel<<<dim3(rtn_blocks_for((int64_t)ed.size(), LAT_EDGES_PER_GROUP)), dim3(LAT_THREADS), 0, h->stream>>>(st.at<const LEdge>(0), (int64_t)ed.size(), hm, vm, cover, edges);
     RTN_CHECK_LAUNCH(h, "edge_kernel");
     return RTN_OK;
 }
@@ -291,17 +277,17 @@ extern "C" int rtn_lattice_cells(rtn_handle_t h, int n_boxes, const int32_t* cro
     std::vector<LGrid> gr;
     std::vector<LCell> ce;
     int64_t need = 0;
-    LAT_PLAN(h, "rtn_lattice_cells", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(h, "rtn_lattice_cells", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
-    LAT_PLAN(h, "rtn_lattice_cells", lat_plan_cells(cr, gr, cell_offsets, &need, &ce));
+    RTN_PLAN(h, "rtn_lattice_cells", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(h, "rtn_lattice_cells", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
+    RTN_PLAN(h, "rtn_lattice_cells", lat_plan_cells(cr, gr, cell_offsets, &need, &ce));
     if ((uint64_t)need > cells_count) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_cells: %lld cells, room for %zu", (long long)need, cells_count);
     if (ce.empty()) return RTN_OK;
     if (ce.size() > 0x7fffffffull) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_cells: %zu cells are more than one launch takes", ce.size());
     if (!ink || !cell_ink || !cell_box) return rtn_fail(h, RTN_EINVAL, "rtn_lattice_cells: the ink mask and the two cell tables expected");
-    if (const int rc = check_ws(h, "rtn_lattice_cells", workspace, workspace_bytes, item_tables_bytes(n_boxes, (int64_t)ce.size()))) return rc;
-    const LCell* tc;
-    if (const int rc = upload(h, ce, static_cast<uint8_t*>(workspace), 0, &tc)) return rc;
-    cell_kernel<<<dim3((unsigned)ce.size()), dim3(LAT_THREADS), 0, h->stream>>>(tc, ink, cell_ink, cell_box);
+    rtn_stage st;
+    st.put(items_room(st, n_boxes, (int64_t)ce.size()), ce);
+    if (const int rc = st.commit(h, "rtn_lattice_cells", workspace, workspace_bytes)) return rc;
+    cell_kernel<<<dim3((unsigned)ce.size()), dim3(LAT_THREADS), 0, h->stream>>>(st.at<const LCell>(0), ink, cell_ink, cell_box);
     RTN_CHECK_LAUNCH(h, "cell_kernel");
     return RTN_OK;
 }
@@ -320,8 +306,8 @@ extern "C" int rtn_lattice_masks_host(int n, const uint8_t* const* pages, const 
                                       int n_boxes, const int32_t* box_page, const int32_t* crops, int line_scale, const int64_t* offsets,
                                       uint8_t* bw, uint8_t* hm, uint8_t* vm, uint8_t* ink, size_t mask_bytes) {
     std::vector<LCrop> cr;
-    LAT_PLAN(nullptr, "rtn_lattice_masks_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(nullptr, "rtn_lattice_masks_host", lat_plan_pages(n, pages, heights, widths, channels, n_boxes, box_page, line_scale, &cr));
+    RTN_PLAN(nullptr, "rtn_lattice_masks_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(nullptr, "rtn_lattice_masks_host", lat_plan_pages(n, pages, heights, widths, channels, n_boxes, box_page, line_scale, &cr));
     if (n_boxes && (!bw || !hm || !vm || !ink)) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_masks_host: the four mask buffers expected");
     std::vector<uint8_t> page_bw;
     for (int i = 0; i < n; ++i) {                                               // a page's threshold once, whatever the number of its boxes
@@ -341,8 +327,8 @@ extern "C" int rtn_lattice_profiles_host(int n_boxes, const int32_t* crops, cons
                                          size_t profiles_count) {
     std::vector<LCrop> cr;
     std::vector<LProf> pr;
-    LAT_PLAN(nullptr, "rtn_lattice_profiles_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(nullptr, "rtn_lattice_profiles_host", lat_plan_profiles(cr, prof_offsets, profiles_count, &pr));
+    RTN_PLAN(nullptr, "rtn_lattice_profiles_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(nullptr, "rtn_lattice_profiles_host", lat_plan_profiles(cr, prof_offsets, profiles_count, &pr));
     if (n_boxes && (!hm || !vm || !ink || !profiles)) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_profiles_host: the three masks and the profiles expected");
     for (const LProf& p : pr) lat_profiles_crop(p, hm, vm, ink, profiles);
     return RTN_OK;
@@ -356,9 +342,9 @@ extern "C" int rtn_lattice_edges_host(int n_boxes, const int32_t* crops, const i
     std::vector<LGrid> gr;
     std::vector<LEdge> ed;
     int64_t need = 0;
-    LAT_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
-    LAT_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_edges(cr, gr, edge_offsets, line_tol, cover, &need, &ed));
+    RTN_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
+    RTN_PLAN(nullptr, "rtn_lattice_edges_host", lat_plan_edges(cr, gr, edge_offsets, line_tol, cover, &need, &ed));
     if ((uint64_t)need > edges_bytes) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_edges_host: %lld edges, room for %zu", (long long)need, edges_bytes);
     if (!ed.empty() && (!hm || !vm || !edges)) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_edges_host: the two masks and the edges expected");
     for (const LEdge& e : ed) edges[e.out] = lat_edge(e, hm, vm, cover);
@@ -372,9 +358,9 @@ extern "C" int rtn_lattice_cells_host(int n_boxes, const int32_t* crops, const i
     std::vector<LGrid> gr;
     std::vector<LCell> ce;
     int64_t need = 0;
-    LAT_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
-    LAT_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
-    LAT_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_cells(cr, gr, cell_offsets, &need, &ce));
+    RTN_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_crops(n_boxes, crops, offsets, mask_bytes, &cr));
+    RTN_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_grids(cr, R, C, sep_offsets, runs, runs_count, &gr));
+    RTN_PLAN(nullptr, "rtn_lattice_cells_host", lat_plan_cells(cr, gr, cell_offsets, &need, &ce));
     if ((uint64_t)need > cells_count) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_cells_host: %lld cells, room for %zu", (long long)need, cells_count);
     if (!ce.empty() && (!ink || !cell_ink || !cell_box)) return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_lattice_cells_host: the ink mask and the two cell tables expected");
     for (const LCell& c : ce) lat_cell(c, ink, cell_ink, cell_box);

@@ -5,8 +5,7 @@
 // rectangle meet the tile (one operation per thread and pass, positions from wave ballots: no atomics), and then moves the tile in
 // 16-byte destination units (render_unit of rtn_render.h): most tiles collect nothing and are a copy.  The rule, the operation test
 // and the unit are the text the CPU twins run (rtn_render_host, rtn_render_tiles_host).
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_render.h"
 
 namespace {
@@ -51,14 +50,15 @@ __global__ __launch_bounds__(RND_THREADS) void render_kernel(RTables t) {
     }
 }
 
-size_t render_ws_layout(int n_pages, int n_ops, int n_out, size_t* off_ops, size_t* off_outs, size_t* off_tiles) {
-    size_t pos = (size_t)rtn_align256((long long)n_pages * (long long)sizeof(RPage));
-    if (off_ops) *off_ops = pos;
-    pos += (size_t)rtn_align256((long long)n_ops * (long long)sizeof(ROp));
-    if (off_outs) *off_outs = pos;
-    pos += (size_t)rtn_align256((long long)n_out * (long long)sizeof(ROut));
-    if (off_tiles) *off_tiles = pos;
-    return pos + (size_t)rtn_align256(((long long)n_out + 1) * 4);
+// the workspace: the page, operation and output tables, then the first tile of every output
+struct Layout { size_t pages, ops, outs, tiles; };
+Layout render_ws_layout(rtn_stage& st, int n_pages, int n_ops, int n_out) {
+    Layout l;
+    l.pages = st.reserve((int64_t)n_pages * sizeof(RPage));
+    l.ops = st.reserve((int64_t)n_ops * sizeof(ROp));
+    l.outs = st.reserve((int64_t)n_out * sizeof(ROut));
+    l.tiles = st.reserve(((int64_t)n_out + 1) * 4);
+    return l;
 }
 
 int render_host_call(const RArgs& a, bool tiles, const char* name) {
@@ -77,7 +77,9 @@ int render_host_call(const RArgs& a, bool tiles, const char* name) {
 // rtn_render_workspace_bytes / rtn_render_pages / rtn_render_host / rtn_render_tiles_host: see include/rtn.h
 extern "C" size_t rtn_render_workspace_bytes(int n_pages, int n_ops, int n_out) {
     if (n_pages < 0 || n_ops < 0 || n_out < 0) return 0;
-    return render_ws_layout(n_pages, n_ops, n_out, nullptr, nullptr, nullptr);
+    rtn_stage st;
+    render_ws_layout(st, n_pages, n_ops, n_out);
+    return st.bytes();
 }
 
 extern "C" int rtn_render_pages(rtn_handle_t h, int n_pages, const uint8_t* const* pages, const int32_t* heights,
@@ -94,24 +96,18 @@ extern "C" int rtn_render_pages(rtn_handle_t h, int n_pages, const uint8_t* cons
     const int rc = render_plan(a, &pl, why, sizeof(why));
     if (rc) return rtn_fail(h, rc, "rtn_render_pages: %s", why);
     if (n_out == 0) return RTN_OK;
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "rtn_render_pages: the workspace must be 256-byte aligned");
-    size_t off_ops, off_outs, off_tiles;
-    const size_t need = render_ws_layout(n_pages, n_ops, n_out, &off_ops, &off_outs, &off_tiles);
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_render_pages: workspace %zu < %zu bytes", workspace_bytes, need);
-    // one copy of the four tables; the host image lives in this call, so the call waits for the copy
-    std::vector<uint8_t> image(need, 0);
-    memcpy(image.data(), pl.pages.data(), pl.pages.size() * sizeof(RPage));
-    if (n_ops) memcpy(image.data() + off_ops, pl.ops.data(), pl.ops.size() * sizeof(ROp));
-    memcpy(image.data() + off_outs, pl.outs.data(), pl.outs.size() * sizeof(ROut));
-    memcpy(image.data() + off_tiles, pl.tile_begin.data(), pl.tile_begin.size() * 4);
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    RTN_HIP(h, hipMemcpyAsync(ws, image.data(), need, hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipStreamSynchronize(h->stream));
+    rtn_stage st;
+    const Layout l = render_ws_layout(st, n_pages, n_ops, n_out);
+    st.put(l.pages, pl.pages);
+    st.put(l.ops, pl.ops);
+    st.put(l.outs, pl.outs);
+    st.put(l.tiles, pl.tile_begin);
+    if (const int rc2 = st.commit(h, "rtn_render_pages", workspace, workspace_bytes)) return rc2;
     RTables t;
-    t.pages = reinterpret_cast<const RPage*>(ws);
-    t.ops = reinterpret_cast<const ROp*>(ws + off_ops);
-    t.outs = reinterpret_cast<const ROut*>(ws + off_outs);
-    t.tile_begin = reinterpret_cast<const int32_t*>(ws + off_tiles);
+    t.pages = st.at<const RPage>(l.pages);
+    t.ops = st.at<const ROp>(l.ops);
+    t.outs = st.at<const ROut>(l.outs);
+    t.tile_begin = st.at<const int32_t>(l.tiles);
     t.masks = masks;
     t.out = out;
     t.n_out = n_out; t.lo = pl.lo; t.hi = pl.hi;

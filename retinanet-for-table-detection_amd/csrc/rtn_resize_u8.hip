@@ -14,8 +14,7 @@
 // changes from row to row.  The per-sample rules are the text the CPU twin runs (rtn_resize_u8.h).
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_resize_u8.h"
 
 namespace {
@@ -147,6 +146,9 @@ int forced_path() {
     return v == RSZ_PATH_TILED || v == RSZ_PATH_DIRECT ? v : 0;
 }
 
+// the workspace: the page table alone -> its offset
+size_t page_table_room(rtn_stage& st, int n) { return st.reserve((int64_t)n * sizeof(RszPage)); }
+
 }  // namespace
 
 // rtn_resize_u8_*: see include/rtn.h
@@ -164,7 +166,9 @@ extern "C" int rtn_resize_u8_path(double inv_y) {
 
 extern "C" size_t rtn_resize_u8_workspace_bytes(int n) {
     if (n < 1 || n > RSZ_MAX_PAGES) return 0;
-    return (size_t)rtn_align256((long long)n * (long long)sizeof(RszPage));
+    rtn_stage st;
+    page_table_room(st, n);
+    return st.bytes();
 }
 
 extern "C" int rtn_resize_u8(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths,
@@ -173,15 +177,13 @@ extern "C" int rtn_resize_u8(rtn_handle_t h, int n, const uint8_t* const* pages,
     if (!h) return RTN_EINVAL;
     std::vector<RszPage> table((size_t)(n > 0 && n <= RSZ_MAX_PAGES ? n : 0));
     int64_t tiles = 0;
-    if (const char* why = rsz_plan(n, pages, heights, widths, channels, out_heights, out_widths, inv_x, inv_y, outs, forced_path(), table.data(), &tiles))
-        return rtn_fail_host(h, RTN_EINVAL, "rtn_resize_u8: %s", why);
+    RTN_PLAN(h, "rtn_resize_u8", rsz_plan(n, pages, heights, widths, channels, out_heights, out_widths, inv_x, inv_y, outs, forced_path(), table.data(), &tiles));
     if (n == 0) return RTN_OK;
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "rtn_resize_u8: the workspace must be 256-byte aligned");
-    const size_t need = rtn_resize_u8_workspace_bytes(n);
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_resize_u8: workspace %zu < %zu bytes", workspace_bytes, need);
-    RTN_HIP(h, hipMemcpyAsync(workspace, table.data(), table.size() * sizeof(RszPage), hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipStreamSynchronize(h->stream));                             // the host image lives in this call
-    resize_u8_kernel<<<dim3((unsigned)tiles), dim3(RSZ_THREADS), 0, h->stream>>>(static_cast<const RszPage*>(workspace), n);
+    rtn_stage st;
+    const size_t off = page_table_room(st, n);
+    st.put(off, table);
+    if (const int rc = st.commit(h, "rtn_resize_u8", workspace, workspace_bytes)) return rc;
+    resize_u8_kernel<<<dim3((unsigned)tiles), dim3(RSZ_THREADS), 0, h->stream>>>(st.at<const RszPage>(off), n);
     RTN_CHECK_LAUNCH(h, "resize_u8_kernel");
     return RTN_OK;
 }
@@ -190,7 +192,6 @@ extern "C" int rtn_resize_u8(rtn_handle_t h, int n, const uint8_t* const* pages,
 extern "C" int rtn_resize_u8_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
                                   const int32_t* out_heights, const int32_t* out_widths, const double* inv_x, const double* inv_y,
                                   uint8_t* const* outs) {
-    if (const char* why = rsz_host(n, pages, heights, widths, channels, out_heights, out_widths, inv_x, inv_y, outs, forced_path()))
-        return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_resize_u8_host: %s", why);
+    RTN_PLAN(nullptr, "rtn_resize_u8_host", rsz_host(n, pages, heights, widths, channels, out_heights, out_widths, inv_x, inv_y, outs, forced_path()));
     return RTN_OK;
 }

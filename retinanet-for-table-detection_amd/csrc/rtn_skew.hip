@@ -12,8 +12,7 @@
 //   skew_pick        a workgroup a page: the best angle by the tie rule
 #include <algorithm>
 #include <vector>
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_page_launch.h"
 #include "rtn_skew.h"
 
 namespace {
@@ -236,17 +235,14 @@ __global__ __launch_bounds__(SKW_THREADS) void skew_pick_kernel(const unsigned l
 }
 
 // the workspace: the page table, the shear factors, the histograms, the counts
-struct Layout {
-    size_t table, shear, hist, counts, total;
-};
+struct Layout { size_t table, shear, hist, counts; };
 
-Layout layout_of(int n, int K, int64_t counts_bytes) {
+Layout layout_of(rtn_stage& st, int n, int K, int64_t counts_bytes) {
     Layout l;
-    l.table = 0;
-    l.shear = (size_t)rtn_align256((long long)n * (long long)sizeof(SkwPage));
-    l.hist = l.shear + (size_t)rtn_align256((long long)K * 4);
-    l.counts = l.hist + (size_t)rtn_align256((long long)n * 1024);
-    l.total = l.counts + (size_t)rtn_align256((long long)counts_bytes);
+    l.table = st.reserve((int64_t)n * sizeof(SkwPage));
+    l.shear = st.reserve((int64_t)K * 4);
+    l.hist = st.reserve((int64_t)n * 1024);
+    l.counts = st.reserve(counts_bytes);
     return l;
 }
 
@@ -264,13 +260,15 @@ int64_t counts_bytes_of(int n, const int32_t* heights, const int32_t* widths, in
 // rtn_skew_*: see include/rtn.h
 extern "C" size_t rtn_skew_workspace_bytes(int n, const int32_t* heights, const int32_t* widths, int band, int K) {
     if (n < 1 || skw_check_sizes(n, heights, widths, band, K)) return 0;
-    return layout_of(n, K, counts_bytes_of(n, heights, widths, band, nullptr)).total;
+    rtn_stage st;
+    layout_of(st, n, K, counts_bytes_of(n, heights, widths, band, nullptr));
+    return st.bytes();
 }
 
 extern "C" int rtn_skew_counts_layout(int n, const int32_t* heights, const int32_t* widths, int band, int K, int64_t* offsets) {
     if (!offsets || n < 1 || skw_check_sizes(n, heights, widths, band, K)) return RTN_EINVAL;
-    const int64_t bytes = counts_bytes_of(n, heights, widths, band, offsets);
-    const Layout l = layout_of(n, K, bytes);
+    rtn_stage st;
+    const Layout l = layout_of(st, n, K, counts_bytes_of(n, heights, widths, band, offsets));
     for (int i = 0; i < n; ++i) offsets[i] += (int64_t)l.counts;
     return RTN_OK;
 }
@@ -282,21 +280,18 @@ extern "C" int rtn_skew_estimate(rtn_handle_t h, int n, const uint8_t* const* pa
     std::vector<SkwPage> table((size_t)(n > 0 && n <= SKW_MAX_PAGES ? n : 0));
     int64_t counts_bytes = 0, tiles = 0;
     int max_h = 0, max_nb = 0;
-    if (const char* why = skw_plan(n, pages, heights, widths, channels, threshold, band, K, shear_q16, table.data(), &counts_bytes, &tiles, &max_h, &max_nb))
-        return rtn_fail_host(h, RTN_EINVAL, "rtn_skew_estimate: %s", why);
+    RTN_PLAN(h, "rtn_skew_estimate", skw_plan(n, pages, heights, widths, channels, threshold, band, K, shear_q16, table.data(), &counts_bytes, &tiles, &max_h, &max_nb));
     if (n == 0) return RTN_OK;
     if (!thresholds || !ink || !best || !scores) return rtn_fail(h, RTN_EINVAL, "rtn_skew_estimate: the four result arrays expected");
-    if (!workspace || ((uintptr_t)workspace & 255)) return rtn_fail(h, RTN_EINVAL, "rtn_skew_estimate: the workspace must be 256-byte aligned");
-    const Layout l = layout_of(n, K, counts_bytes);
-    if (workspace_bytes < l.total) return rtn_fail(h, RTN_ENOMEM, "rtn_skew_estimate: workspace %zu < %zu bytes", workspace_bytes, l.total);
-    uint8_t* ws = static_cast<uint8_t*>(workspace);
-    const SkwPage* d_table = reinterpret_cast<const SkwPage*>(ws + l.table);
-    const int32_t* d_shear = reinterpret_cast<const int32_t*>(ws + l.shear);
-    uint32_t* d_hist = reinterpret_cast<uint32_t*>(ws + l.hist);
-    uint8_t* d_counts = ws + l.counts;
-    RTN_HIP(h, hipMemcpyAsync(ws + l.table, table.data(), table.size() * sizeof(SkwPage), hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipMemcpyAsync(ws + l.shear, shear_q16, (size_t)K * 4, hipMemcpyHostToDevice, h->stream));
-    RTN_HIP(h, hipStreamSynchronize(h->stream));                             // the host images live in this call
+    rtn_stage st;
+    const Layout l = layout_of(st, n, K, counts_bytes);
+    st.put(l.table, table);
+    st.put(l.shear, shear_q16, (size_t)K * 4);
+    if (const int rc = st.commit(h, "rtn_skew_estimate", workspace, workspace_bytes)) return rc;
+    const SkwPage* d_table = st.at<const SkwPage>(l.table);
+    const int32_t* d_shear = st.at<const int32_t>(l.shear);
+    uint32_t* d_hist = st.at<uint32_t>(l.hist);
+    uint8_t* d_counts = st.at<uint8_t>(l.counts);
     RTN_HIP(h, hipMemsetAsync(ink, 0, (size_t)n * 8, h->stream));
     if (!threshold) {
         RTN_HIP(h, hipMemsetAsync(d_hist, 0, (size_t)n * 1024, h->stream));
@@ -310,14 +305,10 @@ extern "C" int rtn_skew_estimate(rtn_handle_t h, int n, const uint8_t* const* pa
     RTN_CHECK_LAUNCH(h, "skew_counts_kernel");
     const int shift_slots = (max_nb + 3) & ~3;
     const unsigned lds = (unsigned)shift_slots * 4u + (((unsigned)max_h * 2u + 15u) & ~15u);
-    static std::atomic<unsigned long long> attr_set{0ull};                   // the 64 KiB default refuses the tallest pages: raised once a device
-    const unsigned long long bit = 1ull << (h->device & 63);
-    if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-        RTN_HIP(h, hipFuncSetAttribute((const void*)skew_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SWEEP_LDS_LIMIT));
-        attr_set.fetch_or(bit, std::memory_order_relaxed);
-    }
-    skew_sweep_kernel<<<dim3((unsigned)K, (unsigned)n), dim3(SKW_THREADS), lds, h->stream>>>(d_table, d_shear, band, K, shift_slots, d_counts,
-                                                                                          reinterpret_cast<unsigned long long*>(scores));
+    // the 64 KiB default refuses the tallest pages
+    if (const int rc = rtn_launch_lds<skew_sweep_kernel>(h, dim3((unsigned)K, (unsigned)n), dim3(SKW_THREADS), lds, SWEEP_LDS_LIMIT, d_table, d_shear, band, K,
+                                                         shift_slots, d_counts, reinterpret_cast<unsigned long long*>(scores)))
+        return rc;
     RTN_CHECK_LAUNCH(h, "skew_sweep_kernel");
     skew_pick_kernel<<<dim3((unsigned)n), dim3(SKW_THREADS), 0, h->stream>>>(reinterpret_cast<const unsigned long long*>(scores), K, best);
     RTN_CHECK_LAUNCH(h, "skew_pick_kernel");
@@ -328,7 +319,6 @@ extern "C" int rtn_skew_estimate(rtn_handle_t h, int n, const uint8_t* const* pa
 extern "C" int rtn_skew_estimate_host(int n, const uint8_t* const* pages, const int32_t* heights, const int32_t* widths, const int32_t* channels,
                                       int threshold, int band, int K, const int32_t* shear_q16, int32_t* thresholds, int64_t* ink,
                                       int32_t* best, uint64_t* scores) {
-    if (const char* why = skw_host(n, pages, heights, widths, channels, threshold, band, K, shear_q16, thresholds, ink, best, scores))
-        return rtn_fail_host(nullptr, RTN_EINVAL, "rtn_skew_estimate_host: %s", why);
+    RTN_PLAN(nullptr, "rtn_skew_estimate_host", skw_host(n, pages, heights, widths, channels, threshold, band, K, shear_q16, thresholds, ink, best, scores));
     return RTN_OK;
 }

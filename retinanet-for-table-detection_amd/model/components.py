@@ -29,13 +29,12 @@ Differences from the reference:
   * interpolateImages is not provided;
   * findContours' own order of the contours is replaced by the raster order of the first pixels, which no scheduling changes;
   * pages with a side below 30 (the reference fails: its structuring element has length 0) or above 16384 raise ValueError."""
-import ctypes as C
 import os
 
 import numpy as np
-import torch
 
-from . import _rt
+from . import _pages, _rt
+from ._pages import Device as _Device, Twins as _Twins, i32 as _i32, pointers as _pointers, ptr as _ptr, starts as _starts
 
 L = _rt.L
 
@@ -45,89 +44,9 @@ BINS, RANGE = 25, (0, 100)               # drawPDFHist: num_bins, _range
 FILL, OUTLINE = 0, 1                     # rtn_cca_paint modes
 
 
-def _i32(a):
-    return np.ascontiguousarray(a, np.int32)
-
-
-def _ptr(a):
-    return a.ctypes.data if a.size else None
-
-
 def max_components(h, w):
     """The most 8-connected components an h x w image can hold: one pixel on every second row and column."""
     return ((int(h) + 1) // 2) * ((int(w) + 1) // 2)
-
-
-def _shapes(pages, kind):
-    """[(h, w, channels)] of a batch, or ValueError naming the page; nothing is launched before this."""
-    out = []
-    for i, p in enumerate(pages):
-        shape = tuple(p.shape)
-        ok = p.dtype == kind and (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3))
-        if not ok:
-            raise ValueError("page %d: a uint8 (H,W,3) or (H,W) page expected, got %s %s" % (i, p.dtype, shape))
-        if not (MIN_SIDE <= shape[0] <= MAX_SIDE and MIN_SIDE <= shape[1] <= MAX_SIDE):
-            raise ValueError("page %d: sides within %d .. %d expected, got %d x %d" % (i, MIN_SIDE, MAX_SIDE, shape[0], shape[1]))
-        out.append((shape[0], shape[1], 1 if len(shape) == 2 else 3))
-    return out
-
-
-class _Twins:
-    """The stages through the CPU twins (rtn_cca_*_host) over NumPy arrays."""
-    device = False
-
-    def check(self, rc):
-        if rc != 0:
-            raise L.RtnError(rc, L.lib.rtn_last_error(None).decode("utf-8", "replace"))
-
-    def empty(self, n, dtype=np.uint8):
-        return np.zeros(n, dtype)
-
-    def ptr(self, a):
-        return a.ctypes.data
-
-    def host(self, a):
-        return a
-
-    def view(self, buf, off, shape):
-        return buf[off:off + int(np.prod(shape))].reshape(shape)
-
-    def clone(self, a):
-        return a.copy()
-
-    def call(self, name, args, sizes=None, n_boxes=0, extra=(None,)):
-        self.check(getattr(L.lib, name + "_host")(*args, *extra))
-
-
-class _Device:
-    """The stages through the kernels, on the current stream, over CUDA tensors."""
-    device = True
-
-    def __init__(self, dev):
-        self.dev = dev
-        self.h = _rt.handle()
-        self.check = self.h.check
-
-    def empty(self, n, dtype=np.uint8):
-        return torch.zeros(n, dtype={np.uint8: torch.uint8, np.int32: torch.int32}[dtype], device=self.dev)
-
-    def ptr(self, a):
-        return a.data_ptr()
-
-    def host(self, a):
-        return a.cpu().numpy()
-
-    def view(self, buf, off, shape):
-        return buf[off:off + int(np.prod(shape))].view(shape)
-
-    def clone(self, a):
-        return a.clone()
-
-    def call(self, name, args, sizes=None, n_boxes=0, extra=()):
-        hs, ws_ = sizes
-        wsb = int(L.lib.rtn_cca_workspace_bytes(len(hs), _ptr(hs), _ptr(ws_), n_boxes))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=self.dev)
-        self.check(getattr(L.lib, name)(self.h.raw, *args, ws.data_ptr(), wsb))
 
 
 def _backend(pages, device):
@@ -137,26 +56,17 @@ def _backend(pages, device):
 
 
 def _check_batch(pages, device):
-    pages = list(pages)
-    if device:
-        for i, p in enumerate(pages):
-            if not (isinstance(p, torch.Tensor) and p.is_cuda):
-                raise ValueError("page %d: a CUDA uint8 tensor expected, got %s" % (i, type(p).__name__))
-        shapes = _shapes(pages, torch.uint8)
-        return [p.contiguous() for p in pages], shapes
-    pages = [np.ascontiguousarray(p) for p in pages]
-    return pages, _shapes(pages, np.uint8)
+    """The pages of a public call, CUDA tensors on the device path and NumPy arrays for the twins -> (pages, [(h, w, channels)])."""
+    return _pages.check_pages(pages, MIN_SIDE, MAX_SIDE, device, upload=False)
+
+
+def _workspace(hs, ws, n_boxes=0):
+    return lambda: L.lib.rtn_cca_workspace_bytes(len(hs), _ptr(hs), _ptr(ws), n_boxes)
 
 
 def _layout(shapes):
     hs, ws, ch = _i32([s[0] for s in shapes]), _i32([s[1] for s in shapes]), _i32([s[2] for s in shapes])
-    px = hs.astype(np.int64) * ws
-    off = np.concatenate([[0], np.cumsum(px)]).astype(np.int64)
-    return hs, ws, ch, off[:-1].copy(), int(off[-1])
-
-
-def _pointers(be, arrays):
-    return (C.c_void_p * max(len(arrays), 1))(*[be.ptr(a) for a in arrays])
+    return (hs, ws, ch) + _starts(hs.astype(np.int64) * ws)
 
 
 def _lines_mask(be, pages, shapes, bw=False):
@@ -167,7 +77,7 @@ def _lines_mask(be, pages, shapes, bw=False):
     if not be.device:
         extra = (be.empty(total),) if bw else (None,)
     be.call("rtn_cca_lines_mask", [len(pages), _pointers(be, pages), _ptr(hs), _ptr(ws), _ptr(ch), _ptr(off), be.ptr(hor), be.ptr(ver),
-                                   total], sizes=(hs, ws), extra=tuple(None if e is None else be.ptr(e) for e in extra))
+                                   total], _workspace(hs, ws), extra=tuple(None if e is None else be.ptr(e) for e in extra))
     return (hor, ver, off) + ((extra[0],) if bw else ())
 
 
@@ -179,7 +89,7 @@ def _text_mask(be, pages, shapes, stages=False):
     if not be.device:
         extra = (be.empty(4 * total),) if stages else (None,)
     be.call("rtn_cca_text_mask", [len(pages), _pointers(be, pages), _ptr(hs), _ptr(ws), _ptr(ch), _ptr(off), be.ptr(closed), total],
-            sizes=(hs, ws), extra=tuple(None if e is None else be.ptr(e) for e in extra))
+            _workspace(hs, ws), extra=tuple(None if e is None else be.ptr(e) for e in extra))
     return (closed, off) + ((extra[0],) if stages else ())
 
 
@@ -190,11 +100,10 @@ def _label(be, images, sizes, external_only=True, capacity=None):
     n = len(images)
     hs, ws = _i32([s[0] for s in sizes]), _i32([s[1] for s in sizes])
     cap = _i32([max_components(h, w) for h, w in zip(hs, ws)] if capacity is None else capacity)
-    box_off = np.concatenate([[0], np.cumsum(cap.astype(np.int64))]).astype(np.int64)
-    counts, boxes = be.empty(max(n, 1), np.int32), be.empty(4 * max(int(box_off[-1]), 1), np.int32)
-    first = box_off[:-1].copy()
+    first, room = _starts(cap)
+    counts, boxes = be.empty(max(n, 1), np.int32), be.empty(4 * max(room, 1), np.int32)
     be.call("rtn_cca_label", [n, _pointers(be, images), _ptr(hs), _ptr(ws), int(bool(external_only)), _ptr(cap), _ptr(first),
-                              be.ptr(counts), be.ptr(boxes), 16 * max(int(box_off[-1]), 1)], sizes=(hs, ws), extra=())
+                              be.ptr(counts), be.ptr(boxes), 16 * max(room, 1)], _workspace(hs, ws))
     counts_h = be.host(counts)[:n]
     out = []
     for i in range(n):
@@ -211,7 +120,7 @@ def _paint(be, pages, shapes, boxes, mode):
     if not len(page):
         return
     be.call("rtn_cca_paint", [len(pages), _pointers(be, pages), _ptr(hs), _ptr(ws), _ptr(ch), len(page), _ptr(page), _ptr(flat), mode],
-            sizes=(hs, ws), n_boxes=len(page), extra=())
+            _workspace(hs, ws, len(page)))
 
 
 def _mask_views(be, buf, off, shapes):

@@ -17,13 +17,13 @@ Differences from the reference:
     another order, which can show after .astype(int) only where the exact value is an integer.
 The colour conversions restate OpenCV's 8-bit BGR2HSV / HSV2BGR from its published source (recalled, not verifiable offline)."""
 import colorsys
-import ctypes as C
 import os
 
 import numpy as np
 import torch
 
-from . import _rt
+from . import _pages, _rt
+from ._pages import Device as _Device, Twins as _Twins, pointers as _pointers, ptr as _ptr, starts as _starts
 
 L = _rt.L
 
@@ -75,69 +75,22 @@ def _plan(shapes):
         dhs.append(dh)
     dst = np.asarray(dhs, np.int32)
     n = dst.astype(np.int64) * WIDTH
-    off = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+    offsets, total = _starts(n)
     return {"n": len(idx), "idx": idx, "heights": np.asarray(hs, np.int32), "widths": np.asarray(ws, np.int32), "dst": dst,
-            "points": n, "offsets": off[:-1].copy(), "total": int(off[-1])}
+            "points": n, "offsets": offsets, "total": total}
 
 
-def _ptr(a):
-    return a.ctypes.data if a.size else None
-
-
-class _Twins:
-    """The four stages through the CPU twins (rtn_header_*_host) over NumPy arrays."""
-    device = False
-
-    def check(self, rc):
-        if rc != 0:
-            raise L.RtnError(rc, L.lib.rtn_last_error(None).decode("utf-8", "replace"))
-
-    def empty(self, n, dtype=np.uint8):
-        return np.zeros(n, dtype)
-
-    def ptr(self, a):
-        return a.ctypes.data
-
-    def host(self, a):
-        return a
-
-    def call(self, name, before_ws, n_patches=0):
-        self.check(getattr(L.lib, name + "_host")(*before_ws))
-
-
-class _Device:
-    """The four stages through the kernels, on the current stream, over CUDA tensors."""
-    device = True
-
-    def __init__(self, dev):
-        self.dev = dev
-        self.h = _rt.handle()
-        self.check = self.h.check
-
-    def empty(self, n, dtype=np.uint8):
-        t = {np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32, np.uint32: torch.int32, np.uint64: torch.int64}[dtype]
-        return torch.zeros(n, dtype=t, device=self.dev)
-
-    def ptr(self, a):
-        return a.data_ptr()
-
-    def host(self, a):
-        return a.cpu().numpy()
-
-    def call(self, name, before_ws, n_patches=0):
-        n = before_ws[0]
-        wsb = int(L.lib.rtn_header_workspace_bytes(n, n_patches))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=self.dev)
-        self.check(getattr(L.lib, name)(self.h.raw, *before_ws, ws.data_ptr(), wsb))
+def _workspace(n, n_patches=0):
+    return lambda: L.lib.rtn_header_workspace_bytes(n, n_patches)
 
 
 def _sample(be, plan, crops):
     """Stage 1 -> the packed H,S,V buffer (3 bytes per point)."""
     n = plan["n"]
     hsv = be.empty(3 * plan["total"])
-    ptrs = (C.c_void_p * max(n, 1))(*[be.ptr(crops[i]) for i in plan["idx"]])
+    ptrs = _pointers(be, [crops[i] for i in plan["idx"]])
     be.call("rtn_header_sample", [n, ptrs, _ptr(plan["heights"]), _ptr(plan["widths"]), _ptr(plan["dst"]), _ptr(plan["offsets"]),
-                                  be.ptr(hsv), 3 * plan["total"]])
+                                  be.ptr(hsv), 3 * plan["total"]], _workspace(n))
     return hsv
 
 
@@ -149,7 +102,7 @@ def _cluster(be, plan, hsv, max_iter):
     labels = be.empty(MAX_K * plan["total"])
     be.call("rtn_header_cluster", [n, _ptr(plan["dst"]), _ptr(plan["offsets"]), be.ptr(hsv), 3 * plan["total"], int(max_iter),
                                    be.ptr(centres), be.ptr(counts), be.ptr(passes), be.ptr(dist), be.ptr(labels),
-                                   MAX_K * plan["total"]])
+                                   MAX_K * plan["total"]], _workspace(n))
     return centres, counts, passes, dist, labels
 
 
@@ -159,7 +112,7 @@ def _stats(be, plan, ks, hsv, labels):
     ks = np.ascontiguousarray(ks, np.int32)
     hist = be.empty(n * MAX_K * 3 * 256, np.uint32)
     be.call("rtn_header_stats", [n, _ptr(plan["dst"]), _ptr(plan["offsets"]), _ptr(ks), be.ptr(hsv), 3 * plan["total"],
-                                 be.ptr(labels), MAX_K * plan["total"], be.ptr(hist)])
+                                 be.ptr(labels), MAX_K * plan["total"], be.ptr(hist)], _workspace(n))
     return hist
 
 
@@ -168,12 +121,12 @@ def _patches(be, plan, hsv, patch_crop, low, high):
     patch_crop = np.ascontiguousarray(patch_crop, np.int32)
     low, high = np.ascontiguousarray(low, np.uint8), np.ascontiguousarray(high, np.uint8)
     sizes = plan["points"][patch_crop] * 3 if len(patch_crop) else np.zeros(0, np.int64)
-    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    out = be.empty(max(int(offs[-1]), 1))
-    first = offs[:-1].copy()
+    first, total = _starts(sizes)
+    offs = np.append(first, total)
+    out = be.empty(max(total, 1))
     be.call("rtn_header_patches", [plan["n"], _ptr(plan["dst"]), _ptr(plan["offsets"]), be.ptr(hsv), 3 * plan["total"],
                                    len(patch_crop), _ptr(patch_crop), _ptr(low), _ptr(high), _ptr(first), be.ptr(out),
-                                   int(offs[-1])], n_patches=len(patch_crop))
+                                   total], _workspace(plan["n"], len(patch_crop)))
     return out, offs
 
 

@@ -4,7 +4,8 @@ and utils.resize_image's cv2.resize (model/utils.py:152), plus Generator.compute
 import numpy as np
 import torch
 
-from . import _rt
+from . import _pages, _rt
+from ._pages import i32, pointers
 from .page_io import read_images_bgr, write_images_bgr
 
 L = _rt.L
@@ -142,28 +143,13 @@ def interpolate_images(pages, fx=None, fy=None, dsize=None):
     all pages or one pair per page; fx and fy are then not taken.  One rtn_resize_u8 launch on the current stream resizes the whole
     batch; pages already on the device are not copied to the host.  Returns a list of CUDA uint8 tensors.  The arithmetic is
     OpenCV's 8-bit fixed-point form as recalled (csrc/rtn_resize_u8.h)."""
-    import ctypes as C
-    pages = list(pages)
-    n = len(pages)
     if dsize is not None:
         if fx is not None or fy is not None:
             raise ValueError("either factors or dsize, not both")
     elif fx is None:
         raise ValueError("fx or dsize is required")
-    src = []
-    for i, p in enumerate(pages):
-        if isinstance(p, torch.Tensor):
-            if p.dtype != torch.uint8:
-                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, p.dtype))
-            p = p.cuda().contiguous()
-        else:
-            a = np.asarray(p)
-            if a.dtype != np.uint8:
-                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, a.dtype))
-            p = torch.as_tensor(np.ascontiguousarray(a)).cuda()
-        if not (p.dim() == 2 or (p.dim() == 3 and p.shape[2] == 3)) or not (1 <= p.shape[0] <= RESIZE_MAX_SIDE and 1 <= p.shape[1] <= RESIZE_MAX_SIDE):
-            raise ValueError("page %d: shape (H,W,3) or (H,W) with sides 1..%d expected, got %s" % (i, RESIZE_MAX_SIDE, tuple(p.shape)))
-        src.append(p)
+    src, shapes = _pages.check_pages(pages, 1, RESIZE_MAX_SIDE)
+    n = len(src)
     if n == 0:
         return []
     sizes, inv_x, inv_y = [], [], []
@@ -185,16 +171,13 @@ def interpolate_images(pages, fx=None, fy=None, dsize=None):
             sizes.append(interpolated_size(p.shape[0], p.shape[1], a, b))
             inv_x.append(1.0 / a)
             inv_y.append(1.0 / b)
-    h = _rt.handle()
+    be = _pages.Device(src[0].device)
     outs = [torch.empty((ho, wo) + tuple(p.shape[2:]), dtype=torch.uint8, device=p.device) for p, (ho, wo) in zip(src, sizes)]
-    i32 = lambda v: np.ascontiguousarray(v, np.int32)
-    arrays = (i32([p.shape[0] for p in src]), i32([p.shape[1] for p in src]), i32([3 if p.dim() == 3 else 1 for p in src]),
+    arrays = (i32([s[0] for s in shapes]), i32([s[1] for s in shapes]), i32([s[2] for s in shapes]),
               i32([s[0] for s in sizes]), i32([s[1] for s in sizes]), np.ascontiguousarray(inv_x, np.float64),
               np.ascontiguousarray(inv_y, np.float64))
-    wsb = int(L.lib.rtn_resize_u8_workspace_bytes(n))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=src[0].device)
-    h.check(L.lib.rtn_resize_u8(h.raw, n, (C.c_void_p * n)(*[p.data_ptr() for p in src]), *[a.ctypes.data for a in arrays],
-                                (C.c_void_p * n)(*[o.data_ptr() for o in outs]), ws.data_ptr(), wsb))
+    be.call("rtn_resize_u8", [n, pointers(be, src), *[a.ctypes.data for a in arrays], pointers(be, outs)],
+            lambda: L.lib.rtn_resize_u8_workspace_bytes(n))
     return outs                                                 # queued on the current stream, like the sources' uploads
 
 
@@ -238,27 +221,7 @@ def skew_shears(max_angle=5.0, step=0.1):
     return np.ascontiguousarray(shear), n_steps
 
 
-def _skew_pages(pages):
-    """The pages as contiguous CUDA uint8 tensors, (H,W) or (H,W,3) with sides 1..32767."""
-    out = []
-    for i, p in enumerate(pages):
-        if isinstance(p, torch.Tensor):
-            if p.dtype != torch.uint8:
-                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, p.dtype))
-            q = p if (p.is_cuda and p.is_contiguous()) else p.cuda().contiguous()
-        else:
-            a = np.asarray(p)
-            if a.dtype != np.uint8:
-                raise ValueError("page %d: uint8 pixels expected, got %s" % (i, a.dtype))
-            q = torch.as_tensor(np.ascontiguousarray(a)).cuda()
-        if not (q.dim() == 2 or (q.dim() == 3 and q.shape[2] == 3)) or not (1 <= q.shape[0] <= SKEW_MAX_SIDE and 1 <= q.shape[1] <= SKEW_MAX_SIDE):
-            raise ValueError("page %d: shape (H,W,3) or (H,W) with sides 1..%d expected, got %s" % (i, SKEW_MAX_SIDE, tuple(q.shape)))
-        out.append(q)
-    return out
-
-
 def _estimate_skew(src, max_angle, step, threshold, band, return_scores):
-    import ctypes as C
     if band not in (8, 16, 32, 64):
         raise ValueError("band must be 8, 16, 32 or 64, got %r" % (band,))
     threshold = 0 if threshold is None else int(threshold)
@@ -270,21 +233,17 @@ def _estimate_skew(src, max_angle, step, threshold, band, return_scores):
         raise ValueError("at most 65535 pages a call")
     if n == 0:
         return ([], []) if return_scores else []
-    hs = np.ascontiguousarray([p.shape[0] for p in src], np.int32)
-    wd = np.ascontiguousarray([p.shape[1] for p in src], np.int32)
-    ch = np.ascontiguousarray([3 if p.dim() == 3 else 1 for p in src], np.int32)
-    h = _rt.handle()
-    dev = src[0].device
+    hs, wd, ch = i32([p.shape[0] for p in src]), i32([p.shape[1] for p in src]), i32([3 if p.dim() == 3 else 1 for p in src])
+    be = _pages.Device(src[0].device)
     # one result block: scores (uint64 [n][K]), ink (int64 [n]), thresholds and best (int32 [n] each), read back in one copy
-    res = torch.empty(n * K + n + n, dtype=torch.int64, device=dev)
+    res = torch.empty(n * K + n + n, dtype=torch.int64, device=be.dev)
     scores_ptr = res.data_ptr()
     ink_ptr = scores_ptr + 8 * n * K
     thr_ptr = ink_ptr + 8 * n
     best_ptr = thr_ptr + 4 * n
-    wsb = int(L.lib.rtn_skew_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, band, K))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    h.check(L.lib.rtn_skew_estimate(h.raw, n, (C.c_void_p * n)(*[p.data_ptr() for p in src]), hs.ctypes.data, wd.ctypes.data, ch.ctypes.data,
-                                    threshold, band, K, shear.ctypes.data, thr_ptr, ink_ptr, best_ptr, scores_ptr, ws.data_ptr(), wsb))
+    be.call("rtn_skew_estimate", [n, pointers(be, src), hs.ctypes.data, wd.ctypes.data, ch.ctypes.data, threshold, band, K, shear.ctypes.data,
+                                  thr_ptr, ink_ptr, best_ptr, scores_ptr],
+            lambda: L.lib.rtn_skew_workspace_bytes(n, hs.ctypes.data, wd.ctypes.data, band, K))
     host = res.cpu().numpy()                                      # the single read-back
     scores = host[:n * K].view(np.uint64).reshape(n, K)
     ink = host[n * K:n * K + n]
@@ -304,7 +263,7 @@ def estimate_skew(pages, max_angle=5.0, step=0.1, threshold=None, band=32, retur
     line of a page of angle a lies along y = y0 + (x - W/2) tan(a), y down.  With return_scores, (angles, details): per page a dict of
     threshold, ink, best and the uint64 scores of all angles.  ValueError for max_angle > 15, more than 401 angles, a bad band or
     bad pages."""
-    return _estimate_skew(_skew_pages(list(pages)), max_angle, step, threshold, band, return_scores)
+    return _estimate_skew(_pages.check_pages(pages, 1, SKEW_MAX_SIDE)[0], max_angle, step, threshold, band, return_scores)
 
 
 def deskew_map(angle, height, width):
@@ -321,7 +280,7 @@ def deskew_images(pages, max_angle=5.0, step=0.1, threshold=None, band=32, fill=
     map.  Returns (pages, angles): CUDA uint8 tensors and degrees.  A page below min_angle is returned as the tensor it came in as (a
     NumPy page: as its upload).  No pixel comes to the host."""
     import ctypes as C
-    src = _skew_pages(list(pages))
+    src = _pages.check_pages(pages, 1, SKEW_MAX_SIDE)[0]
     angles = _estimate_skew(src, max_angle, step, threshold, band, False)
     min_angle = float(step) if min_angle is None else float(min_angle)
     fill = int(fill)

@@ -38,15 +38,15 @@ The rules, for one box on one page of H x W (all arithmetic is integer):
 Differences from camelot: the window lengths come from the box, not from the page; the separators come from projections, not
 from the joints of contours; and nothing can confirm the grids against camelot offline: PARITY UNPINNED."""
 import collections
-import ctypes as C
 import math
 import os
 
 import numpy as np
 import torch
 
-from . import _rt
+from . import _pages, _rt
 from . import components
+from ._pages import Device as _Device, Twins as _Twins, i32 as _i32, pointers as _pointers, ptr as _ptr, starts as _starts
 
 L = _rt.L
 
@@ -56,18 +56,6 @@ CSV_HEADER = "row,col,rowspan,colspan,x1,y1,x2,y2,ink,ink_x,ink_y,ink_w,ink_h"
 
 Cell = collections.namedtuple("Cell", "r0 c0 r1 c1 x1 y1 x2 y2 ink ink_box rect")
 TableGrid = collections.namedtuple("TableGrid", "flavor rows cols h_edges v_edges cell_ink cell_ink_box cells")
-
-
-def _i32(a):
-    return np.ascontiguousarray(a, np.int32)
-
-
-def _i64(a):
-    return np.ascontiguousarray(a, np.int64)
-
-
-def _ptr(a):
-    return a.ctypes.data if a.size else None
 
 
 def max_runs(n):
@@ -83,71 +71,13 @@ def crop_of(box, H, W, margin):
     return xa, ya, xb - xa, yb - ya
 
 
-class _Twins:
-    """The stages through the CPU twins (rtn_lattice_*_host) over NumPy arrays."""
-    device = False
-
-    def check(self, rc):
-        if rc != 0:
-            raise L.RtnError(rc, L.lib.rtn_last_error(None).decode("utf-8", "replace"))
-
-    def empty(self, n, dtype):
-        return np.zeros(n, dtype)
-
-    def ptr(self, a):
-        return a.ctypes.data
-
-    def host(self, a):
-        return a
-
-    def call(self, name, args, crops=None, n_items=0):
-        self.check(getattr(L.lib, name + "_host")(*args))
-
-
-class _Device:
-    """The stages through the kernels, on the current stream, over CUDA tensors."""
-    device = True
-    _kinds = {np.uint8: torch.uint8, np.int32: torch.int32}
-
-    def __init__(self, dev):
-        self.dev = dev
-        self.h = _rt.handle()
-        self.check = self.h.check
-
-    def empty(self, n, dtype):
-        return torch.zeros(n, dtype=self._kinds[dtype], device=self.dev)
-
-    def ptr(self, a):
-        return a.data_ptr()
-
-    def host(self, a):
-        return a.cpu().numpy()
-
-    def call(self, name, args, crops=None, n_items=0):
-        wsb = int(L.lib.rtn_lattice_workspace_bytes(len(crops), _ptr(crops), int(n_items)))
-        ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=self.dev)
-        self.check(getattr(L.lib, name)(self.h.raw, *args, ws.data_ptr(), wsb))
-
-
 def _check_pages(pages, device):
     """-> (the pages as contiguous CUDA tensors / NumPy arrays, [(h, w, channels)]); ValueError naming the page before any launch."""
-    out, shapes = [], []
-    for i, p in enumerate(pages):
-        if not isinstance(p, (torch.Tensor, np.ndarray)):
-            raise ValueError("page %d: a uint8 NumPy array or tensor expected, got %s" % (i, type(p).__name__))
-        shape = tuple(p.shape)
-        if p.dtype not in (torch.uint8, np.uint8) or not (len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)):
-            raise ValueError("page %d: a uint8 (H,W,3) or (H,W) page expected, got %s %s" % (i, p.dtype, shape))
-        if not (MIN_SIDE <= shape[0] <= MAX_SIDE and MIN_SIDE <= shape[1] <= MAX_SIDE):
-            raise ValueError("page %d: sides within %d .. %d expected, got %d x %d" % (i, MIN_SIDE, MAX_SIDE, shape[0], shape[1]))
-        shapes.append((shape[0], shape[1], 1 if len(shape) == 2 else 3))
-    for p in pages:
-        if device:
-            t = p if isinstance(p, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(p))
-            out.append(t.cuda().contiguous())
-        else:
-            out.append(np.ascontiguousarray(p.cpu().numpy() if isinstance(p, torch.Tensor) else p))
-    return out, shapes
+    return _pages.check_pages(pages, MIN_SIDE, MAX_SIDE, device)
+
+
+def _workspace(crops, n_items=0):
+    return lambda: L.lib.rtn_lattice_workspace_bytes(len(crops), _ptr(crops), int(n_items))
 
 
 def _check_boxes(boxes, n_pages):
@@ -174,10 +104,6 @@ def _check_params(flavor, line_scale, line_tol, cover, col_gap, row_gap, margin)
     for name, v, lo in (("line_tol", line_tol, 0), ("col_gap", col_gap, 1), ("row_gap", row_gap, 1), ("margin", margin, 0)):
         if not lo <= int(v) <= MAX_SIDE:
             raise ValueError("%s within %d .. %d expected, got %r" % (name, lo, MAX_SIDE, v))
-
-
-def _pointers(be, arrays):
-    return (C.c_void_p * max(len(arrays), 1))(*[be.ptr(a) for a in arrays])
 
 
 def _buffer(be, bufs, name, n, dtype):
@@ -207,31 +133,26 @@ def separators(profile, mode, param, capacity=None):
 def _masks(be, pages, shapes, box_page, crops, line_scale, bufs=None):
     """-> (bw, hm, vm, ink, offsets, total): the packed masks of every crop."""
     hs, ws, ch = _i32([s[0] for s in shapes]), _i32([s[1] for s in shapes]), _i32([s[2] for s in shapes])
-    px = crops[:, 2].astype(np.int64) * crops[:, 3]
-    offsets = _i64(np.concatenate([[0], np.cumsum(px)])[:-1])
-    total = int(px.sum())
+    offsets, total = _starts(crops[:, 2].astype(np.int64) * crops[:, 3])
     m = [_buffer(be, bufs, k, total, np.uint8) for k in ("bw", "hm", "vm", "ink")]
     be.call("rtn_lattice_masks", [len(pages), _pointers(be, pages), _ptr(hs), _ptr(ws), _ptr(ch), len(crops), _ptr(box_page), _ptr(crops),
-                                  int(line_scale), _ptr(offsets)] + [be.ptr(a) for a in m] + [total], crops=crops)
+                                  int(line_scale), _ptr(offsets)] + [be.ptr(a) for a in m] + [total], _workspace(crops))
     return m[0], m[1], m[2], m[3], offsets, total
 
 
 def _profiles(be, crops, offsets, total, hm, vm, ink, bufs=None):
     """-> (profiles, prof_offsets): box j's rowH[h], rowInk[h], colV[w], colInk[w] from prof_offsets[j]."""
-    sizes = 2 * (crops[:, 2].astype(np.int64) + crops[:, 3])
-    prof_offsets = _i64(np.concatenate([[0], np.cumsum(sizes)])[:-1])
-    count = int(sizes.sum())
+    prof_offsets, count = _starts(2 * (crops[:, 2].astype(np.int64) + crops[:, 3]))
     profiles = _buffer(be, bufs, "profiles", count, np.int32)
     be.call("rtn_lattice_profiles", [len(crops), _ptr(crops), _ptr(offsets), be.ptr(hm), be.ptr(vm), be.ptr(ink), total, _ptr(prof_offsets),
-                                     be.ptr(profiles), count], crops=crops)
+                                     be.ptr(profiles), count], _workspace(crops))
     return profiles, prof_offsets
 
 
 def _runs_table(rows, cols):
     """Per-box run lists -> (R, C, sep_offsets, runs (n, 2))."""
     R, Cn = _i32([len(r) for r in rows]), _i32([len(c) for c in cols])
-    per = R.astype(np.int64) + Cn
-    sep_offsets = _i64(np.concatenate([[0], np.cumsum(per)])[:-1])
+    sep_offsets, _total = _starts(R.astype(np.int64) + Cn)
     parts = [np.reshape(a, (-1, 2)) for pair in zip(rows, cols) for a in pair]
     runs = _i32(np.concatenate(parts) if parts else np.zeros((0, 2)))
     return R, Cn, sep_offsets, runs.reshape(-1, 2)
@@ -240,24 +161,24 @@ def _runs_table(rows, cols):
 def _edges(be, crops, offsets, total, R, Cn, sep_offsets, runs, line_tol, cover, hm, vm, bufs=None, capacity=None):
     """-> (edges, edge_offsets): box j's R (C - 1) horizontal then (R - 1) C vertical flags (uint8) from edge_offsets[j]."""
     per = np.where((R >= 1) & (Cn >= 1), R.astype(np.int64) * (Cn - 1) + (R.astype(np.int64) - 1) * Cn, 0)
-    edge_offsets = _i64(np.concatenate([[0], np.cumsum(per)])[:-1])
-    count = int(per.sum()) if capacity is None else int(capacity)
+    edge_offsets, n_items = _starts(per)
+    count = n_items if capacity is None else int(capacity)
     edges = _buffer(be, bufs, "edges", count, np.uint8)
     be.call("rtn_lattice_edges", [len(crops), _ptr(crops), _ptr(offsets), _ptr(R), _ptr(Cn), _ptr(sep_offsets), _ptr(runs), len(runs),
                                   int(line_tol), int(cover), _ptr(edge_offsets), be.ptr(hm), be.ptr(vm), total, be.ptr(edges), count],
-            crops=crops, n_items=int(per.sum()))
+            _workspace(crops, n_items))
     return edges, edge_offsets
 
 
 def _cells(be, crops, offsets, total, R, Cn, sep_offsets, runs, ink, bufs=None, capacity=None):
     """-> (cell_ink, cell_box, cell_offsets): box j's (R - 1) (C - 1) counts and boxes (x, y, w, h in the page) from cell_offsets[j]."""
     per = np.where((R >= 1) & (Cn >= 1), (R.astype(np.int64) - 1) * (Cn - 1), 0)
-    cell_offsets = _i64(np.concatenate([[0], np.cumsum(per)])[:-1])
-    count = int(per.sum()) if capacity is None else int(capacity)
+    cell_offsets, n_items = _starts(per)
+    count = n_items if capacity is None else int(capacity)
     cell_ink, cell_box = _buffer(be, bufs, "cell_ink", count, np.int32), _buffer(be, bufs, "cell_box", 4 * count, np.int32)
     be.call("rtn_lattice_cells", [len(crops), _ptr(crops), _ptr(offsets), _ptr(R), _ptr(Cn), _ptr(sep_offsets), _ptr(runs), len(runs),
                                   _ptr(cell_offsets), be.ptr(ink), total, be.ptr(cell_ink), be.ptr(cell_box), count],
-            crops=crops, n_items=int(per.sum()))
+            _workspace(crops, n_items))
     return cell_ink, cell_box, cell_offsets
 
 
@@ -387,7 +308,7 @@ def table_cells(pages, boxes, flavor="auto", line_scale=15, line_tol=2, cover=50
     ink, ink_box, rect).  device=False runs the CPU twins (no GPU needed), which give the same bytes.  ValueError naming the page,
     before anything is launched, for a page that is not uint8 (H,W,3) / (H,W) or has a side outside 30 .. 16384."""
     _check_params(flavor, line_scale, line_tol, cover, col_gap, row_gap, margin)
-    pages, shapes = _check_pages(list(pages), device)
+    pages, shapes = _check_pages(pages, device)
     boxes = _check_boxes(boxes, len(pages))
     be = _Device(pages[0].device) if device and pages else _Twins()
     return _grids(be, pages, shapes, boxes, flavor, int(line_scale), int(line_tol), int(cover), int(col_gap), int(row_gap), int(margin))
@@ -418,12 +339,12 @@ def write_csvs(grids, names, out_dir):
 def outline_cells(pages, grids):
     """New pages (CUDA tensors) with the outer box of every merged cell outlined by rtn_cca_paint mode 1 (draw_box's bands, (0, 255, 0),
     255 on a gray page); coordinates left of or above the page are drawn from 0."""
-    pages, shapes = _check_pages(list(pages), True)
+    pages, shapes = _check_pages(pages, True)
     drawn = [p.clone() for p in pages]
     boxes = [np.array([[max(c.x1, 0), max(c.y1, 0), c.x2 - max(c.x1, 0), c.y2 - max(c.y1, 0)] for g in page_grids for c in g.cells],
                       np.int32).reshape(-1, 4) for page_grids in grids]
     if drawn:
-        components._paint(components._Device(drawn[0].device), drawn, shapes, boxes, components.OUTLINE)
+        components._paint(_Device(drawn[0].device), drawn, shapes, boxes, components.OUTLINE)
     return drawn
 
 

@@ -220,30 +220,29 @@ def visual_effect_batch(pages, params, flags=None, handle=None, in_place=False):
     params: one (contrast_factor, brightness_delta, hue_delta, saturation_factor) per page; flags: None or one RTN_EFFECT_* word per
     page.  Runs on `handle` and its stream (default: the package's handle on the current stream) and returns the new pages, or the
     pages themselves with in_place."""
-    import ctypes
     import torch
-    from . import _rt
-    L = _rt.L
+    from . import _pages
+    L = _pages.L
     n = len(pages)
     if n == 0:
         return []
     for p in pages:
         if not isinstance(p, torch.Tensor) or not p.is_cuda or p.dtype != torch.uint8 or p.dim() != 3 or p.shape[2] != 3 or not p.is_contiguous():
             raise ValueError("visual_effect_batch: contiguous uint8 (H,W,3) CUDA tensors expected")
-    h = _rt.handle() if handle is None else handle
+    be = _pages.Device(pages[0].device, handle)
     par = np.ascontiguousarray(np.asarray(params, np.float64).reshape(n, 4))
     fl = np.zeros(n, np.uint32) if flags is None else np.ascontiguousarray(np.asarray(flags, np.uint32).reshape(n))
     heights = np.array([p.shape[0] for p in pages], np.int32)
     widths = np.array([p.shape[1] for p in pages], np.int32)
     outs = list(pages) if in_place else [torch.empty_like(p) for p in pages]
-    src = (ctypes.c_void_p * n)(*[p.data_ptr() for p in pages])
-    dst = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    wsb = int(L.lib.rtn_visual_effect_workspace_bytes(n, heights.ctypes.data, widths.ctypes.data))
-    if wsb == 0:
-        raise ValueError("visual_effect_batch: at most 65535 pages with sides 1 .. 65500")
-    ws = torch.empty(wsb, dtype=torch.uint8, device=pages[0].device)
-    h.check(L.lib.rtn_visual_effect_u8(h.raw, n, src, heights.ctypes.data, widths.ctypes.data, par.ctypes.data, fl.ctypes.data, dst,
-                                       ws.data_ptr(), wsb))
+
+    def room():
+        wsb = L.lib.rtn_visual_effect_workspace_bytes(n, heights.ctypes.data, widths.ctypes.data)
+        if wsb == 0:
+            raise ValueError("visual_effect_batch: at most 65535 pages with sides 1 .. 65500")
+        return wsb
+    be.call("rtn_visual_effect_u8", [n, _pages.pointers(be, pages), heights.ctypes.data, widths.ctypes.data, par.ctypes.data, fl.ctypes.data,
+                                     _pages.pointers(be, outs)], room)
     return outs
 
 

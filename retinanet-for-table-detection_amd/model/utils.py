@@ -5,7 +5,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _rt
+from . import _pages, _rt
 from .Parameters import image_scaling_factor, image_subtraction_factor
 from .page_io import write_image, write_images_bgr, encode_jpeg_bgr, encode_png_bgr, decode_png_bgr, decode_tiff_bgr, encode_tiff_bgr, JPEG_EXTENSIONS  # noqa: F401
 
@@ -370,13 +370,11 @@ def _render_device(plan, pages):
     (h, w, 3) views in the order of plan["images"]); (None, []) for a plan without images."""
     if not plan["images"]:
         return None, []
-    h = _rt.handle()
     out = torch.empty(plan["out_bytes"], dtype=torch.uint8, device=pages[0].device)
     masks = torch.from_numpy(plan["masks"].copy()).to(out.device) if plan["masks"].size else None
-    wsb = int(L.lib.rtn_render_workspace_bytes(len(pages), len(plan["boxes"]), len(plan["images"])))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=out.device)
     args = _render_args(plan, [p.data_ptr() for p in pages], masks.data_ptr() if masks is not None else None, out.data_ptr())
-    h.check(L.lib.rtn_render_pages(h.raw, *args, ws.data_ptr(), wsb))
+    _pages.Device(out.device).call("rtn_render_pages", args,
+                                   lambda: L.lib.rtn_render_workspace_bytes(len(pages), len(plan["boxes"]), len(plan["images"])))
     return out, [out[off:off + hh * ww * 3].view(hh, ww, 3) for (_p, _k, hh, ww, off) in plan["images"]]
 
 

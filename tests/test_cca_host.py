@@ -10,12 +10,12 @@ import cca_ref as R
 
 CCA = K.CCA
 L = CCA.L
-TW = CCA._Twins()
+TW = CCA._pages.Twins()
 
 
 def batch():
     names = list(K.pages())
-    pages, shapes = CCA._check_batch([K.pages()[nm] for nm in names], False)
+    pages, shapes = CCA._pages.check_pages([K.pages()[nm] for nm in names], CCA.MIN_SIDE, CCA.MAX_SIDE, False, upload=False)
     return names, pages, shapes
 
 
@@ -79,11 +79,11 @@ def test_outlines_are_clipped_at_the_page_edges():
     gray = np.full((33, 31), 7, np.uint8)
     boxes = [np.asarray([[0, 0, 20, 5], [30, 35, 20, 5], [10, 10, 30, 8], [49, 0, 1, 40]], np.int32),
              np.asarray([[0, 0, 31, 33], [5, 6, 20, 4]], np.int32)]
-    pages, shapes = CCA._check_batch([page.copy(), gray.copy()], False)
+    pages, shapes = CCA._pages.check_pages([page.copy(), gray.copy()], CCA.MIN_SIDE, CCA.MAX_SIDE, False, upload=False)
     CCA._paint(TW, pages, shapes, boxes, CCA.OUTLINE)
     assert np.array_equal(pages[0], R.outline(page, boxes[0])) and np.array_equal(pages[1], R.outline(gray, boxes[1]))
     assert (pages[0] == (0, 255, 0)).all(-1).any() and (pages[1] == 255).any()
-    pages, shapes = CCA._check_batch([page.copy(), gray.copy()], False)
+    pages, shapes = CCA._pages.check_pages([page.copy(), gray.copy()], CCA.MIN_SIDE, CCA.MAX_SIDE, False, upload=False)
     CCA._paint(TW, pages, shapes, boxes, CCA.FILL)
     for p, src, bs in zip(pages, (page, gray), boxes):
         want = src.copy()
@@ -103,7 +103,7 @@ def test_the_golden_sample_page_equals_the_oracle():
 
 def test_pages_of_the_largest_side_equal_the_oracle():
     for nm, page in K.long_pages().items():
-        pages, shapes = CCA._check_batch([page], False)
+        pages, shapes = CCA._pages.check_pages([page], CCA.MIN_SIDE, CCA.MAX_SIDE, False, upload=False)
         hor, ver, _off, bw = CCA._lines_mask(TW, pages, shapes, bw=True)
         wbw, whor, wver = R.line_masks(page)
         assert np.array_equal(bw.reshape(page.shape), wbw) and np.array_equal(hor.reshape(page.shape), whor), nm

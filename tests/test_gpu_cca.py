@@ -21,11 +21,11 @@ def test_labelling_equals_the_twins_on_every_binary_image_in_one_batch(pkg):
     names = list(K.binaries())
     imgs = [K.binaries()[nm] for nm in names]
     dev = [cuda(a) for a in imgs]
-    be = CCA._Device(dev[0].device)
+    be = CCA._pages.Device(dev[0].device)
     sizes = [a.shape for a in imgs]
     for external in (True, False):
         got = CCA._label(be, dev, sizes, external_only=external)
-        want = CCA._label(CCA._Twins(), imgs, sizes, external_only=external)
+        want = CCA._label(CCA._pages.Twins(), imgs, sizes, external_only=external)
         for nm, g, w in zip(names, got, want):
             assert np.array_equal(g, w), (nm, external)
             assert np.array_equal(g, K.oracle_components(nm, external)), (nm, external)
@@ -35,14 +35,14 @@ def test_labelling_equals_the_twins_on_every_binary_image_in_one_batch(pkg):
 def test_label_overflow_reports_the_true_count(pkg):
     img = K.binaries()["isolated_pixels"]
     true = len(K.oracle_components("isolated_pixels", True))
-    be = CCA._Device(torch.device("cuda", torch.cuda.current_device()))
+    be = CCA._pages.Device(torch.device("cuda", torch.cuda.current_device()))
     hs, ws = np.asarray([img.shape[0]], np.int32), np.asarray([img.shape[1]], np.int32)
     cap, off = np.asarray([10], np.int32), np.zeros(1, np.int64)
     d = cuda(img)
     counts, boxes = torch.full((1,), -1, dtype=torch.int32, device="cuda"), torch.full((40,), -1, dtype=torch.int32, device="cuda")
     wsb = int(L.lib.rtn_cca_workspace_bytes(1, hs.ctypes.data, ws.ctypes.data, 0))
     wsp = torch.empty(wsb, dtype=torch.uint8, device="cuda")
-    ptrs = (CCA.C.c_void_p * 1)(d.data_ptr())
+    ptrs = CCA._pointers(be, [d])
     rc = L.lib.rtn_cca_label(be.h.raw, 1, ptrs, hs.ctypes.data, ws.ctypes.data, 1, cap.ctypes.data, off.ctypes.data, counts.data_ptr(),
                              boxes.data_ptr(), 160, wsp.data_ptr(), wsb)
     assert rc == -1                                                             # RTN_EINVAL
@@ -67,11 +67,11 @@ def test_every_device_output_equals_the_twins_on_the_mixed_batch(pkg):
     pages = [K.pages()[nm] for nm in names]
     assert len({p.shape for p in pages}) == len(pages) and any(p.ndim == 2 for p in pages)
     dev = [cuda(p) for p in pages]
-    dev, shapes = CCA._check_batch(dev, True)
-    be = CCA._Device(dev[0].device)
+    dev, shapes = CCA._pages.check_pages(dev, CCA.MIN_SIDE, CCA.MAX_SIDE, True, upload=False)
+    be = CCA._pages.Device(dev[0].device)
     got, boxes, heights = stages(be, dev, shapes)
     torch.cuda.synchronize()
-    want, wboxes, wheights = stages(CCA._Twins(), pages, shapes)
+    want, wboxes, wheights = stages(CCA._pages.Twins(), pages, shapes)
     assert all(np.array_equal(d.cpu().numpy(), p) for d, p in zip(dev, pages))                # the pages are only read
     for key in want:
         assert np.array_equal(got[key].cpu().numpy(), want[key]), key
@@ -115,9 +115,9 @@ def test_every_device_output_equals_the_twins_on_the_mixed_batch(pkg):
 def test_pages_of_the_largest_side_equal_the_twins(pkg):
     """30 x 16384 and 16384 x 30: a thread of a row kernel owns 64 pixels, the line windows are 546 long."""
     pages = list(K.long_pages().values())
-    dev, shapes = CCA._check_batch([cuda(p) for p in pages], True)
-    got, boxes, heights = stages(CCA._Device(dev[0].device), dev, shapes)
-    want, wboxes, wheights = stages(CCA._Twins(), pages, shapes)
+    dev, shapes = CCA._pages.check_pages([cuda(p) for p in pages], CCA.MIN_SIDE, CCA.MAX_SIDE, True, upload=False)
+    got, boxes, heights = stages(CCA._pages.Device(dev[0].device), dev, shapes)
+    want, wboxes, wheights = stages(CCA._pages.Twins(), pages, shapes)
     for key in want:
         assert np.array_equal(got[key].cpu().numpy(), want[key]), key
     for i in range(len(pages)):

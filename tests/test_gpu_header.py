@@ -46,10 +46,10 @@ def test_every_device_output_equals_the_twins_on_one_mixed_batch(pkg):
     plan = HDR._plan([c.shape[:2] for c in crops])
     assert plan["n"] == len(names) - 1 and len(set(plan["dst"].tolist())) > 4
     dev_crops = [torch.from_numpy(c.copy()).cuda() for c in crops]
-    be = HDR._Device(dev_crops[0].device)
+    be = HDR._pages.Device(dev_crops[0].device)
     got, ks, pc = stages(be, plan, dev_crops)
     torch.cuda.synchronize()
-    want, wks, wpc = stages(HDR._Twins(), plan, crops)
+    want, wks, wpc = stages(HDR._pages.Twins(), plan, crops)
     assert ks == wks and pc == wpc
     assert all(np.array_equal(d.cpu().numpy(), c) for d, c in zip(dev_crops, crops))      # the crops are only read
     first = {key: t.cpu().numpy().copy() for key, t in got.items()}
@@ -62,7 +62,7 @@ def test_every_device_output_equals_the_twins_on_one_mixed_batch(pkg):
     wsb = int(L.lib.rtn_header_workspace_bytes(n, len(pc)))
     ws = torch.empty(wsb, dtype=torch.uint8, device="cuda")
     ptr = lambda key: got[key].data_ptr()
-    ptrs = (HDR.C.c_void_p * n)(*[dev_crops[i].data_ptr() for i in plan["idx"]])
+    ptrs = HDR._pointers(be, [dev_crops[i] for i in plan["idx"]])
     be.check(L.lib.rtn_header_sample(be.h.raw, n, ptrs, plan["heights"].ctypes.data, plan["widths"].ctypes.data, *layout[1:],
                                      ptr("hsv"), 3 * total, ws.data_ptr(), wsb))
     be.check(L.lib.rtn_header_cluster(be.h.raw, *layout, ptr("hsv"), 3 * total, 300, ptr("centres"), ptr("counts"), ptr("passes"),

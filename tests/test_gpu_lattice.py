@@ -22,8 +22,8 @@ def cuda(a):
 
 
 def stages(pages, boxes, device, bufs=None):
-    pages, shapes = S._check_pages(pages, device)
-    be = S._Device(pages[0].device) if device else S._Twins()
+    pages, shapes = S._pages.check_pages(pages, S.MIN_SIDE, S.MAX_SIDE, device)
+    be = S._pages.Device(pages[0].device) if device else S._pages.Twins()
     raw = {}
     grids = S._grids(be, pages, shapes, S._check_boxes(boxes, len(pages)), bufs=bufs, raw=raw, **KW)
     return grids, raw

@@ -137,7 +137,7 @@ def test_explicit_k_keeps_the_indices_of_non_empty_clusters():
 
 def test_a_crop_past_the_point_limit_raises_before_any_entry_is_called(monkeypatch):
     calls = []
-    monkeypatch.setattr(HDR._Twins, "call", lambda self, name, args, n_patches=0: calls.append(name))
+    monkeypatch.setattr(HDR._pages.Twins, "call", lambda self, name, args, workspace=None, extra=(): calls.append(name))
     assert R.sampled_height(*K.TOO_LARGE.shape[:2]) * 500 > 2 ** 21
     with pytest.raises(ValueError, match="crop 1"):
         HDR.detect_headers_twins([K.cases()["two_colours"], K.TOO_LARGE])

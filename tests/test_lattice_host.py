@@ -9,13 +9,13 @@ import lattice_ref as R
 
 S = K.S
 L = S.L
-TW = S._Twins()
+TW = S._pages.Twins()
 KW = dict(flavor="auto", line_scale=15, line_tol=2, cover=50, col_gap=12, row_gap=4, margin=10)
 
 
 def run(case, **kw):
     """One case through the twins -> (grids of its page, raw stages)."""
-    pages, shapes = S._check_pages([case["page"]], False)
+    pages, shapes = S._pages.check_pages([case["page"]], S.MIN_SIDE, S.MAX_SIDE, False)
     raw = {}
     grids = S._grids(TW, pages, shapes, S._check_boxes([case["boxes"]], 1), raw=raw, **dict(KW, **kw))
     return grids[0], raw
@@ -95,7 +95,7 @@ def test_separators_report_the_true_count_when_the_room_is_short():
 
 def stage_args():
     c = K.cases()["table"]
-    pages, shapes = S._check_pages([c["page"]], False)
+    pages, shapes = S._pages.check_pages([c["page"]], S.MIN_SIDE, S.MAX_SIDE, False)
     crops, box_page = np.array([[8, 13, 185, 116]], np.int32), np.zeros(1, np.int32)
     bw, hm, vm, ink, offsets, total = S._masks(TW, pages, shapes, box_page, crops, 15)
     g = K.oracle("table")[0]
@@ -116,7 +116,7 @@ def test_edge_and_cell_tables_report_the_true_count_when_the_room_is_short():
 def test_argument_checks():
     crops, offsets, total, hm, vm, ink, (Rn, Cn, sep, runs) = stage_args()
     c = K.cases()["table"]
-    pages, shapes = S._check_pages([c["page"]], False)
+    pages, shapes = S._pages.check_pages([c["page"]], S.MIN_SIDE, S.MAX_SIDE, False)
     page0 = np.zeros(1, np.int32)
     for bad_crop, why in (([8, 13, 29, 116], "side outside"), ([-1, 13, 185, 116], "negative origin"), ([8, 13, 193, 116], "outside its page")):
         with pytest.raises(L.RtnError, match=why):

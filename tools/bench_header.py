@@ -58,19 +58,19 @@ def stage_calls(be, plan, crops, bufs):
     """The four entries as closures over preallocated buffers (ks and the patch table from a first run)."""
     n, total = plan["n"], plan["total"]
     layout = [n, plan["dst"].ctypes.data, plan["offsets"].ctypes.data]
-    ptrs = (HDR.C.c_void_p * n)(*[be.ptr(crops[i]) for i in plan["idx"]])
+    ptrs = HDR._pointers(be, [crops[i] for i in plan["idx"]])
     p = lambda key: be.ptr(bufs[key])                                         # noqa: E731
     keep = bufs["tables"]
     return {
         "sample": lambda: be.call("rtn_header_sample", [n, ptrs, plan["heights"].ctypes.data, plan["widths"].ctypes.data, *layout[1:],
-                                                        p("hsv"), 3 * total]),
+                                                        p("hsv"), 3 * total], HDR._workspace(n)),
         "cluster": lambda: be.call("rtn_header_cluster", [*layout, p("hsv"), 3 * total, 300, p("centres"), p("counts"), p("passes"),
-                                                          p("fx"), p("labels"), 9 * total]),
+                                                          p("fx"), p("labels"), 9 * total], HDR._workspace(n)),
         "stats": lambda: be.call("rtn_header_stats", [*layout, keep["ks"].ctypes.data, p("hsv"), 3 * total, p("labels"), 9 * total,
-                                                      p("hist")]),
+                                                      p("hist")], HDR._workspace(n)),
         "patches": lambda: be.call("rtn_header_patches", [*layout, p("hsv"), 3 * total, len(keep["pc"]), keep["pc"].ctypes.data,
                                                           keep["lo"].ctypes.data, keep["hi"].ctypes.data, keep["offs"].ctypes.data,
-                                                          p("out"), int(keep["bytes"])], n_patches=len(keep["pc"])),
+                                                          p("out"), int(keep["bytes"])], HDR._workspace(n, len(keep["pc"]))),
     }
 
 
@@ -107,7 +107,7 @@ def main():
     plan = HDR._plan([c.shape[:2] for c in host])
     results = HDR.detect_headers(dev)                                         # also the warm-up of every kernel
     torch.cuda.synchronize()
-    be = HDR._Device(dev[0].device)
+    be = HDR._pages.Device(dev[0].device)
     calls = stage_calls(be, plan, dev, buffers(be, plan, results))
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     stage_ms = {k: [] for k in calls}
@@ -144,7 +144,7 @@ def main():
     if m:
         torch.set_num_threads(1)
         sub = HDR._plan([c.shape[:2] for c in host[:m]])
-        tw = HDR._Twins()
+        tw = HDR._pages.Twins()
         tcalls = stage_calls(tw, sub, host, buffers(tw, sub, results[:m]))
         twin_total = 0.0
         for name, fn in tcalls.items():

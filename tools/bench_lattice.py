@@ -126,8 +126,8 @@ def step_cells(a):
         "%s %dx%d separators, %d cells" % (g.flavor, len(g.rows), len(g.cols), len(g.cells)) for g in g0)))
     print("(1) %-12s %8.2f ms per batch (%.2f .. %.2f), %.0f pages/s" % ("table_cells", med(whole), min(whole), max(whole), n / med(whole) * 1e3))
     out["table_cells_ms"] = round(med(whole), 2)
-    pages, shapes = S._check_pages(dev, True)
-    st, fns = stage_functions(S, S._Device(pages[0].device), pages, shapes, boxes)
+    pages, shapes = S._pages.check_pages(dev, S.MIN_SIDE, S.MAX_SIDE)
+    st, fns = stage_functions(S, S._pages.Device(pages[0].device), pages, shapes, boxes)
     for name, fn in fns:
         ms, _ = event_ms(fn, a.iters)
         out[name + "_ms"] = round(med(ms), 3)
@@ -137,8 +137,8 @@ def step_cells(a):
     m = min(a.twin_pages, n)
     twin = {}
     if m:
-        tp, tshapes = S._check_pages([page] * m, False)
-        tst, tfns = stage_functions(S, S._Twins(), tp, tshapes, boxes[:m])
+        tp, tshapes = S._pages.check_pages([page] * m, S.MIN_SIDE, S.MAX_SIDE, False)
+        tst, tfns = stage_functions(S, S._pages.Twins(), tp, tshapes, boxes[:m])
         for name, fn in tfns:
             t0 = time.perf_counter()
             fn()
