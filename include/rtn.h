@@ -808,6 +808,12 @@ size_t rtn_tiff_decode_workspace_bytes(int n, const void* host_blobs, const int6
 int rtn_tiff_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                     uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes);
 int rtn_tiff_decode_host(const void* blob, uint8_t* out_bgr, size_t out_bytes, int32_t* status);
+/* rtn_tiff_inspect_flags: rtn_tiff_inspect with the caller's say instead of the environment's.  RTN_TIFF_ALLOW_G4_ONE_STRIP takes a Group 4
+ *   page of more than 64 rows in one strip (the normal form inside a PDF: model/pdf.py) whatever RTN_TIFF_G4_ONE_STRIP
+ *   says; without the flag the call is rtn_tiff_inspect.  Any other bit is RTN_EINVAL. */
+#define RTN_TIFF_ALLOW_G4_ONE_STRIP 1
+int rtn_tiff_inspect_flags(rtn_handle_t h, const void* file, size_t file_bytes, int flags, rtn_tiff_info_t* info, void* blob,
+                           size_t blob_capacity);
 
 /* ---- TIFF encode (bilevel pages as CCITT Group 4 strip TIFFs, on the device) -------------------------------------------------
  * A page (uint8 (H, W) gray or (H, W, 3) B,G,R, rows without padding) is thresholded (gray as rtn_skew's: (1868 B + 9617 G + 4899 R +
@@ -1140,6 +1146,38 @@ int rtn_lattice_edges_host(int n_boxes, const int32_t* crops, const int64_t* off
 int rtn_lattice_cells_host(int n_boxes, const int32_t* crops, const int64_t* offsets, const int32_t* R, const int32_t* C,
                            const int64_t* sep_offsets, const int32_t* runs, size_t runs_count, const int64_t* cell_offsets,
                            const uint8_t* ink, size_t mask_bytes, int32_t* cell_ink, int32_t* cell_box, size_t cells_count);
+
+/* ---- decoded images onto pages (the strips, turned and mirrored images of scanned PDF pages; model/pdf.py) ---------------
+ * A batch is n_pages pages, uint8 (heights[p], widths[p], 3) B,G,R with sides 1 .. 65535 and rows without padding, and n_items items
+ * (at most 1048576 of each).  An item is a decoded image src of (h, w, 3) B,G,R bytes as every decoder leaves it (sides 1 .. 65535),
+ * an orientation code 1 .. 8 (TIFF / EXIF), an invert flag and a rectangle.  The oriented image O has (h, w) pixels for codes 1 .. 4
+ * and (w, h) for 5 .. 8: O[y][x] = src[fy ? h - 1 - u : u][fx ? w - 1 - v : v] with (u, v) = (y, x) for 1 .. 4 and (x, y) for 5 .. 8,
+ * fy for codes 3, 4, 6, 7 and fx for 2, 3, 7, 8 (6 is a quarter turn clockwise, 8 one counter-clockwise).  The pixels crop_y ..
+ * crop_y + crop_h - 1, crop_x .. crop_x + crop_w - 1 of O go to the rectangle of page `page` whose top-left pixel is (x, y), every
+ * byte v as it is, or as 255 - v with invert = 1.  What no item of a page covers becomes 255.  items, widths, heights and the array
+ * of page pointers are host arrays; the images, the pages and the workspace (256-byte aligned, >= rtn_page_compose_workspace_bytes)
+ * are device memory.
+ * rtn_page_compose checks everything before anything is launched: RTN_EINVAL and a reason for a rectangle outside its page or outside
+ *   its image as the orientation turns it (a size that contradicts the orientation), for two items of a page that overlap, a code
+ *   outside 1 .. 8, a page index outside the batch.  It copies its two tables into the workspace (for which the call waits on the
+ *   stream) and queues at most two launches on the handle's stream: one fill over the pages that their items do not cover, one
+ *   compose over the 64 x 64 tiles of all items, whatever their sizes.  Every byte of a page has one writer and nothing is
+ *   accumulated: the same arguments give the same bytes whatever the pages held.
+ * rtn_page_compose_host (host only, no handle; rtn_last_error(NULL) gives this thread's failure text): the same arguments with host
+ *   pointers and no workspace, through csrc/rtn_compose.h, per destination pixel; the device's bytes. */
+typedef struct {
+    const uint8_t* src;
+    int32_t h, w;                            /* of the decoded image */
+    int32_t orientation, invert;
+    int32_t page, x, y;                      /* the destination page and the top-left of the (clipped) destination rectangle */
+    int32_t crop_x, crop_y, crop_w, crop_h;  /* the rectangle of the oriented image that survives clipping */
+    int32_t reserved_;
+} rtn_compose_item_t;
+size_t rtn_page_compose_workspace_bytes(int n_items, int n_pages);
+int rtn_page_compose(rtn_handle_t h, int n_items, const rtn_compose_item_t* items, int n_pages, uint8_t* const* pages,
+                     const int32_t* widths, const int32_t* heights, void* workspace, size_t workspace_bytes);
+int rtn_page_compose_host(int n_items, const rtn_compose_item_t* items, int n_pages, uint8_t* const* pages, const int32_t* widths,
+                          const int32_t* heights);
 
 #ifdef __cplusplus
 }

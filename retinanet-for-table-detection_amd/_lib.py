@@ -120,6 +120,17 @@ class TiffInfo(C.Structure):
     ]
 
 
+RTN_TIFF_ALLOW_G4_ONE_STRIP = 1
+
+
+class ComposeItem(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("orientation", C.c_int32), ("invert", C.c_int32),
+        ("page", C.c_int32), ("x", C.c_int32), ("y", C.c_int32),
+        ("crop_x", C.c_int32), ("crop_y", C.c_int32), ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("reserved_", C.c_int32),
+    ]
+
+
 def png_blob_bound(file_bytes):
     """RTN_PNG_BLOB_BOUND of include/rtn.h: the most bytes rtn_png_inspect writes for a file of that size."""
     return 128 + 2 * int(file_bytes)
@@ -244,6 +255,7 @@ SIGNATURES = {
     "rtn_png_layout_pixels_host": (_I, [_P, _P, _SZ, _P, C.POINTER(C.c_int32)]),
     "rtn_tiff_blob_bound": (_SZ, [_SZ]),
     "rtn_tiff_inspect": (_I, [_P, _P, _SZ, C.POINTER(TiffInfo), _P, _SZ]),
+    "rtn_tiff_inspect_flags": (_I, [_P, _P, _SZ, _I, C.POINTER(TiffInfo), _P, _SZ]),
     "rtn_tiff_decode_workspace_bytes": (_SZ, [_I, _P, _P]),
     "rtn_tiff_decode": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _SZ]),
     "rtn_tiff_decode_host": (_I, [_P, _P, _SZ, C.POINTER(C.c_int32)]),
@@ -295,6 +307,9 @@ SIGNATURES = {
     "rtn_lattice_profiles_host": (_I, [_I, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ]),
     "rtn_lattice_edges_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _P, _P, _P, _SZ, _P, _SZ]),
     "rtn_lattice_cells_host": (_I, [_I, _P, _P, _P, _P, _P, _P, _SZ, _P, _P, _SZ, _P, _P, _SZ]),
+    "rtn_page_compose_workspace_bytes": (_SZ, [_I, _I]),
+    "rtn_page_compose": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _SZ]),
+    "rtn_page_compose_host": (_I, [_I, _P, _I, _P, _P, _P]),
 }
 
 

@@ -1,5 +1,5 @@
 // rtn_page_launch.h — what the host side of the page-analysis entries shares (rtn_render.hip, rtn_header.hip, rtn_cca.hip,
-// rtn_effect.hip, rtn_resize_u8.hip, rtn_skew.hip, rtn_lattice.hip): the plan check, the workspace layout and the upload of the host
+// rtn_effect.hip, rtn_resize_u8.hip, rtn_skew.hip, rtn_lattice.hip, rtn_compose.hip): the plan check, the workspace layout and the upload of the host
 // tables.  Host only, and for those .hip files only: the host+device headers (rtn_cca.h, rtn_header.h, ...) do not include it, the
 // stand-alone programs under tools/ compile them without HIP.
 #pragma once

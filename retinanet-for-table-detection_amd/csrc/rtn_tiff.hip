@@ -204,20 +204,26 @@ extern "C" size_t rtn_tiff_blob_bound(size_t file_bytes) {
     return 1024 + file_bytes + 21 * strips;
 }
 
-extern "C" int rtn_tiff_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_tiff_info_t* info, void* blob_out, size_t blob_capacity) {
+extern "C" int rtn_tiff_inspect_flags(rtn_handle_t h, const void* file, size_t file_bytes, int flags, rtn_tiff_info_t* info, void* blob_out,
+                                      size_t blob_capacity) {
     if (!info) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect: info is NULL");
     memset(info, 0, sizeof(*info));
     if (!file) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect: file is NULL");
+    if (flags & ~RTN_TIFF_ALLOW_G4_ONE_STRIP) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect_flags: unknown flag bits %d", flags);
     rtn_env_sync();
     char why[200];
     why[0] = 0;
-    const int rc = tf_inspect(static_cast<const uint8_t*>(file), file_bytes, rtn_env_int("RTN_TIFF_G4_ONE_STRIP", 0) != 0, info, blob_out, blob_capacity,
-                              why, sizeof(why));
+    const bool one_strip = (flags & RTN_TIFF_ALLOW_G4_ONE_STRIP) || rtn_env_int("RTN_TIFF_G4_ONE_STRIP", 0) != 0;
+    const int rc = tf_inspect(static_cast<const uint8_t*>(file), file_bytes, one_strip, info, blob_out, blob_capacity, why, sizeof(why));
     if (rc != RTN_OK) {
         memset(info, 0, sizeof(*info));
         return rtn_fail_host(h, rc, "%s", why);
     }
     return RTN_OK;
+}
+
+extern "C" int rtn_tiff_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_tiff_info_t* info, void* blob_out, size_t blob_capacity) {
+    return rtn_tiff_inspect_flags(h, file, file_bytes, 0, info, blob_out, blob_capacity);
 }
 
 extern "C" size_t rtn_tiff_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {

@@ -5,7 +5,8 @@ layouts (1-, 2- and 4-bit gray, palette, alpha, 16-bit R,G,B, Adam7 interlace, t
 calls of at least RTN_PNG_LAYOUT_MIN files (default 2), strip TIFF pages (uncompressed, PackBits, LZW, Deflate or CCITT Group 4;
 bilevel, 8-bit gray, palette or R,G,B) in calls of at least RTN_TIFF_MIN files (default 2), bilevel pages are
 written as CCITT Group 4 TIFFs on the device on request (encode_tiff_bgr, write_images_bgr(tiff="g4")), every other
-file (16-bit gray PNG, tiled, JPEG-in-TIFF or 16-bit TIFF, BMP, ...) is left to Pillow.  csv_generator.py,
+file (16-bit gray PNG, tiled, JPEG-in-TIFF or 16-bit TIFF, BMP, ...) is left to Pillow.  Scanned PDFs are model/pdf.py's, which
+wraps their image streams as such files held in memory and hands them to _decode_datas.  csv_generator.py,
 model/utils.py and model/preprocess.py import from here; the public names stay importable from the first two (re-exports)."""
 import contextlib
 import ctypes as C
@@ -167,9 +168,9 @@ def _blob_bound(d):
     return _JPEG.blob_bound(len(d))
 
 
-def _decode_datas(datas, host_decode, device, handle, stream):
+def _decode_datas(datas, host_decode, device, handle, stream, formats=None):
     """The pages of the files `datas` (list of bytes, or None for a file left to the host): every file that the inspector of one
-    of _ALL_FORMATS accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
+    of `formats` (by default _ALL_FORMATS; model/pdf.py passes the same records with another TIFF inspector) accepts (the first that does takes it; a format whose min_files() is 0 or above len(datas) is not tried) is decoded on the device, each decoder running at most once, after ONE host->device copy of all blobs; the status
     words of all are read once, on `stream`; the other pages (and the pages whose status is non-zero) come
     from host_decode(i), in page order, and are uploaded.  Returns (pages, status) with status[i] the device's word for page i
     (None where no device decoder took the file)."""
@@ -179,7 +180,7 @@ def _decode_datas(datas, host_decode, device, handle, stream):
     # a file with the PNG or a TIFF signature fails rtn_jpeg_inspect at its first two bytes, before anything is written, and the
     # other inspectors refuse at the signature likewise (a PNG blob is bounded by the larger of its inspectors' bounds)
     cap = sum(_blob_bound(d) for d in datas if d is not None)
-    every = _ALL_FORMATS
+    every = _ALL_FORMATS if formats is None else formats
     with torch.cuda.stream(stream):
         host = torch.empty(max(cap, 16), dtype=torch.uint8, pin_memory=True)
         hp = host.data_ptr()

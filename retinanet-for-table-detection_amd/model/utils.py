@@ -499,6 +499,30 @@ def detect_files(model, src_paths, orig_paths, result_dir, batch_size=8, score_t
     return kept
 
 
+def _raw_batch(model, eng, dtype, pages, factors, names, result_dir, score_threshold, labels_to_names, png, min_side, max_side, headers,
+               deskew, cells):
+    """The body of one batch that detect_raw_files and detect_pdf_files share, from the pages as they were read (CUDA tensors) to the
+    files: deskew, interpolate_images where a factor is not 1, the distance maps, the network's inputs, detect, the output step and
+    the cells.  Returns (the kept list of every page, the deskew angles or None, the (H, W) of every page as it was read)."""
+    from . import preprocess
+    pages = list(pages)
+    sizes = [(int(p.shape[0]), int(p.shape[1])) for p in pages]
+    angles = None
+    if deskew:
+        pages, angles = preprocess.deskew_images(pages)
+    grow = [k for k, f in enumerate(factors) if f != 1.0]
+    if grow:
+        for k, big in zip(grow, preprocess.interpolate_images([pages[k] for k in grow], [factors[k] for k in grow])):
+            pages[k] = big
+    processed = preprocess.preprocess_device_pages(pages)
+    canvas, scales = preprocess.compute_inputs_device(processed, min_side=min_side, max_side=max_side, dtype=dtype)
+    boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
+    kept = _render_batch(pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers)
+    if cells:
+        _cells_batch(pages, kept, result_dir, names)
+    return kept, angles, sizes
+
+
 def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
                      min_side=800, max_side=1333, headers=False, deskew=False, cells=False):
     """Raw scans to detections in one call, in batches of batch_size, with every pixel on the device: read_images_bgr of the scans,
@@ -531,18 +555,68 @@ def detect_raw_files(model, orig_paths, result_dir, factors=None, batch_size=8, 
     kept = []
     for i in range(0, len(orig_paths), int(batch_size)):
         orig, fs = orig_paths[i:i + int(batch_size)], factors[i:i + int(batch_size)]
-        pages = read_images_bgr(orig)
-        if deskew:
-            pages = preprocess.deskew_images(pages)[0]
-        grow = [k for k, f in enumerate(fs) if f != 1.0]
-        if grow:
-            for k, big in zip(grow, preprocess.interpolate_images([pages[k] for k in grow], [fs[k] for k in grow])):
-                pages[k] = big
-        processed = preprocess.preprocess_device_pages(pages)
-        canvas, scales = preprocess.compute_inputs_device(processed, min_side=min_side, max_side=max_side, dtype=dtype)
-        boxes, scores, labels = eng.detect(canvas, nms=model.nms, class_specific_filter=model.class_specific_filter)
         names = [os.path.basename(str(p)) for p in orig]
-        kept += _render_batch(pages, boxes, scores, labels, scales, result_dir, names, labels_to_names, score_threshold, png, headers)
-        if cells:
-            _cells_batch(pages, kept[i:], result_dir, names)
+        kept += _raw_batch(model, eng, dtype, read_images_bgr(orig), fs, names, result_dir, score_threshold, labels_to_names, png,
+                           min_side, max_side, headers, deskew, cells)[0]
     return kept
+
+
+def detect_pdf_files(model, pdf_paths, result_dir, pages=None, factors=None, batch_size=8, score_threshold=0.6, labels_to_names=None, png="host",
+                     min_side=800, max_side=1333, headers=False, deskew=False, cells=False):
+    """Scanned PDFs to detections in one call: detect_raw_files' loop with its pages coming from model/pdf.py's read_pdfs_pages (DESIGN
+    §3.4p) instead of read_images_bgr.  The pages of all files are read in one device batch and then go through the network in batches
+    of batch_size, whatever file they belong to.  pages: None, or per file the page indices (from 0) to read (None: all); factors:
+    None (1.0 for every page) or one enlargement factor per read page, in file and page order.  The image name of page k (from 1) of
+    <stem>.pdf is the reference's convertPdfsToImages name, "<stem>_Page<k>-<dpi>.png" with dpi = round(72 sx); the rendered files are
+    detect_raw_files' under those names.  A page that is not image-only (or that no decoder takes) is skipped with a warning.  Besides
+    the rendered files, result_dir/pdfResults/<stem>_tables.csv holds every kept box of a file in the reference's PDF-CSV layout
+    (header image_id,xmin,ymin,xmax,ymax,label; image_id "<stem>_Page<k>") in integer points of the unrotated page, y upwards
+    (pdf.boxes_to_pdf, truncated as PDFCSVtoImageCSV truncates); with deskew=True the boxes are first mapped back to the scan by
+    preprocess.boxes_to_scan.  Returns a list of (path, page_index, kept), kept None for a skipped page, in file and page order."""
+    import csv
+    import os
+    from . import pdf, preprocess
+    if not getattr(model, "bbox", False):
+        raise ValueError("detect_pdf_files: the inference model (retinanet_bbox) is required")
+    pdf_paths = list(pdf_paths)
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be >= 1")
+    labels_to_names = labels_to_names or {0: 'table'}
+    read, infos = pdf.read_pdfs_pages(pdf_paths, pages=pages, return_info=True)
+    out, todo = [], []                                             # todo: (position in out, file, PdfPage, tensor)
+    for f, (path, tensors, info) in enumerate(zip(pdf_paths, read, infos)):
+        want = None if pages is None or pages[f] is None else set(int(v) for v in pages[f])
+        for page, t in zip(info.pages, tensors):
+            if want is not None and page.index not in want:
+                continue
+            if t is None:
+                warnings.warn("%s, page %d skipped: %s" % (path, page.index + 1, page.refused))
+            else:
+                todo.append((len(out), f, page, t))
+            out.append((path, page.index, None))
+    factors = [1.0] * len(todo) if factors is None else [float(v) for v in factors]
+    if len(factors) != len(todo):
+        raise ValueError("%d factors for %d pages" % (len(factors), len(todo)))
+    dtype = torch.float32 if model._root().dtype == "f32" else torch.bfloat16
+    eng = model.engine()
+    rows = {f: [] for f in range(len(pdf_paths))}
+    stem = lambda f: os.path.splitext(os.path.basename(str(pdf_paths[f])))[0]
+    for i in range(0, len(todo), int(batch_size)):
+        batch, fs = todo[i:i + int(batch_size)], factors[i:i + int(batch_size)]
+        names = ["%s_Page%d-%d.png" % (stem(f), page.index + 1, int(round(72 * page.sx))) for _pos, f, page, _t in batch]
+        kept, angles, sizes = _raw_batch(model, eng, dtype, [t for _pos, _f, _page, t in batch], fs, names, result_dir, score_threshold,
+                                         labels_to_names, png, min_side, max_side, headers, deskew, cells)
+        for k, ((pos, f, page, _t), mine, factor) in enumerate(zip(batch, kept, fs)):
+            out[pos] = (out[pos][0], page.index, mine)
+            boxes = np.array([b for b, _score, _label in mine], np.float64).reshape(-1, 4)
+            if deskew and len(boxes):
+                boxes = preprocess.boxes_to_scan(boxes / factor, angles[k], sizes[k][0], sizes[k][1]) * factor
+            for (x1, y1, x2, y2), (_b, _score, label) in zip(pdf.boxes_to_pdf(boxes, page, factor=factor), mine):
+                rows[f].append(("%s_Page%d" % (stem(f), page.index + 1), int(x1), int(y1), int(x2), int(y2), labels_to_names[int(label)]))
+    os.makedirs(os.path.join(result_dir, "pdfResults"), exist_ok=True)
+    for f in range(len(pdf_paths)):
+        with open(os.path.join(result_dir, "pdfResults", stem(f) + "_tables.csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["image_id", "xmin", "ymin", "xmax", "ymax", "label"])
+            w.writerows(rows[f])
+    return out
