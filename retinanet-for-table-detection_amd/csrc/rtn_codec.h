@@ -1,4 +1,5 @@
-// rtn_codec.h — what the four page codecs (rtn_jpeg.hip, rtn_jpeg_enc.hip, rtn_png_enc.hip, rtn_png_dec.hip) share.
+// rtn_codec.h — what the seven page-codec files (rtn_jpeg.hip, rtn_jpeg_enc.hip, rtn_png_enc.hip, rtn_png_dec.hip, rtn_png_stream.hip,
+// rtn_tiff.hip, rtn_tiff_enc.hip) and the page-analysis files share, device and host; the codec entries' host side: rtn_codec_launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -15,8 +15,7 @@
 // non-zero status word: the caller decodes that page on the host.
 // The blob layout, the inspector and every decode function live in rtn_jpeg_decode.h, which a plain C++ compiler also compiles:
 // rtn_jpeg_decode_host runs the same functions for any number of virtual threads on the CPU, behind a bounds-checking context.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_jpeg_decode.h"
 
 namespace {
@@ -143,19 +142,20 @@ __global__ __launch_bounds__(256) void jpeg_color_kernel(const uint8_t* __restri
 
 thread_local JHostStats g_host_stats = {0, 0};
 
+// off >= 0: the callers (rtn_codec_blobs, and the walk behind it) have looked at the sign
+const JHdr* jd_blob(const void* host_blobs, int64_t off) {
+    const uint8_t* b = static_cast<const uint8_t*>(host_blobs) + off;
+    return jpeg_blob_ok(b) ? reinterpret_cast<const JHdr*>(b) : nullptr;
+}
+
 }  // namespace
 
 // rtn_jpeg_inspect: see include/rtn.h
 extern "C" int rtn_jpeg_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_jpeg_info_t* info, void* blob_out,
                                 size_t blob_capacity) {
-    if (!info) return rtn_fail_host(h, RTN_EINVAL, "rtn_jpeg_inspect: info is NULL");
-    memset(info, 0, sizeof(*info));
-    if (!file) return rtn_fail_host(h, RTN_EINVAL, "rtn_jpeg_inspect: file is NULL");
-    char why[200];
-    why[0] = 0;
-    const int rc = jpeg_inspect(static_cast<const uint8_t*>(file), file_bytes, info, blob_out, blob_capacity, why, sizeof(why));
-    if (rc != RTN_OK) return rtn_fail_host(h, rc, "%s", why);
-    return RTN_OK;
+    return rtn_codec_inspect(h, "rtn_jpeg_inspect", file, info, false, [&](char* why, size_t bytes) {
+        return jpeg_inspect(static_cast<const uint8_t*>(file), file_bytes, info, blob_out, blob_capacity, why, bytes);
+    });
 }
 
 // rtn_jpeg_decode_host, rtn_jpeg_decode_host_counters: see include/rtn.h
@@ -174,59 +174,36 @@ extern "C" void rtn_jpeg_decode_host_counters(int32_t* passes, int32_t* busy_thr
 }
 
 extern "C" size_t rtn_jpeg_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
-    if (n <= 0 || !host_blobs || !offsets) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const uint8_t* b = static_cast<const uint8_t*>(host_blobs) + offsets[i];
-        if (!jpeg_blob_ok(b)) return 0;
-        tot += (size_t)reinterpret_cast<const JHdr*>(b)->ws_bytes;
-    }
-    return tot;
+    return rtn_codec_blob_bytes(n, host_blobs, offsets, jd_blob);
 }
 
 extern "C" int rtn_jpeg_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                                uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: n < 0");
-    if (n == 0) return RTN_OK;
-    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace)
-        return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: NULL argument");
-    if (((uintptr_t)dev_blobs & 15) || ((uintptr_t)workspace & 255))
-        return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: blobs must be 16-byte aligned, the workspace 256-byte aligned");
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: blob %d offset not 16-byte aligned", i);
-        const uint8_t* b = static_cast<const uint8_t*>(host_blobs) + offsets[i];
-        if (!jpeg_blob_ok(b)) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: blob %d is not an rtn_jpeg_inspect blob", i);
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_decode: page %d is NULL", i);
-        need += (size_t)reinterpret_cast<const JHdr*>(b)->ws_bytes;
-    }
-    if (workspace_bytes < need)
-        return rtn_fail(h, RTN_ENOMEM, "rtn_jpeg_decode: workspace %zu < %zu bytes", workspace_bytes, need);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        JBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        long long maxpix = 0;
-        int maxblocks = 0;
-        for (int j = 0; j < bt.n; ++j) {
-            const JHdr* hd = reinterpret_cast<const JHdr*>(static_cast<const uint8_t*>(host_blobs) + offsets[i0 + j]);
-            bt.blob_off[j] = offsets[i0 + j];
-            bt.ws_off[j] = ws;
-            bt.out[j] = pages[i0 + j];
-            ws += hd->ws_bytes;
+    const int rc = rtn_decode_check(h, "rtn_jpeg_decode", "rtn_jpeg_inspect", n, host_blobs, dev_blobs, offsets, pages, status, workspace,
+                                    workspace_bytes, jd_blob, rtn_codec_no_extra);
+    if (rc != RTN_CODEC_GO) return rc;
+    const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
+    uint8_t* wsp = static_cast<uint8_t*>(workspace);
+    long long maxpix = 0;
+    int maxblocks = 0;
+    return rtn_codec_walk<JBatch>(n,
+        [&](JBatch& bt, int k, int i, long long ws) {
+            const JHdr* hd = jd_blob(host_blobs, offsets[i]);
+            if (k == 0) maxpix = 0, maxblocks = 0;
+            bt.blob_off[k] = offsets[i];
+            bt.ws_off[k] = ws;
+            bt.out[k] = pages[i];
             maxblocks = hd->total_blocks > maxblocks ? hd->total_blocks : maxblocks;
             maxpix = (long long)hd->W * hd->H > maxpix ? (long long)hd->W * hd->H : maxpix;
-        }
-        const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
-        uint8_t* wsp = static_cast<uint8_t*>(workspace);
-        jpeg_huffman_kernel<<<bt.n, JPG_THREADS, 0, h->stream>>>(db, wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "jpeg_huffman_kernel");
-        jpeg_idct_kernel<<<dim3((maxblocks + 255) / 256, bt.n), 256, 0, h->stream>>>(db, wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "jpeg_idct_kernel");
-        jpeg_color_kernel<<<dim3((unsigned)((maxpix + 255) / 256), bt.n), 256, 0, h->stream>>>(db, wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "jpeg_color_kernel");
-    }
-    return RTN_OK;
+            return (long long)hd->ws_bytes;
+        },
+        [&](const JBatch& bt, int i0) {
+            jpeg_huffman_kernel<<<bt.n, JPG_THREADS, 0, h->stream>>>(db, wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "jpeg_huffman_kernel");
+            jpeg_idct_kernel<<<dim3((maxblocks + 255) / 256, bt.n), 256, 0, h->stream>>>(db, wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "jpeg_idct_kernel");
+            jpeg_color_kernel<<<dim3((unsigned)((maxpix + 255) / 256), bt.n), 256, 0, h->stream>>>(db, wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "jpeg_color_kernel");
+            return RTN_OK;
+        });
 }

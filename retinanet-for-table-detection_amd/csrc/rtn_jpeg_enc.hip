@@ -16,8 +16,7 @@
 //   5. jenc_assemble_kernel: one workgroup per page: pads the last byte with 1-bits, counts the 0xFF bytes per thread chunk,
 //      scans, and writes header + stuffed stream + EOI into the page's output slot, and the file length.
 // A page whose file would not fit its slot gets a non-zero status word and a length of 0: the caller encodes it on the host.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 
 namespace {
 
@@ -595,45 +594,29 @@ extern "C" size_t rtn_jpeg_encode_bound(int width, int height, int components, i
 extern "C" size_t rtn_jpeg_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components,
                                                   const int32_t* subsampling) {
     if (n <= 0 || !widths || !heights || !components || !subsampling) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        if (je_check(nullptr, widths[i], heights[i], components[i], subsampling[i], 75, "rtn_jpeg_encode_workspace_bytes")) return 0;
-        tot += (size_t)je_layout(je_geom(widths[i], heights[i], components[i], subsampling[i])).total;
-    }
-    return tot;
+    return rtn_codec_page_bytes(
+        n, [&](int i) { return je_check(nullptr, widths[i], heights[i], components[i], subsampling[i], 75, "rtn_jpeg_encode_workspace_bytes"); },
+        [&](int i) { return je_layout(je_geom(widths[i], heights[i], components[i], subsampling[i])).total; });
 }
 
 extern "C" int rtn_jpeg_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* widths, const int32_t* heights,
                                const int32_t* components, const int32_t* subsampling, const int32_t* quality, uint8_t* out,
                                const int64_t* out_offsets, int64_t* out_bytes, int32_t* status, void* workspace,
                                size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_encode: n < 0");
-    if (n == 0) return RTN_OK;
-    if (!pages || !widths || !heights || !components || !subsampling || !quality || !out || !out_offsets || !out_bytes || !status ||
-        !workspace)
-        return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_encode: NULL argument");
-    if ((uintptr_t)workspace & 255) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_encode: the workspace must be 256-byte aligned");
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        const int rc = je_check(h, widths[i], heights[i], components[i], subsampling[i], quality[i], "rtn_jpeg_encode");
-        if (rc) return rc;
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_encode: page %d is NULL", i);
-        if (out_offsets[i] < 0 || out_offsets[i + 1] < out_offsets[i])
-            return rtn_fail(h, RTN_EINVAL, "rtn_jpeg_encode: output slot %d is [%lld, %lld)", i, (long long)out_offsets[i],
-                            (long long)out_offsets[i + 1]);
-        need += (size_t)je_layout(je_geom(widths[i], heights[i], components[i], subsampling[i])).total;
-    }
-    if (workspace_bytes < need)
-        return rtn_fail(h, RTN_ENOMEM, "rtn_jpeg_encode: workspace %zu < %zu bytes", workspace_bytes, need);
+    const char* name = "rtn_jpeg_encode";
+    const int rc = rtn_encode_check(
+        h, name, n, {pages, widths, heights, components, subsampling, quality, out, out_offsets, out_bytes, status, workspace}, pages, workspace,
+        workspace_bytes, [&](int i) { return je_check(h, widths[i], heights[i], components[i], subsampling[i], quality[i], name); },
+        [&](int i) {
+            if (out_offsets[i] < 0 || out_offsets[i + 1] < out_offsets[i])
+                return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is [%lld, %lld)", name, i, (long long)out_offsets[i], (long long)out_offsets[i + 1]);
+            return RTN_OK;
+        },
+        [&](int i) { return je_layout(je_geom(widths[i], heights[i], components[i], subsampling[i])).total; });
+    if (rc != RTN_CODEC_GO) return rc;
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        JEBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        for (int k = 0; k < bt.n; ++k) {
-            const int i = i0 + k;
+    return rtn_codec_walk<JEBatch>(n,
+        [&](JEBatch& bt, int k, int i, long long ws) {
             const JEGeom g = je_geom(widths[i], heights[i], components[i], subsampling[i]);
             const JELayout L = je_layout(g);
             JEPage& p = bt.p[k];
@@ -644,21 +627,22 @@ extern "C" int rtn_jpeg_encode(rtn_handle_t h, int n, const uint8_t* const* page
             p.off_bits = L.bits; p.off_tiles = L.tiles; p.off_stream = L.stream;
             p.W = widths[i]; p.H = heights[i]; p.nc = components[i]; p.ss = subsampling[i]; p.q = quality[i];
             p.nblocks = g.nblocks; p.ntiles = L.ntiles; p.stream_words = L.stream_words;
-            ws += L.total;
             bt.maxblocks = g.nblocks > bt.maxblocks ? g.nblocks : bt.maxblocks;
-        }
-        const dim3 grid((bt.maxblocks + JE_TILE - 1) / JE_TILE, bt.n);
-        jenc_transform_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "jenc_transform_kernel");
-        jenc_bits_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "jenc_bits_kernel");
-        jenc_scan_kernel<<<bt.n, JE_SCAN_THREADS, 0, h->stream>>>(wsp, status + i0, reinterpret_cast<long long*>(out_bytes + i0), bt);
-        RTN_CHECK_LAUNCH(h, "jenc_scan_kernel");
-        jenc_pack_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "jenc_pack_kernel");
-        jenc_assemble_kernel<<<bt.n, JE_SCAN_THREADS, 0, h->stream>>>(wsp, status + i0, reinterpret_cast<long long*>(out_bytes + i0),
-                                                                       bt);
-        RTN_CHECK_LAUNCH(h, "jenc_assemble_kernel");
-    }
-    return RTN_OK;
+            return L.total;
+        },
+        [&](const JEBatch& bt, int i0) {
+            const dim3 grid((bt.maxblocks + JE_TILE - 1) / JE_TILE, bt.n);
+            long long* lengths = reinterpret_cast<long long*>(out_bytes + i0);
+            jenc_transform_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "jenc_transform_kernel");
+            jenc_bits_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "jenc_bits_kernel");
+            jenc_scan_kernel<<<bt.n, JE_SCAN_THREADS, 0, h->stream>>>(wsp, status + i0, lengths, bt);
+            RTN_CHECK_LAUNCH(h, "jenc_scan_kernel");
+            jenc_pack_kernel<<<grid, JE_TILE, 0, h->stream>>>(wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "jenc_pack_kernel");
+            jenc_assemble_kernel<<<bt.n, JE_SCAN_THREADS, 0, h->stream>>>(wsp, status + i0, lengths, bt);
+            RTN_CHECK_LAUNCH(h, "jenc_assemble_kernel");
+            return RTN_OK;
+        });
 }

@@ -19,8 +19,7 @@
 // ends at the payload's last byte, with no match before its first byte.  An inflater reading the concatenated IDATs is therefore at
 // a block boundary on a byte boundary wherever a payload ends, decodes the same blocks, and finds every match source inside the
 // same chunk: it produces the same bytes, and after the last payload the final block and the Adler-32 the page kernel compared.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_png_crc.h"
 #include "rtn_png_inflate.h"
 #include <vector>
@@ -334,6 +333,7 @@ __global__ __launch_bounds__(PD_THREADS) void pdec_up_kernel(const uint8_t* ws, 
     }
 }
 
+// off >= 0: the callers (rtn_codec_blobs, and the walk behind it) have looked at the sign
 const PDHdr* pd_blob(const void* host_blobs, int64_t off) {
     const PDHdr* hd = reinterpret_cast<const PDHdr*>(static_cast<const uint8_t*>(host_blobs) + off);
     return (hd->magic == PD_MAGIC && hd->nchunks > 0 && hd->ws_bytes > 0) ? hd : nullptr;
@@ -472,65 +472,43 @@ extern "C" int rtn_png_inflate_chunk_host(const void* in, size_t in_bytes, void*
 }
 
 extern "C" size_t rtn_png_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
-    if (n <= 0 || !host_blobs || !offsets) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const PDHdr* hd = pd_blob(host_blobs, offsets[i]);
-        if (!hd) return 0;
-        tot += (size_t)hd->ws_bytes;
-    }
-    return tot;
+    return rtn_codec_blob_bytes(n, host_blobs, offsets, pd_blob);
 }
 
 extern "C" int rtn_png_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                               uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: n < 0");
-    if (n == 0) return RTN_OK;
-    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace)
-        return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: NULL argument");
-    if (((uintptr_t)dev_blobs & 15) || ((uintptr_t)workspace & 255))
-        return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: blobs must be 16-byte aligned, the workspace 256-byte aligned");
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: blob %d offset not 16-byte aligned", i);
-        const PDHdr* hd = pd_blob(host_blobs, offsets[i]);
-        if (!hd) return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: blob %d is not an rtn_png_inspect blob", i);
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "rtn_png_decode: page %d is NULL", i);
-        need += (size_t)hd->ws_bytes;
-    }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_png_decode: workspace %zu < %zu bytes", workspace_bytes, need);
+    const int rc = rtn_decode_check(h, "rtn_png_decode", "rtn_png_inspect", n, host_blobs, dev_blobs, offsets, pages, status, workspace,
+                                    workspace_bytes, pd_blob, rtn_codec_no_extra);
+    if (rc != RTN_CODEC_GO) return rc;
     const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        PDBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        long long maxcols = 0;
-        for (int j = 0; j < bt.n; ++j) {
-            const PDHdr* hd = pd_blob(host_blobs, offsets[i0 + j]);
-            PDPage& p = bt.p[j];
-            p.blob_off = offsets[i0 + j];
+    long long maxcols = 0;
+    return rtn_codec_walk<PDBatch>(n,
+        [&](PDBatch& bt, int k, int i, long long ws) {
+            const PDHdr* hd = pd_blob(host_blobs, offsets[i]);
+            if (k == 0) maxcols = 0;
+            PDPage& p = bt.p[k];
+            p.blob_off = offsets[i];
             p.ws_off = ws;
             p.off_meta = (long long)hd->nchunks * PD_CHUNK;
             p.stream = (long long)hd->H * (1 + (long long)hd->W * hd->nc);
-            p.out = pages[i0 + j];
+            p.out = pages[i];
             p.W = hd->W; p.H = hd->H; p.nc = hd->nc; p.nchunks = hd->nchunks;
             p.adler = hd->adler; p.zhdr = hd->zhdr; p.off_table = hd->off_table;
-            ws += hd->ws_bytes;
             bt.maxchunks = p.nchunks > bt.maxchunks ? p.nchunks : bt.maxchunks;
             bt.maxrows = p.H > bt.maxrows ? p.H : bt.maxrows;
             maxcols = (long long)p.W * p.nc > maxcols ? (long long)p.W * p.nc : maxcols;
-        }
-        pdec_inflate_kernel<<<dim3(bt.maxchunks, bt.n), PD_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "pdec_inflate_kernel");
-        pdec_page_kernel<<<bt.n, PD_WAVE, 0, h->stream>>>(wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "pdec_page_kernel");
-        pdec_sub_kernel<<<dim3(bt.maxrows < PD_MAX_GRID ? bt.maxrows : PD_MAX_GRID, bt.n), PD_THREADS, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "pdec_sub_kernel");
-        pdec_up_kernel<<<dim3((unsigned)((maxcols + PD_THREADS - 1) / PD_THREADS), bt.n), PD_THREADS, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "pdec_up_kernel");
-    }
-    return RTN_OK;
+            return (long long)hd->ws_bytes;
+        },
+        [&](const PDBatch& bt, int i0) {
+            pdec_inflate_kernel<<<dim3(bt.maxchunks, bt.n), PD_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "pdec_inflate_kernel");
+            pdec_page_kernel<<<bt.n, PD_WAVE, 0, h->stream>>>(wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "pdec_page_kernel");
+            pdec_sub_kernel<<<dim3(rtn_min_grid(bt.maxrows, PD_MAX_GRID), bt.n), PD_THREADS, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "pdec_sub_kernel");
+            pdec_up_kernel<<<dim3((unsigned)((maxcols + PD_THREADS - 1) / PD_THREADS), bt.n), PD_THREADS, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "pdec_up_kernel");
+            return RTN_OK;
+        });
 }

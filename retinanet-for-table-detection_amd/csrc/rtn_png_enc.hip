@@ -24,8 +24,7 @@
 // flush), and its IDAT adds 12 bytes of framing; the file adds the signature (8), IHDR (25), IEND (12), the zlib header (2), the
 // final empty stored block (5) and the Adler-32 (4).  So a file is at most 56 + stream + 22 * chunks bytes, and the host path
 // has nothing to catch.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_png_crc.h"
 
 namespace {
@@ -694,45 +693,33 @@ extern "C" size_t rtn_png_encode_bound(int width, int height, int components) {
 
 extern "C" size_t rtn_png_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components) {
     if (n <= 0 || !widths || !heights || !components) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        if (pe_check(nullptr, widths[i], heights[i], components[i], "rtn_png_encode_workspace_bytes")) return 0;
-        tot += (size_t)pe_layout(widths[i], heights[i], components[i]).total;
-    }
-    return tot;
+    return rtn_codec_page_bytes(n, [&](int i) { return pe_check(nullptr, widths[i], heights[i], components[i], "rtn_png_encode_workspace_bytes"); },
+                                [&](int i) { return pe_layout(widths[i], heights[i], components[i]).total; });
 }
 
 extern "C" int rtn_png_encode(rtn_handle_t h, int n, const uint8_t* const* pages, const int32_t* widths, const int32_t* heights,
                               const int32_t* components, uint8_t* out, const int64_t* out_offsets, int64_t* out_bytes,
                               int32_t* status, void* workspace, size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "rtn_png_encode: n < 0");
-    if (n == 0) return RTN_OK;
-    if (!pages || !widths || !heights || !components || !out || !out_offsets || !out_bytes || !status || !workspace)
-        return rtn_fail(h, RTN_EINVAL, "rtn_png_encode: NULL argument");
-    if ((uintptr_t)workspace & 255) return rtn_fail(h, RTN_EINVAL, "rtn_png_encode: the workspace must be 256-byte aligned");
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        const int rc = pe_check(h, widths[i], heights[i], components[i], "rtn_png_encode");
-        if (rc) return rc;
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "rtn_png_encode: page %d is NULL", i);
-        if (out_offsets[i] < 0 || out_offsets[i + 1] - out_offsets[i] < pe_bound(widths[i], heights[i], components[i]))
-            return rtn_fail(h, RTN_EINVAL, "rtn_png_encode: output slot %d is [%lld, %lld), rtn_png_encode_bound asks for %lld bytes", i,
-                            (long long)out_offsets[i], (long long)out_offsets[i + 1],
-                            pe_bound(widths[i], heights[i], components[i]));
-        need += (size_t)pe_layout(widths[i], heights[i], components[i]).total;
-    }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "rtn_png_encode: workspace %zu < %zu bytes", workspace_bytes, need);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        PEBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.ws = static_cast<uint8_t*>(workspace);
-        bt.out_bytes = reinterpret_cast<long long*>(out_bytes + i0);
-        bt.status = status + i0;
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        for (int k = 0; k < bt.n; ++k) {
-            const int i = i0 + k;
+    const char* name = "rtn_png_encode";
+    const int rc = rtn_encode_check(
+        h, name, n, {pages, widths, heights, components, out, out_offsets, out_bytes, status, workspace}, pages, workspace, workspace_bytes,
+        [&](int i) { return pe_check(h, widths[i], heights[i], components[i], name); },
+        [&](int i) {
+            const long long bound = pe_bound(widths[i], heights[i], components[i]);
+            if (out_offsets[i] < 0 || out_offsets[i + 1] - out_offsets[i] < bound)
+                return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is [%lld, %lld), rtn_png_encode_bound asks for %lld bytes", name, i,
+                                (long long)out_offsets[i], (long long)out_offsets[i + 1], bound);
+            return RTN_OK;
+        },
+        [&](int i) { return pe_layout(widths[i], heights[i], components[i]).total; });
+    if (rc != RTN_CODEC_GO) return rc;
+    return rtn_codec_walk<PEBatch>(n,
+        [&](PEBatch& bt, int k, int i, long long ws) {
+            if (k == 0) {
+                bt.ws = static_cast<uint8_t*>(workspace);
+                bt.out_bytes = reinterpret_cast<long long*>(out_bytes + i);
+                bt.status = status + i;
+            }
             const PELayout L = pe_layout(widths[i], heights[i], components[i]);
             PEPage& p = bt.p[k];
             p.src = pages[i];
@@ -742,20 +729,21 @@ extern "C" int rtn_png_encode(rtn_handle_t h, int n, const uint8_t* const* pages
             p.stream = pe_stream(widths[i], heights[i], components[i]);
             p.W = widths[i]; p.H = heights[i]; p.nc = components[i];
             p.nchunks = (int)pe_chunks(p.stream);
-            ws += L.total;
             bt.maxrows = p.H > bt.maxrows ? p.H : bt.maxrows;
             bt.maxchunks = p.nchunks > bt.maxchunks ? p.nchunks : bt.maxchunks;
-        }
-        penc_filter_kernel<<<dim3(bt.maxrows < PE_MAX_GRID ? bt.maxrows : PE_MAX_GRID, bt.n), PE_THREADS, 0, h->stream>>>(bt);
-        RTN_CHECK_LAUNCH(h, "penc_filter_kernel");
-        const int rc = rtn_launch_lds<penc_deflate_kernel>(h, dim3(bt.maxchunks, bt.n), dim3(PE_THREADS), (unsigned)sizeof(PELds),
-                                                           (int)sizeof(PELds), bt);
-        if (rc) return rc;
-        RTN_CHECK_LAUNCH(h, "penc_deflate_kernel");
-        penc_scan_kernel<<<bt.n, PE_SCAN_THREADS, 0, h->stream>>>(bt);
-        RTN_CHECK_LAUNCH(h, "penc_scan_kernel");
-        penc_copy_kernel<<<dim3(bt.maxchunks, bt.n), PE_THREADS, 0, h->stream>>>(bt);
-        RTN_CHECK_LAUNCH(h, "penc_copy_kernel");
-    }
-    return RTN_OK;
+            return L.total;
+        },
+        [&](const PEBatch& bt, int) {
+            penc_filter_kernel<<<dim3(rtn_min_grid(bt.maxrows, PE_MAX_GRID), bt.n), PE_THREADS, 0, h->stream>>>(bt);
+            RTN_CHECK_LAUNCH(h, "penc_filter_kernel");
+            const int rc = rtn_launch_lds<penc_deflate_kernel>(h, dim3(bt.maxchunks, bt.n), dim3(PE_THREADS), (unsigned)sizeof(PELds),
+                                                               (int)sizeof(PELds), bt);
+            if (rc) return rc;
+            RTN_CHECK_LAUNCH(h, "penc_deflate_kernel");
+            penc_scan_kernel<<<bt.n, PE_SCAN_THREADS, 0, h->stream>>>(bt);
+            RTN_CHECK_LAUNCH(h, "penc_scan_kernel");
+            penc_copy_kernel<<<dim3(bt.maxchunks, bt.n), PE_THREADS, 0, h->stream>>>(bt);
+            RTN_CHECK_LAUNCH(h, "penc_copy_kernel");
+            return RTN_OK;
+        });
 }

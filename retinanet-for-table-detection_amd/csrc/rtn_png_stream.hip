@@ -24,8 +24,7 @@
 //   8b. pld_expand_kernel   one thread per four pixels of the page: sample -> B,G,R, every pass gathered into the page.
 // No workgroup waits on another, no loop's end depends on file bytes alone, and every position derived from them is checked before
 // use.  Any non-zero status word sends the page to the host decoder.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_png_stream.h"
 
 namespace {
@@ -528,8 +527,8 @@ __global__ __launch_bounds__(PL_THREADS) void pld_expand_kernel(const uint8_t* b
     }
 }
 
-const PSHdr* psd_blob(const void* host_blobs, int64_t off, uint32_t magic = PS_MAGIC) {
-    if (off < 0) return nullptr;
+// off >= 0: the callers (rtn_codec_blobs, and the walk behind it) have looked at the sign
+const PSHdr* psd_blob(const void* host_blobs, int64_t off, uint32_t magic) {
     const PSHdr* hd = reinterpret_cast<const PSHdr*>(static_cast<const uint8_t*>(host_blobs) + off);
     if (hd->magic != magic || hd->blob_bytes < (int64_t)sizeof(PSHdr)) return nullptr;
     return ps_blob(hd, (size_t)hd->blob_bytes, magic);
@@ -543,109 +542,78 @@ uint32_t psd_segment_bytes() {
 
 int psd_inspect(const char* name, bool layout, rtn_handle_t h, const void* file, size_t file_bytes, rtn_png_info_t* info, void* blob_out,
                 size_t blob_capacity) {
-    if (!info) return rtn_fail_host(h, RTN_EINVAL, "%s: info is NULL", name);
-    memset(info, 0, sizeof(*info));
-    if (!file) return rtn_fail_host(h, RTN_EINVAL, "%s: file is NULL", name);
-    char why[200];
-    why[0] = 0;
-    const int rc = ps_inspect_any(static_cast<const uint8_t*>(file), file_bytes, psd_segment_bytes(), info, blob_out, blob_capacity, why,
-                                  sizeof(why), layout);
-    if (rc != RTN_OK) {
-        memset(info, 0, sizeof(*info));
-        return rtn_fail_host(h, rc, "%s", why);
-    }
-    return RTN_OK;
+    return rtn_codec_inspect(h, name, file, info, true, [&](char* why, size_t bytes) {
+        return ps_inspect_any(static_cast<const uint8_t*>(file), file_bytes, psd_segment_bytes(), info, blob_out, blob_capacity, why, bytes, layout);
+    });
 }
 
 size_t psd_workspace_bytes(uint32_t magic, int n, const void* host_blobs, const int64_t* offsets) {
-    if (n <= 0 || !host_blobs || !offsets) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const PSHdr* hd = psd_blob(host_blobs, offsets[i], magic);
-        if (!hd) return 0;
-        tot += (size_t)hd->ws_bytes;
-    }
-    return tot;
+    return rtn_codec_blob_bytes(n, host_blobs, offsets, [=](const void* blobs, int64_t off) { return psd_blob(blobs, off, magic); });
 }
 
 // rtn_png_stream_decode (magic PS_MAGIC) and rtn_png_layout_decode (PL_MAGIC): stages 1 - 7 are the same launches, the last stage is
 // psd_unfilter_kernel for the one and pld_unfilter_kernel + pld_expand_kernel for the other.
 int psd_decode(const char* name, uint32_t magic, rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets,
                uint8_t* const* pages, int32_t* status, void* workspace, size_t workspace_bytes) {
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "%s: n < 0", name);
-    if (n == 0) return RTN_OK;
-    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace) return rtn_fail(h, RTN_EINVAL, "%s: NULL argument", name);
-    if (((uintptr_t)dev_blobs & 15) || ((uintptr_t)workspace & 255))
-        return rtn_fail(h, RTN_EINVAL, "%s: blobs must be 16-byte aligned, the workspace 256-byte aligned", name);
-    const char* inspector = magic == PL_MAGIC ? "rtn_png_layout_inspect" : "rtn_png_stream_inspect";
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "%s: blob %d offset not 16-byte aligned", name, i);
-        const PSHdr* hd = psd_blob(host_blobs, offsets[i], magic);
-        if (!hd) return rtn_fail(h, RTN_EINVAL, "%s: blob %d is not an %s blob", name, i, inspector);
-        if (hd->ws_bytes != ps_layout(ps_want(hd), hd->nsegs).total)
-            return rtn_fail(h, RTN_EINVAL, "%s: blob %d: workspace size does not match its header", name, i);
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "%s: page %d is NULL", name, i);
-        need += (size_t)hd->ws_bytes;
-    }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
+    const auto header_at = [=](const void* blobs, int64_t off) { return psd_blob(blobs, off, magic); };
+    const int rc = rtn_decode_check(h, name, magic == PL_MAGIC ? "rtn_png_layout_inspect" : "rtn_png_stream_inspect", n, host_blobs, dev_blobs,
+                                    offsets, pages, status, workspace, workspace_bytes, header_at, [](const PSHdr* hd) {
+                                        return hd->ws_bytes != ps_layout(ps_want(hd), hd->nsegs).total ? "workspace size does not match its header" : nullptr;
+                                    });
+    if (rc != RTN_CODEC_GO) return rc;
     const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        PSBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        unsigned maxsegs = 1, maxidat = 1, maxpass = 1;
-        long long maxchunks = 1, maxgroups = 1;
-        for (int j = 0; j < bt.n; ++j) {
-            const PSHdr* hd = psd_blob(host_blobs, offsets[i0 + j], magic);
-            PSPage& p = bt.p[j];
-            p.blob_off = offsets[i0 + j];
+    struct { unsigned segs = 1, idat = 1, pass = 1; long long chunks = 1, groups = 1; } most;      // of the table being filled
+    return rtn_codec_walk<PSBatch>(n,
+        [&](PSBatch& bt, int k, int i, long long ws) {
+            const PSHdr* hd = header_at(host_blobs, offsets[i]);
+            if (k == 0) most = {};
+            PSPage& p = bt.p[k];
+            p.blob_off = offsets[i];
             p.ws_off = ws;
-            p.out = pages[i0 + j];
+            p.out = pages[i];
             p.W = hd->W; p.H = hd->H; p.nc = hd->nc;
             p.nsegs = hd->nsegs; p.nidat = hd->nidat; p.S = hd->seg_bytes; p.in_bytes = hd->in_bytes; p.adler = hd->adler;
             p.off_table = hd->off_table; p.off_data = hd->off_data;
             p.stream = (uint32_t)ps_want(hd); p.fmt = ps_fmt(hd);
-            ws += hd->ws_bytes;
             const long long nchunks = ps_layout(ps_want(hd), hd->nsegs).nchunks, groups = ((long long)hd->W * hd->H + 3) / 4;
-            maxsegs = p.nsegs > maxsegs ? p.nsegs : maxsegs;
-            maxidat = p.nidat > maxidat ? p.nidat : maxidat;
-            maxchunks = nchunks > maxchunks ? nchunks : maxchunks;
-            maxgroups = groups > maxgroups ? groups : maxgroups;
-            if (pl_interlace(p.fmt)) maxpass = 7;
-        }
-        const dim3 per_seg(maxsegs, bt.n);
-        psd_find_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_find_kernel");
-        psd_count_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_count_kernel");
-        psd_crc_kernel<<<dim3(maxidat < (unsigned)PS_MAX_GRID ? maxidat : (unsigned)PS_MAX_GRID, bt.n), PS_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_crc_kernel");
-        psd_chain_kernel<<<bt.n, PS_WAVE, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_chain_kernel");
-        psd_decode_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_decode_kernel");
-        psd_window_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_window_kernel");
-        psd_resolve_kernel<<<dim3((unsigned)maxchunks, bt.n), PS_THREADS, 0, h->stream>>>(wsp, bt);
-        RTN_CHECK_LAUNCH(h, "psd_resolve_kernel");
-        psd_page_kernel<<<bt.n, PS_WAVE, 0, h->stream>>>(wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "psd_page_kernel");
-        if (magic == PS_MAGIC) {
-            psd_unfilter_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
-            RTN_CHECK_LAUNCH(h, "psd_unfilter_kernel");
-        } else {
-            pld_unfilter_kernel<<<dim3(maxpass, bt.n), PS_BAND, 0, h->stream>>>(wsp, bt);
-            RTN_CHECK_LAUNCH(h, "pld_unfilter_kernel");
-            const long long blocks = (maxgroups + PL_THREADS - 1) / PL_THREADS;
-            pld_expand_kernel<<<dim3((unsigned)(blocks < PL_MAX_GRID ? blocks : PL_MAX_GRID), bt.n), PL_THREADS, 0, h->stream>>>(db, wsp, bt);
-            RTN_CHECK_LAUNCH(h, "pld_expand_kernel");
-        }
-    }
-    return RTN_OK;
+            most.segs = p.nsegs > most.segs ? p.nsegs : most.segs;
+            most.idat = p.nidat > most.idat ? p.nidat : most.idat;
+            most.chunks = nchunks > most.chunks ? nchunks : most.chunks;
+            most.groups = groups > most.groups ? groups : most.groups;
+            if (pl_interlace(p.fmt)) most.pass = 7;
+            return (long long)hd->ws_bytes;
+        },
+        [&](const PSBatch& bt, int i0) {
+            const dim3 per_seg(most.segs, bt.n);
+            psd_find_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_find_kernel");
+            psd_count_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_count_kernel");
+            psd_crc_kernel<<<dim3(rtn_min_grid(most.idat, PS_MAX_GRID), bt.n), PS_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_crc_kernel");
+            psd_chain_kernel<<<bt.n, PS_WAVE, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_chain_kernel");
+            psd_decode_kernel<<<per_seg, PS_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_decode_kernel");
+            psd_window_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_window_kernel");
+            psd_resolve_kernel<<<dim3((unsigned)most.chunks, bt.n), PS_THREADS, 0, h->stream>>>(wsp, bt);
+            RTN_CHECK_LAUNCH(h, "psd_resolve_kernel");
+            psd_page_kernel<<<bt.n, PS_WAVE, 0, h->stream>>>(wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "psd_page_kernel");
+            if (magic == PS_MAGIC) {
+                psd_unfilter_kernel<<<bt.n, PS_BAND, 0, h->stream>>>(wsp, bt);
+                RTN_CHECK_LAUNCH(h, "psd_unfilter_kernel");
+            } else {
+                pld_unfilter_kernel<<<dim3(most.pass, bt.n), PS_BAND, 0, h->stream>>>(wsp, bt);
+                RTN_CHECK_LAUNCH(h, "pld_unfilter_kernel");
+                const long long blocks = (most.groups + PL_THREADS - 1) / PL_THREADS;
+                pld_expand_kernel<<<dim3(rtn_min_grid(blocks, PL_MAX_GRID), bt.n), PL_THREADS, 0, h->stream>>>(db, wsp, bt);
+                RTN_CHECK_LAUNCH(h, "pld_expand_kernel");
+            }
+            return RTN_OK;
+        });
 }
 
 }  // namespace

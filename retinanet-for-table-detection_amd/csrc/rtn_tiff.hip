@@ -14,8 +14,7 @@
 // No workgroup waits on another and there are no atomics.  Every loop of a decoder consumes input bits or produces output bytes and is
 // bounded by the strip's byte count and its rows; every position is checked against those before use (csrc/rtn_tiff_decode.h).  Any
 // non-zero status word sends the page to the host decoder.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_tiff_decode.h"
 
 namespace {
@@ -189,8 +188,8 @@ __global__ __launch_bounds__(TF_THREADS) void tfd_pixel_kernel(const uint8_t* bl
     }
 }
 
+// off >= 0: the callers (rtn_codec_blobs, and the walk behind it) have looked at the sign
 const TFHdr* tfd_blob(const void* host_blobs, int64_t off) {
-    if (off < 0) return nullptr;
     const TFHdr* hd = reinterpret_cast<const TFHdr*>(static_cast<const uint8_t*>(host_blobs) + off);
     if (hd->magic != TF_MAGIC || hd->blob_bytes < (int64_t)sizeof(TFHdr)) return nullptr;
     return tf_blob_ok(hd, (size_t)hd->blob_bytes) ? hd : nullptr;
@@ -206,20 +205,15 @@ extern "C" size_t rtn_tiff_blob_bound(size_t file_bytes) {
 
 extern "C" int rtn_tiff_inspect_flags(rtn_handle_t h, const void* file, size_t file_bytes, int flags, rtn_tiff_info_t* info, void* blob_out,
                                       size_t blob_capacity) {
-    if (!info) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect: info is NULL");
-    memset(info, 0, sizeof(*info));
-    if (!file) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect: file is NULL");
-    if (flags & ~RTN_TIFF_ALLOW_G4_ONE_STRIP) return rtn_fail_host(h, RTN_EINVAL, "rtn_tiff_inspect_flags: unknown flag bits %d", flags);
-    rtn_env_sync();
-    char why[200];
-    why[0] = 0;
-    const bool one_strip = (flags & RTN_TIFF_ALLOW_G4_ONE_STRIP) || rtn_env_int("RTN_TIFF_G4_ONE_STRIP", 0) != 0;
-    const int rc = tf_inspect(static_cast<const uint8_t*>(file), file_bytes, one_strip, info, blob_out, blob_capacity, why, sizeof(why));
-    if (rc != RTN_OK) {
-        memset(info, 0, sizeof(*info));
-        return rtn_fail_host(h, rc, "%s", why);
-    }
-    return RTN_OK;
+    return rtn_codec_inspect(h, "rtn_tiff_inspect", file, info, true, [&](char* why, size_t bytes) {
+        if (flags & ~RTN_TIFF_ALLOW_G4_ONE_STRIP) {
+            snprintf(why, bytes, "rtn_tiff_inspect_flags: unknown flag bits %d", flags);
+            return (int)RTN_EINVAL;
+        }
+        rtn_env_sync();
+        const bool one_strip = (flags & RTN_TIFF_ALLOW_G4_ONE_STRIP) || rtn_env_int("RTN_TIFF_G4_ONE_STRIP", 0) != 0;
+        return tf_inspect(static_cast<const uint8_t*>(file), file_bytes, one_strip, info, blob_out, blob_capacity, why, bytes);
+    });
 }
 
 extern "C" int rtn_tiff_inspect(rtn_handle_t h, const void* file, size_t file_bytes, rtn_tiff_info_t* info, void* blob_out, size_t blob_capacity) {
@@ -227,14 +221,7 @@ extern "C" int rtn_tiff_inspect(rtn_handle_t h, const void* file, size_t file_by
 }
 
 extern "C" size_t rtn_tiff_decode_workspace_bytes(int n, const void* host_blobs, const int64_t* offsets) {
-    if (n <= 0 || !host_blobs || !offsets) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        const TFHdr* hd = tfd_blob(host_blobs, offsets[i]);
-        if (!hd) return 0;
-        tot += (size_t)hd->ws_bytes;
-    }
-    return tot;
+    return rtn_codec_blob_bytes(n, host_blobs, offsets, tfd_blob);
 }
 
 extern "C" int rtn_tiff_decode_host(const void* blob, uint8_t* out_bgr, size_t out_bytes, int32_t* status) {
@@ -252,48 +239,33 @@ extern "C" int rtn_tiff_decode_host(const void* blob, uint8_t* out_bgr, size_t o
 
 extern "C" int rtn_tiff_decode(rtn_handle_t h, int n, const void* host_blobs, const void* dev_blobs, const int64_t* offsets, uint8_t* const* pages,
                                int32_t* status, void* workspace, size_t workspace_bytes) {
-    const char* name = "rtn_tiff_decode";
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "%s: n < 0", name);
-    if (n == 0) return RTN_OK;
-    if (!host_blobs || !dev_blobs || !offsets || !pages || !status || !workspace) return rtn_fail(h, RTN_EINVAL, "%s: NULL argument", name);
-    if (((uintptr_t)dev_blobs & 15) || ((uintptr_t)workspace & 255))
-        return rtn_fail(h, RTN_EINVAL, "%s: blobs must be 16-byte aligned, the workspace 256-byte aligned", name);
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        if (offsets[i] < 0 || (offsets[i] & 15)) return rtn_fail(h, RTN_EINVAL, "%s: blob %d offset not 16-byte aligned", name, i);
-        const TFHdr* hd = tfd_blob(host_blobs, offsets[i]);
-        if (!hd) return rtn_fail(h, RTN_EINVAL, "%s: blob %d is not an rtn_tiff_inspect blob", name, i);
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "%s: page %d is NULL", name, i);
-        need += (size_t)hd->ws_bytes;
-    }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
+    const int rc = rtn_decode_check(h, "rtn_tiff_decode", "rtn_tiff_inspect", n, host_blobs, dev_blobs, offsets, pages, status, workspace,
+                                    workspace_bytes, tfd_blob, rtn_codec_no_extra);
+    if (rc != RTN_CODEC_GO) return rc;
     const uint8_t* db = static_cast<const uint8_t*>(dev_blobs);
     uint8_t* wsp = static_cast<uint8_t*>(workspace);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        TFBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        unsigned maxstrips = 1, maxrows = 1;
-        for (int j = 0; j < bt.n; ++j) {
-            const TFHdr* hd = tfd_blob(host_blobs, offsets[i0 + j]);
-            TFPage& p = bt.p[j];
-            p.blob_off = offsets[i0 + j];
+    unsigned maxstrips = 1, maxrows = 1;
+    return rtn_codec_walk<TFBatch>(n,
+        [&](TFBatch& bt, int k, int i, long long ws) {
+            const TFHdr* hd = tfd_blob(host_blobs, offsets[i]);
+            if (k == 0) maxstrips = 1, maxrows = 1;
+            TFPage& p = bt.p[k];
+            p.blob_off = offsets[i];
             p.ws_off = ws;
-            p.out = pages[i0 + j];
+            p.out = pages[i];
             p.W = hd->W; p.H = hd->H;
             p.compression = hd->compression; p.layout = hd->layout; p.invert = hd->invert; p.predictor = hd->predictor;
             p.nstrips = hd->nstrips; p.rowbytes = hd->rowbytes;
             p.off_table = hd->off_table; p.off_pal = hd->off_pal; p.off_data = hd->off_data;
-            ws += hd->ws_bytes;
             maxstrips = p.nstrips > maxstrips ? p.nstrips : maxstrips;
             maxrows = (unsigned)p.H > maxrows ? (unsigned)p.H : maxrows;
-        }
-        tfd_strip_kernel<<<dim3(maxstrips < (unsigned)TF_MAX_GRID ? maxstrips : (unsigned)TF_MAX_GRID, bt.n), TF_WAVE, 0, h->stream>>>(db, wsp, bt);
-        RTN_CHECK_LAUNCH(h, "tfd_strip_kernel");
-        tfd_pixel_kernel<<<dim3(maxrows < (unsigned)TF_MAX_GRID ? maxrows : (unsigned)TF_MAX_GRID, bt.n), TF_THREADS, 0, h->stream>>>(db, wsp, status + i0, bt);
-        RTN_CHECK_LAUNCH(h, "tfd_pixel_kernel");
-    }
-    return RTN_OK;
+            return (long long)hd->ws_bytes;
+        },
+        [&](const TFBatch& bt, int i0) {
+            tfd_strip_kernel<<<dim3(rtn_min_grid(maxstrips, TF_MAX_GRID), bt.n), TF_WAVE, 0, h->stream>>>(db, wsp, bt);
+            RTN_CHECK_LAUNCH(h, "tfd_strip_kernel");
+            tfd_pixel_kernel<<<dim3(rtn_min_grid(maxrows, TF_MAX_GRID), bt.n), TF_THREADS, 0, h->stream>>>(db, wsp, status + i0, bt);
+            RTN_CHECK_LAUNCH(h, "tfd_pixel_kernel");
+            return RTN_OK;
+        });
 }

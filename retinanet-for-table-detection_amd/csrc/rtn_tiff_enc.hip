@@ -16,8 +16,7 @@
 //   6. tfe_finish_kernel   a workgroup per page: the 8-byte header and the IFD, then per strip its EOFB and its entries of the two arrays
 // RTN_TIFF_ENC_WAVE_ROW=1 runs kernels 2 and 5 with a wave per row (lane 0 codes, as the Group 4 decoder does) instead of a lane per
 // row: the variant tools/bench_encode_tiff.py measures against the default.  No workgroup waits on another.
-#include "rtn_internal.h"
-#include "rtn_codec.h"
+#include "rtn_codec_launch.h"
 #include "rtn_tiff_encode.h"
 
 namespace {
@@ -229,7 +228,7 @@ int te_launch(rtn_handle_t h, uint8_t* ws, long long* out_bytes, int32_t* status
     const int row_threads = WAVE_ROW ? TE_THREADS : 64;
     const long long pack = (maxitems + TE_THREADS / 64 - 1) / (TE_THREADS / 64);
     // the bitmap's layout goes with the row kernels' (te_bitmap_row)
-    tfe_pack_kernel<<<dim3((unsigned)(pack < TE_MAX_GRID ? pack : TE_MAX_GRID), bt.n), TE_THREADS, 0, h->stream>>>(ws, bt);
+    tfe_pack_kernel<<<dim3(rtn_min_grid(pack, TE_MAX_GRID), bt.n), TE_THREADS, 0, h->stream>>>(ws, bt);
     RTN_CHECK_LAUNCH(h, "tfe_pack_kernel");
     tfe_rows_kernel<false, WAVE_ROW><<<rows, row_threads, 0, h->stream>>>(ws, bt);
     RTN_CHECK_LAUNCH(h, "tfe_rows_kernel (lengths)");
@@ -255,12 +254,9 @@ extern "C" size_t rtn_tiff_encode_bound(int width, int height, int rows_per_stri
 extern "C" size_t rtn_tiff_encode_workspace_bytes(int n, const int32_t* widths, const int32_t* heights, const int32_t* components,
                                                   const int32_t* rows_per_strip) {
     if (n <= 0 || !widths || !heights || !components || !rows_per_strip) return 0;
-    size_t tot = 0;
-    for (int i = 0; i < n; ++i) {
-        if (te_check(nullptr, widths[i], heights[i], components[i], rows_per_strip[i], "rtn_tiff_encode_workspace_bytes")) return 0;
-        tot += (size_t)te_layout(widths[i], heights[i], te_strips(heights[i], rows_per_strip[i])).total;
-    }
-    return tot;
+    return rtn_codec_page_bytes(
+        n, [&](int i) { return te_check(nullptr, widths[i], heights[i], components[i], rows_per_strip[i], "rtn_tiff_encode_workspace_bytes"); },
+        [&](int i) { return te_layout(widths[i], heights[i], te_strips(heights[i], rows_per_strip[i])).total; });
 }
 
 extern "C" int rtn_tiff_encode_host(int width, int height, int components, const uint8_t* page, int threshold, int rows_per_strip,
@@ -277,40 +273,29 @@ extern "C" int rtn_tiff_encode(rtn_handle_t h, int n, const uint8_t* const* page
                                const int32_t* photometric, uint8_t* out, const int64_t* out_offsets, int64_t* out_bytes, int32_t* status,
                                void* workspace, size_t workspace_bytes) {
     const char* name = "rtn_tiff_encode";
-    if (!h) return RTN_EINVAL;
-    if (n < 0) return rtn_fail(h, RTN_EINVAL, "%s: n < 0", name);
-    if (n == 0) return RTN_OK;
-    if (!pages || !widths || !heights || !components || !thresholds || !rows_per_strip || !photometric || !out || !out_offsets || !out_bytes ||
-        !status || !workspace)
-        return rtn_fail(h, RTN_EINVAL, "%s: NULL argument", name);
-    if ((uintptr_t)workspace & 255) return rtn_fail(h, RTN_EINVAL, "%s: the workspace must be 256-byte aligned", name);
-    rtn_env_sync();
+    const int rc = rtn_encode_check(
+        h, name, n, {pages, widths, heights, components, thresholds, rows_per_strip, photometric, out, out_offsets, out_bytes, status, workspace}, pages,
+        workspace, workspace_bytes, [&](int i) { return te_check(h, widths[i], heights[i], components[i], rows_per_strip[i], name); },
+        [&](int i) {
+            if (thresholds[i] < 1 || thresholds[i] > 255) return rtn_fail(h, RTN_EINVAL, "%s: page %d: threshold %d (1 .. 255)", name, i, thresholds[i]);
+            if (photometric[i] != 0 && photometric[i] != 1) return rtn_fail(h, RTN_EINVAL, "%s: page %d: photometric %d (0 or 1)", name, i, photometric[i]);
+            const long long bound = (long long)te_bound(widths[i], heights[i], rows_per_strip[i]);
+            if (out_offsets[i] < 0 || out_offsets[i + 1] - out_offsets[i] < bound)
+                return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is [%lld, %lld), rtn_tiff_encode_bound asks for %lld bytes", name, i,
+                                (long long)out_offsets[i], (long long)out_offsets[i + 1], bound);
+            if (((uintptr_t)out + (uintptr_t)out_offsets[i]) & 3) return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is not 4-byte aligned", name, i);
+            return RTN_OK;
+        },
+        [&](int i) { return te_layout(widths[i], heights[i], te_strips(heights[i], rows_per_strip[i])).total; });
+    if (rc != RTN_CODEC_GO) return rc;
+    rtn_env_sync();                                                    // only a call that launches reads the knob
     const bool wave_row = rtn_env_int("RTN_TIFF_ENC_WAVE_ROW", 0) != 0;
-    size_t need = 0;
-    for (int i = 0; i < n; ++i) {
-        const int rc = te_check(h, widths[i], heights[i], components[i], rows_per_strip[i], name);
-        if (rc) return rc;
-        if (!pages[i]) return rtn_fail(h, RTN_EINVAL, "%s: page %d is NULL", name, i);
-        if (thresholds[i] < 1 || thresholds[i] > 255) return rtn_fail(h, RTN_EINVAL, "%s: page %d: threshold %d (1 .. 255)", name, i, thresholds[i]);
-        if (photometric[i] != 0 && photometric[i] != 1) return rtn_fail(h, RTN_EINVAL, "%s: page %d: photometric %d (0 or 1)", name, i, photometric[i]);
-        const long long bound = (long long)te_bound(widths[i], heights[i], rows_per_strip[i]);
-        if (out_offsets[i] < 0 || out_offsets[i + 1] - out_offsets[i] < bound)
-            return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is [%lld, %lld), rtn_tiff_encode_bound asks for %lld bytes", name, i,
-                            (long long)out_offsets[i], (long long)out_offsets[i + 1], bound);
-        if (((uintptr_t)out + (uintptr_t)out_offsets[i]) & 3) return rtn_fail(h, RTN_EINVAL, "%s: output slot %d is not 4-byte aligned", name, i);
-        need += (size_t)te_layout(widths[i], heights[i], te_strips(heights[i], rows_per_strip[i])).total;
-    }
-    if (workspace_bytes < need) return rtn_fail(h, RTN_ENOMEM, "%s: workspace %zu < %zu bytes", name, workspace_bytes, need);
-    long long ws = 0;
-    for (int i0 = 0; i0 < n; i0 += RTN_CODEC_BATCH) {
-        TEBatch bt;
-        memset(&bt, 0, sizeof(bt));
-        bt.n = n - i0 < RTN_CODEC_BATCH ? n - i0 : RTN_CODEC_BATCH;
-        bt.row_major = wave_row ? 1 : 0;
-        int maxrows = 1;
-        long long maxitems = 1, maxwords = 1;
-        for (int k = 0; k < bt.n; ++k) {
-            const int i = i0 + k;
+    uint8_t* wsp = static_cast<uint8_t*>(workspace);
+    int maxrows = 1;
+    long long maxitems = 1, maxwords = 1;
+    return rtn_codec_walk<TEBatch>(n,
+        [&](TEBatch& bt, int k, int i, long long ws) {
+            if (k == 0) bt.row_major = wave_row ? 1 : 0, maxrows = 1, maxitems = 1, maxwords = 1;
             TEPage& p = bt.p[k];
             p.src = pages[i];
             p.out = out + out_offsets[i];
@@ -319,16 +304,15 @@ extern "C" int rtn_tiff_encode(rtn_handle_t h, int n, const uint8_t* const* page
             p.W = widths[i]; p.H = heights[i]; p.nc = components[i]; p.t = thresholds[i]; p.rps = rows_per_strip[i];
             p.photometric = photometric[i];
             p.nstrips = te_strips(p.H, p.rps);
-            ws += te_layout(p.W, p.H, p.nstrips).total;
             maxrows = p.H > maxrows ? p.H : maxrows;
             const long long items = (long long)p.H * te_words(p.W);
             maxitems = items > maxitems ? items : maxitems;
             maxwords = p.bound / 4 > maxwords ? p.bound / 4 : maxwords;
-        }
-        uint8_t* wsp = static_cast<uint8_t*>(workspace);
-        const int rc = wave_row ? te_launch<true>(h, wsp, reinterpret_cast<long long*>(out_bytes + i0), status + i0, bt, maxrows, maxitems, maxwords)
-                                : te_launch<false>(h, wsp, reinterpret_cast<long long*>(out_bytes + i0), status + i0, bt, maxrows, maxitems, maxwords);
-        if (rc) return rc;
-    }
-    return RTN_OK;
+            return te_layout(p.W, p.H, p.nstrips).total;
+        },
+        [&](const TEBatch& bt, int i0) {
+            long long* lengths = reinterpret_cast<long long*>(out_bytes + i0);
+            return wave_row ? te_launch<true>(h, wsp, lengths, status + i0, bt, maxrows, maxitems, maxwords)
+                            : te_launch<false>(h, wsp, lengths, status + i0, bt, maxrows, maxitems, maxwords);
+        });
 }
