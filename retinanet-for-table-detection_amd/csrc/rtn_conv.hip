@@ -1264,15 +1264,9 @@ int rtn_env_int(const char* name, int dflt) {
 
 // ---- the conv launcher: check the descriptor -> try generations 4 / 6 / 5 -> check the groups -> choose -> fill KParams -> launch.
 // A workspace query (rtn_conv2d_workspace_bytes) runs the same steps up to `choose` and returns the bytes that choice needs.
-static constexpr long long kMaxConvWorkspace = 256ll << 20;
+// (kMaxConvWorkspace, what a query offers as capacity, and ConvCall are in rtn_conv_persistent.h)
 
 namespace {
-struct ConvCall {                  // one launch as the entry points see it
-    const rtn_conv_desc_t* d;
-    const rtn_conv_src2_t* s2;     // K-concatenated second source (rtn_conv1x1_dual_fwd) or null
-    const rtn_conv_fp8_t* q8;      // fp8 operands (rtn_conv2d_fp8_fwd) or null
-    float out8_scale;              // != 0: bf16 layer with e4m3 output (rtn_conv2d_fwd_fp8out)
-};
 struct ConvShape {                 // what the descriptor checks derive on the way
     int es, cshift;
     long long K1, Ktot;            // elements of the first source's K range, of the whole K range
@@ -1367,9 +1361,11 @@ int conv_check_desc(rtn_handle_t h, const ConvCall& c, ConvShape* sh) {
 }
 
 // Step 2: the persistent kernels, in this order, each where its precondition holds and its knob (or RTN_CONV_IMPL) lets it run.
-// They check their own bounds and answer 1 = "not mine" on anything odd, which the generic checks of step 3 then name.
-// RTN_OK: launched (or, for a workspace query, *query answered: their sizes come out of their own cost models); 1: none of them
-// takes the layer; < 0: error.
+// Per generation: *_takes (the descriptor: "not mine" on anything odd, which the generic checks of step 3 then name) -> *_choose (tile,
+// slices, grid, scratch bytes; "not mine" below its share of the chip) -> EITHER answer the query with the choice's workspace_bytes OR
+// fill + launch (rtn_conv_*_run).  takes and choose are rtn_conv_persistent.h: pure functions, the same for a query and a launch; this
+// function is the only place that tells the two apart.
+// RTN_OK: launched (or *query answered); 1: none of them takes the layer; < 0: error.
 //  4 (rtn_conv_halo8.hip): every stride-1 3x3 bf16 layer with 129..256 output channels and a bias/ReLU epilogue (the grouped head
 //    towers, P3-P5, res4 branch2b), and the fp8 layers.  Measured against generation 3 / 2 in one process (tools/ab_conv.py): head
 //    layer 0.225 -> 0.150 ms, P3 0.201 -> 0.150, res4 3x3 0.063 -> 0.049, P4 0.062 -> 0.047.  RTN_CONV_H8=0 turns it off (A/B);
@@ -1379,6 +1375,14 @@ int conv_check_desc(rtn_handle_t h, const ConvCall& c, ConvShape* sh) {
 //  5 (rtn_conv_gemm8.hip): the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or two sources.  RTN_CONV_G8=0;
 //    RTN_CONV_G8_MI pins the tile height (2 | 3 row fragments per wave); RTN_CONV_G8_SK: its stream-K form (-1 = cost model,
 //    0 = never, 1 = wherever the shape allows).
+// What a query does differently, all of it here:
+//  * its capacity is kMaxConvWorkspace and scratch counts as usable (conv_plan hands in a ConvScratch without pointers);
+//  * an fp8 layer never answers a query through generation 4, and generation 6 (no scratch) answers none: the rows' `!query`;
+//  * generation 4 answers after the quarter-chip test of h8_choose (a layer it declines is sized by generations 1-3);
+//  * generation 5 answers only when it would use stream-K; otherwise the query goes on to the other paths, whatever the 5/8-chip
+//    test of g8_choose would say (that test never applies to a stream-K choice, so asking before or after it is the same).
+// At launch, generation 4 having chosen K slices on a null or misaligned workspace says "not mine" (it does not choose again
+// unsliced), and generation 5 without a usable sync block and slab area considers only its plain form: `have_scratch`.
 int conv_try_persistent(rtn_handle_t h, const ConvCall& c, int forced, const ConvScratch& ws, size_t* query) {
     const rtn_conv_desc_t* d = c.d;
     const bool plain = c.out8_scale == 0.f;
@@ -1388,17 +1392,44 @@ int conv_try_persistent(rtn_handle_t h, const ConvCall& c, int forced, const Con
         {6, !query && !c.s2 && plain && bf16 && d->N <= 48 && (d->flags & RTN_CONV_OUT_F32), rtn_env_int("RTN_CONV_HN", 1) != 0},
         {5, plain && bf16 && d->KH == 1 && d->KW == 1, rtn_env_int("RTN_CONV_G8", 1) != 0},
     };
-    const int grid_limit = rtn_env_int("RTN_CONV_H8_GRID", 0);
-    const bool stagger = rtn_env_int("RTN_CONV_H8_STAGGER", 1) != 0;
+    ConvKnobs k;
+    k.forced = forced;
+    k.grid_limit = rtn_env_int("RTN_CONV_H8_GRID", 0);
+    k.stagger = rtn_env_int("RTN_CONV_H8_STAGGER", 1) != 0;
+    k.h8_mi = rtn_env_int("RTN_CONV_H8_MI", 0);
+    k.h8_ksplit = rtn_env_int("RTN_CONV_H8_KSPLIT", 0);
+    k.h8_half = rtn_env_int("RTN_CONV_H8_HALF", 1) != 0;
+    k.g8_mi = rtn_env_int("RTN_CONV_G8_MI", 0);
+    k.g8_sk = rtn_env_int("RTN_CONV_G8_SK", -1);
+    k.g8_n128 = rtn_env_int("RTN_CONV_G8_N128", 1) != 0;
+    k.g8_narrow = rtn_env_int("RTN_CONV_G8_NARROW", 1) != 0;
+    const int cus = h->num_cus > 0 ? h->num_cus : 256;
+    const bool slabs = query || (ws.ptr && !conv_misaligned16(ws.ptr));
+    const bool slabs_sync = query || (slabs && ws.sync && !conv_misaligned16(ws.sync));
     for (const auto& g : gens) {
         if (!g.applies || !(forced == g.impl || (forced == 0 && g.on))) continue;
-        const int rc = g.impl == 4 ? rtn_conv_halo8_try(h, d, grid_limit, stagger, forced == 4, rtn_env_int("RTN_CONV_H8_MI", 0), ws.ptr, ws.cap, query,
-                                                        rtn_env_int("RTN_CONV_H8_KSPLIT", 0), c.q8)
-                     : g.impl == 6 ? rtn_conv_halon_try(h, d, grid_limit, forced == 6)
-                                   : rtn_conv_gemm8_try(h, d, c.s2, grid_limit, stagger, forced == 5, rtn_env_int("RTN_CONV_G8_MI", 0), ws.sync, ws.ptr,
-                                                        ws.cap, query, rtn_env_int("RTN_CONV_G8_SK", -1));
-        if (rc == RTN_OK && !query) h->last_conv_impl = g.impl;
-        if (rc <= 0) return rc;                        // launched (or failed): done; 1 = not eligible, the next one
+        int rc;
+        if (g.impl == 4) {
+            H8Choice ch;
+            if (!h8_takes(c, k) || !h8_choose(c, cus, ws.cap, slabs, k, &ch)) continue;
+            if (query) { *query = ch.workspace_bytes; return RTN_OK; }
+            rc = rtn_conv_halo8_run(h, c, ch, ws.ptr);
+        } else if (g.impl == 6) {
+            HNChoice ch;
+            if (!hn_takes(c, k) || !hn_choose(c, cus, ws.cap, false, k, &ch)) continue;
+            rc = rtn_conv_halon_run(h, c, ch);
+        } else {
+            G8Choice ch;
+            if (!g8_takes(c, k) || !g8_choose(c, cus, ws.cap, slabs_sync, k, &ch)) continue;
+            if (query) {
+                if (!ch.sk_grid) continue;             // nothing to reserve: the other paths answer the query
+                *query = ch.workspace_bytes;
+                return RTN_OK;
+            }
+            rc = rtn_conv_gemm8_run(h, c, ch, ws.sync, ws.ptr);
+        }
+        if (rc == RTN_OK) h->last_conv_impl = g.impl;
+        if (rc <= 0) return rc;                        // launched (or failed): done
     }
     return 1;
 }

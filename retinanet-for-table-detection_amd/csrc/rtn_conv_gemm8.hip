@@ -36,6 +36,10 @@
 // are the FIRST thing their workgroups do: no wait can depend on a wait.  The poll is bounded (2 s of the 100 MHz clock); a timeout
 // counts up the error word of the sync block and goes on (wrong values, never a hang).  Flags are reset by the owner after the poll:
 // the sync block (first 4 KiB of the workspace) is zero before and after every launch.
+//
+// Host side: which layers this kernel takes and on which tile height, plain or stream-K grid (g8_takes / g8_choose, with the cost model
+// of the stream-K form) is decided in rtn_conv_persistent.h, without HIP; here are g8_fill (G8Params from the call and that choice),
+// g8_launch (choice -> kernel instance) and the entry rtn_conv_gemm8_run the conv launcher calls.
 #include "rtn_internal.h"
 #include "rtn_device.h"
 #include "rtn_conv_epilogue.h"
@@ -57,8 +61,6 @@ __device__ unsigned long long g_g8_stamps[1024][8];
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr unsigned G8_OOB = 0xFFFF0000u;              // beyond every descriptor even with the largest uniform offset (K bytes) added
-constexpr int G8_THREADS = 512;
 constexpr int G8_LDS = 160 * 1024;
 constexpr unsigned G8_STAGE = 32768, G8_B_BASE = 3 * 32768, G8_BIAS_OFF = 24576;
 constexpr unsigned G8_SYNC_OFF = G8_STAGE + 24576;    // SK: two words in the unused tail of A stage 1 (tiles have at most 192 rows = 24 KiB per stage)
@@ -100,7 +102,6 @@ struct G8Params {
     unsigned sk_slab_bytes;
     unsigned* sk_flags;
 };
-constexpr int SK_ERR_WORD = 1023;
 
 // EPI: bit 0 = residual add (the `Add` closing a bottleneck block; accumulated gradient contributions in training), bit 1 = ReLU mask
 // of the tensor being differentiated (rtn_conv2d_dgrad): 16 bytes per lane and row, loaded one row fragment ahead of their use.
@@ -516,161 +517,35 @@ int g8_pick(rtn_handle_t h, int grid, const G8Params& p, bool dual, bool stagger
     if (!stagger && epi == 0) return g8_go<MI, false, false, 0>(h, grid, p);      // lockstep variant: A/B only
     return rtn_with_epi<3>(epi, [&](auto e) { return g8_go<MI, true, false, decltype(e)::value>(h, grid, p); });
 }
-}  // namespace
+G8Src g8_src(const void* ptr, long long elems, long long img_stride, long long row_stride, int pix_stride, int step) {
+    return G8Src{(const char*)ptr, (unsigned)(elems * 2), img_stride * 2, (int)(row_stride * 2), pix_stride * 2, step};
+}
 
-// Launcher: RTN_OK after a launch, 1 when the layer is not one this kernel takes, < 0 on error.
-// `sync` / `ws` / `ws_cap`: the caller-owned workspace of the stream-K form - its 4-KiB sync block (zero before and after every launch)
-// and the slab area behind it; `query` != nullptr: no launch, *query = slab bytes this layer would use (0: no stream-K for it).
-// `sk_mode`: -1 = cost model, 0 = never, 1 = wherever the shape allows (tests, A/B).
-int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2, int grid_limit, bool stagger, bool forced,
-                       int mi_force, unsigned* sync, void* ws, long long ws_cap, size_t* query, int sk_mode) {
-    if (query) *query = 0;
-    if (d->dtype != RTN_BF16 || d->ngroups != 1) return 1;
-    if (d->KH != 1 || d->KW != 1 || d->pad_t != 0 || d->pad_l != 0 || d->sy != d->sx || d->sy < 1 || d->sy > 2) return 1;
-    if (d->flags & ~(RTN_CONV_RELU | RTN_CONV_RES_SAME | RTN_CONV_RES_UPSAMPLE | RTN_CONV_RELU_MASK | RTN_CONV_MASK_PRE)) return 1;
-    if ((d->flags & RTN_CONV_MASK_PRE) && !(d->flags & RTN_CONV_RELU_MASK)) return 1;
-    if ((d->flags & RTN_CONV_RES_SAME) && (d->flags & RTN_CONV_RES_UPSAMPLE)) return 1;
-    const bool res_up = d->flags & RTN_CONV_RES_UPSAMPLE;
-    const int epi = ((d->flags & (RTN_CONV_RES_SAME | RTN_CONV_RES_UPSAMPLE)) ? 1 : 0) | ((d->flags & RTN_CONV_RELU_MASK) ? 2 : 0);
-    if (epi && s2) return 1;
-    // N = 128: half of the 256-column tile multiplies zeros (weight rows past w_rows come from the descriptor's range check).  The
-    // layers this is for are bound by their pixel traffic: res3 branch2a in the step's sequence 0.063 -> 0.055 ms (RTN_CONV_G8_N128=0: off)
-    const bool n128 = d->N == 128 && (forced || rtn_env_int("RTN_CONV_G8_N128", 1) != 0);
-    if (!n128 && (d->N < 256 || d->N % 256)) return 1;
-    if (d->N > 2048 || d->w_rows != d->N || d->out_ld % 8) return 1;
-    if ((d->Crun * 2) % 128 || d->Crun <= 0 || d->pix_stride < d->Crun || (d->pix_stride * 2) % 16) return 1;
-    if (((uintptr_t)d->w & 15) || ((uintptr_t)d->bias & 15)) return 1;
-    const rtn_conv_group_t& g = d->g[0];
-    if (!g.in || !g.out || ((uintptr_t)g.in & 15) || ((uintptr_t)g.out & 15)) return 1;
-    const long long cells = (long long)g.Hout * g.Wout, M = cells * d->batch;
-    if (M < 1 || M >= (1ll << 24)) return 1;
-    const bool scatter = g.out_step > 1;                  // dgrad of a stride-2 1x1 'valid' conv: rows land on the stride grid
-    if (scatter && (res_up || g.out_pix_w < (g.Wout - 1) * g.out_step + 1 || g.out_img_stride % d->out_ld || g.out_img_stride <= 0)) return 1;
-    const long long img_pix = scatter ? g.out_img_stride / d->out_ld : cells;            // pixels per image of out / res / mask
-    const long long last_pix = scatter ? (long long)(g.Hout - 1) * g.out_step * g.out_pix_w + (long long)(g.Wout - 1) * g.out_step : cells - 1;
-    if (scatter && last_pix >= img_pix) return 1;
-    // measured (tools/profile_train.py, batch 8): the scatter pays on the long-K gradients (res3a / res5a branch1: 0.096 -> 0.077,
-    // 0.071 -> 0.063 ms) and loses on the short-K ones (res3a / res4a branch2a, K = 128 / 256: 0.061 -> 0.076, 0.037 -> 0.049 against
-    // generation 2's 64-wide tiles): taken from K = 512 on
-    if (scatter && !forced && d->Crun < 512) return 1;
-    if (g.out_off != 0 || (!scatter && g.out_img_stride != cells * d->out_ld)) return 1;
-    if ((long long)(g.Hout - 1) * d->sy >= g.Hin || (long long)(g.Wout - 1) * d->sx >= g.Win) return 1;
-    if (g.in_elems * 2 >= (long long)G8_OOB || g.out_elems * 2 >= (long long)G8_OOB) return 1;
-    const long long max_pix = (long long)(d->batch - 1) * img_pix + last_pix;             // the farthest pixel a row maps to
-    if (g.out_elems < max_pix * d->out_ld + d->N) return 1;
-    if ((epi & 1) && !res_up) {
-        if (!g.res || ((uintptr_t)g.res & 15) || g.res_ld % 8 || g.res_img_stride != img_pix * g.res_ld) return 1;
-        if (g.res_elems < max_pix * g.res_ld + d->N || g.res_elems * 2 >= (long long)G8_OOB) return 1;
-    }
-    if (res_up) {
-        if (!g.res || ((uintptr_t)g.res & 15) || g.res_ld % 8 || g.res_img_stride % 8 || g.Hres < 1 || g.Wres < 1) return 1;
-        if (g.res_img_stride < 0 || (long long)(d->batch - 1) * g.res_img_stride + ((long long)g.Hres * g.Wres - 1) * g.res_ld + d->N > g.res_elems) return 1;
-        if (g.res_elems * 2 >= (long long)G8_OOB) return 1;
-    }
-    if (epi & 2) {
-        if (!g.mask || ((uintptr_t)g.mask & 15) || g.mask_ld % 8 || g.mask_img_stride != img_pix * g.mask_ld) return 1;
-        if (g.mask_elems < max_pix * g.mask_ld + d->N || g.mask_elems * 2 >= (long long)G8_OOB) return 1;
-    }
-    const long long in_max = (long long)(d->batch - 1) * g.in_img_stride + (long long)(g.Hout - 1) * d->sy * g.in_row_stride +
-                             (long long)(g.Wout - 1) * d->sx * d->pix_stride + d->Crun;
-    if (in_max > g.in_elems) return 1;
-    long long Kel = d->Crun;
-    G8Params p;
+// the kernel's parameters of a layer g8_takes accepted, on the tile and grid g8_choose picked; `sync` / `scratch`: the stream-K form's
+// sync block (zero before and after every launch) and the slab area behind it
+void g8_fill(G8Params* pp, const ConvCall& c, const G8Choice& ch, unsigned* sync, void* scratch) {
+    G8Params& p = *pp;
     memset(&p, 0, sizeof(p));
-    p.s1.ptr = (const char*)g.in;
-    p.s1.bytes = (unsigned)(g.in_elems * 2);
-    p.s1.img_stride_b = g.in_img_stride * 2;
-    p.s1.row_stride_b = (int)((long long)g.in_row_stride * 2);
-    p.s1.pix_b = d->pix_stride * 2;
-    p.s1.step = d->sy;
+    const rtn_conv_desc_t* d = c.d;
+    const rtn_conv_src2_t* s2 = c.s2;
+    const rtn_conv_group_t& g = d->g[0];
+    const int epi = ch.epi;
+    const long long cells = (long long)g.Hout * g.Wout;
+    long long Kel = d->Crun;
+    p.s1 = g8_src(g.in, g.in_elems, g.in_img_stride, g.in_row_stride, d->pix_stride, d->sy);
     p.nk1 = d->Crun * 2 / 128;
     if (s2) {
-        if (!s2->in || ((uintptr_t)s2->in & 15) || s2->C < 1 || (s2->C * 2) % 128 || s2->step < 1) return 1;
-        if ((long long)(g.Hout - 1) * s2->step >= s2->Hin || (long long)(g.Wout - 1) * s2->step >= s2->Win) return 1;
-        const long long in2_max = (long long)(d->batch - 1) * s2->in_img_stride + (long long)(g.Hout - 1) * s2->step * s2->in_row_stride +
-                                  (long long)(g.Wout - 1) * s2->step * s2->pix_stride + s2->C;
-        if (in2_max > s2->in_elems || s2->in_elems * 2 >= (long long)G8_OOB) return 1;
-        p.s2.ptr = (const char*)s2->in;
-        p.s2.bytes = (unsigned)(s2->in_elems * 2);
-        p.s2.img_stride_b = s2->in_img_stride * 2;
-        p.s2.row_stride_b = (int)((long long)s2->in_row_stride * 2);
-        p.s2.pix_b = s2->pix_stride * 2;
-        p.s2.step = s2->step;
+        p.s2 = g8_src(s2->in, s2->in_elems, s2->in_img_stride, s2->in_row_stride, s2->pix_stride, s2->step);
         Kel += s2->C;
     }
     const long long Kbytes = Kel * 2;
-    if (Kbytes > 16384 || Kbytes * d->N >= (long long)G8_OOB) return 1;
-    const int cus = h->num_cus > 0 ? h->num_cus : 256;
-    const int ntn = n128 ? 1 : (d->N + 255) / 256;         // N = 128: the 128-column instance, one column tile
-    const long long nk_all = Kbytes / 128;
-    int mi = mi_force;
-    double plain_cost = 0;                             // in units of one 64-row fragment row x one K step
-    {                                                  // tile height by rounds x K steps x (rows + a fixed per-step cost)
-        double best = 0;
-        int pick = 0;
-        for (int cand = 3; cand >= 2; --cand) {
-            if (mi_force >= 2 && mi_force <= 3 && cand != mi_force) continue;
-            const long long tl = ((M + 64 * cand - 1) / (64 * cand)) * ntn;
-            const double cost = (double)((tl + cus - 1) / cus) * (cand + 0.4);
-            if (pick == 0 || cost < best * 0.97) { best = cost; pick = cand; }
-        }
-        mi = pick;
-        plain_cost = best * (double)nk_all;
-    }
-    // Stream-K: every workgroup an equal share of the tiles x K steps (see the header).  Taken when it saves at least TEN K steps per
-    // workgroup against whole rounds of whole tiles - measured at batch 8, 800 x 1333 (profiles/r4_streamk_gemm8.txt): the hand-off costs
-    // 8-10 us whatever the layer (every workgroup publishes one partial tile and owns one: 50 MB out and back at the end of the launch,
-    // all owners at once), and a K step does not stay 1.25 us when more CUs run it - between 175 and 256 busy CUs it grows to 1.6-1.9 us
-    // (shader clock 2.08 -> 2.01 GHz only; the staging rate of the chip, 8-9 TB/s L2 -> LDS, is the same in both cases).  So the layers
-    // with 175 of 256 tiles (stage 4, C4_reduced: 5 steps saved) LOSE 4-7 us, and the ones on 44-88 CUs (stage 5 branch2a 21 steps,
-    // C5_reduced 26, res5a branch2c + shortcut 15) gain 6-15 us.  Grid: the CUs, at most 8 pieces per tile.
-    int sk_grid = 0;
-    const bool sk_shape = !n128 && !(epi & 2) && !scatter && stagger && nk_all >= 2 && nk_all <= 256;
-    if (sk_shape && sk_mode != 0 && (query || (sync && ws && !((uintptr_t)ws & 15) && !((uintptr_t)sync & 15)))) {
-        double best = 0;
-        int pick = 0, pick_grid = 0;
-        for (int cand = 3; cand >= 2; --cand) {
-            if (mi_force >= 2 && mi_force <= 3 && cand != mi_force) continue;
-            const long long tl = ((M + 64 * cand - 1) / (64 * cand)) * ntn, total = tl * nk_all;
-            long long G = cus;
-            if (grid_limit > 0 && grid_limit < G) G = grid_limit;
-            if (G > tl * 8) G = tl * 8;
-            if (G > total) G = total;
-            if (G > SK_ERR_WORD) G = SK_ERR_WORD;
-            if (G < 1 || total >= (1ll << 30)) continue;
-            const long long slab_need = G * (long long)(cand * 4 * 2) * G8_THREADS * 16;
-            if (!query && slab_need > ws_cap) continue;
-            if (slab_need >= (long long)G8_OOB) continue;
-            const long long share_i = (total + G - 1) / G;
-            const double share = (double)share_i;
-            const bool whole = total % G == 0 && share_i % nk_all == 0;               // every range = whole tiles: nothing is handed over
-            const double partners = (double)((nk_all + share_i - 1) / share_i);      // pieces the longest-cut tile has besides its head
-            const double fix = whole ? 0.0 : 10.0 + 2.0 * (partners > 2.0 ? partners - 2.0 : 0.0);
-            const double cost = (share + fix) * (cand + 0.4);
-            if (pick == 0 || cost < best * 0.97) { best = cost; pick = cand; pick_grid = (int)G; }
-        }
-        if (pick && (sk_mode > 0 || best <= plain_cost)) { mi = pick; sk_grid = pick_grid; }
-    }
-    const long long ntm = (M + 64 * mi - 1) / (64 * mi), tiles = ntm * ntn;
-    if (tiles > 0x3fffffff) return 1;
-    if (query) {
-        if (!sk_grid) return 1;                        // nothing to reserve: the caller's other paths answer the query
-        *query = (size_t)sk_grid * (size_t)(mi * 4 * 2) * G8_THREADS * 16;
-        return RTN_OK;
-    }
-    // too few tiles to be worth one workgroup per CU: below ~5/8 of the chip the 64-wide tiles of generation 2 (four times the
-    // workgroups) win (res5 branch2a, 132 tiles: 0.049 ms here against 0.043; C5_reduced, 66 tiles: 0.046 against 0.041), above
-    // it this kernel does (res4 branch2a, 175 tiles: 0.037 against 0.046).  (Round 3 re-measured: back-to-back launches of ONE layer
-    // say the opposite for res5 branch2a - 0.034 against 0.039 - because its 2 MB of filters then sit in the L2; in the step's own
-    // sequence, tools/profile_layers.py, it is 0.049 against 0.046-0.047 as before.  Judge such layers in sequence.)
-    if (!forced && !sk_grid && tiles * 8 < cus * 5) return 1;
     p.w = (const char*)d->w;
     p.bias = d->bias;
     p.out = (char*)g.out;
     p.w_bytes = (unsigned)(Kbytes * d->N);
     p.out_bytes = (unsigned)(g.out_elems * 2);
-    p.M = (int)M; p.N = d->N; p.Kbytes = (int)Kbytes; p.nk = (int)(Kbytes / 128);
-    p.ntiles_m = (int)ntm; p.ntiles_n = ntn; p.ntiles = (int)tiles;
+    p.M = (int)(cells * d->batch); p.N = d->N; p.Kbytes = (int)Kbytes; p.nk = (int)(Kbytes / 128);
+    p.ntiles_m = (int)ch.ntm; p.ntiles_n = ch.ntn; p.ntiles = (int)ch.tiles;
     p.Hout = g.Hout; p.Wout = g.Wout;
     p.inv_cells = 1.0f / (float)cells;
     p.inv_w = 1.0f / (float)g.Wout;
@@ -679,34 +554,41 @@ int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_
     if (epi & 1) { p.res = (const char*)g.res; p.res_bytes = (unsigned)(g.res_elems * 2); p.res_ld = g.res_ld; }
     if (epi & 2) { p.mask = (const char*)g.mask; p.mask_bytes = (unsigned)(g.mask_elems * 2); p.mask_ld = g.mask_ld; }
     p.mask_pre = (d->flags & RTN_CONV_MASK_PRE) ? 1 : 0;
-    p.out_step = scatter ? g.out_step : 1; p.out_pix_w = g.out_pix_w; p.out_img_pix = (unsigned)img_pix;
-    if (res_up) {
+    p.out_step = ch.scatter ? g.out_step : 1; p.out_pix_w = g.out_pix_w;
+    p.out_img_pix = (unsigned)(ch.scatter ? g.out_img_stride / d->out_ld : cells);       // pixels per image of out / res / mask
+    if (d->flags & RTN_CONV_RES_UPSAMPLE) {
         p.res_up = 1; p.Hres = g.Hres; p.Wres = g.Wres;
         p.res_img_stride = (unsigned)g.res_img_stride;
         p.rs_h = (float)g.Hres / (float)g.Hout;
         p.rs_w = (float)g.Wres / (float)g.Wout;
     }
-    int grid = cus;
-    if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
-    if (grid > p.ntiles) grid = p.ntiles;
-    if (sk_grid) {
-        grid = sk_grid;
-        p.sk_total = (int)(tiles * nk_all);
-        p.sk_slab = (char*)ws;
-        p.sk_slab_bytes = (unsigned)((size_t)sk_grid * (size_t)(mi * 4 * 2) * G8_THREADS * 16);
+    if (ch.sk_grid) {
+        p.sk_total = (int)(ch.tiles * (Kbytes / 128));
+        p.sk_slab = (char*)scratch;
+        p.sk_slab_bytes = (unsigned)ch.workspace_bytes;
         p.sk_flags = sync;
     }
-    const bool narrow = n128 && !s2 && stagger && rtn_env_int("RTN_CONV_G8_NARROW", 1) != 0;      // 0: N = 128 on the 256-column tile (A/B)
-    const bool dual = s2 != nullptr;
+}
+
+int g8_launch(rtn_handle_t h, const G8Params& p, const G8Choice& ch) {
+    const bool dual = p.s2.ptr != nullptr;
+    const int mi = ch.mi, grid = ch.grid, epi = ch.epi;
     int lrc;
-    if (sk_grid)     lrc = mi == 3 ? g8_pick_sk<3>(h, grid, p, dual, epi) : g8_pick_sk<2>(h, grid, p, dual, epi);
-    else if (narrow) lrc = mi == 3 ? g8_pick_narrow<3>(h, grid, p, epi) : g8_pick_narrow<2>(h, grid, p, epi);
-    else             lrc = mi == 3 ? g8_pick<3>(h, grid, p, dual, stagger, epi) : g8_pick<2>(h, grid, p, dual, stagger, epi);
+    if (ch.sk_grid)     lrc = mi == 3 ? g8_pick_sk<3>(h, grid, p, dual, epi) : g8_pick_sk<2>(h, grid, p, dual, epi);
+    else if (ch.narrow) lrc = mi == 3 ? g8_pick_narrow<3>(h, grid, p, epi) : g8_pick_narrow<2>(h, grid, p, epi);
+    else                lrc = mi == 3 ? g8_pick<3>(h, grid, p, dual, ch.stagger, epi) : g8_pick<2>(h, grid, p, dual, ch.stagger, epi);
     if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_gemm8_kernel");
-    h->last_conv_streamk = sk_grid;
-    h->last_conv_tile = ((64 * mi) << 16) | (narrow ? 128 : 256);
+    h->last_conv_streamk = ch.sk_grid;
+    h->last_conv_tile = ((64 * mi) << 16) | (ch.narrow ? 128 : 256);
     return RTN_OK;
+}
+}  // namespace
+
+int rtn_conv_gemm8_run(rtn_handle_t h, const ConvCall& c, const G8Choice& ch, unsigned* sync, void* scratch) {
+    G8Params p;
+    g8_fill(&p, c, ch, sync, scratch);
+    return g8_launch(h, p, ch);
 }
 
 #ifdef RTN_G8_STAMP

@@ -23,6 +23,10 @@
 //     ZERO row (TM = 256 - KW output rows per tile) and a lane whose tap leaves the image reads that row.
 //
 // LDS (160 KiB, all of it): B ring 3 x 32 KiB at 0, halos 2 x 32 KiB at 96 KiB.  One workgroup (512 threads) per CU.
+//
+// Host side: which layers this kernel takes and on which tile height, K slices and grid (h8_takes / h8_choose) is decided in
+// rtn_conv_persistent.h, without HIP; here are h8_fill (H8Params from the call and that choice), h8_launch (choice -> kernel instance,
+// then the K-slice finish) and the entry rtn_conv_halo8_run the conv launcher calls.
 #include "rtn_internal.h"
 #include "rtn_device.h"
 #include "rtn_conv_epilogue.h"
@@ -51,7 +55,7 @@ __device__ unsigned long long g_h8_stamps[2][64];
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr unsigned OOB = 0xFFFFFF00u;                 // beyond every descriptor: loads return zeros, stores are dropped
+constexpr unsigned OOB = H8_OOB;                      // beyond every descriptor: loads return zeros, stores are dropped
 constexpr int H8_THREADS = 512;
 constexpr int H8_LDS = 160 * 1024;
 constexpr unsigned B_STAGE = 32768, A_BASE = 3 * 32768, A_TOGGLE = 0x18000u ^ 0x20000u;
@@ -611,90 +615,18 @@ int h8_pick(rtn_handle_t h, int grid, const H8Params& p, bool fp8, bool half, bo
     if (!stagger && epi == 0) return h8_go<MI, false, 0, false>(h, grid, p);      // lockstep variant: A/B only
     return rtn_with_epi<3>(epi, [&](auto e) { return h8_go<MI, true, decltype(e)::value, false>(h, grid, p); });
 }
-}  // namespace
-
-// Launcher.  Returns RTN_OK after a launch, 1 when the layer is not one this kernel takes (the caller falls through to the other
-// kernels), < 0 on a launch error.  `forced`: take every eligible layer (tests), otherwise the caller decides.  `ws` / `ws_cap`: the
-// caller-owned workspace (K-slice slabs); `query` != nullptr: no launch, *query = workspace bytes this layer would use.
-// `ksplit_force`: 0 = cost model, 1 = never slice, n > 1 = n slices when n divides the group count.
-int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool stagger, bool forced, int mi_force, float* ws,
-                       long long ws_cap, size_t* query, int ksplit_force, const rtn_conv_fp8_t* q8) {
-    if (query) *query = 0;
-    if (q8 ? d->dtype != RTN_FP8 : d->dtype != RTN_BF16) return 1;
-    const int es = q8 ? 1 : 2;                         // bytes per input / weight element
-    if (q8 && (query || (d->flags & ~RTN_CONV_RELU) || d->N <= 128 || d->N > 256)) return 1;     // fp8: one full-width column block, bias / ReLU
-    if (d->KW != 3 || d->KH < 1 || d->KH > 7 || d->sy != 1 || d->sx != 1) return 1;
-    if (d->flags & ~(RTN_CONV_RELU | RTN_CONV_RES_SAME | RTN_CONV_RELU_MASK | RTN_CONV_MASK_PRE)) return 1;
-    if ((d->flags & RTN_CONV_MASK_PRE) && !(d->flags & RTN_CONV_RELU_MASK)) return 1;
-    const int epi = ((d->flags & RTN_CONV_RES_SAME) ? 1 : 0) | ((d->flags & RTN_CONV_RELU_MASK) ? 2 : 0);
-    const int ncb = (d->N + 255) / 256;                // column blocks of 256 channels
-    if (d->N <= 64 || ncb > 8 || d->w_rows < d->N || d->N % 8 || d->out_ld % 8) return 1;    // weight rows past w_rows read as zeros (descriptor range)
-    if (ncb > 1 && epi) return 1;
-    const bool half = d->N <= 128;                     // the 128-column instance (NW = 4): plain epilogue, no slices
-    if (half && !forced && rtn_env_int("RTN_CONV_H8_HALF", 1) == 0) return 1;
-    if (d->Crun != d->pix_stride || (d->Crun * es) % 128 || d->Crun <= 0) return 1;
-    if (d->pad_l < 0 || d->pad_l >= d->KW || d->pad_t < 0 || d->pad_t >= d->KH) return 1;
-    if (((uintptr_t)d->w & 15) || ((uintptr_t)d->bias & 15)) return 1;
-    const int nchunk = d->Crun * es / 128;
-    const int G = d->KH * nchunk;
-    const long long Kbytes = (long long)d->KH * d->KW * d->Crun * es;
-    if (Kbytes * 256 * ncb >= 0xFFFFFF00ll) return 1;                  // the staging offsets of the last column block
-    H8Params p;
+// the kernel's parameters of a layer h8_takes accepted, on the tile, slices and grid h8_choose picked
+void h8_fill(H8Params* pp, const ConvCall& c, const H8Choice& ch, float* scratch) {
+    H8Params& p = *pp;
     memset(&p, 0, sizeof(p));
-    const int cus = h->num_cus > 0 ? h->num_cus : 256;
-    long long Mtot = 0;
-    for (int i = 0; i < d->ngroups; ++i) Mtot += (long long)d->g[i].Hout * d->g[i].Wout * d->batch;
-    // Tile height (rows = 64 mi) and K slices by a cost model in microseconds: rounds of workgroups x K steps of an item (+ 5 for its
-    // prologue / epilogue) x 1.53 us per 256-row step, + for S > 1 the finish launch and the slabs' round trip at 4 TB/s.
-    // RTN_CONV_H8_MI / RTN_CONV_H8_KSPLIT pin them (A/B, tests).
-    const bool can_split = !half && !q8 && d->ngroups == 1 && epi == 0 && ksplit_force != 1 && (ws_cap > 0 || query);
-    const long long slab_ld = 256ll * ncb;
-    int mi = 0, S = 1;
-    {
-        double best = 0;
-        for (int cand = 4; cand >= 3; --cand) {
-            if (!q8 && mi_force >= 3 && mi_force <= 4 && cand != mi_force) continue;
-            if (q8 && cand == 4) continue;                 // fp8 holds both k halves' A fragments: the 256-row instance spills, 192 rows fit (256 VGPRs)
-            long long t = 0;
-            for (int i = 0; i < d->ngroups; ++i) t += ((long long)d->g[i].Hout * d->g[i].Wout * d->batch + 64 * cand - 4) / (64 * cand - 3);
-            const double step_us = 1.53 * (cand + 0.3) / 4.3;
-            for (int sc = 1; sc <= 8; ++sc) {
-                if (sc > 1 && (!can_split || G % sc || (ksplit_force > 1 && sc != ksplit_force))) continue;
-                if (sc == 1 && ksplit_force > 1 && can_split && G % ksplit_force == 0) continue;
-                if (sc > 1 && (double)sc * Mtot * slab_ld * 4 > (double)(query ? (256ll << 20) : ws_cap)) continue;
-                const long long items = t * ncb * sc;
-                double cost = (double)((items + cus - 1) / cus) * (3.0 * G / sc + 5.0) * step_us;
-                if (sc > 1) cost += 4.0 + ((double)sc * Mtot * slab_ld * 4 + (double)Mtot * d->N * 2) / 4.0e6;
-                if (mi == 0 || cost < best * 0.97) { best = cost; mi = cand; S = sc; }
-            }
-        }
-        if (mi == 0) return 1;
-    }
-    if (S > 1 && !query && (!ws || ((uintptr_t)ws & 15))) return 1;
-    const bool split = ncb > 1 || S > 1;
-    const int TM = 64 * mi - 3;
+    const rtn_conv_desc_t* d = c.d;
+    const rtn_conv_fp8_t* q8 = c.q8;
+    const H8Shape sh = h8_shape(c);
+    const int es = sh.es, epi = ch.epi, TM = 64 * ch.mi - 3;
     long long tiles = 0;
     for (int i = 0; i < d->ngroups; ++i) {
         const rtn_conv_group_t& s = d->g[i];
-        if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
-            s.in_img_stride < (long long)s.Hin * s.in_row_stride) return 1;
-        if (s.in_elems < (long long)(d->batch - 1) * s.in_img_stride + (long long)s.Hin * s.in_row_stride) return 1;
         const long long cells = (long long)s.Hout * s.Wout, M = cells * d->batch;
-        if (s.out_step > 1 || s.out_off != 0 || s.out_img_stride != cells * d->out_ld) return 1;      // dense [M][out_ld] output
-        if (M >= (1ll << 24) || M < 1) return 1;
-        if (!s.in || !s.out || ((uintptr_t)s.in & 15) || ((uintptr_t)s.out & 15)) return 1;
-        if (s.in_elems < M * d->Crun || s.out_elems < (M - 1) * d->out_ld + d->N) return 1;
-        if (s.in_elems * 2 >= 0xFFFFFF00ll || s.out_elems * 2 >= 0xFFFFFF00ll) return 1;
-        if (epi & 1) {
-            if (!s.res || ((uintptr_t)s.res & 15) || s.res_ld % 8 || s.res_img_stride != cells * s.res_ld) return 1;
-            if (s.res_elems < (M - 1) * s.res_ld + d->N || s.res_elems * 2 >= 0xFFFFFF00ll) return 1;
-        }
-        if (epi & 2) {
-            if (!s.mask || ((uintptr_t)s.mask & 15) || s.mask_ld % 8 || s.mask_img_stride != cells * s.mask_ld) return 1;
-            if (s.mask_elems < (M - 1) * s.mask_ld + d->N || s.mask_elems * 2 >= 0xFFFFFF00ll) return 1;
-        }
-        if (i > 0 && ((epi & 1) && s.res_ld != d->g[0].res_ld)) return 1;
-        if (i > 0 && ((epi & 2) && s.mask_ld != d->g[0].mask_ld)) return 1;
         H8Group& g = p.g[i];
         g.res = (epi & 1) ? (const char*)s.res : nullptr;
         g.mask = (epi & 2) ? (const char*)s.mask : nullptr;
@@ -712,24 +644,15 @@ int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
         g.inv_w = 1.0f / (float)s.Win;
         tiles += (M + TM - 1) / TM;
     }
-    const long long items = tiles * ncb * S;
-    if (tiles < 1 || items > 0x3fffffff) return 1;
-    // one 256 x 256 tile per CU: below a quarter of the chip the narrow tiles of generation 2 (four times the workgroups) are
-    // faster (P5 at batch 8 unsliced: 34 tiles, 0.049 ms here against 0.037 ms); from half the chip on this kernel wins (res4 3x3,
-    // P4: 133 tiles, 0.054 against 0.067 ms)
-    if (!forced && items * 4 < cus) return 1;
-    const long long slice_bytes = Mtot * slab_ld * 4;
-    if (S > 1 && slice_bytes >= 0xFFFFFF00ll) return 1;
-    if (query) { *query = S > 1 ? (size_t)(slice_bytes * S) : 0; return RTN_OK; }
     p.w = (const char*)d->w;
     p.bias = d->bias;
-    p.w_bytes = (unsigned)(Kbytes * d->w_rows);
+    p.w_bytes = (unsigned)(sh.Kbytes * d->w_rows);
     p.ngroups = d->ngroups;
-    p.ntiles = (int)tiles;
+    p.ntiles = (int)ch.tiles;
     p.N = d->N;
-    p.Kbytes = (int)Kbytes;
+    p.Kbytes = (int)sh.Kbytes;
     p.KH = d->KH;
-    p.nchunk = nchunk;
+    p.nchunk = sh.nchunk;
     p.pad_t = d->pad_t; p.pad_l = d->pad_l;
     p.relu = (d->flags & RTN_CONV_RELU) ? 1 : 0;
     p.out_ld = d->out_ld;
@@ -738,22 +661,30 @@ int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
     p.res_ld = (epi & 1) ? d->g[0].res_ld : 0;
     p.mask_ld = (epi & 2) ? d->g[0].mask_ld : 0;
     p.mask_pre = (d->flags & RTN_CONV_MASK_PRE) ? 1 : 0;
-    p.ncb = ncb; p.S = S; p.gps = G / S; p.nitems = (int)items;
+    p.ncb = sh.ncb; p.S = ch.S; p.gps = sh.G / ch.S; p.nitems = (int)ch.items;
     p.xcd = 1;                                         // XCD-contiguous item order (0 = workgroup b starts at item b: round-2 A/B, 274 -> 202 MB fetched per tower launch)
     p.kh_fast = 1;                                     // the kernel rows of a channel chunk back to back (round-2 A/B: profiles/r2_v3_ab_xcd_item_order.txt)
-    p.slab = S > 1 ? ws : nullptr;
-    p.slab_slice_bytes = S > 1 ? (unsigned)slice_bytes : 0u;
-    p.slab_ld = (int)slab_ld;
-    int grid = cus;
-    if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
-    if (grid > p.nitems) grid = p.nitems;
-    const int lrc = mi == 4 ? h8_pick<4>(h, grid, p, q8 != nullptr, half, split, stagger, epi)
-                            : h8_pick<3>(h, grid, p, q8 != nullptr, half, split, stagger, epi);
+    p.slab = ch.S > 1 ? scratch : nullptr;
+    p.slab_slice_bytes = ch.S > 1 ? (unsigned)ch.slice_bytes : 0u;
+    p.slab_ld = (int)ch.slab_ld;
+}
+
+// the kernel instance of the choice, then for K slices the finish launch that sums the slabs (a sliced layer has one group)
+int h8_launch(rtn_handle_t h, const H8Params& p, const H8Choice& ch) {
+    const int lrc = ch.mi == 4 ? h8_pick<4>(h, ch.grid, p, ch.fp8, ch.half, ch.split, ch.stagger, ch.epi)
+                               : h8_pick<3>(h, ch.grid, p, ch.fp8, ch.half, ch.split, ch.stagger, ch.epi);
     if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_halo8_kernel");
-    h->last_conv_tile = ((64 * mi) << 16) | (half ? 128 : 256);
-    if (S > 1) return rtn_conv_ksplit_finish(h, ws, S, Mtot, d->N, (int)slab_ld, d->bias, p.relu, d->g[0].out, d->out_ld);
+    h->last_conv_tile = ((64 * ch.mi) << 16) | (ch.half ? 128 : 256);
+    if (ch.S > 1) return rtn_conv_ksplit_finish(h, p.slab, ch.S, p.g[0].M, p.N, p.slab_ld, p.bias, p.relu, p.g[0].out, p.out_ld);
     return RTN_OK;
+}
+}  // namespace
+
+int rtn_conv_halo8_run(rtn_handle_t h, const ConvCall& c, const H8Choice& ch, float* scratch) {
+    H8Params p;
+    h8_fill(&p, c, ch, scratch);
+    return h8_launch(h, p, ch);
 }
 
 #ifdef RTN_H8_STAMP

@@ -15,6 +15,9 @@
 //     output channels of one pixel: one 16-byte f32 store per fragment straight from registers (dword stores when the channel
 //     count is not a multiple of 4), bias as the accumulators' initial value, sigmoid in registers.
 // LDS: 3 x (32 KiB + 6 NF KiB) + 1 KiB that swallows the surplus DMA pieces = 151 KiB for NF = 3.
+//
+// Host side: hn_takes / hn_choose (rtn_conv_persistent.h, without HIP) decide whether a layer is this kernel's and on how many
+// workgroups; here are hn_fill (HNParams), hn_launch (channel fragments -> kernel instance) and the entry rtn_conv_halon_run.
 #include "rtn_internal.h"
 #include "rtn_device.h"
 
@@ -23,9 +26,7 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr unsigned HN_OOB = 0xFFFFFF00u;              // beyond every descriptor: loads return zeros, stores are dropped
 constexpr int HN_THREADS = 512;
-constexpr int HN_R = 256, HN_TM = HN_R - 3;            // halo rows / output pixels of a tile (row 255 of a halo = zeros)
 constexpr unsigned HN_HALO = 32768, HN_ZERO_ROW = (HN_R - 1) * 128u;
 
 template <int NF>
@@ -304,37 +305,16 @@ __global__ __launch_bounds__(HN_THREADS, 2) void conv_halon_kernel(const HNParam
 #undef HN_ISSUE
 }
 
-}  // namespace
-
-// Launcher: RTN_OK after a launch, 1 when the layer is not one this kernel takes, < 0 on error.
-int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool forced) {
-    if (d->dtype != RTN_BF16) return 1;
-    if (d->KW != 3 || d->KH != 3 || d->sy != 1 || d->sx != 1) return 1;
-    if (!(d->flags & RTN_CONV_OUT_F32) || (d->flags & ~(RTN_CONV_OUT_F32 | RTN_CONV_RELU | RTN_CONV_SIGMOID))) return 1;
-    if (d->N < 1 || d->N > 48 || d->out_ld < d->N) return 1;
-    const int nf = (d->N + 15) / 16;
-    if (d->w_rows < 16 * nf) return 1;
-    if (d->Crun != d->pix_stride || (d->Crun * 2) % 128 || d->Crun <= 0) return 1;
-    if (d->pad_l < 0 || d->pad_l >= 3 || d->pad_t < 0 || d->pad_t >= 3) return 1;
-    if (((uintptr_t)d->w & 15) || ((uintptr_t)d->bias & 15)) return 1;
-    const int nchunk = d->Crun * 2 / 128;
-    const long long Kbytes = 9ll * d->Crun * 2;
-    if (Kbytes * d->w_rows >= 0xFFFFFF00ll) return 1;
-    HNParams p;
+// the kernel's parameters of a layer hn_takes accepted, on the grid hn_choose picked
+void hn_fill(HNParams* pp, const ConvCall& c, const HNChoice& ch) {
+    HNParams& p = *pp;
     memset(&p, 0, sizeof(p));
-    const int cus = h->num_cus > 0 ? h->num_cus : 256;
+    const rtn_conv_desc_t* d = c.d;
+    const long long Kbytes = 9ll * d->Crun * 2;
     long long tiles = 0;
-    bool vec = d->N % 4 == 0 && d->out_ld % 4 == 0;
     for (int i = 0; i < d->ngroups; ++i) {
         const rtn_conv_group_t& s = d->g[i];
-        if (s.Hin != s.Hout || s.Win != s.Wout || s.in_row_stride != (long long)s.Win * d->pix_stride ||
-            s.in_img_stride != (long long)s.Hin * s.in_row_stride) return 1;
         const long long cells = (long long)s.Hout * s.Wout, M = cells * d->batch;
-        if (s.out_step > 1 || s.out_off < 0 || M >= (1ll << 24) || M < 1) return 1;
-        if (!s.in || !s.out || ((uintptr_t)s.in & 15) || ((uintptr_t)s.out & 3)) return 1;
-        if (s.in_elems < M * d->Crun || s.in_elems * 2 >= 0xFFFFFF00ll || s.out_elems * 4 >= 0xFFFFFF00ll) return 1;
-        if (s.out_img_stride < 0 || (d->batch - 1) * s.out_img_stride + s.out_off + (cells - 1) * d->out_ld + d->N > s.out_elems) return 1;
-        if (((uintptr_t)s.out & 15) || s.out_img_stride % 4 || s.out_off % 4) vec = false;
         HNGroup& g = p.g[i];
         g.in = (const char*)s.in;
         g.out = (char*)s.out;
@@ -350,32 +330,38 @@ int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit,
         g.inv_w = 1.0f / (float)s.Win;
         tiles += (M + HN_TM - 1) / HN_TM;
     }
-    if (tiles < 1 || tiles > 0x3fffffff) return 1;
-    if (!forced && tiles * 4 < cus) return 1;
     p.w = (const char*)d->w;
     p.bias = d->bias;
     p.w_bytes = (unsigned)(Kbytes * d->w_rows);
     p.ngroups = d->ngroups;
-    p.ntiles = (int)tiles;
+    p.ntiles = (int)ch.tiles;
     p.N = d->N;
     p.Kbytes = (int)Kbytes;
-    p.nchunk = nchunk;
+    p.nchunk = d->Crun * 2 / 128;
     p.pad_t = d->pad_t; p.pad_l = d->pad_l;
     p.relu = (d->flags & RTN_CONV_RELU) ? 1 : 0;
     p.sigmoid = (d->flags & RTN_CONV_SIGMOID) ? 1 : 0;
     p.out_ld = d->out_ld;
     p.pix_b = d->pix_stride * 2;
-    p.vec = vec ? 1 : 0;
+    p.vec = ch.vec ? 1 : 0;
     p.xcd = 1;
     p.kh_fast = 1;
-    int grid = cus;
-    if (grid_limit > 0 && grid_limit < grid) grid = grid_limit;
-    if (grid > p.ntiles) grid = p.ntiles;
-    const dim3 gdim((unsigned)grid), bdim(HN_THREADS);
+}
+
+int hn_launch(rtn_handle_t h, const HNParams& p, const HNChoice& ch) {
+    const dim3 gdim((unsigned)ch.grid), bdim(HN_THREADS);
+    const int nf = ch.nf;
     const int lrc = nf == 1 ? rtn_launch_lds<conv_halon_kernel<1>>(h, gdim, bdim, HNCfg<1>::LDS, HNCfg<1>::LDS, p)
                   : nf == 2 ? rtn_launch_lds<conv_halon_kernel<2>>(h, gdim, bdim, HNCfg<2>::LDS, HNCfg<2>::LDS, p)
                             : rtn_launch_lds<conv_halon_kernel<3>>(h, gdim, bdim, HNCfg<3>::LDS, HNCfg<3>::LDS, p);
     if (lrc != RTN_OK) return lrc;
     RTN_CHECK_LAUNCH(h, "conv_halon_kernel");
     return RTN_OK;
+}
+}  // namespace
+
+int rtn_conv_halon_run(rtn_handle_t h, const ConvCall& c, const HNChoice& ch) {
+    HNParams p;
+    hn_fill(&p, c, ch);
+    return hn_launch(h, p, ch);
 }

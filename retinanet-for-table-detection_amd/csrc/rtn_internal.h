@@ -10,6 +10,7 @@
 #include <cstring>
 #include <type_traits>
 #include "rtn.h"
+#include "rtn_conv_persistent.h"
 
 struct rtn_ctx {
     int device;
@@ -80,16 +81,13 @@ inline int rtn_with_epi(int epi, F&& f) {
 int rtn_env_int(const char* name, int dflt);
 void rtn_env_sync();
 
-// rtn_conv_halo8.hip: persistent 8-phase kernel for the stride-1 3x3 layers with 129..256 output channels (head towers, P3-P5,
-// res4 branch2b).  RTN_OK = launched, 1 = not a layer this kernel takes, < 0 = error.
-int rtn_conv_halo8_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool stagger, bool forced, int mi_force, float* ws,
-                       long long ws_cap, size_t* query, int ksplit_force, const rtn_conv_fp8_t* q8 = nullptr);
-// rtn_conv_gemm8.hip: the same schedule as a plain GEMM for the 1x1 layers with N % 256 == 0 and a bias / ReLU epilogue, one or
-// two (K-concatenated) sources, stride 1 or 2.
-int rtn_conv_gemm8_try(rtn_handle_t h, const rtn_conv_desc_t* d, const rtn_conv_src2_t* s2, int grid_limit, bool stagger, bool forced,
-                       int mi_force, unsigned* sync, void* ws, long long ws_cap, size_t* query, int sk_mode);
-// rtn_conv_halon.hip: the head output convolutions (3x3, <= 48 channels, f32 result in the concatenated tensor)
-int rtn_conv_halon_try(rtn_handle_t h, const rtn_conv_desc_t* d, int grid_limit, bool forced);
+// The persistent convolution kernels (generations 4 / 5 / 6).  rtn_conv_persistent.h decides, without HIP, whether a layer is theirs
+// (*_takes) and on which tile, slices, grid and scratch it runs (*_choose); these entries fill the kernel's parameters from the call and
+// that choice and launch.  `scratch`: the caller's workspace behind its sync block (`sync`), used as the choice says.
+// RTN_OK = launched, < 0 = error.
+int rtn_conv_halo8_run(rtn_handle_t h, const ConvCall& c, const H8Choice& ch, float* scratch);
+int rtn_conv_gemm8_run(rtn_handle_t h, const ConvCall& c, const G8Choice& ch, unsigned* sync, void* scratch);
+int rtn_conv_halon_run(rtn_handle_t h, const ConvCall& c, const HNChoice& ch);
 // rtn_conv_ksplit.hip: sums the K-slice slabs of a conv launch in slice order and applies bias / ReLU
 int rtn_conv_ksplit_finish(rtn_handle_t h, const float* slab, int S, long long M, int N, int ld, const float* bias, int relu, void* out,
                            int out_ld);
